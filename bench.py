@@ -7,15 +7,19 @@ per layer, 859 rounds, from the pre-drawn verifier tape) -> commit_public on eq(
 final codeword — every prover call of the reference's verifier::verify() except answering the queries, and nothing of the verifier.  The
 circuit, the witness and every verifier draw are resident / known before the timed region; no field data crosses PCIe inside it except the
 transcript (45 KB) coming back.  Rank r proves its own instance (witness drawn after srandom(1 + r)), no data-path collective: "scaling": "weak".
-Rank 0's transcript, FRI roots and final codeword are compared byte for byte with the REAL reference's recorded run on every run.
 
-stdout carries ONE compact JSON line (<= 4 KB, strict JSON: compact_line): the contract fields, `roofline` (the kernel with the largest share of
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given (dump_outputs), and prints the
+line: the contract fields (`ms_per_step` = wall milliseconds of one timed step) and the per-call seconds of the timed steps.  With --full the run
+goes on after the timed steps: rank 0's transcript, FRI roots and final codeword are compared byte for byte with the REAL reference's recorded run,
+the host verifier checks the proof, and the other legs run.
+
+stdout carries ONE compact JSON line (<= 4 KB, strict JSON: compact_line).  With --full it also holds `roofline` (the kernel with the largest share of
 the step: k_leaf_hash, Keccak-f/s against its instruction-count floor, HIP events around every launch on the library stream), `cpu_baseline`
 (the real reference binary on a bounded sample: the same protocol at x64 on one host core), one-number summaries of the other legs; the tables —
 per kernel, per launch, per interactive round, the nested x64 GKR-only leg (BASELINE configs[1]), the oracle port's full-size GKR proof on one
-core, the multi-rank `sharded` sub-leg — go to the detail file named in the line (gpurun_out/bench_detail_n<N>.json).
+core, the multi-rank `sharded` sub-leg — go to the detail file named in the line (write_detail).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--blocks B] [--no-pc] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--blocks B] [--no-pc] [--no-cpu-baseline]
     python bench.py --blocks 64 --no-pc              the round-1..3 headline (BASELINE configs[1]: GKR only, commitment off)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -714,6 +718,8 @@ def gkr_workload(vp, a, pws, golden, world, rank, local, blocks, shard_req, cpu_
     first_proof_sec = time.perf_counter() - t_f
     steps, warmup = (a.steps, a.warmup) if not nested else (max(5, a.steps), max(2, a.warmup))
     tr, res, elapsed, dev_ms = gkr_leg(vp, circ, sess, steps, warmup, world, shard, local)
+    if a.dump_outputs and rank == 0 and not nested:
+        dump_outputs(a.dump_outputs, {"transcript": tr})
     elapsed, proofs = aggregate(world, elapsed, float(steps))
     shard_info = None
     if shard:
@@ -728,10 +734,11 @@ def gkr_workload(vp, a, pws, golden, world, rank, local, blocks, shard_req, cpu_
                       "collective": ("one RCCL all-reduce (u64 sum) of the transcript%s per proof inside vp_prove_gkr (vp_comm_init: no torch tensor, no host bounce)"
                                      % (" + export area" if a.shard_split else "")) if shard == "rccl"
                                     else "one all-reduce (sum, int64) of the %d-byte transcript per proof through torch, backend %s" % (len(tr), dist.get_backend())}
-        sess.set_shard(0, 1)                       # the roofline / verifier legs below run the whole proof on every rank
-        tr_full, _ = sess.prove_gkr()
-        assert tr_full == tr, "assembled sharded transcript differs from the unsharded proof"
-    if a.batched_only:            # profiling runs: the timed batched proofs and nothing else on the device (no profiled replay, no interactive run, no second session)
+        if not a.lean:
+            sess.set_shard(0, 1)                   # the roofline / verifier legs below run the whole proof on every rank
+            tr_full, _ = sess.prove_gkr()
+            assert tr_full == tr, "assembled sharded transcript differs from the unsharded proof"
+    if a.lean:            # no --full: the timed batched proofs and nothing else on the device (no profiled replay, no interactive run, no second session)
         rows, per_launch, roof, res_p = [], [], None, None
     else:
         rows, per_launch, roof, res_p = profile_gkr(sess, tr, pmc_tag(blocks, a.randomize))
@@ -784,12 +791,12 @@ def gkr_workload(vp, a, pws, golden, world, rank, local, blocks, shard_req, cpu_
                      "note": "each shard run alone on this GPU; a W-GPU run adds one all-reduce of the transcript (and, with the index split, of the export area) per proof"}
 
     pipelined = None
-    if rank == 0 and world == 1 and not shard and not a.no_two_in_flight and not nested and not a.batched_only:
+    if rank == 0 and world == 1 and not shard and not a.no_two_in_flight and not nested and not a.lean:
         g_ = golden.get(gname)
         pipelined = two_in_flight_leg(vp, circ, sess, tr, a.steps, a.warmup, local, (g_["mult_counter"] + g_["add_counter"]) if g_ else None)
 
     interactive = None
-    if rank == 0 and not a.batched_only:
+    if rank == 0 and not a.lean:
         # the drop-in path of the reference's own call pattern (one vp_round per verifier message), outside the timed region
         t_i = time.perf_counter()
         tr_i, res_i, ok_i = sess.prove_interactive()
@@ -809,14 +816,14 @@ def gkr_workload(vp, a, pws, golden, world, rank, local, blocks, shard_req, cpu_
     if gname in golden:
         g = golden[gname]
         ref_ops = g["mult_counter"] + g["add_counter"]
-        if rank == 0:
+        if rank == 0 and not a.lean:
             gold = open(os.path.join(ROOT, "tests", "golden", g["transcript"]), "rb").read()[g["gkr_slice"][0]:g["gkr_slice"][1]]
             bit_exact = (tr == gold)
     # the reported flag is the FULL replay check (per-round identities, wiring predicates and getFinalValue on the device, Liu
     # check, input check): the per-round identities alone hold by construction for the rounds whose b is derived
-    ok, sec_d = (True, None) if a.batched_only else sess.check(tr, device_predicates=True)
+    ok, sec_d = (None, None) if a.lean else sess.check(tr, device_predicates=True)
     verify = None
-    if rank == 0 and not a.batched_only:      # the verifier's side of the same proof (outside the timed region): O(|C|) predicate loops on host vs on the GPU
+    if rank == 0 and not a.lean:      # the verifier's side of the same proof (outside the timed region): O(|C|) predicate loops on host vs on the GPU
         ok_h, sec_h = sess.check(tr)
         verify = {"host_predicates_sec": sec_h, "device_predicates_sec": sec_d, "accepted": bool(ok_h and ok),
                   "note": "the verifier's O(|C|) loops on the device: wiring predicates (vp_predicates), gr of verifyLiu (vp_liu_gr), input-layer MLE (vp_layer_mle); the per-round checks stay on the host"}
@@ -843,7 +850,7 @@ def gkr_workload(vp, a, pws, golden, world, rank, local, blocks, shard_req, cpu_
             "prover_sec_device": 1e-3 * dev_ms / steps,
             "first_proof_sec": first_proof_sec,
             "rounds": res["rounds"], "kernel_launches_per_proof": res["launches"],
-            "bit_exact_vs_reference_golden": bit_exact, "host_verifier_accepts": bool(ok),
+            "bit_exact_vs_reference_golden": bit_exact, "host_verifier_accepts": None if ok is None else bool(ok),
             "host_verifier_check": "full replay: per-round identities, wiring predicates + getFinalValue (device loops), Liu check, input-layer check",
             "golden_origin": (golden[gname].get("origin", "the real reference binary (oracle/_ref/ref_run)") if gname in golden else None),
             "two_in_flight": pipelined,
@@ -958,6 +965,8 @@ def protocol_workload(vp, a, pws, golden, world, rank, local, blocks):
     gpu_sync(local)
     barrier(world)
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"transcript": tr, "fri_roots": np.frombuffer(roots, dtype=np.uint8).reshape(-1, 32), "fri_final_codeword": fin})
     elapsed_max, proofs = aggregate(world, elapsed, float(a.steps))
     # the other two forms, a few passes each (rank 0's own numbers, outside the headline's timed region): what the queueing is worth on this box
     modes = {a.pass_mode: 1e3 * elapsed / a.steps}
@@ -973,6 +982,28 @@ def protocol_workload(vp, a, pws, golden, world, rank, local, blocks):
                 sess.prove_protocol(**mkw)
             gpu_sync(local)
             modes[mname] = 1e3 * (time.perf_counter() - t_m) / max(4, a.steps // 3)
+    config = {"workload": "SHA-256 %d-block circuit (SHA256_64.pws x%d, %d gates, %d layers, 2^%d input wires), GKR sumcheck + Virgo FFT/LDT commit on GPU (BASELINE configs[%d]%s)"
+                          % (blocks, blocks, circ.gates, circ.layers, circ.layer_bitlen(0), 2 if world == 1 else 3,
+                             "" if world == 1 else ": %d independent proofs, one per GPU, witness seeds 1..%d" % (world, world)),
+              "mode": "one prover pass per step: commit_private -> GKR (batched, tape pre-drawn) -> commit_public(eq(r_liu,.) built on device) -> fft_gkr -> FRI commit phase; "
+                      + {"pipelined": "calls queued without host waits, each pass queues the next pass's commit_private behind its FRI folds (same work per step, no idle device between proofs)",
+                         "deferred": "calls queued without host waits inside a pass", "sync": "every call waits for its result"}[a.pass_mode],
+              "pass_mode": a.pass_mode,
+              "proofs_per_step": world, "field_ops_per_proof": (g["mult_counter"] + g["add_counter"]) if g else None}
+    if a.lean:
+        # a run without --full (and the profiling runs of tools/gpu_profile.sh): nothing but the batched passes in this process, no parity or verifier checks
+        sess.close(); circ.close()
+        if rank != 0:
+            return None
+        ref_ops = config["field_ops_per_proof"]
+        per = {k: v / a.steps for k, v in acc.items()}
+        return {"metric": METRIC, "value": (ref_ops * proofs / elapsed_max) if ref_ops else None, "unit": "field-ops/s", "n_gpus": distinct_gpus(world), "ranks": world,
+                "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed_max / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE,
+                "data": "synthetic", "config": config,
+                "prover_sec": {"step_wall": elapsed_max / a.steps, "gkr": per.get("gkr"), "commit_private": per.get("commit_private"), "commit_public": per.get("commit_public"),
+                               "fft_gkr": per.get("fft_gkr"), "fri_commit": per.get("fri_commit")},
+                "roofline": None, "cpu_baseline": None,
+                "first_proof_sec": {"gkr_first_call_incl_plan_tuner_and_graph_capture": first_gkr, "vp_warm_commitment_sec": warm_sec, "first_complete_pass_after_vp_warm": first_pass}}
     # ---- parity: rank 0 against the REAL reference's files; every rank through the complete protocol's host verifier
     exact = {}
     if g and rank == 0:
@@ -986,20 +1017,6 @@ def protocol_workload(vp, a, pws, golden, world, rank, local, blocks):
         fx = os.path.join(GOLDEN, "oracle_sha256_x1024_gkr_seed2.bin")
         if os.path.exists(fx):
             exact["gkr_slice_vs_oracle_seed2"] = tr[32:32 + os.path.getsize(fx)] == open(fx, "rb").read()
-    if a.batched_only:
-        # profiling runs (tools/gpu_profile.sh): nothing but the batched passes in this process — the line carries the contract fields and the parity of the passes
-        sess.close(); circ.close()
-        if rank != 0:
-            return None
-        ref_ops = (g["mult_counter"] + g["add_counter"]) if g else None
-        per = {k: v / a.steps for k, v in acc.items()}
-        return {"metric": METRIC, "value": (ref_ops * proofs / elapsed_max) if ref_ops else None, "unit": "field-ops/s", "n_gpus": distinct_gpus(world), "ranks": world,
-                "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed_max / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE,
-                "data": "synthetic", "config": {"workload": "SHA-256 %d-block circuit, GKR + commitment, batched passes only (--batched-only: a profiling run)" % blocks, "pass_mode": a.pass_mode},
-                "prover_sec": {"step_wall": elapsed_max / a.steps, "gkr": per.get("gkr"), "commit_private": per.get("commit_private"), "commit_public": per.get("commit_public"),
-                               "fft_gkr": per.get("fft_gkr"), "fri_commit": per.get("fri_commit")},
-                "bit_exact": exact, "bit_exact_all_ranks": True, "roofline": None, "cpu_baseline": None,
-                "first_proof_sec": {"gkr_first_call_incl_plan_tuner_and_graph_capture": first_gkr, "vp_warm_commitment_sec": warm_sec, "first_complete_pass_after_vp_warm": first_pass}}
     trf, ok_full, times = sess.prove_and_verify_full(reps=33)      # interactive GKR + commitment verification, 33 query repetitions
     exact["complete_protocol_accepted"] = bool(ok_full)
     exact["interactive_run_equals_batched"] = trf == tr
@@ -1055,14 +1072,7 @@ def protocol_workload(vp, a, pws, golden, world, rank, local, blocks):
                             "gkr_field_ops_per_sec is the same count over the GKR part alone (the round-1..3 headline's definition)",
         "n_gpus": distinct_gpus(world), "ranks": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed_max / a.steps,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
-        "config": {"workload": "SHA-256 %d-block circuit (SHA256_64.pws x%d, %d gates, %d layers, 2^%d input wires), GKR sumcheck + Virgo FFT/LDT commit on GPU (BASELINE configs[%d]%s)"
-                               % (blocks, blocks, circ.gates, circ.layers, circ.layer_bitlen(0), 2 if world == 1 else 3,
-                                  "" if world == 1 else ": %d independent proofs, one per GPU, witness seeds 1..%d" % (world, world)),
-                   "mode": "one prover pass per step: commit_private -> GKR (batched, tape pre-drawn) -> commit_public(eq(r_liu,.) built on device) -> fft_gkr -> FRI commit phase; "
-                           + {"pipelined": "calls queued without host waits, each pass queues the next pass's commit_private behind its FRI folds (same work per step, no idle device between proofs)",
-                              "deferred": "calls queued without host waits inside a pass", "sync": "every call waits for its result"}[a.pass_mode],
-                   "pass_mode": a.pass_mode,
-                   "proofs_per_step": world, "field_ops_per_proof": ref_ops},
+        "config": config,
         "prover_sec": {"step_wall": elapsed_max / a.steps, "gkr": per.get("gkr"), "commit_private": per.get("commit_private"), "commit_public": per.get("commit_public"),
                        "fft_gkr": per.get("fft_gkr"), "fri_commit": per.get("fri_commit"),
                        "pc_prove_reference_definition": per.get("commit_private", 0) + per.get("commit_public", 0) + per.get("fft_gkr", 0) + per.get("fri_commit", 0),
@@ -1435,20 +1445,47 @@ def write_detail(d, n_gpus, path=None):
     return None
 
 
-class OneLine:
-    """Exactly one JSON line on stdout, whoever gets there first (the normal end of main() or the watchdog)."""
+DUMP_BUDGET_BYTES = 64 << 20
 
-    def __init__(self):
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: what the timed path returned in its last step, one `path`/<name>.npy per array, so that two builds can be compared output for
+    output.  The values are 64-bit field words (F_p^2: real, imaginary) and hash bytes; each array holds them as little-endian 32-bit words (a 64-bit word
+    is its low half, then its high half) in float64, which represents every such word exactly.  Rows keep the caller's first axis (one codeword entry, one
+    FRI root); bytes come out as one row.  Past DUMP_BUDGET_BYTES in all, every array keeps the same fraction of its rows, a sample drawn with a fixed seed."""
+    import numpy as np
+    arrs = {}
+    for name, v in outputs.items():
+        b = bytes(v) if isinstance(v, (bytes, bytearray)) else np.ascontiguousarray(v).tobytes()
+        w = np.frombuffer(b + b"\0" * (-len(b) % 4), dtype="<u4").astype(np.float64)
+        arrs[name] = w.reshape(len(v), -1) if isinstance(v, np.ndarray) and v.ndim > 1 else w
+    total = sum(x.nbytes for x in arrs.values())
+    budget = DUMP_BUDGET_BYTES - 1024 * len(arrs)          # room for the .npy headers
+    if total > budget:
+        rng = np.random.default_rng(0)
+        for name, x in arrs.items():
+            keep = max(1, len(x) * budget // total)
+            arrs[name] = x[np.sort(rng.choice(len(x), size=keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
+class OneLine:
+    """Exactly one JSON line on stdout, whoever gets there first (the normal end of main() or the watchdog).  write_file: the detail file too."""
+
+    def __init__(self, write_file=True):
         import threading
         self.lock = threading.Lock()
         self.done = False
+        self.write_file = write_file
 
     def emit(self, detail, n_gpus, path=None):
         with self.lock:
             if self.done:
                 return False
             self.done = True
-            f = write_detail(detail, n_gpus, path)
+            f = write_detail(detail, n_gpus, path) if self.write_file else None
             print(compact_line(detail, f), flush=True)
             return True
 
@@ -1484,17 +1521,27 @@ def main():
     ap.add_argument("--no-two-in-flight", action="store_true", help="GKR-only legs: skip the `two_in_flight` sub-leg (two sessions of the circuit, two host threads)")
     ap.add_argument("--no-sharded-leg", action="store_true", help="N > 1: skip the `sharded` sub-leg (one proof + its commitment over all ranks, RCCL)")
     ap.add_argument("--subleg-timeout", type=float, default=300.0, help="N > 1: seconds the multi-rank sub-leg may take before the line is printed without it and the ranks exit 3")
-    ap.add_argument("--detail-file", default=None, help="where everything the line leaves out goes (default gpurun_out/bench_detail_n<N>.json)")
+    ap.add_argument("--detail-file", default=None, help="where everything the line leaves out goes (default with --full: see write_detail; a run without "
+                    "--full writes it only when this is given)")
     ap.add_argument("--first-proof-child", type=int, default=0, metavar="BLOCKS", help="internal: the fresh-process leg of first_proof_sec (see first_proof_child)")
     ap.add_argument("--no-fresh-process-leg", action="store_true", help="N = 1 headline: skip the fresh-process first proof with the plan cache file")
     ap.add_argument("--batched-only", action="store_true", help="profiling runs: the headline's setup, warm-up and timed batched passes and NOTHING else in the process (no profiled "
                     "replay, no interactive run, no verification, no nested legs) — per-kernel counters of such a run are the headline's launches alone")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: parity with the reference's recorded runs, the host verifier, "
+                    "the profiled replay and rooflines, the interactive path, the other pass modes, the nested x64 and randomize(16, 20) legs, the CPU baselines, "
+                    "the fresh-process first proof, the multi-rank `sharded` sub-leg, and the detail file.  Without it a run sets up, warms up, times the steps "
+                    "and prints the line (the same as --batched-only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned as DIR/<name>.npy (see dump_outputs)")
     a = ap.parse_args()
     if a.first_proof_child:
         first_proof_child(a.first_proof_child)
         return
-    if a.batched_only:
+    if a.steps < 1:
+        sys.stderr.write("bench.py: --steps must be >= 1\n"); sys.exit(2)
+    a.lean = a.batched_only or not a.full
+    if a.lean:
         a.no_cpu_baseline = a.no_x64_leg = a.no_randomize_leg = a.no_pass_modes = a.no_fresh_process_leg = True
+        a.no_two_in_flight = a.no_sharded_leg = True
 
     # ---- one process per GPU, always.  N > 1 without a launcher: start the ranks (before anything of this process touches the GPU).
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
@@ -1522,7 +1569,7 @@ def main():
     gkr_only = a.no_pc or a.randomize or a.shard_chains or a.shard_sim
     if a.randomize:
         a.no_cpu_baseline = True
-    out = OneLine()
+    out = OneLine(write_file=not a.lean or a.detail_file is not None)
     failed_subleg = False
     t_bench0 = time.perf_counter()
     with tempfile.TemporaryDirectory() as tmp:

@@ -177,3 +177,35 @@ def test_issue_share_record_is_read_and_is_a_fraction():
     rec = json.load(open(os.path.join(ROOT, src)))
     assert os.path.exists(os.path.join(ROOT, rec["pmc_summary"]))
     assert bench.issue_share("no_such_workload") == ({}, None)
+
+
+def test_dumped_outputs_are_exact_and_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: 64-bit field words and hash bytes come out as their 32-bit halves in float64, exactly; past the budget every array keeps a seeded
+    sample of its rows, the same one on every run."""
+    import numpy as np
+    import bench
+    words = np.array([0, 1, (1 << 61) - 2, (1 << 61) - 1, 0x123456789abcdef], dtype=np.uint64)
+    tr = words.tobytes()
+    fin = np.stack([words, words[::-1]], axis=1)
+    roots = np.frombuffer(bytes(range(64)), dtype=np.uint8).reshape(2, 32)
+    bench.dump_outputs(str(tmp_path / "d"), {"transcript": tr, "fri_roots": roots, "fri_final_codeword": fin})
+    back = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("transcript", "fri_roots", "fri_final_codeword")}
+    assert all(x.dtype == np.float64 for x in back.values())
+    assert back["transcript"].shape == (10,) and back["fri_roots"].shape == (2, 8) and back["fri_final_codeword"].shape == (5, 4)
+    assert back["transcript"].astype(np.uint64).astype("<u4").tobytes() == tr
+    assert back["fri_roots"].astype(np.uint64).astype("<u4").tobytes() == roots.tobytes()
+    assert back["fri_final_codeword"].astype(np.uint64).astype("<u4").tobytes() == fin.tobytes()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 16)
+    big = np.arange(20000, dtype=np.uint64).reshape(-1, 2)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "transcript": tr})
+    assert sum(os.path.getsize(str(p)) for p in (tmp_path / "s1").iterdir()) <= 1 << 16
+    for n in ("big.npy", "transcript.npy"):
+        assert np.array_equal(np.load(str(tmp_path / "s1" / n)), np.load(str(tmp_path / "s2" / n)))
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr and r.stdout == ""

@@ -1620,7 +1620,7 @@ def _bench_two_ranks(extra_env, timeout_s, *flags):
     import subprocess, sys
     env = dict(os.environ, VP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "16", "--no-cpu-baseline"] + list(flags)
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "16", "--no-cpu-baseline", "--full"] + list(flags)
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout_s, env=env, cwd=ROOT)
 
 
@@ -1647,6 +1647,32 @@ def test_bench_multi_rank_line_and_exit_code_when_a_rank_fails(vp, tmp_path, inj
     else:
         assert r.returncode != 0
         assert "multi_gpu_sublegs_error" in o and any(w in o["multi_gpu_sublegs_error"] for w in ("failed", "timed out", "went away", "terminated"))
+
+
+def test_bench_plain_run_dumps_the_references_outputs(vp, golden, tmp_path):
+    """bench.py without --full (set-up, warm-up, the timed steps, the line) at x16 with --dump-outputs: one line with the contract fields and no
+    detail file, and what the last timed step returned — transcript, FRI roots, final codeword — is the real reference's recorded run, word for word."""
+    import subprocess, sys
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--blocks", "16", "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2500:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-800:]
+    o = json.loads(lines[0])
+    assert o["steps"] == 3 and o["warmup"] == 1 and o["ms_per_step"] > 0 and o["value"] > 0 and o["unit"] == "field-ops/s" and o["higher_is_better"] is True
+    assert o["detail_file"] is None and o["roofline"] is None and o["cpu_baseline"] is None
+
+    def words(name):
+        x = np.load(str(out / (name + ".npy")))
+        assert x.dtype == np.float64 and np.all(x == np.floor(x)) and x.max() < 2.0 ** 32
+        return x.astype(np.uint64).astype("<u4").tobytes()
+    g = golden["sha256_x16"]
+    st = g["fri_steps"]
+    fri = open(os.path.join(GOLDEN_DIR, g["fri"]), "rb").read()
+    assert words("transcript") == open(os.path.join(GOLDEN_DIR, g["transcript"]), "rb").read()
+    assert words("fri_roots") == b"".join(fri[48 * k + 16:48 * k + 48] for k in range(st))
+    assert words("fri_final_codeword") == fri[48 * st:48 * st + 2048 * 16]
 
 
 _EXIT_WORKER = r"""

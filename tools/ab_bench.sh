@@ -3,6 +3,7 @@
 # numbers are compared):  tools/ab_bench.sh TAG path/to/variantA/libvpgpu.so [bench flags...]   ("" = the product library)
 # Alternates A, product, A, product; one JSON line each into gpurun_out/TAG_{a,b}{1,2}.json
 T=$1; A=$2; shift 2
+set -- --full "$@"          # the comparison below reads the roofline and parity fields, which a --full run prints
 mkdir -p gpurun_out
 for i in 1 2; do
   VP_LIBGPU=$A python bench.py "$@" > gpurun_out/${T}_a$i.json || exit 1

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; B=$1; shift
 for S in "$@"; do
   if [ "$S" = "-" ]; then E=""; else E="$S"; fi
-  env $E python3 $R/bench.py --blocks $B --no-pc --steps 8 --warmup 2 --no-cpu-baseline 2> /dev/null | python3 -c "
+  env $E python3 $R/bench.py --blocks $B --no-pc --steps 8 --warmup 2 --no-cpu-baseline --full 2> /dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 ip=d.get('interactive_path') or {}
