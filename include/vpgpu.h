@@ -446,6 +446,7 @@ int vp_set_profiling(vp_ctx *, int level);
 enum { VP_K_BETA = 0, VP_K_LIGHT, VP_K_CHUNKS, VP_K_COMBINE, VP_K_DOT, VP_K_DOTFIN, VP_K_SFGEN, VP_K_SF, VP_K_SEG, VP_K_EMIT,
        VP_K_FIXUP, VP_K_NTT_SPLIT, VP_K_NTT_LDS, VP_K_NTT_UNSPLIT, VP_K_LEAF_HASH, VP_K_MERKLE, VP_K_PC_POINTWISE, VP_K_FRI_FOLD,
        VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_COUNT };
+/* VP_K_NTT_UNSPLIT is no longer emitted (the long transforms store in natural order themselves); it keeps its value so the others do not move. */
 typedef struct {
     int32_t kind;             /* VP_K_*                                                          */
     int32_t step;             /* position in the launch order of the call                        */

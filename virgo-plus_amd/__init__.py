@@ -546,10 +546,10 @@ _PUBLIC_OPTIONS = ("use_graph", "plan_autotune", "real_values", "real_pairs", "p
 # internal tuning knobs (csrc/vpgpu.hip, VpOpt): name -> the VP_* environment variable the library reads once per vp_create (tests / benches / A-B only)
 _TUNING_ENV = {"gkr_path": "VP_GKR_PATH", "serial": "VP_GKR_SERIAL", "fuse_init": "VP_FUSE_INIT", "fuse_min_log": "VP_FUSE_MIN_LOG", "fuse_dot": "VP_FUSE_DOT",
                "drop_y": "VP_DROP_Y", "drop_y_round1": "VP_DROP_Y1", "seg_tiny": "VP_SEG_TINY", "sf_big_log": "VP_SF_BIG_LOG", "sf3b_grid": "VP_SF3B_GRID",
-               "dot_blocks": "VP_DOT_BLOCKS", "plan_align": "VP_PLAN_ALIGN", "xcd_map": "VP_XCD_MAP", "round_fused_max": "VP_ROUND_FUSED_MAX",
-               "kernel_copies": "VP_KERNEL_COPIES", "fold_branches": "VP_FOLD_BRANCHES", "ntt_scatter": "VP_NTT_SCATTER", "fuse_combine": "VP_FUSE_COMBINE",
-               "graph_explicit": "VP_GRAPH_EXPLICIT", "ntt_r8": "VP_NTT_R8", "fri_vo_fused": "VP_FRI_VO_FUSED", "fuse_p2": "VP_FUSE_P2", "leaf_asm": "VP_LEAF_ASM",
-               "fft_gkr_batched": "VP_FFT_GKR_BATCHED", "split_vu": "VP_SPLIT_VU", "fri_fold3": "VP_FRI_FOLD3", "sf3c": "VP_SF3C"}
+               "dot_blocks": "VP_DOT_BLOCKS", "plan_align": "VP_PLAN_ALIGN", "round_fused_max": "VP_ROUND_FUSED_MAX",
+               "kernel_copies": "VP_KERNEL_COPIES", "fold_branches": "VP_FOLD_BRANCHES", "fuse_combine": "VP_FUSE_COMBINE",
+               "graph_explicit": "VP_GRAPH_EXPLICIT", "ntt_r8": "VP_NTT_R8", "fuse_p2": "VP_FUSE_P2", "leaf_asm": "VP_LEAF_ASM",
+               "fft_gkr_batched": "VP_FFT_GKR_BATCHED", "split_vu": "VP_SPLIT_VU"}
 VP_OPTIONS_ABI = 0x76700005
 
 

@@ -681,8 +681,8 @@ __global__ void k_leaf_hash_final(const F *__restrict__ cw, int n_slices, Dig *_
 // j = j1*N2 + j2, k = k1 + N1*k2:  w_N^(jk) = w_N1^(j1 k1) * w_N^(j2 k1) * w_N2^(j2 k2).
 //   k_ntt_split : per j2 an N1-point transform over the N1 rows (stride N2) in registers + the w_N^(j2 k1) twiddle
 //                 (+ the coset twist for the encoder), written as [k1][j2] — every access coalesced;
-//   k_ntt_lds   : N1 contiguous N2-point transforms per row (existing kernel, rows = original rows * N1);
-//   k_ntt_unsplit: [k1][k2] -> natural k1 + N1*k2 through an LDS tile (+ the 1/N scale of the inverse).
+//   k_ntt_lds   : N1 contiguous N2-point transforms per row (existing kernel, rows = original rows * N1), stored straight to the natural
+//                 k1 + N1*k2 (NttArgs::scat_l1, + the 1/N scale of the inverse).
 namespace vp {
 
 struct SplitArgs {
@@ -759,27 +759,6 @@ __global__ void __launch_bounds__(VP_BLOCK) k_ntt_split(SplitArgs a) {
             const u32 p = p0 + i;
             dst[(size_t) k1[i] * N2 + j2] = (p == 0 && !twist) ? x[p] : f_mul(x[p], root_fin(w[i], a.half_m, e[i]));
         }
-    }
-}
-
-// in: [rows][N1][N2] (k1-major), out: [rows][N] natural (k = k1 + N1*k2); tile of 64 k2 x N1 k1 through LDS
-__global__ void __launch_bounds__(VP_BLOCK)
-k_ntt_unsplit(const F *__restrict__ in, F *__restrict__ out, int ln, int l1, F scale, int do_scale) {
-    __shared__ F tile[32][65];
-    const u32 N = 1u << ln, N1 = 1u << l1, N2 = N >> l1;
-    const u32 row = blockIdx.y, k2_0 = blockIdx.x * 64;
-    const F *src = in + (size_t) row * N;
-    F *dst = out + (size_t) row * N;
-    for (u32 t = threadIdx.x; t < N1 * 64; t += blockDim.x) {
-        const u32 k1 = t / 64, c = t % 64;
-        tile[k1][c] = src[(size_t) k1 * N2 + k2_0 + c];
-    }
-    __syncthreads();
-    for (u32 t = threadIdx.x; t < N1 * 64; t += blockDim.x) {
-        const u32 c = t / N1, k1 = t % N1;
-        F v = tile[k1][c];
-        if (do_scale) v = f_mul(v, scale);
-        dst[(size_t) (k2_0 + c) * N1 + k1] = v;
     }
 }
 
@@ -878,10 +857,11 @@ k_mask_hcoef(const F *__restrict__ lq_coef, u32 ms, u32 n_pad, F ms_as_f, F *__r
     if (i < n_pad) h_coef[i] = i < ms ? lq_coef[ms + i] : f_zero();
     if (i == 0) { const F s = f_add(lq_coef[0], lq_coef[ms]); *S0 = s; *all_sum64 = f_mul(s, ms_as_f); }
 }
-// Virtual oracle of the mask slice (poly_commit.h:225-245): (l q - (x^ms - 1) h - S0) ms x^-1 at x = w_M^(32 a + b), coset-major like its inputs
+// Virtual oracle of the mask slice (poly_commit.h:225-245): (l q - (x^ms - 1) h - S0) ms x^-1 at x = w_M^(32 a + b), coset-major like its inputs.
+// qm and out may be the same array (vp_fri_step writes in place), so neither is __restrict__.
 __global__ void __launch_bounds__(VP_BLOCK)
-k_mask_vo(const F *__restrict__ lm, const F *__restrict__ qm, const F *__restrict__ hm, const F *__restrict__ S0, u32 N, const F *__restrict__ RT, u32 half_m,
-          F ms_as_f, u32 ms, F *__restrict__ out) {
+k_mask_vo(const F *__restrict__ lm, const F *qm, const F *__restrict__ hm, const F *__restrict__ S0, u32 N, const F *__restrict__ RT, u32 half_m,
+          F ms_as_f, u32 ms, F *out) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 M = 2 * half_m;
     if (t >= M) return;

@@ -108,7 +108,6 @@ struct Plan {
     hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] = ctx->stream; [1..3] owned: fold (low priority), seg, emit (high)
     hipEvent_t ev_root = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     u64 rounds = 0; int n_steps = 0;
-    int sf3c = 0;                                    // the fold nodes were sized for k_sumfold3c (a wave per chunk): fixed when the plan is recorded
     FixJob *d_fix = nullptr; u32 n_fix = 0;          // k_fixup jobs (when round 1 of the sumchecks leaves its b to the fix-up pass)
     std::vector<void *> allocs;                      // device arrays owned by the plan (freed with it)
     // index-split proof: V_u of the split phase-2 chains ahead of the graph (vu_pre_*): per chain one inner-product job over this rank's share of
@@ -137,24 +136,19 @@ struct VpOpt {
     int32_t sf3b_grid;              // VP_SF3B_GRID: its workgroups per launch                                                                           [512]
     int32_t dot_blocks;             // VP_DOT_BLOCKS: workgroups of a stand-alone inner product                                                          [1024]
     int32_t plan_align;             // VP_PLAN_ALIGN=left|right: 0 closing launches aligned at the end, 1 all left, 2 all right                          [0]
-    int32_t xcd_map;                // VP_XCD_MAP: XCD-aware block map of the plan nodes (measured: no gain)                                             [0]
     int32_t round_fused_max;        // VP_ROUND_FUSED_MAX: interactive rounds with at most this many pairs take one launch                               [512]
     int32_t persistent_rounds, poll, debug, prefetch_round1, split_cost_percent;          // public
     int32_t kernel_copies;          // VP_KERNEL_COPIES: tape in / transcript out by two small kernels on pinned memory instead of copy-engine commands  [1]
     int32_t fold_branches;          // VP_FOLD_BRANCHES: an independent fold node of the plan runs on another stream                                     [1]
-    int32_t ntt_scatter;            // VP_NTT_SCATTER: radix-4 long transforms store in natural order themselves                                         [1]
     int32_t fuse_combine;           // VP_FUSE_COMBINE: heavy rows finished by the chunk launch (2: and the chain keeps the empty step)                   [2]
     int32_t plan_autotune, pc_tensor_pub, persistent_timeout_ms;                          // public
     int32_t graph_explicit;         // VP_GRAPH_EXPLICIT: the plan's hipGraph built node by node (1..3: forms, see plan_graph_explicit)                   [0]
     int32_t ntt_r8;                 // VP_NTT_R8: transforms of 2^13..2^17 points by the radix-8 Stockham pair (0: radix-4 pair, the cross-check)        [1]
-    int32_t fri_vo_fused;           // VP_FRI_VO_FUSED: first FRI fold straight from the committed codewords                                              [1]
     int32_t interactive_fast_init;  // public
     int32_t fuse_p2;                // VP_FUSE_P2: phase-2 init inside the first fold launch too                                                          [1]
     int32_t leaf_asm;               // VP_LEAF_ASM: leaf chains by the generated fixed-register block (0: the compiler's Keccak-f, the cross-check)       [1]
     int32_t real_pairs;             // public
     int32_t fft_gkr_batched;        // VP_FFT_GKR_BATCHED: the 2 lg inverse-FFT sumchecks of vp_fft_gkr as one batch                                      [1]
-    int32_t fri_fold3;              // VP_FRI_FOLD3: vp_fri_commit folds levels 0, 1, 2 in one pass                                                        [1]
-    int32_t sf3c;                   // VP_SF3C: the fold launches of the plan give a WAVE a chunk (k_sumfold3c: permlane swaps, no LDS, no barriers; measured slower) [0]
     int32_t split_vu;               // VP_SPLIT_VU: index-split proof: V_u of a split phase 2 from per-rank partial inner products ahead of the graph      [1]
 };
 
@@ -887,21 +881,18 @@ static void opt_defaults(VpOpt *o) {
     memset(o, 0, sizeof *o);
     o->gkr_path = VP_PATH_PLAN; o->use_graph = 1; o->serial = 0; o->fuse_init = 1; o->fuse_min_log = 0; o->fuse_dot = 0;
     o->drop_y = 1; o->drop_y_round1 = 0; o->real_values = 1; o->seg_tiny = 1; o->sf_big_log = 14;
-    o->sf3b_grid = 512; o->dot_blocks = 1024; o->plan_align = 0; o->xcd_map = 0; o->round_fused_max = 512;
-    o->persistent_rounds = 1; o->poll = 1; o->debug = 0; o->prefetch_round1 = 1; o->split_cost_percent = 50; o->kernel_copies = 1; o->fold_branches = 1; o->ntt_scatter = 1; o->fuse_combine = 2; o->plan_autotune = 1;
+    o->sf3b_grid = 512; o->dot_blocks = 1024; o->plan_align = 0; o->round_fused_max = 512;
+    o->persistent_rounds = 1; o->poll = 1; o->debug = 0; o->prefetch_round1 = 1; o->split_cost_percent = 50; o->kernel_copies = 1; o->fold_branches = 1; o->fuse_combine = 2; o->plan_autotune = 1;
     o->pc_tensor_pub = 1;
     o->persistent_timeout_ms = 10000;
     o->graph_explicit = 0;
     o->ntt_r8 = 1;
-    o->fri_vo_fused = 1;
     o->interactive_fast_init = 1;
     o->fuse_p2 = 1;
     o->leaf_asm = 1;
     o->real_pairs = 1;
     o->fft_gkr_batched = 1;
     o->split_vu = 1;
-    o->fri_fold3 = 1;
-    o->sf3c = 0;
 }
 static void opt_to_public(const VpOpt &o, vp_options *p) {
     memset(p, 0, sizeof *p);
@@ -927,13 +918,13 @@ struct OptName { const char *name; int32_t VpOpt::*field; };
 static const OptName g_opt_names[] = {
     {"gkr_path", &VpOpt::gkr_path}, {"use_graph", &VpOpt::use_graph}, {"serial", &VpOpt::serial}, {"fuse_init", &VpOpt::fuse_init}, {"fuse_min_log", &VpOpt::fuse_min_log},
     {"fuse_dot", &VpOpt::fuse_dot}, {"drop_y", &VpOpt::drop_y}, {"drop_y_round1", &VpOpt::drop_y_round1}, {"real_values", &VpOpt::real_values}, {"seg_tiny", &VpOpt::seg_tiny},
-    {"sf_big_log", &VpOpt::sf_big_log}, {"sf3b_grid", &VpOpt::sf3b_grid}, {"dot_blocks", &VpOpt::dot_blocks}, {"plan_align", &VpOpt::plan_align}, {"xcd_map", &VpOpt::xcd_map},
+    {"sf_big_log", &VpOpt::sf_big_log}, {"sf3b_grid", &VpOpt::sf3b_grid}, {"dot_blocks", &VpOpt::dot_blocks}, {"plan_align", &VpOpt::plan_align},
     {"round_fused_max", &VpOpt::round_fused_max}, {"persistent_rounds", &VpOpt::persistent_rounds}, {"poll", &VpOpt::poll}, {"debug", &VpOpt::debug},
     {"prefetch_round1", &VpOpt::prefetch_round1}, {"split_cost_percent", &VpOpt::split_cost_percent}, {"kernel_copies", &VpOpt::kernel_copies},
-    {"fold_branches", &VpOpt::fold_branches}, {"ntt_scatter", &VpOpt::ntt_scatter}, {"fuse_combine", &VpOpt::fuse_combine}, {"plan_autotune", &VpOpt::plan_autotune},
+    {"fold_branches", &VpOpt::fold_branches}, {"fuse_combine", &VpOpt::fuse_combine}, {"plan_autotune", &VpOpt::plan_autotune},
     {"pc_tensor_pub", &VpOpt::pc_tensor_pub}, {"persistent_timeout_ms", &VpOpt::persistent_timeout_ms}, {"graph_explicit", &VpOpt::graph_explicit}, {"ntt_r8", &VpOpt::ntt_r8},
-    {"fri_vo_fused", &VpOpt::fri_vo_fused}, {"interactive_fast_init", &VpOpt::interactive_fast_init}, {"fuse_p2", &VpOpt::fuse_p2}, {"leaf_asm", &VpOpt::leaf_asm},
-    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}, {"fri_fold3", &VpOpt::fri_fold3}, {"sf3c", &VpOpt::sf3c}};
+    {"interactive_fast_init", &VpOpt::interactive_fast_init}, {"fuse_p2", &VpOpt::fuse_p2}, {"leaf_asm", &VpOpt::leaf_asm},
+    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}};
 int vp_tuning_get(const vp_ctx *ctx, const char *name, int32_t *value) {
     if (!ctx || !name || !value) return VP_EINVAL;
     for (const OptName &n : g_opt_names) if (!strcmp(n.name, name)) { *value = ctx->opt.*(n.field); return VP_OK; }
@@ -960,7 +951,7 @@ static int resolve_options(VpOpt *o, const vp_options *user, uint32_t *pinned) {
     if (const char *p = getenv("VP_PLAN_ALIGN")) o->plan_align = !strcmp(p, "left") ? 1 : !strcmp(p, "right") ? 2 : 0;
     flag("VP_GKR_GRAPH", o->use_graph); flag("VP_GKR_SERIAL", o->serial); flag("VP_FUSE_INIT", o->fuse_init); flag("VP_FUSE_DOT", o->fuse_dot);
     flag("VP_DROP_Y", o->drop_y); flag("VP_DROP_Y1", o->drop_y_round1); flag("VP_REAL_V", o->real_values);
-    flag("VP_SEG_TINY", o->seg_tiny); flag("VP_XCD_MAP", o->xcd_map); flag("VP_PERSIST", o->persistent_rounds);
+    flag("VP_SEG_TINY", o->seg_tiny); flag("VP_PERSIST", o->persistent_rounds);
     flag("VP_POLL", o->poll); flag("VP_PREFETCH_R1", o->prefetch_round1);
     num("VP_FUSE_MIN_LOG", o->fuse_min_log); num("VP_SF_BIG_LOG", o->sf_big_log);
     num("VP_SF3B_GRID", o->sf3b_grid); num("VP_DOT_BLOCKS", o->dot_blocks);
@@ -968,17 +959,13 @@ static int resolve_options(VpOpt *o, const vp_options *user, uint32_t *pinned) {
     num("VP_SPLIT_COST_PERCENT", o->split_cost_percent);
     flag("VP_KERNEL_COPIES", o->kernel_copies);
     flag("VP_FOLD_BRANCHES", o->fold_branches);
-    flag("VP_NTT_SCATTER", o->ntt_scatter);
     flag("VP_NTT_R8", o->ntt_r8);
-    flag("VP_FRI_VO_FUSED", o->fri_vo_fused);
     flag("VP_FAST_INIT", o->interactive_fast_init);
     flag("VP_FUSE_P2", o->fuse_p2);
     flag("VP_LEAF_ASM", o->leaf_asm);
     flag("VP_REAL_PAIRS", o->real_pairs);
     flag("VP_FFT_GKR_BATCHED", o->fft_gkr_batched);
     flag("VP_SPLIT_VU", o->split_vu);
-    flag("VP_FRI_FOLD3", o->fri_fold3);
-    flag("VP_SF3C", o->sf3c);
     flag("VP_PC_TENSOR", o->pc_tensor_pub);
     num("VP_PERSIST_TIMEOUT_MS", o->persistent_timeout_ms);
     num("VP_GRAPH_EXPLICIT", o->graph_explicit);

@@ -112,9 +112,7 @@ int run_sumcheck_seg(vp_ctx *ctx, const FusedSumcheck &sc) {
             }
             a.n_tab = nt; a.total_chunks = chunks;
             const u32 sf3b_grid = (u32) ctx->opt.sf3b_grid;
-            // k_sumfold3c (plan path): a wave per chunk, four to a workgroup
-            const bool wave_chunks = ctx->rec && ctx->opt.sf3c != 0;
-            const u32 grid = std::max<u32>(1, std::min<u32>(wave_chunks ? (chunks + 3) / 4 : chunks, std::min<u32>(sf3b_grid, MAX_BLOCKS)));
+            const u32 grid = std::max<u32>(1, std::min<u32>(chunks, std::min<u32>(sf3b_grid, MAX_BLOCKS)));
             a.part = new_part(k, SFR, grid); a.part_stride = grid * 3;
             if (!a.part) { ctx->err = "partial buffer exhausted"; return VP_ELIMIT; }
             const int sl = !ctx->rec ? prof_begin(ctx, ctx->ln->stream, VP_K_SF, grid, 1, bytes, pairs, (u32) SFR, (u32) k) : -1;
@@ -855,7 +853,7 @@ static int build_plan(vp_ctx *ctx) {
     if (rc != VP_OK) return rc;
     Plan *P = new Plan();
     ctx->plan = P; ctx->plan_vreal = ctx->vreal;
-    P->rounds = rounds; P->sf3c = ctx->opt.sf3c;
+    P->rounds = rounds;
     static const int kind_stream[NK_COUNT] = {0, 0, 0, 0, 0, 1, 2, 3, 0};     // init kernels and the closing launch | fused init + fold | fold | k_seg
     size_t T = 0;
     for (auto &c : rec.chains) T = std::max(T, c.size());
@@ -878,7 +876,6 @@ static int build_plan(vp_ctx *ctx) {
         pos[c].resize(ch.size());
         for (size_t k = 0; k < ch.size(); ++k) pos[c][k] = k < suf ? k : T - (ch.size() - k);
     }
-    const bool xcd_map = ctx->opt.xcd_map != 0;
     std::vector<size_t> cursor(rec.chains.size(), 0);
     std::vector<int> last_node(rec.chains.size(), -1), pending(rec.chains.size(), -1);
     int last_on_stream[4] = {-1, -1, -1, -1};
@@ -922,21 +919,6 @@ static int build_plan(vp_ctx *ctx) {
                     if (std::find(nd.deps.begin(), nd.deps.end(), x) == nd.deps.end()) nd.deps.push_back(x);
                 }
                 pending[c] = (int) P->nodes.size();                  // this node (pushed below); becomes last_node at the end of the step
-            }
-            // VP_XCD_MAP=1 (experiment, off by default): XCD-aware placement of the gather kernels.  The dispatcher deals workgroups
-            // round-robin over the 8 XCDs (w -> XCD w % 8), each with its own L2; with this map workgroup w takes entry
-            // start(w % 8) + w / 8 of the node's (job, block) list, so each XCD walks one contiguous eighth of the target-sorted rows
-            // and neighbouring rows' operand gathers meet in one L2.  Measured SLOWER on the block-structured SHA circuits
-            // (k_light_multi 168 -> 265 us at x64, k_chunks_multi 0.88 -> 2.4 ms at x1024, profiles/r01_j_ab_xcd_*.csv): dealt
-            // round-robin, all XCDs work on the same neighbourhood at the same time and the operand lines one XCD fetched are
-            // served to the others from the Infinity Cache; eight far-apart streams lose that.
-            if (nd.count && xcd_map && (kind == NK_LIGHT || kind == NK_CHUNKS || kind == NK_COMBINE || kind == NK_SFGEN) && nd.grid >= 16) {
-                const u32 G = nd.grid, q = G / 8, r = G % 8;
-                std::vector<BlkMap> tmp(map.begin() + nd.map_off, map.begin() + nd.map_off + G);
-                for (u32 w = 0; w < G; ++w) {
-                    const u32 x = w % 8, k = w / 8;
-                    map[nd.map_off + w] = tmp[x * q + std::min(x, r) + k];
-                }
             }
             if (nd.count) {
                 // A fold node that does not wait for the fold node before it on the fold stream (the first fold launch of the phase-2
@@ -1035,12 +1017,8 @@ static void launch_node(const Plan &P, const PNode &nd, hipStream_t st) {
         case NK_DOTFIN: hipLaunchKernelGGL(k_dotfin_multi, dim3(nd.count), dim3(VP_BLOCK), 0, st, P.d_dotfin + nd.first); break;
         case NK_CHUNKS: hipLaunchKernelGGL(k_chunks_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_chunks + nd.first, mp); break;
         case NK_COMBINE: hipLaunchKernelGGL(k_combine_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_combine + nd.first, mp); break;
-        case NK_SFGEN: if (P.sf3c) hipLaunchKernelGGL(k_sumfold3c_gen_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sfgen + nd.first, mp);
-                       else hipLaunchKernelGGL(k_sumfold3b_gen_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sfgen + nd.first, mp);
-                       break;
-        case NK_SF: if (P.sf3c) hipLaunchKernelGGL(k_sumfold3c_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sf + nd.first, mp);
-                    else hipLaunchKernelGGL(k_sumfold3b_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sf + nd.first, mp);
-                    break;
+        case NK_SFGEN: hipLaunchKernelGGL(k_sumfold3b_gen_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sfgen + nd.first, mp); break;
+        case NK_SF: hipLaunchKernelGGL(k_sumfold3b_multi, dim3(nd.grid), dim3(VP_BLOCK), 0, st, P.d_sf + nd.first, mp); break;
         case NK_SEG: hipLaunchKernelGGL(k_seg_multi, dim3(nd.grid), dim3(VP_SEG_THREADS), 0, st, P.d_seg + nd.first, mp); break;
         default: hipLaunchKernelGGL(k_emit_multi, dim3(nd.count), dim3(VP_EMIT_THREADS), nd.lds, st, P.d_emit + nd.first); break;
     }
@@ -1132,8 +1110,8 @@ static int plan_graph_explicit(vp_ctx *ctx, hipGraph_t *out) {
             case NK_DOTFIN: jobs = P.d_dotfin + nd.first; func = (void *) k_dotfin_multi; grid = nd.count; with_map = false; break;
             case NK_CHUNKS: jobs = P.d_chunks + nd.first; func = (void *) k_chunks_multi; break;
             case NK_COMBINE: jobs = P.d_combine + nd.first; func = (void *) k_combine_multi; break;
-            case NK_SFGEN: jobs = P.d_sfgen + nd.first; func = P.sf3c ? (void *) k_sumfold3c_gen_multi : (void *) k_sumfold3b_gen_multi; break;
-            case NK_SF: jobs = P.d_sf + nd.first; func = P.sf3c ? (void *) k_sumfold3c_multi : (void *) k_sumfold3b_multi; break;
+            case NK_SFGEN: jobs = P.d_sfgen + nd.first; func = (void *) k_sumfold3b_gen_multi; break;
+            case NK_SF: jobs = P.d_sf + nd.first; func = (void *) k_sumfold3b_multi; break;
             case NK_SEG: jobs = P.d_seg + nd.first; func = (void *) k_seg_multi; block = VP_SEG_THREADS; break;
             default: jobs = P.d_emit + nd.first; func = (void *) k_emit_multi; grid = nd.count; block = VP_EMIT_THREADS; lds = nd.lds; with_map = false; break;
         }
@@ -1228,9 +1206,9 @@ static u64 plan_shape_key(const vp_ctx *ctx) {
     auto mix = [&](u64 v) { for (int b = 0; b < 8; ++b) { h ^= (v >> (8 * b)) & 0xff; h *= 1099511628211ull; } };
     mix((u64) ctx->n_layers); mix((u64) ctx->device); mix((u64) ctx->vreal); mix((u64) ctx->opt_pinned);
     mix((u64) ctx->opt.fuse_init); mix((u64) ctx->opt.fuse_dot); mix((u64) ctx->opt.drop_y); mix((u64) ctx->opt.drop_y_round1); mix((u64) ctx->opt.seg_tiny);
-    mix((u64) ctx->opt.sf_big_log); mix((u64) ctx->opt.dot_blocks); mix((u64) ctx->opt.xcd_map);
+    mix((u64) ctx->opt.sf_big_log); mix((u64) ctx->opt.dot_blocks);
     mix((u64) ctx->opt.fuse_combine); mix((u64) ctx->opt.fold_branches); mix((u64) ctx->opt.plan_align); mix((u64) ctx->opt.fuse_min_log);
-    mix((u64) ctx->opt.sf3b_grid); mix((u64) ctx->opt.graph_explicit); mix((u64) ctx->opt.sf3c);
+    mix((u64) ctx->opt.sf3b_grid); mix((u64) ctx->opt.graph_explicit);
     for (int i = 0; i < ctx->n_layers; ++i) {
         const LayerDev &L = ctx->L[i];
         mix(L.size); mix((u64) L.bl); mix((u64) (L.max_dad_bl + 2)); mix((u64) L.n_assert); mix((u64) L.l_n);

@@ -82,7 +82,6 @@ int pc_circle_roots(vp_ctx *ctx, int lm, int lo, const F **out) {
 
 // the pre-split copy of a root table (lz_presplit: what k_ntt8_colsx / k_ntt8_rows multiply with), built once per table
 int pc_presplit(vp_ctx *ctx, const F *src, u32 n, const F **out) {
-#if VP_NTT_PS
     const auto key = std::make_pair((const void *) src, 7777);
     auto it = ctx->pc_rtc.find(key);
     if (it == ctx->pc_rtc.end()) {
@@ -92,9 +91,6 @@ int pc_presplit(vp_ctx *ctx, const F *src, u32 n, const F **out) {
         it = ctx->pc_rtc.emplace(key, t).first;
     }
     *out = it->second;
-#else
-    (void) ctx; (void) n; *out = src;
-#endif
     return VP_OK;
 }
 
@@ -198,9 +194,7 @@ int pc_launch_ntt8(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse
     }
     Ntt8Args b = a;
     b.in = ctx->pc_scr; b.out = out; b.RTn = rt9p; b.do_scale = inverse ? 1 : 0; b.scale = inverse ? host_inv_real(1ull << ln) : f_one();
-#if VP_NTT_PS
     b.scale = lz_presplit(b.scale);
-#endif
     b.in2 = nullptr; b.pair_rows = pair_fwd ? pair_rows : 0; b.e0 = b.pair_rows ? in : nullptr;
     if (b.pair_rows) { b.RT = rtz; b.half_m = nc / 2; }
     {
@@ -220,8 +214,8 @@ static inline u64 split_dft_mults(int l1) { u64 n = 0; const u32 N1 = 1u << l1; 
 static inline u64 ntt_lds_mults(int ln) { const u64 N = 1ull << ln; const int np = (ln & 1) ? (ln - 1) / 2 : std::max(0, ln / 2 - 1); return 3 * (N / 4) * (u64) np; }
 
 // rows transforms of size 2^ln.  forward: `cosets` twisted copies (coset-major output [row][coset][N]); inverse: scaled
-// by 1/N.  Sizes above 2^13 go through k_ntt_split -> k_ntt_lds (N1 x 2^13) -> k_ntt_unsplit and need `scratch`
-// (rows * cosets * N elements, twice).
+// by 1/N.  Sizes above 2^13 go through k_ntt_split -> k_ntt_lds (N1 x 2^13, stored in natural order) and need `scratch`
+// (rows * cosets * N elements, reserved twice).
 int pc_launch_ntt(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse, u32 rows, u32 cosets, u32 in_stride) {
     if (ctx->opt.ntt_r8 && ln >= 13 && ln <= 17 && (u64) rows * (inverse ? 1 : cosets) <= 65535)
         return pc_launch_ntt8(ctx, in, out, ln, lm, inverse, rows, cosets, in_stride);
@@ -243,7 +237,7 @@ int pc_launch_ntt(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse,
     const size_t total = (size_t) rows * nc * N;
     VPCHK(pc_scratch_reserve(ctx, 2 * total));
     if (ctx->pc_dry) { const F *rtp = nullptr; return pc_compact_roots(ctx, lm, PC_SPLIT_LN, &rtp); }
-    F *s1 = ctx->pc_scr, *s2 = ctx->pc_scr + total;
+    F *s1 = ctx->pc_scr;
     SplitArgs sa{};
     sa.in = in; sa.out = s1; sa.RT = ctx->pc_rt; sa.half_m = 1u << (lm - 1); sa.ln = ln; sa.l1 = l1; sa.inverse = inverse;
     sa.in_stride = in_stride; sa.ncoset = nc;
@@ -261,35 +255,21 @@ int pc_launch_ntt(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse,
     }
     // N1 contiguous N2-point transforms per (row, coset): plain (untwisted, unscaled) forward / inverse kernels
     NttArgs a{};
-    a.in = s1; a.out = s2; a.RT = ctx->pc_rt; a.half_m = 1u << (lm - 1); a.lm = lm; a.ln = PC_SPLIT_LN; a.inverse = inverse;
+    a.in = s1; a.RT = ctx->pc_rt; a.half_m = 1u << (lm - 1); a.lm = lm; a.ln = PC_SPLIT_LN; a.inverse = inverse;
     a.in_stride = N2; a.inv_n = f_one();
     VPCHK(pc_compact_roots(ctx, lm, PC_SPLIT_LN, &a.RTp));
     a.half_p = a.RTp == ctx->pc_rt ? a.half_m : 1u << (PC_SPLIT_LN - 1);
-    if (ctx->opt.ntt_scatter) {
-        // the sub-transforms store in natural order themselves (NttArgs::scat_l1): no k_ntt_unsplit pass
-        const u32 long_rows = rows * nc;
-        for (u32 r0 = 0; r0 < long_rows; r0 += 1024) {
-            NttArgs b = a;
-            const u32 nr = std::min<u32>(1024, long_rows - r0);
-            b.in = s1 + (size_t) r0 * N; b.out = out + (size_t) r0 * N;
-            b.scat_l1 = l1; b.scat_rows = nr; b.scat_do_scale = inverse ? 1 : 0; b.scat_scale = inverse ? host_inv_real(1ull << ln) : f_one();
-            const u64 nt = (u64) ((nr + 7) / 8 * 8) << l1;
-            PC_PROF(VP_K_NTT_LDS, nt, (u64) nr << l1, 32ull * N2 * ((u64) nr << l1), ((u64) nr << l1) * ntt_lds_mults(PC_SPLIT_LN) + (inverse ? (u64) N * nr : 0),
-                    hipLaunchKernelGGL(k_ntt_lds, dim3((u32) nt, 1), dim3(1024), sizeof(F) << PC_SPLIT_LN, ctx->stream, b));
-        }
-        return VP_OK;
-    }
-    const u32 sub_rows = rows * nc << l1;
-    for (u32 r0 = 0; r0 < sub_rows; r0 += 32768) {      // gridDim.x limit safety
+    // the sub-transforms store in natural order themselves (NttArgs::scat_l1)
+    const u32 long_rows = rows * nc;
+    for (u32 r0 = 0; r0 < long_rows; r0 += 1024) {
         NttArgs b = a;
-        b.in = s1 + (size_t) r0 * N2; b.out = s2 + (size_t) r0 * N2;
-        const u64 nt = std::min<u32>(32768, sub_rows - r0);
-        PC_PROF(VP_K_NTT_LDS, nt, nt, 32ull * N2 * nt, nt * ntt_lds_mults(PC_SPLIT_LN),
+        const u32 nr = std::min<u32>(1024, long_rows - r0);
+        b.in = s1 + (size_t) r0 * N; b.out = out + (size_t) r0 * N;
+        b.scat_l1 = l1; b.scat_rows = nr; b.scat_do_scale = inverse ? 1 : 0; b.scat_scale = inverse ? host_inv_real(1ull << ln) : f_one();
+        const u64 nt = (u64) ((nr + 7) / 8 * 8) << l1;
+        PC_PROF(VP_K_NTT_LDS, nt, (u64) nr << l1, 32ull * N2 * ((u64) nr << l1), ((u64) nr << l1) * ntt_lds_mults(PC_SPLIT_LN) + (inverse ? (u64) N * nr : 0),
                 hipLaunchKernelGGL(k_ntt_lds, dim3((u32) nt, 1), dim3(1024), sizeof(F) << PC_SPLIT_LN, ctx->stream, b));
     }
-    PC_PROF(VP_K_NTT_UNSPLIT, (u64) (N2 / 64) * rows * nc, (u64) rows * nc, 32ull * N * rows * nc, inverse ? (u64) N * rows * nc : 0,
-            hipLaunchKernelGGL(k_ntt_unsplit, dim3(N2 / 64, rows * nc), dim3(VP_BLOCK), 0, ctx->stream, s2, out, ln, l1,
-                               inverse ? host_inv_real(1ull << ln) : f_one(), inverse));
     return VP_OK;
 }
 
@@ -848,20 +828,14 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     hipEvent_t ev_a = nullptr;
     VPCHK(defer_begin(ctx, &ev_a));
     EvGuard ev_guard{ctx, &ev_a};
-    // the virtual oracle (poly_commit.h:294-318) is consumed by the first fold only: fused into it (k_fri_fold0_vo) unless vo_fused is off
-    const bool vo_fused = ctx->opt.fri_vo_fused != 0;
-    if (!vo_fused)
-        PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 64 * M), 1, 64ull * 64 * M, (u64) 4 * 64 * M,
-                hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) 64 * M)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw,
-                                   ctx->pc_hcw, ctx->pc_small + 1025 + 80, N, ctx->pc_rt, M >> 1, f_make(N, 0), 64u,
-                                   (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr)));
+    // the virtual oracle (poly_commit.h:294-318) is consumed by the first fold only: fused into it (k_fri_fold0_vo / k_fri_fold0_vo3)
     ctx->fri_step = 0; ctx->fri_tree_used = 0;
     ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
     // folds of every level, back to back
     FriLeafArgs la{}; MerkleArgs ma{};
     u32 blocks = 0; size_t cw_off = 0;
     // folds 0, 1, 2 in one pass (k_fri_fold0_vo3): every challenge is here before the first fold starts
-    const bool fold3 = vo_fused && ctx->opt.fri_fold3 && n_steps >= 3 && ln >= 9;       // (E = N / 8 >= 64: a wave per offset)
+    const bool fold3 = n_steps >= 3 && ln >= 9;       // (E = N / 8 >= 64: a wave per offset)
     for (int k = 0; k < n_steps; ++k) {
         const u32 Nk = N >> k, No = Nk >> 1;
         const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + ctx->fri_cw_off[k - 1];
@@ -892,7 +866,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                         (void) hipLaunchKernel(fold3, dim3(grid3), dim3(256), args3, 0, ctx->stream));
             }
         }
-        else if (k == 0 && vo_fused)      // algorithmic bytes: l and h at both positions + the output (q is one slice of a tensor vector, or read like l)
+        else if (k == 0)      // algorithmic bytes: l and h at both positions + the output (q is one slice of a tensor vector, or read like l)
         {
             // x^-1 = w_M^-(32 a + b) = w_N^-a . w_M^-b: the a part from the contiguous order-N circle (lanes run along a), the b part and x^N - 1 =
             // w_32^b - 1 from 2 x 32 per-coset constants (before: one gather per output from the 32 MB order-M table at a stride of 512 bytes —
