@@ -248,8 +248,9 @@ int vp_shard_chains(vp_ctx *, int32_t *owner, double *cost, int capacity, int *n
  * merkle_tree.cpp:7-51): Reed-Solomon encode (rate 1/32) the 64 slices of the input layer, hash the leaf
  * chains with SHA3-256 and build the Merkle tree; returns the root (merkle_root_l).  The codeword and the
  * tree stay in HBM for the later openings.  Needs bit_length(layer 0) >= 7 (vpd_verifier.cpp:115);
- * VP_ELIMIT if a slice is longer than 2^17 elements (input layer of more than 2^23 wires): transforms up to 2^13 run
- * in LDS, longer ones through a register split in front of it.                                         */
+ * VP_ELIMIT above an input layer of 2^25 wires (slices of 2^19 elements; the reference's own commitment indexes its
+ * codeword with int, poly_commit.h:87-166, which overflows at 2^26): transforms up to 2^13 run in LDS, 2^13..2^17 as
+ * two radix-8 LDS passes, 2^18 / 2^19 as one radix-2 / radix-4 step around those passes.                  */
 int vp_commit_private(vp_ctx *, uint8_t root[32]);
 /* prover::commit_public(pub, inner_product_sum, mask, all_sum) (src/prover.cpp:542-546 ->
  * poly_commit_prover::commit_public_array, poly_commit.h:126-349 -> fri::request_init_commit(.., 1)):
@@ -313,7 +314,7 @@ int vp_fft_gkr_cancel(vp_ctx *);
  * the 65th block of every leaf chain of both oracles, all_sum[64], its own virtual oracle and fold on every FRI level (vp_fri_step / vp_fri_commit), the last pair
  * of every opening (vp_fri_open), its final codeword (vp_fri_final_mask) — bit-exact against the reference called directly (tests/golden/pc_masked_*.bin).
  * Limits: ms >= 8 (below that the reference's own transforms read stale scratch, RS_polynomial.cpp:104-133: VP_EINVAL), gap >= 2 (the reference asserts it,
- * poly_commit.h:195: VP_EINVAL) and ms <= 2^16 (the quotient's 2 ms-point transform must be one of this library's: VP_ELIMIT); not on a sharded commitment;
+ * poly_commit.h:195: VP_EINVAL) and ms <= 2^16 (the quotient's 2 ms-point transform is at most 2^17 points: VP_ELIMIT); not on a sharded commitment;
  * vp_commit_public_eq refuses a masked commitment.  vp_commit_private (or a new witness) returns the context to the zero mask.
  * What the reference's VERIFIER makes of it (vpd_verifier.cpp:76-328 with the public mask, oracle/integration/masked_main.cpp): a commitment whose ms is at most a
  * slice's message length 2^(n-6) is accepted; a longer mask is committed exactly as the reference's prover commits it and rejected exactly as the reference's verifier
@@ -445,7 +446,7 @@ int vp_set_profiling(vp_ctx *, int level);
  * launch on every table it holds; closing kernels: the remaining ones), `first_round` the earliest of them (1-based).   */
 enum { VP_K_BETA = 0, VP_K_LIGHT, VP_K_CHUNKS, VP_K_COMBINE, VP_K_DOT, VP_K_DOTFIN, VP_K_SFGEN, VP_K_SF, VP_K_SEG, VP_K_EMIT,
        VP_K_FIXUP, VP_K_NTT_SPLIT, VP_K_NTT_LDS, VP_K_NTT_UNSPLIT, VP_K_LEAF_HASH, VP_K_MERKLE, VP_K_PC_POINTWISE, VP_K_FRI_FOLD,
-       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_COUNT };
+       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_NTT_LONG_SPLIT, VP_K_NTT_LONG_MERGE, VP_K_COUNT };
 /* VP_K_NTT_UNSPLIT is no longer emitted (the long transforms store in natural order themselves); it keeps its value so the others do not move. */
 typedef struct {
     int32_t kind;             /* VP_K_*                                                          */
@@ -471,7 +472,7 @@ int vp_test_beta(vp_ctx *, const vp_F *r, int n, const vp_F *init, vp_F *out);
 int vp_test_sha3(vp_ctx *, const uint8_t *in, uint8_t *out, uint64_t n);
 /* fast_fourier_transform(coefs, coef_len, order) / inverse_fast_fourier_transform(evals, n, n)
  * (RS_polynomial.cpp:26-220), natural order in and out.  order/coef_len must be 1 or 32 for the forward
- * transform (the two shapes the commitment uses); sizes up to 2^17 per transform.                      */
+ * transform (the two shapes the commitment uses); sizes up to 2^19 per transform (VP_ELIMIT above).       */
 int vp_test_fft(vp_ctx *, const vp_F *coefs, int coef_len, int order, int inverse, vp_F *out);
 
 #ifdef __cplusplus

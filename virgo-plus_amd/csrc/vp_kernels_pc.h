@@ -765,6 +765,7 @@ __global__ void __launch_bounds__(VP_BLOCK) k_ntt_split(SplitArgs a) {
 }  // namespace vp
 
 #include "vp_kernels_ntt8.h"
+#include "vp_kernels_ntt_long.h"
 
 // ---- openings (fri::request_init_value_with_merkle, fri.cpp:148-205; fri::request_step_commit, :229-287) ----
 namespace vp {

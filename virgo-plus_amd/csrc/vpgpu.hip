@@ -1867,7 +1867,8 @@ int vp_get_launch_stats(vp_ctx *ctx, vp_launch_stat *out, int capacity, int *n) 
 const char *vp_kernel_name(int kind) {
     static const char *names[VP_K_COUNT] = {"k_beta_half_direct", "k_light_multi", "k_chunks_multi", "k_combine_multi", "k_dot_multi", "k_dotfin_multi",
         "k_sumfold3b_gen_multi", "k_sumfold3b_multi", "k_seg_multi", "k_emit_multi", "k_fixup", "k_ntt_split", "k_ntt_lds", "k_ntt_unsplit",
-        "k_leaf_hash", "k_merkle", "k_pc_pointwise", "k_fri_fold", "k_round", "k_ntt8_cols", "k_ntt8_rows"};
+        "k_leaf_hash", "k_merkle", "k_pc_pointwise", "k_fri_fold", "k_round", "k_ntt8_cols", "k_ntt8_rows",
+        "k_ntt_long_split", "k_ntt_long_merge"};
     return (kind >= 0 && kind < VP_K_COUNT) ? names[kind] : "?";
 }
 

@@ -207,16 +207,64 @@ int pc_launch_ntt8(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse
     return VP_OK;
 }
 
-constexpr int PC_MAX_LN_SPLIT = 17;      // with the register split in front: N1 <= 16
+constexpr int PC_MAX_LN_SPLIT = 17;      // with the register split in front: N1 <= 16; also the largest k_ntt8_cols / k_ntt8_rows pair
+constexpr int PC_MAX_LN_LONG = 19;       // one radix-2 / radix-4 step around the 2^17-point pair (pc_launch_ntt_long)
+constexpr int PC_MAX_N = 25;             // input layer bit length: slices of 2^19 coefficients
+
+// Transforms of 2^18 / 2^19 points (vp_kernels_ntt_long.h): N = N0 x 2^17.  The input rows are dealt into their N0 interleaved sub-sequences
+// (k_ntt_long_split), the unchanged 2^17-point pair transforms rows x N0 of them — forward on the root table of order M / N0, with the same
+// cosets — and k_ntt_long_merge combines each (row, coset)'s N0 sub-transforms with one radix-N0 step into natural order.  Scratch: the pair's
+// own (rows x cosets x N), the sub-transforms' outputs (the same again; none for one coset: they sit in `out` and the merge runs in place)
+// and the dealt input (rows x N).
+int pc_launch_ntt_long(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse, u32 rows, u32 cosets, u32 in_stride) {
+    const int l0 = ln - PC_MAX_LN_SPLIT, ls = PC_MAX_LN_SPLIT;
+    const u32 nc = inverse ? 1 : cosets, N0 = 1u << l0, Ns = 1u << ls;
+    const size_t N = (size_t) 1 << ln, total = (size_t) rows * nc * N;
+    if ((u64) rows * N0 * nc > 65535) { ctx->err = "transform longer than 2^17 points: more than 65535 sub-transforms in one call"; return VP_ELIMIT; }
+    VPCHK(pc_scratch_reserve(ctx, total + (nc > 1 ? total : 0) + (size_t) rows * N));
+    F *C = nc > 1 ? ctx->pc_scr + total : out, *D = ctx->pc_scr + total + (nc > 1 ? total : 0);
+    const F *rt_sub = nullptr, *W = nullptr;
+    VPCHK(pc_compact_roots(ctx, lm, lm - l0, &rt_sub));        // order M / N0, half table
+    VPCHK(pc_circle_roots(ctx, lm, ln, &W));                    // w_N^e, e < N
+    if (!ctx->pc_dry) {
+        const dim3 g(Ns / NTTL_THREADS, rows);
+        PC_PROF(VP_K_NTT_LONG_SPLIT, g.x * g.y, rows, 32ull * N * rows, 0,
+                if (l0 == 1) hipLaunchKernelGGL(k_ntt_long_split<1>, g, dim3(NTTL_THREADS), 0, ctx->stream, in, D, in_stride, ls);
+                else hipLaunchKernelGGL(k_ntt_long_split<2>, g, dim3(NTTL_THREADS), 0, ctx->stream, in, D, in_stride, ls));
+    }
+    // the sub-transforms: the pair and its tables see the order-M / N0 table as the context's root table (its tables are keyed by that table)
+    F *save_rt = ctx->pc_rt; const int save_lm = ctx->pc_lm;
+    ctx->pc_rt = const_cast<F *>(rt_sub); ctx->pc_lm = lm - l0;
+    const int rc = pc_launch_ntt8(ctx, D, C, ls, lm - l0, inverse, rows * N0, cosets, Ns);
+    ctx->pc_rt = save_rt; ctx->pc_lm = save_lm;
+    VPCHK(rc);
+    if (ctx->pc_dry) return VP_OK;
+    NttLongArgs a{};
+    a.in = C; a.out = out; a.W = W; a.RT = ctx->pc_rt; a.half_m = 1u << (lm - 1); a.lsub = ls; a.ncoset = nc;
+    a.scale = lz_presplit(inverse ? host_inv_real(N0) : f_one());
+    const dim3 g(Ns / NTTL_THREADS, rows * nc);
+    const u64 tr = (u64) rows * nc;
+    PC_PROF(VP_K_NTT_LONG_MERGE, g.x * g.y, tr, 32ull * N * tr, tr * Ns * ((N0 - 1) * (!inverse && nc > 1 ? 2 : 1) + (inverse ? N0 : 0)),
+            if (l0 == 1) { if (inverse) hipLaunchKernelGGL((k_ntt_long_merge<1, true>), g, dim3(NTTL_THREADS), 0, ctx->stream, a);
+                           else hipLaunchKernelGGL((k_ntt_long_merge<1, false>), g, dim3(NTTL_THREADS), 0, ctx->stream, a); }
+            else { if (inverse) hipLaunchKernelGGL((k_ntt_long_merge<2, true>), g, dim3(NTTL_THREADS), 0, ctx->stream, a);
+                   else hipLaunchKernelGGL((k_ntt_long_merge<2, false>), g, dim3(NTTL_THREADS), 0, ctx->stream, a); });
+    return VP_OK;
+}
+
 // butterflies of the register DFT of k_ntt_split that multiply (twiddle neither 1 nor iota), per column
 static inline u64 split_dft_mults(int l1) { u64 n = 0; const u32 N1 = 1u << l1; for (int s = l1; s >= 1; --s) for (u32 idx = 0; idx < N1 / 2; ++idx) { const u32 e1 = (idx & ((1u << (s - 1)) - 1)) * (N1 >> s); if (e1 && 4 * e1 != N1) ++n; } return n; }
 // F-multiplications of one k_ntt_lds transform of size 2^ln (radix-4 passes: 3 per 4 points, none in a pass whose twiddles are all 1)
 static inline u64 ntt_lds_mults(int ln) { const u64 N = 1ull << ln; const int np = (ln & 1) ? (ln - 1) / 2 : std::max(0, ln / 2 - 1); return 3 * (N / 4) * (u64) np; }
 
 // rows transforms of size 2^ln.  forward: `cosets` twisted copies (coset-major output [row][coset][N]); inverse: scaled
-// by 1/N.  Sizes above 2^13 go through k_ntt_split -> k_ntt_lds (N1 x 2^13, stored in natural order) and need `scratch`
-// (rows * cosets * N elements, reserved twice).
+// by 1/N.  2^13 .. 2^17: the radix-8 pair (vp_options.ntt_r8, the default) or k_ntt_split -> k_ntt_lds (N1 x 2^13, stored in natural order,
+// rows * cosets * N elements of scratch reserved twice); 2^18 / 2^19: pc_launch_ntt_long, whatever ntt_r8 says.
 int pc_launch_ntt(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse, u32 rows, u32 cosets, u32 in_stride) {
+    if (ln > PC_MAX_LN_SPLIT) {
+        if (ln > PC_MAX_LN_LONG) { ctx->err = "transform longer than 2^19 points"; return VP_ELIMIT; }
+        return pc_launch_ntt_long(ctx, in, out, ln, lm, inverse, rows, cosets, in_stride);
+    }
     if (ctx->opt.ntt_r8 && ln >= 13 && ln <= 17 && (u64) rows * (inverse ? 1 : cosets) <= 65535)
         return pc_launch_ntt8(ctx, in, out, ln, lm, inverse, rows, cosets, in_stride);
     if (ln <= PC_MAX_LN) {
@@ -346,7 +394,7 @@ static int pc_mask_geometry(vp_ctx *ctx, uint64_t n_mask, u32 *ms_out) {
     const u64 ms = M / gap;
     if (ms < 8) { ctx->err = "mask pads to fewer than 8 elements: the reference's transforms of that size read stale scratch (RS_polynomial.cpp:104-133), its commitment is not a function of such a mask"; return VP_EINVAL; }
     if (gap < 2) { ctx->err = "mask longer than half a slice (the reference asserts mask_position_gap != 1, poly_commit.h:195)"; return VP_EINVAL; }
-    if (2 * ms > (1ull << PC_MAX_LN_SPLIT)) { ctx->err = "mask pads to more than 2^16 elements: its quotient needs a transform longer than 2^17 points (not built)"; return VP_ELIMIT; }
+    if (2 * ms > (1ull << PC_MAX_LN_SPLIT)) { ctx->err = "mask pads to more than 2^16 elements: its quotient's transform would be longer than 2^17 points (not supported)"; return VP_ELIMIT; }
     *ms_out = (u32) ms;
     return VP_OK;
 }
@@ -516,7 +564,8 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
     if (n < 7) { ctx->err = "input layer too small for the commitment (bit length < 7)"; return VP_EINVAL; }
     if (ctx->pcs) { if (mask) { ctx->err = "masked commitment: not on a sharded commitment"; return VP_EINVAL; } VPCHK(flush_pending(ctx, (size_t) -1)); return pcs_commit_private(ctx, root); }
     const int ln = n - 6, lm = n - 1;                     // slice_real_ele_cnt = 2^ln, slice_size = 2^lm (poly_commit.h:48-49)
-    if (ln > PC_MAX_LN_SPLIT) { ctx->err = "slice longer than 2^17 elements"; return VP_ELIMIT; }
+    if (n > PC_MAX_N) { ctx->err = "input layer of more than 2^25 wires: the reference's commitment indexes its codeword with int (poly_commit.h:87-166), "
+                                   "which overflows at 2^26 wires"; return VP_ELIMIT; }
     const u32 N = 1u << ln, M = 1u << lm;
     u32 ms = 0;
     if (mask) { VPCHK(pc_mask_geometry(ctx, n_mask, &ms)); VPCHK(flush_pending(ctx, (size_t) -1)); }
@@ -617,7 +666,7 @@ static int pc_warm(vp_ctx *ctx) {
     const int n = ctx->L[0].bl;
     if (n < 7 || ctx->pcs) return VP_OK;
     const int ln = n - 6, lm = n - 1;
-    if (ln > PC_MAX_LN_SPLIT) return VP_OK;
+    if (n > PC_MAX_N) return VP_OK;                        // vp_commit_private refuses it
     const u32 N = 1u << ln, M = 1u << lm;
     VPCHK(pc_root_table(ctx, lm));
     if (!ctx->pc_coef) {
@@ -1044,7 +1093,7 @@ int vp_test_fft(vp_ctx *ctx, const vp_F *coefs, int coef_len, int order, int inv
     if (order != coef_len && order != 32 * coef_len) return VP_EINVAL;
     if (inverse && order != coef_len) return VP_EINVAL;
     int ln = 0; while ((1 << ln) < coef_len) ++ln;
-    if (ln > PC_MAX_LN_SPLIT) return VP_ELIMIT;
+    if (ln > PC_MAX_LN_LONG) return VP_ELIMIT;
     int lo = 0; while ((1 << lo) < order) ++lo;
     VP_ENTER(ctx);
     // private root table of order max(order, 2)

@@ -540,7 +540,8 @@ int vp_pc_set_shard(vp_ctx *ctx, int rank, int world) {
     if (!ctx->evaluated || ctx->L.empty()) { ctx->err = "vp_pc_set_shard: no input layer yet"; return VP_EINVAL; }
     const int ln = ctx->L[0].bl - 6;
     int lw = 0; while ((1 << lw) < world) ++lw;
-    if (world > 1 && (ln - lw < 1 || ln > PC_MAX_LN_SPLIT)) { ctx->err = "vp_pc_set_shard: slice too short for this many ranks"; return VP_ELIMIT; }
+    if (world > 1 && ln - lw < 1) { ctx->err = "vp_pc_set_shard: slice too short for this many ranks"; return VP_ELIMIT; }
+    if (world > 1 && ln > PC_MAX_LN_LONG) { ctx->err = "vp_pc_set_shard: input layer of more than 2^25 wires"; return VP_ELIMIT; }
     VP_ENTER(ctx);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     vp_free_shard_state(ctx);                   // its device arrays stay with the context until the next upload
