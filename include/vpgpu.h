@@ -213,7 +213,7 @@ int vp_gkr_sizes(vp_ctx *, uint64_t *n_tape, uint64_t *n_transcript_bytes);
  * the same assignment on every rank) and leaves all other transcript bytes ZERO: the element-wise u64 sum of the `world`
  * transcripts (one all-reduce over RCCL; the slices are disjoint, so the sum is exact) is the transcript of the unsharded
  * proof, byte for byte.  Every rank holds the whole circuit and witness.  world = 1 restores the unsharded proof.  Only
- * the batched entry point shards; the interactive entry points are unaffected.                                         */
+ * the batched entry point shards; the interactive entry points are unaffected (they shard through vp_set_round_shard).   */
 int vp_set_shard(vp_ctx *, int rank, int world);
 /* On top of vp_set_shard: tables of at least 2^(log2 W' + min_log) entries (W' = the largest power of two <= world) are cut into W' slices by
  * index and slice s is folded by rank s through the rounds that stay inside a slice; the entries the slices end in travel in an export area
@@ -226,6 +226,31 @@ int vp_set_shard(vp_ctx *, int rank, int world);
  * same bound holds for the caller-side u64 sum handed to vp_shard_finish.  vp_set_shard alone (disjoint slices) has no such bound.           */
 int vp_set_shard_split(vp_ctx *, int min_log);
 int vp_shard_finish(vp_ctx *, uint8_t *summed, uint64_t n_bytes, uint64_t *n_transcript_bytes);
+/* The interactive entry points (vp_phase1_init, vp_phase2_init, vp_liu_init, vp_round, vp_finalize) sharded by index over the GPUs of a node.
+ * Opt-in and separate from vp_set_shard: one context per rank, every rank holds the whole circuit and witness and is called with the same
+ * arguments in the same order.  world: a power of two from 1 to 8 (VP_ELIMIT above 8, VP_EINVAL otherwise; rank outside [0, world) is
+ * VP_EINVAL); min_log in [2, 30].  Refused (VP_EINVAL) between an init and its vp_finalize (a sumcheck left unfinished is abandoned by the
+ * next vp_vres, which starts a proof), and on a context with a communicator attached.
+ * world = 1 restores the ordinary context.
+ *   split tables:    at each init a table of len0 >= 2^(log2 world + min_log) entries is cut into `world` slices of S = len0 / world; rank r
+ *                    builds and folds entries [r S, (r+1) S) only (the upper slices of a padded table are short or empty).
+ *   other tables:    built whole on every rank, counted by rank 0 only; add_term likewise.
+ *   vp_round:        the rank's PARTIAL polynomial (canonical limbs).  The sum over the ranks mod p is the round polynomial of the unsharded proof.
+ *   gather:          s_min = log2 of the shortest slice.  At round s_min + 1 the rank packs what its slices have left (two entries of the shortest)
+ *                    and vp_round returns VP_EXCHANGE with one kind-2 collective (all-gather in rank order) pending: vp_shard_exchange_local(ctxs,
+ *                    world), or get / put / done of a caller transport; then call vp_round again with the same challenge.  A call before the
+ *                    exchange returns VP_EXCHANGE again and changes nothing.  From the gather on every rank holds the whole tables: rank 0
+ *                    returns the full polynomial, the others zero.  A phase without a split table runs like that from round 1.
+ *   vp_finalize:     the same claims on every rank.  The resident round kernel starts only once a phase is replicated; round-1 prefetch stays.
+ *                    Ranks that share ONE device must run without it (vp_options.persistent_rounds = 0; the host prover does so): a resident kernel
+ *                    holds its hardware queue until its phase ends, and another rank's launches on the same queue would wait behind it.  So the
+ *                    resident kernel after a gather runs only with one rank per GPU — a configuration the one-GPU tests cannot reach.
+ *   vp_liu_gr:       builds the whole Liu table on a round-sharded context too (it is a verifier-side helper, not a sumcheck of the proof).
+ *   vp_get_round_stats: the algorithmic bytes of the rank's own slices (and of the whole tables it folds).
+ * Ranks in several processes: the caller sums the partial polynomials across processes (mod p), as it sums transcripts for vp_shard_finish.
+ * vp_get_round_shard reports rank, world and whether the current phase still has split tables that have not been gathered.                  */
+int vp_set_round_shard(vp_ctx *, int rank, int world, int min_log);
+int vp_get_round_shard(vp_ctx *, int *rank, int *world, int *split_live);
 /* V_u of the index-split phase-2 chains (src/prover.cpp:494-500: what phase 1's last fold leaves in V, = <eq(r_u, .), V_{i-1}>).  It depends on
  * the tape and the witness only, so it is taken ahead of the proof: every rank adds up its share of the previous layer (1 / W' of it), ONE exchange
  * of 16 bytes per split phase-2 chain completes the sums, and no rank reads a whole layer for a V_u of its own.
@@ -363,7 +388,8 @@ int vp_commit_private_state(vp_ctx *, uint64_t *epoch, int *valid);
 int vp_pc_load_input(vp_ctx *, const vp_F *inputs, uint64_t n_inputs, int bit_length);
 int vp_pc_set_shard(vp_ctx *, int rank, int world);
 int vp_shard_exchange_local(vp_ctx **ctxs, int world);
-/* The same pending collectives through a CALLER-SUPPLIED transport — ranks in different processes without RCCL (more ranks than GPUs in a
+/* vp_shard_exchange_local and the calls below also serve the gather of round-sharded contexts (vp_set_round_shard): one kind-2 collective.
+ * The same pending collectives through a CALLER-SUPPLIED transport — ranks in different processes without RCCL (more ranks than GPUs in a
  * rehearsal, CPU tests over gloo): after VP_EXCHANGE, for i < *n: vp_shard_exchange_info gives kind (1 all-to-all, 2 all-gather) and bytes (per
  * peer / per rank); vp_shard_exchange_get copies the send side to the host (kind 1: world x bytes, peer-major; kind 2: bytes), the caller moves
  * the data, vp_shard_exchange_put copies the world x bytes received back; vp_shard_exchange_done, then call the interrupted function again.   */

@@ -120,6 +120,8 @@ def lib_gpu():
         L.vp_get_options.argtypes = [vp, vp]
         L.vp_get_resident_resumes.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.vp_set_shard_split.argtypes = [vp, ctypes.c_int]
+        L.vp_set_round_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.vp_get_round_shard.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         L.vp_shard_finish.argtypes = [vp, vp, ctypes.c_uint64, vp]
         L.vp_gkr_sizes.argtypes = [vp, vp, vp]
         L.vp_options_default.argtypes = [vp]
@@ -197,6 +199,16 @@ def lib_host():
         L.vph_session_create.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_session_create_opts.restype = vp
         L.vph_session_create_opts.argtypes = [vp, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_session_create_round_sharded.restype = vp
+        L.vph_session_create_round_sharded.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_session_rank_ctx.restype = vp
+        L.vph_session_rank_ctx.argtypes = [vp, ctypes.c_int]
+        L.vph_session_world.argtypes = [vp]
+        L.vph_session_partials.argtypes = [vp, vp, ctypes.c_int]
+        L.vph_session_clear_partials.argtypes = [vp]
+        L.vph_session_drop_rank.argtypes = [vp, ctypes.c_int]
+        L.vph_session_gather_sec.restype = ctypes.c_double
+        L.vph_session_gather_sec.argtypes = [vp]
         L.vph_session_free.argtypes = [vp]
         L.vph_set_profiling.argtypes = [vp, ctypes.c_int]
         L.vph_session_ctx.restype = vp
@@ -586,17 +598,27 @@ PATH_PLAN, PATH_LANES, PATH_SIMPLE = 0, 1, 3
 
 
 class Session:
-    """One prover on one GPU: circuit resident in HBM, witness evaluated on the device."""
+    """One prover on one GPU: circuit resident in HBM, witness evaluated on the device.
 
-    def __init__(self, circuit, device=0, options=None):
+    devices + round_shard_min_log: the interactive sumchecks of one proof sharded by index over len(devices) ranks (1, 2, 4 or 8; a device may
+    repeat), one context per rank (include/vpgpu.h: vp_set_round_shard).  The prove_* calls work unchanged; `device` is then ignored."""
+
+    def __init__(self, circuit, device=0, options=None, devices=None, round_shard_min_log=None):
         err = ctypes.create_string_buffer(512)
+        if (devices is None) != (round_shard_min_log is None):
+            raise ValueError("Session: devices and round_shard_min_log go together")
         self.circuit = circuit
         keep = {}
         for k, v in (options.tuning_env() if options is not None else {}).items():          # internal knobs: the library reads them from the environment at vp_create
             keep[k] = os.environ.get(k)
             os.environ[k] = v
         try:
-            self.h = lib_host().vph_session_create_opts(circuit.h, device, ctypes.byref(options) if options is not None else None, err, len(err))
+            opt = ctypes.byref(options) if options is not None else None
+            if devices is None:
+                self.h = lib_host().vph_session_create_opts(circuit.h, device, opt, err, len(err))
+            else:
+                devs = (ctypes.c_int * max(1, len(devices)))(*devices)
+                self.h = lib_host().vph_session_create_round_sharded(circuit.h, devs, len(devices), int(round_shard_min_log), opt, err, len(err))
         finally:
             for k, v in keep.items():
                 if v is None:
@@ -630,10 +652,39 @@ class Session:
                         "rounds": e.rounds, "first_round": e.first_round, "bytes": e.bytes, "work": e.work, "us": e.us})
         return out
 
-    def round_stats(self):
+    def world(self):
+        """Ranks of a round-sharded session (1 otherwise)."""
+        return int(lib_host().vph_session_world(self.h))
+
+    def rank_ctx(self, rank):
+        """The vp_ctx* of one rank of a round-sharded session (rank 0 = gpu_ctx())."""
+        return ctypes.c_void_p(lib_host().vph_session_rank_ctx(self.h, rank))
+
+    def partials(self):
+        """Round-sharded session: every rank's partial polynomial of every round since the last clear_partials(), as a uint64 array of shape
+        (rounds, world, 3, 2) — canonical limbs {real, img}."""
+        import numpy as np
+        n = lib_host().vph_session_partials(self.h, None, 0)
+        out = np.zeros((max(1, n), 3, 2), dtype=np.uint64)
+        n = lib_host().vph_session_partials(self.h, out.ctypes.data, n)
+        w = self.world()
+        return out[:n].reshape(n // w, w, 3, 2)
+
+    def clear_partials(self):
+        lib_host().vph_session_clear_partials(self.h)
+
+    def drop_rank(self, rank):
+        """Round-sharded session: leave this rank's partial polynomial out of the sum (-1: none) — a test of the verifier's check."""
+        lib_host().vph_session_drop_rank(self.h, rank)
+
+    def gather_sec(self):
+        """Round-sharded session: host seconds spent in the gathers so far."""
+        return float(lib_host().vph_session_gather_sec(self.h))
+
+    def round_stats(self, rank=0):
         """Interactive path, one dict per vp_round since the last prove_interactive() started: {phase, layer, round, how, tables, bytes, us}
-        (include/vpgpu.h: vp_round_stat — algorithmic bytes of the round by SURVEY §8d and the wall time of the call)."""
-        ctx = lib_host().vph_session_ctx(self.h)
+        (include/vpgpu.h: vp_round_stat — algorithmic bytes of the round by SURVEY §8d and the wall time of the call).  rank: of a round-sharded session."""
+        ctx = lib_host().vph_session_rank_ctx(self.h, rank)
         n = ctypes.c_int(0)
         lib_gpu().vp_get_round_stats(ctx, None, 0, ctypes.byref(n))
         arr = (RoundStat * max(1, n.value))()

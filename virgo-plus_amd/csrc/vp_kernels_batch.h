@@ -199,6 +199,11 @@ __global__ void __launch_bounds__(VP_BLOCK)
 k_liu_gather(const u32 *__restrict__ rowptr, const uint8_t *__restrict__ e_q, const u32 *__restrict__ e_g,
              const Half *__restrict__ H, u32 size, F *__restrict__ M) { liu_gather_body(rowptr, e_q, e_g, H, size, M, blockIdx.x); }
 
+// the rows [u0, u0 + size) of the same gather (a round-sharded Liu init builds only its slice): rowptr and M are shifted by u0
+__global__ void __launch_bounds__(VP_BLOCK)
+k_liu_gather_at(const u32 *__restrict__ rowptr, const uint8_t *__restrict__ e_q, const u32 *__restrict__ e_g,
+                const Half *__restrict__ H, u32 size, F *__restrict__ M, u32 u0) { liu_gather_body(rowptr, e_q, e_g, H, size, M, blockIdx.x, u0); }
+
 __global__ void __launch_bounds__(VP_BLOCK)
 k_vres2(Half h, const F *__restrict__ val, u32 size, F *out_dev) {
     __shared__ F lds[4];

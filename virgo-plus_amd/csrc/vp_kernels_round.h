@@ -383,6 +383,10 @@ struct RoundArgs {
     int fold;         // 0: round 1 (tables are read as they are)   1: fold by the previous challenge first
     int has_a;        // 0: the add table is identically zero (Liu phase) and is neither read nor written
     u32 total_pairs;
+    // round-sharded context (vp_set_round_shard): bit j set = table j is folded here but its sums are another rank's to count (a table built
+    // whole on every rank counts on rank 0 only); add_off = 1: add_term is folded and retired as usual but left out of this rank's polynomial
+    unsigned long long skip;
+    int add_off;
     TabDesc t[VP_MAX_TAB];
 };
 
@@ -446,6 +450,7 @@ __device__ __forceinline__ void round_main_body(const RoundArgs &a, u32 bid, u32
             m0 = ld_or_zero(a.inM, i0, vi); m1 = ld_or_zero(a.inM, i0 + 1, vi);
             if (a.has_a) { a0 = ld_or_zero(a.inA, i0, vi); a1 = ld_or_zero(a.inA, i0 + 1, vi); }
         }
+        if ((a.skip >> j) & 1ull) continue;                  // folded above, counted by another rank
         // mult(x)*V(x) + add(x) with X(x) = X0 + x*(X1-X0): Karatsuba on the two evaluation points
         lz_add(X, f_mad_lazy<true>(f_sub_lazy(m1, m0), f_sub_lazy(v1, v0), f_zero()));
         lz_add(Y, f_mad_c<true>(m1, v1, a1));
@@ -481,7 +486,8 @@ __device__ __forceinline__ void round_final_tail(const RoundArgs &a, const F (&a
         at = f_add(at, f_add(f_mul(v, m), ad));
     }
     *add_term = at;
-    const F pa = acc[0], pb = f_sub(f_sub(f_sub(acc[1], acc[0]), acc[2]), at), pc = f_add(acc[2], at);
+    const F atc = a.add_off ? f_zero() : at;                  // the add term of a round-sharded proof is counted once, by rank 0
+    const F pa = acc[0], pb = f_sub(f_sub(f_sub(acc[1], acc[0]), acc[2]), atc), pc = f_add(acc[2], atc);
     poly_dev[0] = pa; poly_dev[1] = pb; poly_dev[2] = pc;
     if (poly_host) {
         poly_host[0] = pa; poly_host[1] = pb; poly_host[2] = pc;
@@ -615,6 +621,45 @@ k_vres(const F *__restrict__ bf, const F *__restrict__ bs, int h1, const F *__re
         acc[0] = f_add(acc[0], f_mul(f_mul(bf[i & mask], bs[i >> h1]), val[i]));
     block_sum<1>(acc, lds);
     if (threadIdx.x == 0) { *out_dev = acc[0]; if (out_host) *out_host = acc[0]; }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Gather of a round-sharded sumcheck (vp_set_round_shard).  Each split table's slice lives at its local offset in the round's input
+// buffers; at the gather round every rank packs the entries its slices have left (V, M and, with an add table, A) into one block,
+// the blocks are all-gathered in rank order, and the unpack writes the `world` blocks into the ordinary (unsharded) layout, so that
+// the round that follows reads exactly what an unsharded context would.  Block of one rank: [comp][table j: n[j] entries].
+// ---------------------------------------------------------------------------------------------------
+struct RsGather {
+    const F *in[3];            // the round's input tables (V, M, A)
+    F *out[3];                 // the same buffers, written in the unsharded layout by the unpack
+    int n_tab, comps, world;   // split tables listed here, 2 or 3 components, ranks
+    u32 N;                     // entries per component of one rank's block (sum of n[])
+    u32 loff[VP_MAX_TAB], goff[VP_MAX_TAB], n[VP_MAX_TAB], valid[VP_MAX_TAB], base[VP_MAX_TAB];
+};
+__device__ __forceinline__ int rs_table_of(const RsGather &g, u32 q) {
+    int j = 0;
+    while (j + 1 < g.n_tab && q >= g.base[j + 1]) ++j;
+    return j;
+}
+__global__ void __launch_bounds__(VP_BLOCK) k_rs_pack(RsGather g, F *__restrict__ send) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= g.N) return;
+    const int j = rs_table_of(g, q);
+    const u32 i = q - g.base[j];
+    for (int c = 0; c < g.comps; ++c) {
+        const F v = i < g.valid[j] ? g.in[c][g.loff[j] + i] : f_zero();      // entries past the slice's valid length: zero, never read after the unpack
+        if (VP_CHK((unsigned long long) g.loff[j] + i < g_vp_chk_cap(), 8, g.loff[j], i, j)) send[(size_t) c * g.N + q] = v;
+    }
+}
+__global__ void __launch_bounds__(VP_BLOCK) k_rs_unpack(RsGather g, const F *__restrict__ recv) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (u32) g.world * g.N) return;
+    const u32 r = q / g.N, p = q - r * g.N;
+    const int j = rs_table_of(g, p);
+    const u32 i = p - g.base[j];
+    const unsigned long long o = (unsigned long long) g.goff[j] + (unsigned long long) r * g.n[j] + i;
+    if (!VP_CHK(o < g_vp_chk_cap(), 8, g.goff[j], r, i)) return;
+    for (int c = 0; c < g.comps; ++c) g.out[c][o] = recv[((size_t) r * g.comps + c) * g.N + p];
 }
 
 __global__ void k_zero_f(F *p, u32 n) {

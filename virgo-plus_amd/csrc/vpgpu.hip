@@ -71,6 +71,22 @@ struct SumcheckState {
 
 struct EvPair { hipEvent_t a, b; u64 bytes; int kind; u32 grid, jobs, rounds, first_round; u64 work; };
 
+// The interactive sumchecks of one proof sharded by index over ranks (vp_set_round_shard).  At each init a table of at least 2^(lw + min_log)
+// entries is split into 2^lw slices and rank `rank` builds and folds slice `rank`; every other table is built whole on every rank and counted by
+// rank 0 only (RoundArgs::skip / add_off).  When the shortest slice is down to two entries (round s_min + 1) the slices' entries are all-gathered
+// (one kind-2 collective, left pending for vp_shard_exchange_local or a caller transport) and the phase goes on replicated.
+struct RoundShard {
+    int rank = 0, world = 1, lw = 0, min_log = 2;
+    bool live = false;                        // the current phase has split tables that have not been gathered yet
+    bool packed = false;                      // the gather round's block is packed; its collective is pending (nx) or done
+    int gather_round = 0;
+    unsigned long long split = 0;             // bit j: table j of the current phase is split
+    u32 goff[VP_MAX_TAB], glen[VP_MAX_TAB], gvalid[VP_MAX_TAB];      // the unsharded layout the gather restores
+    F *send = nullptr, *recv = nullptr; size_t cap = 0;             // device, elements of one block
+    struct X { int kind; const void *send; void *recv; size_t bytes; } x{};
+    int nx = 0;
+};
+
 }  // namespace
 
 struct PcShard;            // commitment sharded over ranks (vpgpu_pc_shard.inc)
@@ -278,6 +294,8 @@ struct vp_ctx {
     std::vector<FixJob> rec_fix;      // record mode: one job per sumcheck, in protocol order
     bool owned(int chain) const { return shard_world <= 1 || chain_owner.empty() || chain_owner[chain] == shard_rank; }
     bool vu_supplied = false; float vu_pre_ms = 0; u64 vu_tape_tag = 0;     // index-split proof, caller-side exchange: vp_shard_vu_set has handed in the summed V_u for the next proof
+    RoundShard *rsh = nullptr;        // non-null while the interactive rounds are sharded by index (vp_set_round_shard, world > 1)
+    bool sc_open = false;             // a sumcheck has been initialised and not finalized yet
 
     F *zero() const { return small; }
     F *one() const { return small + 1; }
@@ -485,6 +503,49 @@ int vp_check_collect(vp_ctx *ctx);
 int do_phase1_init_fast(vp_ctx *ctx, int i);
 int do_phase2_init_fast(vp_ctx *ctx, int i);
 int do_liu_init_fast(vp_ctx *ctx, int i);
+// ... on a round-sharded context (vpgpu_batched.inc): the rows of this rank's slices and of the tables built whole, nothing else
+int do_phase1_init_rs(vp_ctx *ctx, int i);
+int do_phase2_init_rs(vp_ctx *ctx, int i);
+int do_liu_init_rs(vp_ctx *ctx, int i);
+
+// Round-sharded context: cut the tables of the phase just laid out in ctx->sc into this rank's slices (local offsets, lengths and valid
+// counts in sc, the unsharded layout kept for the gather) -> *split, the split mask.  The gather buffers are sized here, inside the init
+// call: vp_round makes no device-wide call (a hipMalloc / hipFree there would wait behind other contexts' resident kernels).
+int rs_split(vp_ctx *ctx, unsigned long long *split) {
+    *split = 0;
+    RoundShard *R = ctx->rsh;
+    if (!R) return VP_OK;
+    SumcheckState &s = ctx->sc;
+    R->live = false; R->packed = false; R->nx = 0; R->split = 0; R->gather_round = 0;
+    int smin = 63;
+    for (int j = 0; j < s.n_tab; ++j) {
+        R->goff[j] = s.off[j]; R->glen[j] = s.len0[j]; R->gvalid[j] = s.valid0[j];
+        const u32 L = s.len0[j];
+        if ((L & (L - 1)) != 0 || (u64) L < (1ull << (R->lw + R->min_log))) continue;
+        const u32 S = L >> R->lw, lo = (u32) R->rank * S;
+        s.off[j] += lo; s.len0[j] = S;
+        s.valid0[j] = s.valid0[j] > lo ? std::min<u32>(S, s.valid0[j] - lo) : 0u;      // the upper slices of a padded table are short or empty
+        R->split |= 1ull << j;
+        int b = 0; while ((1u << b) < S) ++b;
+        smin = std::min(smin, b);
+    }
+    *split = R->split;
+    if (!R->split) return VP_OK;
+    R->live = true; R->gather_round = smin + 1;
+    // the block of the gather round: every split slice's entries as they enter round smin + 1 (shifted by smin - 1), V, M and A if any
+    size_t N = 0;
+    for (int j = 0; j < s.n_tab; ++j) if ((R->split >> j) & 1ull) N += s.len0[j] >> (smin - 1);
+    const size_t blk = (size_t) (s.has_a ? 3 : 2) * N;
+    if (blk > R->cap) {
+        if (R->send) (void) hipFree(R->send);
+        if (R->recv) (void) hipFree(R->recv);
+        R->send = R->recv = nullptr; R->cap = 0;
+        HIPCHK(hipMalloc((void **) &R->send, blk * sizeof(F)));
+        HIPCHK(hipMalloc((void **) &R->recv, blk * R->world * sizeof(F)));
+        R->cap = blk;
+    }
+    return VP_OK;
+}
 
 // Per-round path: wait for the ticket the closing kernel publishes in pinned memory (a few microseconds sooner than the
 // runtime's stream wait, once per round x ~700 rounds per proof); falls back to the stream wait after 2 s or when VP_POLL=0.
@@ -503,6 +564,10 @@ int do_round(vp_ctx *ctx, const F *rp, const F &rv, F *poly_dev, F *poly_host) {
     const int k = s.round + 1;
     RoundArgs a{};
     a.rp = rp; a.rv = rv; a.n_tab = s.n_tab; a.fold = (k >= 2); a.has_a = s.has_a;
+    if (ctx->rsh && ctx->rsh->live && ctx->rsh->rank != 0) {       // before the gather: this rank counts its slices of the split tables only
+        a.skip = ~ctx->rsh->split & (s.n_tab >= 64 ? ~0ull : ((1ull << s.n_tab) - 1));
+        a.add_off = 1;
+    }
     if (k <= 2) { a.inV = s.V0; a.inM = s.M0; a.inA = s.A0; }
     else { F **t = ctx->tab[k & 1]; a.inV = t[0]; a.inM = t[1]; a.inA = t[2]; }       // out of round k-1
     { F **t = ctx->tab[(k + 1) & 1]; a.outV = t[0]; a.outM = t[1]; a.outA = t[2]; }
@@ -565,6 +630,52 @@ int do_finalize(vp_ctx *ctx, const F *rp, const F &rv, F *claims_dev, F *claims_
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, ctx->stream, a, ctx->scalarV(), claims_dev, claims_host,
                        s.phase == 1 ? ctx->Vu() : nullptr, (claims_host && ctx->poll) ? ctx->h_seq : nullptr, ++ctx->seq);
     count_launch(ctx);
+    return VP_OK;
+}
+
+// Gather round of a round-sharded phase (k = s_min + 1 >= 3, inputs in tab[k & 1]): the split tables' entries as they enter round k.
+RsGather rs_gather_args(vp_ctx *ctx, int k) {
+    const RoundShard &R = *ctx->rsh;
+    const SumcheckState &s = ctx->sc;
+    RsGather g{};
+    for (int c = 0; c < 3; ++c) { g.in[c] = ctx->tab[k & 1][c]; g.out[c] = ctx->tab[k & 1][c]; }
+    g.comps = s.has_a ? 3 : 2; g.world = R.world;
+    const int sh = k - 2;
+    u32 N = 0;
+    for (int j = 0; j < s.n_tab; ++j) {
+        if (!((R.split >> j) & 1ull)) continue;
+        const int q = g.n_tab++;
+        g.loff[q] = s.off[j]; g.goff[q] = R.goff[j];
+        g.n[q] = s.len0[j] >> sh;
+        g.valid[q] = (u32) (((u64) s.valid0[j] + (1ull << sh) - 1) >> sh);
+        g.base[q] = N; N += g.n[q];
+    }
+    g.N = N;
+    return g;
+}
+int rs_pack(vp_ctx *ctx) {
+    RoundShard &R = *ctx->rsh;
+    const int k = ctx->sc.round + 1;
+    const RsGather g = rs_gather_args(ctx, k);
+    const size_t blk = (size_t) g.comps * g.N;
+    if (blk > R.cap) { ctx->err = "internal: round-shard gather buffers smaller than the block"; return VP_EINVAL; }      // sized by rs_split
+    hipLaunchKernelGGL(k_rs_pack, dim3(nblk(g.N)), dim3(VP_BLOCK), 0, ctx->stream, g, R.send);
+    count_launch(ctx);
+    VPCHK(check_stream(ctx));                  // the block is complete before any transport reads it
+    R.x = RoundShard::X{2, R.send, R.recv, blk * sizeof(F)};
+    R.nx = 1;
+    return VP_OK;
+}
+// after the all-gather: the world blocks into the unsharded layout, and the phase goes on as an unsharded context's
+int rs_unpack(vp_ctx *ctx) {
+    RoundShard &R = *ctx->rsh;
+    SumcheckState &s = ctx->sc;
+    const int k = s.round + 1;
+    const RsGather g = rs_gather_args(ctx, k);
+    hipLaunchKernelGGL(k_rs_unpack, dim3(nblk((u64) g.world * g.N)), dim3(VP_BLOCK), 0, ctx->stream, g, (const F *) R.recv);
+    count_launch(ctx);
+    for (int j = 0; j < s.n_tab; ++j) { s.off[j] = R.goff[j]; s.len0[j] = R.glen[j]; s.valid0[j] = R.gvalid[j]; }
+    R.live = false; R.packed = false;
     return VP_OK;
 }
 
@@ -798,6 +909,7 @@ int tail_try_launch(vp_ctx *ctx, const F &rv) {
     SumcheckState &s = ctx->sc;
     const int k = s.round + 1;
     if (!ctx->tail_enabled || s.total_rounds - k < 1) return 0;
+    if (ctx->rsh && ctx->rsh->live) return 0;                  // a round-sharded phase takes the resident kernel only once its tables are whole
     PTailArgs a{};
     TailAux &ax = *ctx->h_aux;
     a.aux = ctx->h_aux;
@@ -1062,6 +1174,7 @@ void vp_free_shard_state(vp_ctx *ctx);
 void vp_free_comm(vp_ctx *ctx);
 void vp_free_fgk(vp_ctx *ctx);
 
+static void rs_free(vp_ctx *ctx);
 void vp_destroy(vp_ctx *ctx) {
     if (!ctx) return;
     if (tl_entry_depth == 0) vp_suspend_others(ctx);          // the hipFree calls below synchronise the device
@@ -1072,6 +1185,7 @@ void vp_destroy(vp_ctx *ctx) {
     if (ctx->tail_active) (void) tail_quit(ctx);
     (void) hipStreamSynchronize(ctx->stream);
     vp_free_shard_state(ctx);
+    rs_free(ctx);
     vp_free_comm(ctx);
     vp_free_fgk(ctx);
     if (ctx->gkr_graph) (void) hipGraphExecDestroy(ctx->gkr_graph);
@@ -1489,12 +1603,16 @@ int vp_layer_mle(vp_ctx *ctx, int layer, const vp_F *r, int n, vp_F *out) {
 
 int vp_liu_gr(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, const vp_F *s, const vp_F *r_liu, vp_F *out) {
     if (!ctx || !out) return VP_EINVAL;
+    VP_ENTER(ctx);
     const int keep = ctx->opt.prefetch_round1;
     ctx->opt.prefetch_round1 = 0;                                    // only the table is wanted here: no round is coming
+    RoundShard *rs = ctx->rsh;
+    ctx->rsh = nullptr;                                              // the WHOLE table, also on a round-sharded context (not this rank's slice)
     const int rc = vp_liu_init(ctx, layer, r_u, r_v, s);            // the Liu mult table of this layer, as the prover builds it
+    ctx->rsh = rs;
     ctx->opt.prefetch_round1 = keep;
     if (rc != VP_OK) return rc;
-    ctx->sc.phase = 0;                                               // not a sumcheck in progress
+    ctx->sc.phase = 0; ctx->sc_open = false;                         // not a sumcheck in progress
     LayerDev &pre = ctx->L[layer - 1];
     if (pre.bl && !r_liu) return VP_EINVAL;
     return pred_inner_product(ctx, r_liu, pre.bl, ctx->tab[0][1], (u32) pre.size, out);
@@ -1504,6 +1622,9 @@ int vp_vres(vp_ctx *ctx, const vp_F *r_0, int r_0_size, vp_F *out) {
     if (!ctx || !ctx->evaluated || !out || r_0_size != ctx->L[ctx->n_layers - 1].bl || (r_0_size && !r_0)) return VP_EINVAL;
     VP_ENTER(ctx);
     ctx->rlog.clear();
+    // a new proof starts here: a sumcheck the caller left unfinished is abandoned (vp_set_round_shard accepts the context again)
+    ctx->sc_open = false;
+    if (ctx->rsh) { ctx->rsh->live = false; ctx->rsh->packed = false; ctx->rsh->nx = 0; }
     VPCHK(stage(ctx, 0, r_0, r_0_size));
     LayerDev &T = ctx->L[ctx->n_layers - 1];
     VPCHK(run_beta_half(ctx, ctx->d_tape, T.bl, ctx->one()));
@@ -1521,9 +1642,11 @@ int vp_phase1_init(vp_ctx *ctx, int layer, const vp_F *r_liu, const vp_F *assert
     const u64 off = layer == ctx->n_layers - 1 ? 0 : ctx->rliu_off[layer + 1];
     VPCHK(stage(ctx, off, r_liu, ctx->L[layer].bl));
     VPCHK(stage(ctx, ctx->as_off[layer], assert_random, 1));
-    if (ctx->opt.interactive_fast_init) VPCHK(do_phase1_init_fast(ctx, layer));
+    ctx->sc_open = false;
+    if (ctx->rsh) VPCHK(do_phase1_init_rs(ctx, layer));
+    else if (ctx->opt.interactive_fast_init) VPCHK(do_phase1_init_fast(ctx, layer));
     else VPCHK(do_phase1_init(ctx, layer, ctx->d_tape + off, ctx->d_tape + ctx->as_off[layer]));
-    ctx->rlog_round = 0;
+    ctx->rlog_round = 0; ctx->sc_open = true;
     return round1_prefetch(ctx);
 }
 
@@ -1533,9 +1656,11 @@ int vp_phase2_init(vp_ctx *ctx, int layer, const vp_F *r_u) {
     if (ctx->sc.layer != layer || ctx->L[layer].max_dad_bl == -1) { ctx->err = "phase2 out of order"; return VP_EINVAL; }
     VP_ENTER(ctx);
     VPCHK(stage(ctx, ctx->ru_off[layer], r_u, ctx->L[layer - 1].bl));
-    if (ctx->opt.interactive_fast_init) VPCHK(do_phase2_init_fast(ctx, layer));
+    ctx->sc_open = false;
+    if (ctx->rsh) VPCHK(do_phase2_init_rs(ctx, layer));
+    else if (ctx->opt.interactive_fast_init) VPCHK(do_phase2_init_fast(ctx, layer));
     else VPCHK(do_phase2_init(ctx, layer, ctx->d_tape + ctx->ru_off[layer]));
-    ctx->rlog_round = 0;
+    ctx->rlog_round = 0; ctx->sc_open = true;
     return round1_prefetch(ctx);
 }
 
@@ -1551,9 +1676,11 @@ int vp_liu_init(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v,
             if (!r_v || !r_v[k]) return VP_EINVAL;
             VPCHK(stage(ctx, ctx->rv_off[k], r_v[k], ctx->L[k].dad_bl[layer - 1]));
         }
-    if (ctx->opt.interactive_fast_init) VPCHK(do_liu_init_fast(ctx, layer));
+    ctx->sc_open = false;
+    if (ctx->rsh) VPCHK(do_liu_init_rs(ctx, layer));
+    else if (ctx->opt.interactive_fast_init) VPCHK(do_liu_init_fast(ctx, layer));
     else VPCHK(do_liu_init(ctx, layer));
-    ctx->rlog_round = 0;
+    ctx->rlog_round = 0; ctx->sc_open = true;
     return round1_prefetch(ctx);
 }
 
@@ -1567,6 +1694,8 @@ int vp_round(vp_ctx *ctx, const vp_F *previous_random, vp_F out_poly[3]) {
     const auto t0 = std::chrono::steady_clock::now();
     int how = 0;
     const int rc = vp_round_impl(ctx, previous_random, out_poly, &how);
+    // round-sharded context: once the phase is replicated (gathered, or never split) rank 0 alone returns the polynomial
+    if (rc == VP_OK && ctx->rsh && ctx->rsh->rank != 0 && !ctx->rsh->live) memset(out_poly, 0, 3 * sizeof(vp_F));
     if (rc == VP_OK && ctx->rlog.size() < (size_t) 1 << 16) {
         const int k = ++ctx->rlog_round;
         const SumcheckState &sc = ctx->sc;
@@ -1590,6 +1719,13 @@ static int vp_round_impl(vp_ctx *ctx, const vp_F *previous_random, vp_F out_poly
     // canonical limbs only (header convention); the mailbox of the resident kernel also keeps its sequence tag in bits 61-63 of every word
     if (rv.re >= P61 || rv.im >= P61) { ctx->err = "vp_round: previous_random is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     if (!ctx->r1_pending && ctx->sc.round >= ctx->sc.total_rounds) { ctx->err = "too many rounds"; return VP_EINVAL; }
+    RoundShard *R = ctx->rsh;
+    if (R && R->live && !ctx->r1_pending && ctx->sc.round + 1 == R->gather_round) {
+        // gather round: pack this rank's entries and stop at the all-gather; called again (same challenge) once it is done
+        if (R->nx) { ctx->err = "vp_round: the gather of this round is still pending (vp_shard_exchange_local, or get / put / done)"; return VP_EXCHANGE; }
+        if (!R->packed) { VPCHK(rs_pack(ctx)); R->packed = true; ctx->err = "vp_round: gather pending"; return VP_EXCHANGE; }
+        VPCHK(rs_unpack(ctx));
+    }
     if (ctx->r1_pending) {                                    // round 1 was queued by the init call (it takes no challenge): collect it
         const int how1 = ctx->r1_pending;
         ctx->r1_pending = 0;
@@ -1643,6 +1779,7 @@ int vp_finalize(vp_ctx *ctx, const vp_F *previous_random, vp_F *claims, int n_cl
     if (!ctx || !previous_random || !claims) return VP_EINVAL;
     VP_LOCK(ctx);
     if (ctx->sc.phase == 0 || n_claims != ctx->sc.n_tab) return VP_EINVAL;
+    if (ctx->rsh && ctx->rsh->live) { ctx->err = "vp_finalize: the split tables of this phase have not been gathered"; return VP_EINVAL; }
     HIPCHK(hipSetDevice(ctx->device));
     F rv; memcpy(&rv, previous_random, sizeof(F));
     if (rv.re >= P61 || rv.im >= P61) { ctx->err = "vp_finalize: previous_random is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
@@ -1660,11 +1797,13 @@ int vp_finalize(vp_ctx *ctx, const vp_F *previous_random, vp_F *claims, int n_cl
         VPCHK(rc);
         if (tail_status(ctx) != 0) { ctx->err = "persistent round kernel: protocol error at finalize"; return VP_EHIP; }
         memcpy(claims, ctx->h_pin + 4, (size_t) n_claims * sizeof(F));
+        ctx->sc_open = false;
         return VP_OK;
     }
     VPCHK(do_finalize(ctx, nullptr, rv, ctx->d_tr + ctx->n_tr + 3, ctx->h_pin + 4));
     VPCHK(wait_ticket(ctx));
     memcpy(claims, ctx->h_pin + 4, (size_t) n_claims * sizeof(F));
+    ctx->sc_open = false;
     return VP_OK;
 }
 
@@ -1720,6 +1859,39 @@ int vp_set_shard_split(vp_ctx *ctx, int min_log) {
     ctx->split_lw = (min_log > 0 && ctx->shard_world > 1) ? lw : 0;
     if (min_log > 0) ctx->split_min_log = std::max(9, min_log);      // a slice keeps at least one fold chunk
     ctx->chain_owner.clear(); ctx->chain_cost.clear();
+    return VP_OK;
+}
+
+static void rs_free(vp_ctx *ctx) {
+    if (!ctx->rsh) return;
+    if (ctx->rsh->send) (void) hipFree(ctx->rsh->send);
+    if (ctx->rsh->recv) (void) hipFree(ctx->rsh->recv);
+    delete ctx->rsh;
+    ctx->rsh = nullptr;
+}
+int vp_set_round_shard(vp_ctx *ctx, int rank, int world, int min_log) {
+    if (!ctx) return VP_EINVAL;
+    if (world > 8) { ctx->err = "vp_set_round_shard: at most 8 ranks (one node)"; return VP_ELIMIT; }
+    if (world < 1 || (world & (world - 1)) || rank < 0 || rank >= world) { ctx->err = "vp_set_round_shard: world must be a power of two from 1 to 8 and 0 <= rank < world"; return VP_EINVAL; }
+    if (world > 1 && (min_log < 2 || min_log > 30)) { ctx->err = "vp_set_round_shard: min_log must lie in [2, 30]"; return VP_EINVAL; }
+    VP_ENTER(ctx);
+    if (ctx->sc_open) { ctx->err = "vp_set_round_shard: a sumcheck is in progress"; return VP_EINVAL; }
+    if (vp_comm_attached(ctx)) { ctx->err = "vp_set_round_shard: a communicator is attached (the interactive rounds exchange through the caller)"; return VP_EINVAL; }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    rs_free(ctx);
+    if (world == 1) return VP_OK;
+    ctx->rsh = new RoundShard();
+    RoundShard &R = *ctx->rsh;
+    R.rank = rank; R.world = world; R.min_log = min_log;
+    while ((1 << R.lw) < world) ++R.lw;
+    return VP_OK;
+}
+int vp_get_round_shard(vp_ctx *ctx, int *rank, int *world, int *split_live) {
+    if (!ctx) return VP_EINVAL;
+    VP_LOCK(ctx);
+    if (rank) *rank = ctx->rsh ? ctx->rsh->rank : 0;
+    if (world) *world = ctx->rsh ? ctx->rsh->world : 1;
+    if (split_live) *split_live = (ctx->rsh && ctx->rsh->live) ? 1 : 0;
     return VP_OK;
 }
 

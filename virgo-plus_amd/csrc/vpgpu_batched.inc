@@ -320,6 +320,101 @@ int do_liu_init_fast(vp_ctx *ctx, int i) {
     return VP_OK;
 }
 
+// ---- round-sharded inits (vp_set_round_shard): the rows of this rank's slices, and the tables built whole on every rank ----------------------------
+// Rows [r0, r0 + cnt) of a target-sorted list by direct launches: the light rows on shifted pointers (phase 2: the V gather of those slots only),
+// the heavy rows of the range by their share of the chunk list and its combine — the direct-launch form of init_range / light_range above.
+template <int PHASE>
+int init2_rows_at(vp_ctx *ctx, const Csr &c, InitArgs2 a, u32 r0, u32 cnt) {
+    if (!cnt) return VP_OK;
+    a.rowptr = c.rowptr; a.e_g = c.e_g; a.e_x = c.e_x; a.e_tl = c.e_tl; a.n_rows = c.n_rows;
+    InitArgs2 l = a;
+    l.rowptr = c.rowptr + r0; l.n_rows = cnt; l.M = a.M + r0; l.A = a.A + r0;
+    if (PHASE == 2) { l.V = a.V + r0; l.s_layer = a.s_layer + r0; l.s_idx = a.s_idx + r0; }
+    hipLaunchKernelGGL(k_init2_light<PHASE>, dim3(nblk(cnt)), dim3(VP_BLOCK), 0, ctx->stream, l);
+    count_launch(ctx);
+    const auto &hr = c.h_heavy_row;
+    const u32 h0 = (u32) (std::lower_bound(hr.begin(), hr.end(), r0) - hr.begin()), h1 = (u32) (std::lower_bound(hr.begin(), hr.end(), r0 + cnt) - hr.begin());
+    if (h1 > h0) {
+        const u32 c0 = c.h_heavy_cptr[h0], c1 = c.h_heavy_cptr[h1];
+        hipLaunchKernelGGL(k_init2_chunks<PHASE>, dim3((c1 - c0 + 3) / 4), dim3(VP_BLOCK), 0, ctx->stream, a, c.chunk_beg + c0, c.chunk_end + c0, c1 - c0,
+                           ctx->lane0.chunk_part + 2 * (size_t) c0);
+        hipLaunchKernelGGL(k_init_combine, dim3((h1 - h0 + 3) / 4), dim3(VP_BLOCK), 0, ctx->stream, c.heavy_row + h0, c.heavy_cptr + h0, h1 - h0,
+                           ctx->lane0.chunk_part, a.M, a.A);
+        count_launch(ctx); count_launch(ctx);
+    }
+    return VP_OK;
+}
+int do_phase1_init_rs(vp_ctx *ctx, int i) {
+    LayerDev &cur = ctx->L[i], &pre = ctx->L[i - 1];
+    SumcheckState &s = ctx->sc;
+    s.phase = 1; s.layer = i; s.n_tab = 1; s.round = 0; s.total_rounds = pre.bl; s.has_a = 1;
+    s.off[0] = 0; s.len0[0] = 1u << pre.bl; s.valid0[0] = (u32) pre.size; s.bl[0] = pre.bl;
+    unsigned long long split = 0;
+    VPCHK(rs_split(ctx, &split));
+    if (!split) return do_phase1_init_fast(ctx, i);                 // not split: the ordinary init, on every rank
+    VPCHK(half_tables_of(ctx, cur.job_hg, 1));
+    InitArgs2 a{};
+    a.hg = cur.hg; a.vals = ctx->d_vals; a.valsr = ctx->vreal ? ctx->d_valsr : nullptr; a.gc = cur.gc; a.assert_r = ctx->d_tape + ctx->as_off[i];
+    a.M = ctx->tab[0][1]; a.A = ctx->tab[0][2]; a.vreal = ctx->vreal;
+    VPCHK(init2_rows_at<1>(ctx, cur.c1, a, s.off[0], s.valid0[0]));
+    s.V0 = pre.val; s.M0 = ctx->tab[0][1]; s.A0 = ctx->tab[0][2];       // the slice's entries sit at its global offset (s.off[0])
+    return VP_OK;
+}
+int do_phase2_init_rs(vp_ctx *ctx, int i) {
+    LayerDev &cur = ctx->L[i];
+    SumcheckState &s = ctx->sc;
+    s.phase = 2; s.layer = i; s.n_tab = i; s.round = 0; s.total_rounds = cur.max_dad_bl; s.has_a = 1;
+    for (int j = 0; j < i; ++j) {
+        s.off[j] = cur.t_off[j]; s.len0[j] = cur.t_len[j];
+        s.valid0[j] = (u32) cur.dad_size[j];
+        s.bl[j] = cur.dad_size[j] ? cur.dad_bl[j] : 0;
+    }
+    unsigned long long split = 0;
+    VPCHK(rs_split(ctx, &split));
+    if (!split) return do_phase2_init_fast(ctx, i);
+    VPCHK(half_tables_of(ctx, cur.job_hu, 1));
+    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(64), 0, ctx->stream, ctx->add_term(), 1u);
+    count_launch(ctx);
+    InitArgs2 a{};
+    a.hg = cur.hg; a.hu = cur.hu; a.vals = ctx->d_vals; a.valsr = ctx->vreal ? ctx->d_valsr : nullptr; a.gc = cur.gc; a.assert_r = ctx->d_tape + ctx->as_off[i];
+    a.Vu = ctx->Vu();
+    a.V = ctx->tab[0][0]; a.M = ctx->tab[0][1]; a.A = ctx->tab[0][2];
+    a.s_layer = cur.s_layer; a.s_idx = cur.s_idx; a.vreal = ctx->vreal;
+    // split tables: the slots of this rank's slice; the other tables whole.  Every slot of the range is written, padding included, as the
+    // unsharded init does: a table of ONE entry is retired into add_term at round 1 whatever its valid count (round_final_tail)
+    // Ranges that meet (whole tables side by side, a slice that ends where the next table begins) go out as one range: a few launches per init.
+    u32 r0 = 0, cnt = 0;
+    for (int j = 0; j < i; ++j) {
+        const u32 b = std::min<u32>(s.off[j], cur.c2.n_rows), n = std::min<u32>(s.len0[j], cur.c2.n_rows - b);
+        if (!n) continue;
+        if (cnt && b == r0 + cnt) { cnt += n; continue; }
+        VPCHK(init2_rows_at<2>(ctx, cur.c2, a, r0, cnt));
+        r0 = b; cnt = n;
+    }
+    VPCHK(init2_rows_at<2>(ctx, cur.c2, a, r0, cnt));
+    s.V0 = ctx->tab[0][0]; s.M0 = ctx->tab[0][1]; s.A0 = ctx->tab[0][2];
+    return VP_OK;
+}
+int do_liu_init_rs(vp_ctx *ctx, int i) {
+    LayerDev &cur = ctx->L[i], &pre = ctx->L[i - 1];
+    SumcheckState &s = ctx->sc;
+    s.phase = 3; s.layer = i; s.n_tab = 1; s.round = 0; s.total_rounds = pre.bl; s.has_a = 0;
+    s.off[0] = 0; s.len0[0] = 1u << pre.bl; s.valid0[0] = (u32) pre.size; s.bl[0] = pre.bl;
+    unsigned long long split = 0;
+    VPCHK(rs_split(ctx, &split));
+    if (!split) return do_liu_init_fast(ctx, i);
+    VPCHK(half_tables_of(ctx, cur.job_liu0, cur.job_liun));
+    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(64), 0, ctx->stream, ctx->add_term(), 1u);
+    count_launch(ctx);
+    const u32 u0 = s.off[0], n = s.valid0[0];
+    if (n) {
+        hipLaunchKernelGGL(k_liu_gather_at, dim3(nblk(n)), dim3(VP_BLOCK), 0, ctx->stream, cur.lrow + u0, cur.l_q, cur.l_g, cur.liu_H, n, ctx->tab[0][1] + u0, u0);
+        count_launch(ctx);
+    }
+    s.V0 = pre.val; s.M0 = ctx->tab[0][1]; s.A0 = ctx->tab[0][2];
+    return VP_OK;
+}
+
 }  // namespace
 
 extern "C" {

@@ -553,8 +553,52 @@ int vp_pc_set_shard(vp_ctx *ctx, int rank, int world) {
     return VP_OK;
 }
 
+// the pending collective i of a context: the commitment shard's, else the round shard's gather (vp_set_round_shard)
+static bool pending_x(vp_ctx *ctx, int i, int *kind, const void **send, void **recv, size_t *bytes, int *world) {
+    if (ctx->pcs && ctx->pcs->nx) {
+        if (i < 0 || i >= ctx->pcs->nx) return false;
+        const PcShard::X &x = ctx->pcs->x[i];
+        *kind = x.kind; *send = x.send; *recv = x.recv; *bytes = x.bytes; *world = ctx->pcs->world;
+        return true;
+    }
+    if (ctx->rsh && ctx->rsh->nx) {
+        if (i != 0) return false;
+        const RoundShard::X &x = ctx->rsh->x;
+        *kind = x.kind; *send = x.send; *recv = x.recv; *bytes = x.bytes; *world = ctx->rsh->world;
+        return true;
+    }
+    return false;
+}
+// the gather of round-sharded contexts of one process: rank src's block into slot src of every rank's receive buffer, on the receiver's stream
+static int rs_exchange_local(vp_ctx **ctxs, int world) {
+    vp_ctx *ctx = ctxs[0];
+    const int nx = ctx->rsh->nx;
+    const size_t bytes = ctx->rsh->x.bytes;
+    for (int r = 0; r < world; ++r)
+        if (ctxs[r]->rsh->nx != nx || (nx && ctxs[r]->rsh->x.bytes != bytes)) { ctx->err = "vp_shard_exchange_local: ranks are at different gathers"; return VP_EINVAL; }
+    if (!nx) return VP_OK;
+    for (int dst = 0; dst < world; ++dst) {
+        vp_ctx *d = ctxs[dst];
+        HIPCHK(hipSetDevice(d->device));
+        for (int src = 0; src < world; ++src)
+            HIPCHK(hipMemcpyAsync((char *) d->rsh->x.recv + (size_t) src * bytes, ctxs[src]->rsh->x.send, bytes, hipMemcpyDeviceToDevice, d->stream));
+    }
+    for (int dst = 0; dst < world; ++dst) {
+        HIPCHK(hipSetDevice(ctxs[dst]->device));
+        HIPCHK(hipStreamSynchronize(ctxs[dst]->stream));
+    }
+    for (int r = 0; r < world; ++r) ctxs[r]->rsh->nx = 0;
+    return VP_OK;
+}
+
 int vp_shard_exchange_local(vp_ctx **ctxs, int world) {
     if (!ctxs || world < 1) return VP_EINVAL;
+    {   // round-sharded contexts (vp_set_round_shard) with their gather pending and no commitment collective in the way
+        bool rs = true;
+        for (int r = 0; r < world; ++r)
+            if (!ctxs[r] || !ctxs[r]->rsh || ctxs[r]->rsh->world != world || ctxs[r]->rsh->rank != r || (ctxs[r]->pcs && ctxs[r]->pcs->nx)) rs = false;
+        if (rs && ctxs[0]->rsh->nx) return rs_exchange_local(ctxs, world);
+    }
     for (int r = 0; r < world; ++r) if (!ctxs[r] || !ctxs[r]->pcs || ctxs[r]->pcs->world != world || ctxs[r]->pcs->rank != r) return VP_EINVAL;
     const int nx = ctxs[0]->pcs->nx;
     for (int r = 0; r < world; ++r) if (ctxs[r]->pcs->nx != nx) { ctxs[0]->err = "vp_shard_exchange_local: ranks are at different collectives"; return VP_EINVAL; }
@@ -584,33 +628,39 @@ int vp_shard_pending(vp_ctx *ctx, int *n) {
     if (!ctx || !n) return VP_EINVAL;
     VP_LOCK(ctx);
     *n = ctx->pcs ? ctx->pcs->nx : 0;
+    if (!*n && ctx->rsh) *n = ctx->rsh->nx;
     return VP_OK;
 }
 int vp_shard_exchange_info(vp_ctx *ctx, int i, int *kind, uint64_t *bytes) {
     if (!ctx || !kind || !bytes) return VP_EINVAL;
     VP_LOCK(ctx);
-    if (!ctx->pcs || i < 0 || i >= ctx->pcs->nx) return VP_EINVAL;
-    *kind = ctx->pcs->x[i].kind; *bytes = ctx->pcs->x[i].bytes;
+    const void *snd; void *rcv; size_t b; int w;
+    if (!pending_x(ctx, i, kind, &snd, &rcv, &b, &w)) return VP_EINVAL;
+    *bytes = b;
     return VP_OK;
 }
 int vp_shard_exchange_get(vp_ctx *ctx, int i, void *host_send) {
-    if (!ctx || !ctx->pcs || i < 0 || i >= ctx->pcs->nx || !host_send) return VP_EINVAL;
+    if (!ctx || !host_send) return VP_EINVAL;
+    int kind, world; const void *snd; void *rcv; size_t bytes;
+    { VP_LOCK(ctx); if (!pending_x(ctx, i, &kind, &snd, &rcv, &bytes, &world)) return VP_EINVAL; }
     VP_ENTER(ctx);
-    const PcShard::X &x = ctx->pcs->x[i];
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(host_send, x.send, x.kind == 1 ? (size_t) ctx->pcs->world * x.bytes : x.bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host_send, snd, kind == 1 ? (size_t) world * bytes : bytes, hipMemcpyDeviceToHost));
     return VP_OK;
 }
 int vp_shard_exchange_put(vp_ctx *ctx, int i, const void *host_recv) {
-    if (!ctx || !ctx->pcs || i < 0 || i >= ctx->pcs->nx || !host_recv) return VP_EINVAL;
+    if (!ctx || !host_recv) return VP_EINVAL;
+    int kind, world; const void *snd; void *rcv; size_t bytes;
+    { VP_LOCK(ctx); if (!pending_x(ctx, i, &kind, &snd, &rcv, &bytes, &world)) return VP_EINVAL; }
     VP_ENTER(ctx);
-    const PcShard::X &x = ctx->pcs->x[i];
-    HIPCHK(hipMemcpy(x.recv, host_recv, (size_t) ctx->pcs->world * x.bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rcv, host_recv, (size_t) world * bytes, hipMemcpyHostToDevice));
     return VP_OK;
 }
 int vp_shard_exchange_done(vp_ctx *ctx) {
     if (!ctx) return VP_EINVAL;
     VP_LOCK(ctx);
+    if (ctx->pcs && ctx->pcs->nx) { ctx->pcs->nx = 0; return VP_OK; }
+    if (ctx->rsh) { ctx->rsh->nx = 0; return VP_OK; }
     if (!ctx->pcs) return VP_EINVAL;
     ctx->pcs->nx = 0;
     return VP_OK;

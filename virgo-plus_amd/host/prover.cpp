@@ -1,5 +1,7 @@
 #include "prover.hpp"
 #include <atomic>
+#include <condition_variable>
+#include <mutex>
 #include <functional>
 #include <memory>
 #include <chrono>
@@ -24,9 +26,102 @@ void prover::check(int rc, const char *what) {
 // src/prover.cpp:14-25.  The circuit tables are flattened to structure-of-arrays and copied to HBM once;
 // the constructor then evaluates the circuit on the device like the reference's constructor does on the
 // CPU.  A violated assert gate surfaces as an exception instead of the reference's exit(EXIT_FAILURE).
-prover::prover(const layeredCircuit &cir, int device, const vp_options *options) : C(cir) {
-    int rc = vp_create_with_options(device, options, &ctx);
-    if (rc != VP_OK) throw std::runtime_error("vp_create failed (" + std::to_string(rc) + "): no usable MI355X / HIP device");
+// Worker threads of a round-sharded prover: rank 0 runs on the calling thread, rank r >= 1 on worker r.  A worker spins on the job counter for a
+// while after each job (a round is tens of microseconds; waking a blocked thread costs about as much) and then blocks on the condition variable.
+struct prover::Pool {
+    const int n;
+    std::vector<std::thread> th;
+    std::mutex mu; std::condition_variable cv;
+    std::atomic<unsigned long long> gen{0}; std::atomic<int> left{0};
+    const std::function<void(int)> *job = nullptr;
+    bool quit = false;
+    explicit Pool(int n_) : n(n_) { for (int r = 1; r < n; ++r) th.emplace_back([this, r] { loop(r); }); }
+    ~Pool() {
+        { std::lock_guard<std::mutex> lk(mu); quit = true; gen.fetch_add(1); }
+        cv.notify_all();
+        for (auto &t : th) t.join();
+    }
+    void loop(int r) {
+        unsigned long long seen = 0;
+        for (;;) {
+            for (int spin = 0; gen.load(std::memory_order_acquire) == seen; ++spin) {
+                if (spin < 20000) { std::this_thread::yield(); continue; }
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return gen.load(std::memory_order_acquire) != seen; });
+            }
+            seen = gen.load(std::memory_order_acquire);
+            if (quit) return;
+            (*job)(r);
+            left.fetch_sub(1, std::memory_order_acq_rel);
+        }
+    }
+    void run(const std::function<void(int)> &fn) {
+        job = &fn;
+        left.store(n - 1, std::memory_order_release);
+        { std::lock_guard<std::mutex> lk(mu); gen.fetch_add(1, std::memory_order_acq_rel); }
+        cv.notify_all();
+        fn(0);
+        while (left.load(std::memory_order_acquire)) std::this_thread::yield();
+    }
+};
+
+int prover::onRanks(const std::function<int(int, vp_ctx *)> &fn, const char *what) {
+    if (rk.size() <= 1) { const int rc = fn(0, ctx); if (rc != VP_EXCHANGE) check(rc, what); return rc; }
+    std::vector<int> rc(rk.size(), VP_OK);
+    pool->run([&](int r) { rc[r] = fn(r, rk[r]); });
+    int n_x = 0;
+    for (size_t r = 0; r < rk.size(); ++r) {
+        if (rc[r] == VP_EXCHANGE) { ++n_x; continue; }
+        if (rc[r] != VP_OK) throw std::runtime_error(std::string(what) + " failed on rank " + std::to_string(r) + " (" + std::to_string(rc[r]) + "): " + vp_last_error(rk[r]));
+    }
+    if (n_x && n_x != (int) rk.size()) throw std::runtime_error(std::string(what) + ": only some ranks stopped at the gather");
+    return n_x ? VP_EXCHANGE : VP_OK;
+}
+
+prover::prover(const layeredCircuit &cir, int device, const vp_options *options) : C(cir) { upload({device}, options); }
+
+prover::prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options) : C(cir) {
+    if (devices.empty() || devices.size() > 8 || (devices.size() & (devices.size() - 1)))
+        throw std::invalid_argument("round-sharded prover: 1, 2, 4 or 8 ranks");
+    // Ranks that share a device run without the resident round kernel: it holds the hardware queue it was launched on until its phase ends, and
+    // another rank's launches that the runtime put on the same queue would wait behind it while the prover waits for their answer (each such
+    // round would stall until the kernel's time-out).  Ranks on GPUs of their own keep it.
+    std::vector<int> sorted(devices);
+    std::sort(sorted.begin(), sorted.end());
+    vp_options shared{};
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+        if (options) shared = *options;
+        else vp_options_default(&shared);
+        shared.persistent_rounds = 0;
+        options = &shared;
+    }
+    upload(devices, options);
+    try {
+        for (size_t r = 0; r < rk.size(); ++r) {
+            const int rc = vp_set_round_shard(rk[r], (int) r, (int) rk.size(), min_log);
+            if (rc != VP_OK) throw std::runtime_error("vp_set_round_shard failed (" + std::to_string(rc) + "): " + vp_last_error(rk[r]));
+        }
+    } catch (...) {
+        pool.reset();
+        for (vp_ctx *c : rk) vp_destroy(c);
+        rk.clear(); ctx = nullptr;
+        throw;
+    }
+}
+
+void prover::upload(const std::vector<int> &devices, const vp_options *options) {
+    for (int device : devices) {
+        vp_ctx *c = nullptr;
+        int rc = vp_create_with_options(device, options, &c);
+        if (rc != VP_OK) {
+            for (vp_ctx *o : rk) vp_destroy(o);
+            rk.clear();
+            throw std::runtime_error("vp_create failed (" + std::to_string(rc) + "): no usable MI355X / HIP device");
+        }
+        rk.push_back(c);
+    }
+    ctx = rk[0];
+    if (rk.size() > 1) pool.reset(new Pool((int) rk.size()));
     const int n = C.size;
     const bool dbg = getenv("VP_DEBUG_UPLOAD") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
@@ -123,24 +218,32 @@ prover::prover(const layeredCircuit &cir, int device, const vp_options *options)
     // witness in HBM) before the exception leaves, e.g. when evaluate() reports a violated assert gate (VP_EASSERT)
     try {
         const double t0 = since();
-        check(vp_circuit_upload(ctx, n, desc.data()), "vp_circuit_upload");
+        for (vp_ctx *c : rk) {
+            const int rc = vp_circuit_upload(c, n, desc.data());
+            if (rc != VP_OK) throw std::runtime_error("vp_circuit_upload failed (" + std::to_string(rc) + "): " + vp_last_error(c));
+        }
         const double t1 = since();
         evaluate();
         if (dbg) fprintf(stderr, "[vp upload] flatten %.3f s  vp_circuit_upload %.3f s  evaluate %.3f s\n", t0, t1 - t0, since() - t1);
     } catch (...) {
-        vp_destroy(ctx);
+        pool.reset();
+        for (vp_ctx *c : rk) vp_destroy(c);
+        rk.clear();
         ctx = nullptr;
         throw;
     }
 }
 
-prover::~prover() { vp_destroy(ctx); }
+prover::~prover() {
+    pool.reset();
+    for (vp_ctx *c : rk) vp_destroy(c);
+}
 
 void prover::evaluate() {      // src/prover.cpp:27-91
     const layer &L0 = C.circuit[0];
     std::vector<vp_F> in(L0.size);
     for (u64 g = 0; g < L0.size; ++g) { F x((long long) L0.gates[g].u); in[g].real = x.real; in[g].img = x.img; }
-    check(vp_evaluate(ctx, in.data(), in.size()), "vp_evaluate");
+    onRanks([&](int, vp_ctx *c) { return vp_evaluate(c, in.data(), in.size()); }, "vp_evaluate");
 }
 
 void prover::init() {          // src/prover.cpp:131-155
@@ -156,7 +259,8 @@ void prover::init() {          // src/prover.cpp:131-155
 F prover::Vres(const std::vector<F>::const_iterator &r_0, int r_0_size) {       // src/prover.cpp:99-129
     prove_timer.start();
     F out;
-    check(vp_vres(ctx, r_0_size ? cF(&*r_0) : nullptr, r_0_size, mF(&out)), "vp_vres");
+    // every rank (one small launch): it also starts each rank's log of round stats afresh; rank 0's value is the message
+    onRanks([&](int r, vp_ctx *c) { F o; const int rc = vp_vres(c, r_0_size ? cF(&*r_0) : nullptr, r_0_size, mF(&o)); if (r == 0) out = o; return rc; }, "vp_vres");
     prove_timer.stop();
     return out;
 }
@@ -174,7 +278,7 @@ void prover::sumcheckInit() { --sumcheckLayerId; }                              
 void prover::sumcheckInitPhase1(const F &assert_random) {                        // src/prover.cpp:189-280
     prove_timer.start();
     init_timer.start();
-    check(vp_phase1_init(ctx, sumcheckLayerId, cF(r_liu.data()), cF(&assert_random)), "vp_phase1_init");
+    onRanks([&](int, vp_ctx *c) { return vp_phase1_init(c, sumcheckLayerId, cF(r_liu.data()), cF(&assert_random)); }, "vp_phase1_init");
     init_timer.stop();
     round = 0;
     prove_timer.stop();
@@ -183,7 +287,7 @@ void prover::sumcheckInitPhase1(const F &assert_random) {                       
 void prover::sumcheckInitPhase2() {                                              // src/prover.cpp:282-367
     prove_timer.start();
     init_timer.start();
-    check(vp_phase2_init(ctx, sumcheckLayerId, cF(r_u.data())), "vp_phase2_init");
+    onRanks([&](int, vp_ctx *c) { return vp_phase2_init(c, sumcheckLayerId, cF(r_u.data())); }, "vp_phase2_init");
     init_timer.stop();
     round = 0;
     prove_timer.stop();
@@ -194,7 +298,7 @@ void prover::sumcheckInitLiu(std::vector<F>::const_iterator s) {                
     std::vector<const vp_F *> rv(C.size, nullptr);
     for (int k = sumcheckLayerId; k < C.size; ++k) if (!r_v[k].empty()) rv[k] = cF(r_v[k].data());
     init_timer.start();
-    check(vp_liu_init(ctx, sumcheckLayerId, cF(r_u.data()), rv.data(), cF(&*s)), "vp_liu_init");
+    onRanks([&](int, vp_ctx *c) { return vp_liu_init(c, sumcheckLayerId, cF(r_u.data()), rv.data(), cF(&*s)); }, "vp_liu_init");
     init_timer.stop();
     round = 0;
     prove_timer.stop();
@@ -208,7 +312,23 @@ quadratic_poly prover::sumcheckUpdate(const F &previous_random, std::vector<F> &
     static const bool dbg_rounds = getenv("VP_DEBUG_ROUNDS") != nullptr;      // development aid: per-message latency on stderr
     const auto t_dbg = std::chrono::steady_clock::now();
     round_timer.start();
-    check(vp_round(ctx, cF(&previous_random), mF(p)), "vp_round");
+    if (rk.size() <= 1) check(vp_round(ctx, cF(&previous_random), mF(p)), "vp_round");
+    else {
+        std::vector<std::array<F, 3>> part(rk.size());
+        auto call = [&](int r, vp_ctx *c) { return vp_round(c, cF(&previous_random), mF(part[r].data())); };
+        if (onRanks(call, "vp_round") == VP_EXCHANGE) {         // every rank stopped at the gather of its split tables: exchange, same challenge again
+            gather_timer.start();
+            check(vp_shard_exchange_local(rk.data(), (int) rk.size()), "vp_shard_exchange_local");
+            gather_timer.stop();
+            if (onRanks(call, "vp_round") != VP_OK) throw std::runtime_error("vp_round: gather still pending after the exchange");
+        }
+        p[0] = p[1] = p[2] = F_ZERO;
+        for (size_t r = 0; r < rk.size(); ++r) {
+            part_log.push_back(part[r]);
+            if ((int) r == drop_rank) continue;
+            for (int q = 0; q < 3; ++q) p[q] = p[q] + part[r][q];
+        }
+    }
     round_timer.stop();
     if (dbg_rounds) fprintf(stderr, "[round] layer %d round %d: %.2f us\n", sumcheckLayerId, round, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_dbg).count());
     prove_timer.stop();
@@ -223,7 +343,7 @@ void prover::sumcheckFinalize1(const F &previousRandom, F &claim) {             
     prove_timer.start();
     if (round) r_u[round - 1] = previousRandom;
     fin_timer.start();
-    check(vp_finalize(ctx, cF(&previousRandom), mF(&claim), 1), "vp_finalize");
+    finalizeAll(previousRandom, &claim, 1, "vp_finalize");
     fin_timer.stop();
     prove_timer.stop();
     proof_size += sizeof(F);
@@ -234,7 +354,7 @@ void prover::sumcheckFinalize2(const F &previousRandom, std::vector<F>::iterator
     if (round) r_v[sumcheckLayerId][round - 1] = previousRandom;
     std::vector<F> tmp(sumcheckLayerId);
     fin_timer.start();
-    check(vp_finalize(ctx, cF(&previousRandom), mF(tmp.data()), sumcheckLayerId), "vp_finalize");
+    finalizeAll(previousRandom, tmp.data(), sumcheckLayerId, "vp_finalize");
     fin_timer.stop();
     for (int i = 0; i < sumcheckLayerId; ++i) claims[i] = tmp[i];
     proof_size += sizeof(F) * sumcheckLayerId;
@@ -244,8 +364,19 @@ void prover::sumcheckFinalize2(const F &previousRandom, std::vector<F>::iterator
 void prover::sumcheckLiuFinalize(const F &previousRandom, F &claim) {            // src/prover.cpp:518-521
     if (round) r_liu[round - 1] = previousRandom;
     fin_timer.start();
-    check(vp_finalize(ctx, cF(&previousRandom), mF(&claim), 1), "vp_finalize");
+    finalizeAll(previousRandom, &claim, 1, "vp_finalize");
     fin_timer.stop();
+}
+
+// every rank finalizes; a round-sharded proof's ranks must agree on every claim
+void prover::finalizeAll(const F &previousRandom, F *claims, int n, const char *what) {
+    if (rk.size() <= 1) { check(vp_finalize(ctx, cF(&previousRandom), mF(claims), n), what); return; }
+    std::vector<std::vector<F>> cl(rk.size(), std::vector<F>(std::max(1, n)));
+    onRanks([&](int r, vp_ctx *c) { return vp_finalize(c, cF(&previousRandom), mF(cl[r].data()), n); }, what);
+    for (size_t r = 1; r < rk.size(); ++r)
+        for (int q = 0; q < n; ++q)
+            if (cl[r][q] != cl[0][q]) throw std::runtime_error(std::string(what) + ": rank " + std::to_string(r) + " returned a different claim than rank 0");
+    for (int q = 0; q < n; ++q) claims[q] = cl[0][q];
 }
 
 prover::hhash_digest prover::commit_private() {      // src/prover.cpp:524-530 (mask = one zero element)

@@ -4,7 +4,10 @@
 // libvpgpu.so (include/vpgpu.h); no arithmetic on tables happens on the host and there is no CPU
 // fallback: construction throws if the device library cannot run.
 #pragma once
+#include <array>
 #include <chrono>
+#include <functional>
+#include <memory>
 #include <stdexcept>
 #include <vector>
 
@@ -27,6 +30,10 @@ private:
 class prover {
 public:
     explicit prover(const layeredCircuit &cir, int device = 0, const vp_options *options = nullptr);   // options: include/vpgpu.h (NULL = shipped defaults)
+    // One proof's interactive sumchecks sharded by index over W = devices.size() ranks (vp_set_round_shard, min_log): one context per rank, the same
+    // device may be listed several times.  Every sumcheck method runs on all ranks at once (one worker thread per rank), sums the partial round
+    // polynomials mod p, performs the gather when a rank stops at it, and checks that the ranks' claims agree.  Vres and the commitment run on rank 0.
+    prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options = nullptr);
     ~prover();
     prover(const prover &) = delete;
     prover &operator=(const prover &) = delete;
@@ -100,11 +107,29 @@ public:
     void gkrSizes(u64 &n_tape, u64 &n_transcript_bytes);
     std::vector<F> layerValues(int layer);
     vp_ctx *context() { return ctx; }
+    int world() const { return (int) rk.size(); }
+    vp_ctx *rankContext(int r) { return (r >= 0 && r < (int) rk.size()) ? rk[r] : nullptr; }
+    // round-sharded prover: every rank's partial polynomial of every round since the last clearPartials (test and profiling aid), and a rank whose
+    // partial is left out of the sum (-1: none; a test of the verifier's sumcheck check)
+    const std::vector<std::array<F, 3>> &partials() const { return part_log; }
+    void clearPartials() { part_log.clear(); }
+    void setDropRank(int r) { drop_rank = r; }
+    double gatherTime() const { return gather_timer.elapse_sec(); }
     vp_stats stats();
 
 private:
     quadratic_poly sumcheckUpdate(const F &previous_random, std::vector<F> &r_arr);
     void check(int rc, const char *what);
+    void upload(const std::vector<int> &devices, const vp_options *options);
+    // run fn(rank, context) on every rank concurrently and throw on the first failure (VP_EXCHANGE is returned to the caller when every rank stopped there)
+    int onRanks(const std::function<int(int, vp_ctx *)> &fn, const char *what);
+    void finalizeAll(const F &previousRandom, F *claims, int n, const char *what);
+    struct Pool;
+    std::unique_ptr<Pool> pool;
+    std::vector<vp_ctx *> rk;                            // every rank's context (rk[0] == ctx)
+    std::vector<std::array<F, 3>> part_log;
+    int drop_rank = -1;
+    timer gather_timer;
 
     const layeredCircuit &C;
     vp_ctx *ctx = nullptr;

@@ -97,6 +97,30 @@ vph_session *vph_session_create_opts(vph_circuit *c, int device, const vp_option
         return nullptr;
     }
 }
+vph_session *vph_session_create_round_sharded(vph_circuit *c, const int *devices, int world, int min_log, const vp_options *opt, char *err, int errlen) {
+    if (!c || !devices || world < 1) { set_err(err, errlen, "null circuit / device list"); return nullptr; }
+    try {
+        std::unique_ptr<vph_session> s(new vph_session());
+        s->circ = c;
+        s->p.reset(new prover(c->c, std::vector<int>(devices, devices + world), min_log, opt));
+        return s.release();
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return nullptr;
+    }
+}
+void *vph_session_rank_ctx(vph_session *s, int rank) { return s ? (void *) s->p->rankContext(rank) : nullptr; }
+int vph_session_world(vph_session *s) { return s ? s->p->world() : 0; }
+int vph_session_partials(vph_session *s, vp_F *out, int capacity) {
+    if (!s) return -1;
+    const auto &pl = s->p->partials();
+    for (size_t i = 0; i < pl.size() && (int) i < capacity; ++i)
+        for (int q = 0; q < 3; ++q) { out[3 * i + q].real = pl[i][q].real; out[3 * i + q].img = pl[i][q].img; }
+    return (int) pl.size();
+}
+void vph_session_clear_partials(vph_session *s) { if (s) s->p->clearPartials(); }
+void vph_session_drop_rank(vph_session *s, int rank) { if (s) s->p->setDropRank(rank); }
+double vph_session_gather_sec(vph_session *s) { return s ? s->p->gatherTime() : 0; }
 void vph_session_free(vph_session *s) { delete s; }
 int vph_set_profiling(vph_session *s, int level) { return vp_set_profiling(s->p->context(), level); }
 void *vph_session_ctx(vph_session *s) { return s ? (void *) s->p->context() : nullptr; }

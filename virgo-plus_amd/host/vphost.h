@@ -47,6 +47,18 @@ void vph_session_free(vph_session *);
 int vph_set_profiling(vph_session *, int level);
 /* the vp_ctx behind the session's prover (for the measurement calls of include/vpgpu.h: vp_get_launch_stats, ...) */
 void *vph_session_ctx(vph_session *);
+/* A session whose interactive sumchecks are sharded by index over world = 1, 2, 4 or 8 ranks (vp_set_round_shard, min_log): one context per entry
+ * of `devices` (the same device may repeat).  vph_prove_interactive, vph_prove_full and vph_prove_and_verify_full work on it unchanged; the prover
+ * sums the ranks' partial round polynomials.  vph_session_ctx is rank 0's context, vph_session_rank_ctx(s, r) rank r's (per-rank stats). */
+vph_session *vph_session_create_round_sharded(vph_circuit *, const int *devices, int world, int min_log, const vp_options *opt, char *err, int errlen);
+void *vph_session_rank_ctx(vph_session *, int rank);
+int vph_session_world(vph_session *);
+/* round-sharded session: every rank's partial polynomial of every round since the last clear (rank-major per round, 3 elements each; returns the
+ * number of entries = rounds x world), a rank whose partial the prover leaves out of the sum (-1: none), host seconds spent in the gathers */
+int vph_session_partials(vph_session *, vp_F *out, int capacity);
+void vph_session_clear_partials(vph_session *);
+void vph_session_drop_rank(vph_session *, int rank);
+double vph_session_gather_sec(vph_session *);
 /* circuitValue[layer] copied back (tests).                                                             */
 int vph_layer_values(vph_session *, int layer, uint64_t *out_pairs, uint64_t n);
 
