@@ -490,7 +490,20 @@ const char *vp_kernel_name(int kind);
 
 /* ---- primitives exported for parity tests (thin wrappers over the device functions) -------------- */
 /* out[i] = a[i] op b[i], op: 0 add, 1 sub, 2 mul (device arithmetic of fieldElement.cpp:34-104); op 3: out[i] = a[i] b[i] + a[i+1] b[i+1] (cyclic) through the
- * one-reduction two-product form the FRI fold kernel uses (canonical inputs).                           */
+ * one-reduction two-product form the FRI fold kernel uses (canonical inputs).
+ * Ops 4 .. 38 run the lazy forms (vp_field.h, vp_kernels_ntt8.h, vp_kernels_round.h) on RAW words: nothing is canonicalised on the way in or out, so a
+ * caller can hand in limbs anywhere in a form's stated range and see a weakly reduced result as it is.  c = a[i+1] (cyclic), y = b[i].re:
+ *    4 f_mad_lazy<false>(a,b,c)    5 f_mad_lazy<true>(a,b,c)    6 f_mad_c<false>(a,b,c)    7 f_mad_c<true>(a,b,c)
+ *    8 f_mad31_rb<true>(a,y,c)     9 f_mad31c_rb<false>(a,y,c)  10 f_mad31c_rb<true>(a,y,c)   (4 .. 10 with the GKR kernels' VP_MADSHIFT form of c31_add)
+ *   11 f_mul_plain(a,b)           12 f_half(a)                  13 f_neg(a)
+ *   14 .. 20 = 4 .. 10 in the OTHER form of c31_add;  21 = 11 with the multiplier-shift form (f_mad31c<false, true>(a, b, 0))
+ *   22 lz_mul(a,b) (a the canonical root)    23 lz_mul_ps(lz_presplit(a), b)    24 / 25 lz_mul_w8<false / true>(a)
+ *   26 / 27 lz_mul_w4<false / true, 2p>(a)   28 / 29 lz_mul_w4<false / true, 4p>(a)   30 lz_canon(a)   31 m_fold of either limb of a
+ *   32 / 33 lz_dft8<false / true>, 34 / 35 lz_dft4<false / true>, 36 lz_dft2 on consecutive groups of 8 / 4 / 2 elements of a (n a multiple of the
+ *      group, VP_EINVAL otherwise)
+ *   37 out[i] = wave_sum63 over the 64 elements i belongs to, every lane's word (lane 63 holds the total); elements at and beyond n count as zero
+ *   38 block_sum<3> of (a[i], b[i], (a[i].im, b[i].re)) over each 256 elements: the three totals in out[256 k], out[256 k + 1], out[256 k + 2] as far
+ *      as these are below n, zeros in the block's other elements                                         */
 int vp_test_field(vp_ctx *, int op, const vp_F *a, const vp_F *b, vp_F *out, uint64_t n);
 /* initBetaTable(out, n, r, init) (src/utils.cpp:29-45): out has 2^n entries.                           */
 int vp_test_beta(vp_ctx *, const vp_F *r, int n, const vp_F *init, vp_F *out);

@@ -7,13 +7,18 @@ MUL, ADD, SUB, ANTISUB, NAAB, ANTINAAB, INPUT, MULC, ADDC, XOR, NOT, COPY = rang
 P = (1 << 61) - 1
 
 
-def make(seed, layer_sizes, with_asserts=True):
+def make(seed, layer_sizes, with_asserts=True, values=None, real_consts=False):
+    """values: draw the inputs and the Mulc / Addc constants from this sequence instead of uniformly from [0, p) (edge values: tests/test_gpu_field_edges.py);
+    real_consts: constants (c, 0), so that a circuit with real inputs has real values throughout.  The defaults leave every seed's circuit as it was."""
     rng = np.random.default_rng(seed)
+
+    def draw():
+        return int(rng.integers(0, P)) if values is None else int(values[int(rng.integers(0, len(values)))])
     ty, l, u, v, c, a = [], [], [], [], [], []
     for i, n in enumerate(layer_sizes):
         for g in range(n):
             if i == 0:
-                ty.append(INPUT); l.append(-1); u.append(int(rng.integers(0, P))); v.append(0); c.append((0, 0)); a.append(0)
+                ty.append(INPUT); l.append(-1); u.append(draw()); v.append(0); c.append((0, 0)); a.append(0)
                 continue
             if with_asserts and g == n - 1:
                 # x - x == 0: a legal assert gate (both operands the same wire of layer i-1)
@@ -28,7 +33,7 @@ def make(seed, layer_sizes, with_asserts=True):
             else:
                 ll = int(rng.integers(0, i))
                 l.append(ll); v.append(int(rng.integers(0, layer_sizes[ll])))
-            c.append((int(rng.integers(0, P)), int(rng.integers(0, P))) if t in (MULC, ADDC) else (0, 0))
+            c.append(((draw(), 0) if real_consts else (draw(), draw())) if t in (MULC, ADDC) else (0, 0))
             a.append(0)
     return (np.array(layer_sizes, np.uint64), np.array(ty, np.int32), np.array(l, np.int32), np.array(u, np.uint64),
             np.array(v, np.uint64), np.array(c, np.uint64).reshape(-1, 2), np.array(a, np.uint8))

@@ -42,6 +42,15 @@ def test_long_fft_vs_oracle(vp, ob, ctx, ln, ratio):
     assert lib.vp_test_fft(ctx, c.ctypes.data, 1 << 20, 1 << 20, 0, out.ctypes.data) == VP_ELIMIT     # 2^20 points: above any slice
 
 
+@pytest.mark.parametrize("mode", [1, 32, 0])
+@pytest.mark.parametrize("ln", [18, 19])
+def test_long_fft_structured_inputs_vs_oracle(vp, ob, ctx, ln, mode):
+    """The radix-2 (2^18) and radix-4 (2^19) merges of vp_kernels_ntt_long.h on constant / spike / alternating / real / imaginary vectors (the lazy
+    butterflies at differences of exactly 2p: tests/test_gpu_field_edges.py), forward at ratio 1 and 32 and the inverse against orc_ifft on the same input."""
+    from test_gpu_field_edges import structured_fft_case
+    structured_fft_case(vp, ob, ctx, ln, mode)
+
+
 @pytest.mark.parametrize("lg", [18, 19])
 def test_fft_gkr_long_vs_oracle(vp, ob, ctx, lg):
     """fft_gkr (fft_circuit_GKR.cpp:833-849) at lg = n - 6 of the n = 24 / 25 commitments, against the oracle's restatement (same checks as at lg <= 17)."""

@@ -145,15 +145,6 @@ VP_HD F f_mad31c(const F &a, const F &b, const F &c) {
     const Sp31 nbi = split31(2 * P61 - b.im);
     return f_make(dot2_31c<WEAK, MS>(ar, br, ai, nbi, c.re), dot2_31c<WEAK, MS>(ar, bi, ai, br, c.im));
 }
-// x0 + r*d for a challenge r that the whole launch shares (the fold of a bookkeeping table): the two partial products that carry -r.im take
-// the negated SCALAR p - r.im (wave-uniform, computed once on the scalar unit) instead of a per-element negation of d.im — a 64-bit subtract
-// and one split less per fold than f_mad31c(r, d, x0), and d.im may exceed 2p.  r canonical; limbs of d < 2^62 + 8, of x0 < 2^61 + 8.
-template <bool WEAK, bool MS = false>
-VP_HD F f_fold31(const F &r, const F &d, const F &x0) {
-    const Sp31 rr = split31(r.re), ri = split31(r.im), nri = split31(P61 - r.im);       // p - r.im in [1, p]: hi < 2^30, as dot2_31c wants
-    const Sp31 dr = split31(d.re), di = split31(d.im);
-    return f_make(dot2_31c<WEAK, MS>(rr, dr, nri, di, x0.re), dot2_31c<WEAK, MS>(rr, di, ri, dr, x0.im));
-}
 // The same two forms for a REAL second factor (b = (y, 0)): each limb of a*b + c is ONE product, eight multiplier instructions per
 // F-multiply instead of sixteen.  Circuit values of a circuit with real inputs and constants are real (every gate of
 // src/prover.cpp:27-91 maps reals to reals), so the first round of every sumcheck takes this path when vp_evaluate found no

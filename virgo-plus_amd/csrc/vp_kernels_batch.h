@@ -266,7 +266,7 @@ __device__ __forceinline__ F shfl_xor_F(const F &x, int mask) {
 // (Round 3, built and measured: M and A entries travelling through LDS weakly reduced (<= p + 3) between the rounds of a launch, so that the
 // conditional subtraction disappears from two of the three folds.  The lazy difference of two such values needs an offset that is a multiple
 // of p AND at least p + 3, i.e. 2p, and then exceeds the 2^62 the split multiply takes; with the extra fold that brings it back the net gain
-// is ~3 % of the fold arithmetic.  Not kept.  Nor the fold through f_fold31, the negated challenge limb instead of a negated difference: HISTORY.md.)
+// is ~3 % of the fold arithmetic.  Not kept: HISTORY.md.)
 template <bool WEAK> __device__ __forceinline__ F sf_fold(const F &r, const F &d, const F &x0) { return f_mad_c<WEAK>(r, d, x0); }
 template <bool HAS_A>
 __device__ __forceinline__ void sf_pair_step(const F &v0, const F &v1, const F &m0, const F &m1, const F &a0, const F &a1,

@@ -43,7 +43,9 @@ __device__ __forceinline__ F lz_canon(const F &x) {                      // weak
     u64 a = lz_fold(x.re), b = lz_fold(x.im);
     return f_make(a >= P61 ? a - P61 : a, b >= P61 ? b - P61 : b);
 }
-// root (canonical) x data (limbs < 2^62): weak product, limbs < 2^61 + 4
+// root (canonical) x data: weak product, limbs < 2^61 + 4.  Data limbs in [0, 2p] = [0, 2^62 - 2], f_mad31c's range and not a unit more: the real limb takes
+// -x.im as 2p - x.im, which wraps for x.im = 2^62 - 1 (measured: tests/test_gpu_field_edges.py).  Every caller passes limbs < 2^61 + 8 (canonical loads or the
+// folded outputs of the butterflies below).  lz_mul_ps negates on the root side and takes any limb < 2^62.
 __device__ __forceinline__ F lz_mul(const F &root, const F &x) { return f_mad31c<true, false>(root, x, f_make(0, 0)); }
 // Round 6: the same product with a PRE-SPLIT root.  The root tables of k_ntt8_colsx / k_ntt8_rows hold each limb w = hi 2^31 + lo as the word (hi << 32) | lo
 // (still 16 bytes per root: lz_presplit): the two 31-bit halves are the two dwords of the register pair, no instruction splits them; and the negated imaginary

@@ -887,3 +887,82 @@ k_fri_fold_one(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, con
 }
 }  // namespace vp
 #undef f_mul
+
+// ---- parity-test helpers for the lazy forms (vp_test_field ops 4 ..): thin wrappers, operands and results RAW (nothing is canonicalised here) ----
+namespace vp {
+// the multiply ops in one MS instantiation; c = a[i + 1] (cyclic)
+template <bool MS> __device__ __forceinline__ F test_field_mad(int k, const F &a, const F &b, const F &c) {
+    switch (k) {
+    case 0: return f_mad31<false, MS>(a, b, c);              // f_mad_lazy<false>
+    case 1: return f_mad31<true, MS>(a, b, c);               // f_mad_lazy<true>
+    case 2: return f_mad31c<false, MS>(a, b, c);             // f_mad_c<false>
+    case 3: return f_mad31c<true, MS>(a, b, c);              // f_mad_c<true>
+    case 4: return f_mad31_rb<true, MS>(a, b.re, c);
+    case 5: return f_mad31c_rb<false, MS>(a, b.re, c);
+    case 6: return f_mad31c_rb<true, MS>(a, b.re, c);
+    default: return f_mad31c<false, MS>(a, b, f_make(0, 0));  // f_mul_plain (MS = false) / f_mul of the GKR kernels (MS = true)
+    }
+}
+__global__ void __launch_bounds__(256) k_test_field_lazy(int op, const F *__restrict__ a, const F *__restrict__ b, F *__restrict__ o, u64 n) {
+    const u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F x = a[i], y = b[i], z = a[i + 1 < n ? i + 1 : 0];
+    constexpr bool ms = VP_MADSHIFT != 0;
+    if (op >= 4 && op <= 10) { o[i] = test_field_mad<ms>(op - 4, x, y, z); return; }            // as the GKR kernels instantiate them
+    if (op >= 14 && op <= 20) { o[i] = test_field_mad<!ms>(op - 14, x, y, z); return; }         // the other form of c31_add
+    switch (op) {
+    case 11: o[i] = f_mul_plain(x, y); return;
+    case 12: o[i] = f_half(x); return;
+    case 13: o[i] = f_neg(x); return;
+    case 21: o[i] = test_field_mad<true>(7, x, y, z); return;
+    case 22: o[i] = lz_mul(x, y); return;
+    case 23: o[i] = lz_mul_ps(lz_presplit(x), y); return;
+    case 24: o[i] = lz_mul_w8<false>(x); return;
+    case 25: o[i] = lz_mul_w8<true>(x); return;
+    case 26: o[i] = lz_mul_w4<false, LZ_P2>(x); return;
+    case 27: o[i] = lz_mul_w4<true, LZ_P2>(x); return;
+    case 28: o[i] = lz_mul_w4<false, LZ_P4>(x); return;
+    case 29: o[i] = lz_mul_w4<true, LZ_P4>(x); return;
+    case 30: o[i] = lz_canon(x); return;
+    default: o[i] = f_make(m_fold(x.re), m_fold(x.im)); return;                                 // 31
+    }
+}
+// ops 32 .. 36: one thread per group of G consecutive elements (n is a multiple of G: vp_test_field checks)
+__global__ void __launch_bounds__(256) k_test_field_dft(int op, const F *__restrict__ a, F *__restrict__ o, u64 groups) {
+    const u64 g = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= groups) return;
+    if (op <= 33) {
+        F u[8];
+        for (int m = 0; m < 8; ++m) u[m] = a[8 * g + m];
+        if (op == 32) lz_dft8<false>(u); else lz_dft8<true>(u);
+        for (int m = 0; m < 8; ++m) o[8 * g + m] = u[m];
+    } else if (op <= 35) {
+        F u[4];
+        for (int m = 0; m < 4; ++m) u[m] = a[4 * g + m];
+        if (op == 34) lz_dft4<false>(u); else lz_dft4<true>(u);
+        for (int m = 0; m < 4; ++m) o[4 * g + m] = u[m];
+    } else {
+        F u[2] = {a[2 * g], a[2 * g + 1]};
+        lz_dft2(u);
+        o[2 * g] = u[0]; o[2 * g + 1] = u[1];
+    }
+}
+// op 37: o[i] = wave_sum63 of the wave of element i, every lane's word (lane 63 holds the wave total).  op 38: block_sum<3> of (a[i], b[i], (a[i].im, b[i].re));
+// thread 0 leaves the three block totals in o[256 blk .. 256 blk + 2], as far as they are below n; the block's other elements are zero.  Elements at and
+// beyond n count as zero; every thread of the last block stays in the reduction.
+__global__ void __launch_bounds__(256) k_test_field_sum(int op, const F *__restrict__ a, const F *__restrict__ b, F *__restrict__ o, u64 n) {
+    __shared__ F lds[12];
+    const u64 i = (u64) blockIdx.x * blockDim.x + threadIdx.x;
+    const F x = i < n ? a[i] : f_zero(), y = i < n ? b[i] : f_zero();
+    if (op == 37) {
+        const F s = wave_sum63(x);
+        if (i < n) o[i] = s;
+        return;
+    }
+    F acc[3] = {x, y, f_make(x.im, y.re)};
+    block_sum<3>(acc, lds);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 3; ++k) if (i + k < n) o[i + k] = acc[k];
+    } else if (threadIdx.x >= 3 && i < n) o[i] = f_zero();
+}
+}  // namespace vp

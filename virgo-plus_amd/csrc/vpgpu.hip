@@ -2045,7 +2045,9 @@ const char *vp_kernel_name(int kind) {
 }
 
 int vp_test_field(vp_ctx *ctx, int op, const vp_F *a, const vp_F *b, vp_F *out, uint64_t n) {
-    if (!ctx || !a || !b || !out || op < 0 || op > 3) return VP_EINVAL;
+    if (!ctx || !a || !b || !out || op < 0 || op > 38) return VP_EINVAL;
+    const unsigned group = op == 32 || op == 33 ? 8 : op == 34 || op == 35 ? 4 : op == 36 ? 2 : 1;      // the butterflies take whole groups
+    if (n % group) return VP_EINVAL;
     if (n == 0) return VP_OK;
     VP_ENTER(ctx);
     F *da = nullptr, *db = nullptr, *dout = nullptr;
@@ -2054,7 +2056,11 @@ int vp_test_field(vp_ctx *ctx, int op, const vp_F *a, const vp_F *b, vp_F *out, 
     HIPCHK(hipMalloc((void **) &dout, n * sizeof(F)));
     HIPCHK(hipMemcpy(da, a, n * sizeof(F), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db, b, n * sizeof(F), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_test_field, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream, op, da, db, dout, (u64) n);
+    const dim3 grid((unsigned) ((n / group + 255) / 256));
+    if (op <= 3) hipLaunchKernelGGL(k_test_field, grid, dim3(256), 0, ctx->stream, op, da, db, dout, (u64) n);
+    else if (op <= 31) hipLaunchKernelGGL(k_test_field_lazy, grid, dim3(256), 0, ctx->stream, op, da, db, dout, (u64) n);
+    else if (op <= 36) hipLaunchKernelGGL(k_test_field_dft, grid, dim3(256), 0, ctx->stream, op, da, dout, (u64) (n / group));
+    else hipLaunchKernelGGL(k_test_field_sum, grid, dim3(256), 0, ctx->stream, op, da, db, dout, (u64) n);
     int rc = check_stream(ctx);
     if (rc == VP_OK && hipMemcpy(out, dout, n * sizeof(F), hipMemcpyDeviceToHost) != hipSuccess) rc = VP_EHIP;
     (void) hipFree(da); (void) hipFree(db); (void) hipFree(dout);
