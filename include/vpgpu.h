@@ -121,6 +121,7 @@ int vp_plan_tuning_set(vp_ctx *, const int32_t v[6]);
  * (lib/virgo/src/poly_commit.cpp:4-13, fri.cpp:13-34, RS_polynomial.cpp:9-16).  vp_warm(ctx, VP_WARM_COMMITMENT), after vp_evaluate and before the first
  * prover call, does the same here: the order-M root table, the transforms' circles and twist table, their scratch, every codeword / tree / FRI buffer, the fold
  * constants and a pinned staging area for vp_commit_public's vector (which is then uploaded in pieces at the bus's speed) exist when vp_commit_private starts.
+ * It also sets up the records of the query phase (vp_fri_open_many / vp_fri_query) for 33 x (2 + n - 6) openings.
  * Optional: every call still sets up what it finds missing.  VP_EINVAL before vp_evaluate.                                                              */
 #define VP_WARM_COMMITMENT 1u
 #define VP_WARM_FFT_GKR 2u          /* the ~20 device arrays of vp_fft_gkr at lg = input bit length - 6 (the size lib/virgo's verifier runs it at) */
@@ -309,6 +310,24 @@ int vp_fri_final(vp_ctx *, vp_F *final_code);
  * mask pair) = the two codeword entries of the leaf per slice; path: depth+1 digests, path[k] = sibling at height k,
  * path[depth] = the leaf digest (the reference's com_hhash layout).  *path_len receives depth + 1.           */
 int vp_fri_open(vp_ctx *, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len);
+/* The query phase in one device pass.  vp_fri_open_many answers n requests (oracle[i], leaf[i]) with ONE launch (k_pc_open_many), one device-to-host
+ * copy and one synchronise per 4096 requests; request i's answer is byte for byte what vp_fri_open(ctx, oracle[i], leaf[i], ...) returns:
+ * values + 130 i, paths + path_stride i (path_stride bytes per request, >= 32 x the longest path asked for), path_len[i] digests.  Requests may
+ * repeat; n == 0 is VP_OK and does nothing; more than 2^16 requests is VP_ELIMIT.  Every request is validated before anything is launched, by the
+ * rules of vp_fri_open (oracle committed, level reached, leaf in range, capacity): one bad request fails the whole call with the status
+ * vp_fri_open gives that request, and nothing is written to the caller's buffers.  On a sharded commitment (vp_pc_set_shard) a rank answers the
+ * requests it owns (owner = (leaf >> 5) mod world for the position-sharded oracles, every rank for the tail levels) and reports path_len[i] = 0
+ * for the others, whose output bytes it leaves untouched: the ranks' answers merge into one buffer.  With vp_set_profiling(1) every launch is
+ * one k_pc_open_many entry of vp_get_launch_stats whose bytes are the values and digests it gathers.                                          */
+int vp_fri_open_many(vp_ctx *, int n, const int32_t *oracle, const uint64_t *leaf, vp_F *values /* n x 130 */, uint8_t *paths, int path_stride,
+                     int32_t *path_len /* n */);
+/* The complete answer to n_queries repetitions of the verifier's query (vpd_verifier.cpp:119-306), after the commit phase has finished (VP_EINVAL
+ * before; VP_EINVAL on a sharded commitment, whose caller merges vp_fri_open_many).  leaf0[q] is the leaf of the two first oracles (pow / 2); the
+ * leaf of every FRI level follows from it: t = leaf0, D = M = 2^(n-1); per level Dn = D / 2, leaf = t mod (Dn / 2), t = leaf, D = Dn.  Layout of
+ * `out`, no headers: per query, in the order oracle 0, oracle 1, level 0 .. n - 7, the 130 values (2080 bytes) followed by that opening's path at
+ * its true length (n - 1 digests for l and h, n - 2 - k for level k) in vp_fri_open's order.  vp_fri_query_bytes: the size of that answer.      */
+int vp_fri_query_bytes(vp_ctx *, int n_queries, uint64_t *bytes);
+int vp_fri_query(vp_ctx *, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written);
 /* fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp:833-849), prover side: the self-contained GKR over the inverse-FFT +
  * polynomial-evaluation circuit that verify_poly_commitment runs between commit_public and the FRI commit phase (vpd_verifier.cpp:92,
  * lg = bit_length(layer 0) - 6) and whose prover time the reference adds to "Polynomial commitment: prove time" (:94, src/verifier.cpp:183).
@@ -472,7 +491,7 @@ int vp_set_profiling(vp_ctx *, int level);
  * launch on every table it holds; closing kernels: the remaining ones), `first_round` the earliest of them (1-based).   */
 enum { VP_K_BETA = 0, VP_K_LIGHT, VP_K_CHUNKS, VP_K_COMBINE, VP_K_DOT, VP_K_DOTFIN, VP_K_SFGEN, VP_K_SF, VP_K_SEG, VP_K_EMIT,
        VP_K_FIXUP, VP_K_NTT_SPLIT, VP_K_NTT_LDS, VP_K_NTT_UNSPLIT, VP_K_LEAF_HASH, VP_K_MERKLE, VP_K_PC_POINTWISE, VP_K_FRI_FOLD,
-       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_NTT_LONG_SPLIT, VP_K_NTT_LONG_MERGE, VP_K_COUNT };
+       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_NTT_LONG_SPLIT, VP_K_NTT_LONG_MERGE, VP_K_PC_OPEN_MANY, VP_K_COUNT };
 /* VP_K_NTT_UNSPLIT is no longer emitted (the long transforms store in natural order themselves); it keeps its value so the others do not move. */
 typedef struct {
     int32_t kind;             /* VP_K_*                                                          */

@@ -156,6 +156,9 @@ def lib_gpu():
         L.vp_fri_commit.argtypes = [vp, vp, ctypes.c_int, vp]
         L.vp_fri_final.argtypes = [vp, vp]
         L.vp_fri_open.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.vp_fri_open_many.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp]
+        L.vp_fri_query_bytes.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+        L.vp_fri_query.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.vp_commit_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.vp_comm_unique_id.argtypes = [vp]
         L.vp_comm_init.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
@@ -223,6 +226,9 @@ def lib_host():
         L.vph_commit_public.argtypes = [vp, vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_full.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_and_verify_full.argtypes = [vp, ctypes.c_int, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_char_p, ctypes.c_int]
+        L.vph_prove_and_verify_full_ex.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_char_p, ctypes.c_int]
+        L.vph_last_full_record.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
+        L.vph_verify_full_record.argtypes = [vp, vp, u64]
         L.vph_last_fri.argtypes = [vp, vp, u64, vp, vp]
         L.vph_draw_protocol_tape.argtypes = [vp]
         L.vph_prove_protocol.argtypes = [vp, vp, u64, ctypes.POINTER(u64), vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
@@ -273,6 +279,43 @@ def allreduce_transcript(tr, device=None):
         t = t.cuda(device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM)
     return t.cpu().numpy().tobytes()
+
+
+OPEN_PATH_STRIDE = 32 * 26      # bytes per request that fri_open_many reserves for a path (the longest one, at an input layer of 2^25 wires, is 24 digests)
+
+
+def fri_open_many(ctx, requests, path_stride=OPEN_PATH_STRIDE, fill=0):
+    """vp_fri_open_many on a vp_ctx*: requests = sequence of (oracle, leaf).  Returns (rc, values (n, 130, 2) uint64, paths (n, path_stride) uint8,
+    path_len (n,) int32); the output arrays are pre-filled with the byte `fill`, so that what the library left untouched can be told."""
+    import numpy as np
+    n = len(requests)
+    oracle = np.ascontiguousarray([r[0] for r in requests], dtype=np.int32).reshape(n)
+    leaf = np.ascontiguousarray([r[1] for r in requests], dtype=np.uint64).reshape(n)
+    values = np.full(max(n, 1) * 130 * 16, fill, dtype=np.uint8).view(np.uint64).reshape(-1, 130, 2)
+    paths = np.full((max(n, 1), max(path_stride, 1)), fill, dtype=np.uint8)
+    path_len = np.full(max(n, 1) * 4, fill, dtype=np.uint8).view(np.int32)
+    rc = lib_gpu().vp_fri_open_many(ctx, n, oracle.ctypes.data, leaf.ctypes.data, values.ctypes.data, paths.ctypes.data, path_stride, path_len.ctypes.data)
+    return rc, values[:n], paths[:n], path_len[:n]
+
+
+def fri_query_bytes(ctx, n_queries):
+    """(rc, size in bytes of vp_fri_query's answer to n_queries repetitions)."""
+    b = ctypes.c_uint64(0)
+    rc = lib_gpu().vp_fri_query_bytes(ctx, n_queries, ctypes.byref(b))
+    return rc, b.value
+
+
+def fri_query(ctx, leaf0):
+    """vp_fri_query on a vp_ctx*: (rc, bytes).  leaf0[q] = the leaf of the two first oracles of repetition q."""
+    import numpy as np
+    leaf0 = np.ascontiguousarray(leaf0, dtype=np.uint64)
+    rc, cap = fri_query_bytes(ctx, leaf0.shape[0])
+    if rc:
+        return rc, b""
+    out = ctypes.create_string_buffer(max(cap, 1))
+    n = ctypes.c_uint64(0)
+    rc = lib_gpu().vp_fri_query(ctx, leaf0.shape[0], leaf0.ctypes.data, ctypes.cast(out, ctypes.c_void_p), cap, ctypes.byref(n))
+    return rc, out.raw[: n.value] if rc == 0 else b""
 
 
 class ShardedCommitment:
@@ -367,6 +410,23 @@ class ShardedCommitment:
         if rc:
             return None
         return vals, [path.raw[32 * i:32 * i + 32] for i in range(n.value)]
+
+    def open_many(self, requests, path_stride=OPEN_PATH_STRIDE):
+        """vp_fri_open_many asked of EVERY rank and merged by path_len (a rank reports 0 for a request it does not own and leaves its bytes alone).
+        Returns (values (n, 130, 2), paths (n, path_stride) uint8, path_len (n,), answered (world, n) bool: which rank answered which request)."""
+        import numpy as np
+        n = len(requests)
+        values = np.zeros((n, 130, 2), dtype=np.uint64)
+        paths = np.zeros((n, path_stride), dtype=np.uint8)
+        path_len = np.zeros(n, dtype=np.int32)
+        answered = np.zeros((self.world, n), dtype=bool)
+        for r in range(self.world):
+            rc, v, p, pl = fri_open_many(self.ctx[r], requests, path_stride)
+            self._chk(-abs(rc) if rc else 0, self.ctx[r], "vp_fri_open_many")
+            mine = pl > 0
+            answered[r] = mine
+            values[mine], paths[mine], path_len[mine] = v[mine], p[mine], pl[mine]
+        return values, paths, path_len, answered
 
     def close(self):
         for c in self.ctx:
@@ -541,6 +601,11 @@ class Circuit:
         buf = ctypes.create_string_buffer(bytes(transcript), len(transcript))
         return lib_host().vph_verify_transcript(self.h, ctypes.cast(buf, ctypes.c_void_p), len(transcript),
                                                 1 if skip_predicates else 0) == 0
+
+    def verify_full_record(self, record):
+        """Verify the record of a complete-protocol run (Session.last_full_record) on the host: no GPU, no session."""
+        buf = ctypes.create_string_buffer(bytes(record), max(len(record), 1))
+        return lib_host().vph_verify_full_record(self.h, ctypes.cast(buf, ctypes.c_void_p), len(record)) == 0
 
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
@@ -926,21 +991,55 @@ class Session:
         return (buf.raw[: n.value], roots.raw[:32 * st], fin.copy(),
                 {"total": sec[0], "commit_private": sec[1], "gkr": sec[2], "commit_public": sec[3], "fft_gkr": sec[4], "fri_commit": sec[5]})
 
-    def prove_and_verify_full(self, reps=33):
-        """The complete protocol incl. commitment verification: (transcript bytes, accepted, times dict)."""
+    def prove_and_verify_full(self, reps=33, batched_openings=False):
+        """The complete protocol incl. commitment verification: (transcript bytes, accepted, times dict).  batched_openings: the query phase is
+        answered in one device pass (vp_fri_query) instead of one vp_fri_open per opening; same positions, openings and checks."""
         cap = self._cap + 32 + 32 + 16 + 65 * 16
         buf = ctypes.create_string_buffer(cap)
         n = ctypes.c_uint64(0)
         t = [ctypes.c_double(0) for _ in range(3)]
         err = ctypes.create_string_buffer(512)
-        rc = lib_host().vph_prove_and_verify_full(self.h, reps, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
-                                                  ctypes.byref(t[0]), ctypes.byref(t[1]), ctypes.byref(t[2]), err, len(err))
+        if batched_openings:
+            rc = lib_host().vph_prove_and_verify_full_ex(self.h, reps, 1, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
+                                                         ctypes.byref(t[0]), ctypes.byref(t[1]), ctypes.byref(t[2]), err, len(err))
+        else:
+            rc = lib_host().vph_prove_and_verify_full(self.h, reps, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
+                                                      ctypes.byref(t[0]), ctypes.byref(t[1]), ctypes.byref(t[2]), err, len(err))
         if rc < 0:
             raise RuntimeError("prove_and_verify_full failed: " + err.value.decode())
         pt = (ctypes.c_double * 3)()
         lib_host().vph_last_pc_times(self.h, pt)
         return buf.raw[: n.value], rc == 0, {"gkr_prove_sec": t[0].value, "pc_prove_sec": t[1].value, "verify_sec": t[2].value,
                                             "pc_fft_gkr_sec": pt[1], "pc_query_answer_sec": pt[2]}
+
+    def last_full_record(self):
+        """Record of the last accepted prove_and_verify_full() (layout: host/vphost.h): everything the prover handed over, for
+        Circuit.verify_full_record — which needs no GPU."""
+        n = ctypes.c_uint64(0)
+        lib_host().vph_last_full_record(self.h, None, 0, ctypes.byref(n))
+        if not n.value:
+            raise RuntimeError("no accepted complete-protocol run on this session yet")
+        buf = ctypes.create_string_buffer(n.value)
+        if lib_host().vph_last_full_record(self.h, ctypes.cast(buf, ctypes.c_void_p), n.value, ctypes.byref(n)):
+            raise RuntimeError("vph_last_full_record failed")
+        return buf.raw[: n.value]
+
+    def fri_open_many(self, requests, path_stride=OPEN_PATH_STRIDE):
+        """vp_fri_open_many on this session's commitment: requests = sequence of (oracle, leaf); returns (values (n, 130, 2) uint64,
+        paths (n, path_stride) uint8, path_len (n,) int32).  Raises on a refused list."""
+        ctx = self.gpu_ctx()
+        rc, v, p, pl = fri_open_many(ctx, requests, path_stride)
+        if rc:
+            raise RuntimeError("vp_fri_open_many failed: %d %s" % (rc, (lib_gpu().vp_last_error(ctx) or b"").decode()))
+        return v, p, pl
+
+    def fri_query(self, leaf0):
+        """vp_fri_query: the complete answer to len(leaf0) query repetitions as bytes (layout: include/vpgpu.h)."""
+        ctx = self.gpu_ctx()
+        rc, out = fri_query(ctx, leaf0)
+        if rc:
+            raise RuntimeError("vp_fri_query failed: %d %s" % (rc, (lib_gpu().vp_last_error(ctx) or b"").decode()))
+        return out
 
     def last_fft_gkr(self):
         """Messages of fft_gkr (vp_fft_gkr layout) of the last prove_and_verify_full(), as bytes."""

@@ -797,6 +797,58 @@ __global__ void k_pc_open(const F *__restrict__ cw, u32 Nc, const Dig *__restric
     }
 }
 
+// The whole query phase in one launch (vp_fri_open_many / vp_fri_query): workgroup r answers request r = (oracle, leaf) from a table of per-oracle
+// descriptors (oracle 0 = l, 1 = h, 2 + k = FRI level k) and writes one fixed-stride record: the 130 values, then the path in k_pc_open's layout.
+// top == nullptr: the whole codeword (Nc values per coset) and the whole tree are here (k_pc_open's cases: Nc >= 2, the last level's Nc == 1, a mask
+// slice or zeros).  top != nullptr: a position-sharded oracle (k_pc_open_sh's case): Nc is the LOCAL number of values per coset, tree the local tree
+// (five lowest siblings), top the replicated tree above it with n5 leaves, lw = log2(world).  The host has validated every request; the checked
+// build checks them again (site 9) and the positions they lead to (site 7).
+#define VP_OPEN_MAX_ORACLES 21            // l, h and the 19 levels of an input layer of 2^25 wires
+#define VP_OPEN_MAX_PATH 26
+struct PcOpenDesc { const F *cw; const F *mask; const Dig *tree; const Dig *top; u32 Nc, n_leaves, n5, lw; };
+struct PcOpenRec { F v[130]; Dig path[VP_OPEN_MAX_PATH]; };
+__global__ void __launch_bounds__(128)
+k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *__restrict__ req, u32 n_req, PcOpenRec *__restrict__ out) {
+    const u32 r = blockIdx.x, t = threadIdx.x;
+    if (r >= n_req) return;
+    const u32 o = req[r].x, leaf = req[r].y;
+    if (!VP_CHK(o < n_oracles, 9, o, leaf, n_oracles)) return;
+    const PcOpenDesc d = tab[o];
+    if (!VP_CHK(leaf < d.n_leaves, 9, o, leaf, d.n_leaves)) return;
+    PcOpenRec &rec = out[r];
+    u32 depth = 0;
+    while ((1u << depth) < d.n_leaves) ++depth;
+    if (d.top) {
+        const u32 a = leaf >> 5, b = leaf & 31, al = a >> d.lw, leaf_loc = 32 * al + b, nl = 16 * d.Nc;
+        if (!VP_CHK(al + (d.Nc >> 1) < d.Nc && a < d.n5, 7, a, b, d.Nc)) return;
+        if (t < 64) {
+            const F *row = d.cw + ((size_t) t * 32 + b) * d.Nc;
+            rec.v[2 * t] = row[al]; rec.v[2 * t + 1] = row[al + (d.Nc >> 1)];
+        } else if (t == 64) { rec.v[128] = f_zero(); rec.v[129] = f_zero(); }
+        if (t == depth) rec.path[t] = d.tree[nl + leaf_loc];
+        else if (t < 5) rec.path[t] = d.tree[((nl + leaf_loc) >> t) ^ 1];
+        else if (t < depth) rec.path[t] = d.top[((d.n5 + a) >> (t - 5)) ^ 1];
+        return;
+    }
+    const u32 Nc = d.Nc, a = leaf >> 5, b = leaf & 31;
+    if (!VP_CHK(Nc >= 2 ? a + (Nc >> 1) < Nc : leaf < 16, 7, a, b, Nc)) return;
+    if (t < 64) {
+        F x, y;
+        if (Nc >= 2) { const F *row = d.cw + ((size_t) t * 32 + b) * Nc; x = row[a]; y = row[a + (Nc >> 1)]; }
+        else { x = d.cw[(size_t) t * 32 + leaf]; y = d.cw[(size_t) t * 32 + leaf + 16]; }
+        rec.v[2 * t] = x; rec.v[2 * t + 1] = y;
+    } else if (t == 64) {
+        F x = f_zero(), y = f_zero();
+        if (d.mask) {
+            if (Nc >= 2) { x = d.mask[(size_t) b * Nc + a]; y = d.mask[(size_t) b * Nc + a + (Nc >> 1)]; }
+            else { x = d.mask[leaf]; y = d.mask[leaf + 16]; }
+        }
+        rec.v[128] = x; rec.v[129] = y;
+    }
+    if (t == depth) rec.path[t] = d.tree[d.n_leaves + leaf];
+    else if (t < depth) rec.path[t] = d.tree[((d.n_leaves + leaf) >> t) ^ 1];
+}
+
 // ---- the mask slice WITH CONTENT (round 6; lib/virgo/src/poly_commit.h:42,55-86,138-161,187-191, fri.cpp:96-124,366-386,403-411) --------------------------------
 // The protocol's own calls pass one zero (src/prover.cpp:526, src/verifier.cpp:375-377) and take the kernels above; a caller that hands vp_commit_private_masked /
 // vp_commit_public_masked a non-zero mask gets a 65th slice through every piece of the commitment.  The slice lives in arrays of its own (coset-major like the

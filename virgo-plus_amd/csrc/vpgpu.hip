@@ -226,6 +226,8 @@ struct vp_ctx {
     F *pc_pub = nullptr, *pc_qcw = nullptr, *pc_hcw = nullptr, *pc_tmp = nullptr, *pc_small = nullptr; Dig *pc_tree_h = nullptr; bool pc_private_done = false;
     F *pc_scr = nullptr; size_t pc_scr_cap = 0;
     F *pc_fri_all = nullptr; std::vector<size_t> fri_cw_off, fri_tree_off; F *pc_open_buf = nullptr;
+    // vp_fri_open_many / vp_fri_query: records on the device, descriptor table + request list on the device, pinned staging of both directions
+    PcOpenRec *pc_many_buf = nullptr; unsigned char *pc_many_in = nullptr; u32 pc_many_cap = 0; unsigned char *h_many = nullptr; size_t h_many_cap = 0;
     Dig *pc_fri_roots = nullptr;
     F *pc_fri[2] = {nullptr, nullptr}; Dig *pc_fri_tree = nullptr; int fri_step = -1; size_t fri_tree_used = 0; bool pc_public_done = false;
     // the mask slice with content (vp_commit_private_masked / vp_commit_public_masked; 0 = the protocol's zero mask, nothing below is touched): padded mask length,
@@ -1203,6 +1205,7 @@ void vp_destroy(vp_ctx *ctx) {
     if (ctx->h_io) (void) hipHostFree(ctx->h_io);
     if (ctx->h_ring) (void) hipHostFree(ctx->h_ring);
     if (ctx->h_pub) (void) hipHostFree(ctx->h_pub);
+    if (ctx->h_many) (void) hipHostFree(ctx->h_many);
     for (auto &p : ctx->pending) { (void) hipEventDestroy(p.a); (void) hipEventDestroy(p.b); }
     for (auto e : ctx->ev_spare) (void) hipEventDestroy(e);
     for (auto st : ctx->lane_streams) (void) hipStreamDestroy(st);
@@ -1232,7 +1235,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
     ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
     ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
-    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
+    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
     ctx->pc_fri[0] = ctx->pc_fri[1] = nullptr; ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->fri_m_off.clear(); ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
     int max_bl = 0;
@@ -2040,7 +2043,7 @@ const char *vp_kernel_name(int kind) {
     static const char *names[VP_K_COUNT] = {"k_beta_half_direct", "k_light_multi", "k_chunks_multi", "k_combine_multi", "k_dot_multi", "k_dotfin_multi",
         "k_sumfold3b_gen_multi", "k_sumfold3b_multi", "k_seg_multi", "k_emit_multi", "k_fixup", "k_ntt_split", "k_ntt_lds", "k_ntt_unsplit",
         "k_leaf_hash", "k_merkle", "k_pc_pointwise", "k_fri_fold", "k_round", "k_ntt8_cols", "k_ntt8_rows",
-        "k_ntt_long_split", "k_ntt_long_merge"};
+        "k_ntt_long_split", "k_ntt_long_merge", "k_pc_open_many"};
     return (kind >= 0 && kind < VP_K_COUNT) ? names[kind] : "?";
 }
 

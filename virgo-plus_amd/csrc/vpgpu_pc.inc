@@ -379,6 +379,104 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner,
 int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots);
 int pcs_fri_final(vp_ctx *ctx, vp_F *final_code);
 int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len);
+int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d);
+bool pcs_owns(vp_ctx *ctx, uint64_t leaf);
+
+// ---- the query phase in one device pass (vp_fri_open_many, vp_fri_query; kernel: k_pc_open_many) ----------------------------------------------------------------
+// One launch answers up to PC_MANY_PIECE requests into fixed-stride records, one copy brings them to pinned memory, one synchronise follows; the caller's
+// layout is written from there.  Every request is validated before anything is launched, by the rules vp_fri_open applies to one.
+constexpr int PC_MANY_PIECE = 4096, PC_MANY_MAX = 1 << 16;
+static inline size_t pc_many_in_bytes(u32 cap) { return VP_OPEN_MAX_ORACLES * sizeof(PcOpenDesc) + (size_t) cap * sizeof(uint2); }
+static int pc_many_reserve(vp_ctx *ctx, u32 want) {        // buffers for `want` requests per launch (two sizes: 1024 covers a protocol run up to 33 x (2 + 19))
+    want = std::min<u32>(want, PC_MANY_PIECE);
+    if (ctx->pc_many_buf && ctx->pc_many_cap >= want) return VP_OK;
+    const u32 cap = want <= 1024 ? 1024 : PC_MANY_PIECE;
+    const size_t hb = pc_many_in_bytes(cap) + (size_t) cap * sizeof(PcOpenRec);
+    if (ctx->h_many_cap < hb) {
+        if (ctx->h_many) (void) hipHostFree(ctx->h_many);
+        ctx->h_many = nullptr; ctx->h_many_cap = 0;
+        HIPCHK(hipHostMalloc((void **) &ctx->h_many, hb, hipHostMallocDefault));
+        ctx->h_many_cap = hb;
+    }
+    ctx->pc_many_cap = 0;
+    VPCHK(dalloc(ctx, &ctx->pc_many_buf, (size_t) cap));   // (a smaller one from before stays in ctx->allocs until the next upload)
+    VPCHK(dalloc(ctx, &ctx->pc_many_in, pc_many_in_bytes(cap)));
+    ctx->pc_many_cap = cap;
+    return VP_OK;
+}
+// descriptor of one oracle, refused exactly where vp_fri_open refuses it
+static int pc_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
+    *d = PcOpenDesc{};
+    if (oracle < 0 || ctx->L.empty()) return VP_EINVAL;
+    if (oracle >= VP_OPEN_MAX_ORACLES) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+    if (ctx->pcs) return pcs_open_desc(ctx, oracle, d);
+    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
+    const u32 N = 1u << ln, M = 1u << lm;
+    if (oracle == 0) { if (!ctx->pc_private_done) return VP_EINVAL; d->cw = ctx->pc_cw; d->tree = ctx->pc_tree; d->Nc = N; d->n_leaves = M >> 1; }
+    else if (oracle == 1) { if (!ctx->pc_public_done) return VP_EINVAL; d->cw = ctx->pc_hcw; d->tree = ctx->pc_tree_h; d->Nc = N; d->n_leaves = M >> 1; }
+    else {
+        const int lvl = oracle - 2;
+        if (lvl >= ctx->fri_step || lvl >= (int) ctx->fri_cw_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        d->cw = ctx->pc_fri_all + ctx->fri_cw_off[lvl]; d->tree = ctx->pc_fri_tree + ctx->fri_tree_off[lvl];
+        d->Nc = N >> (lvl + 1); d->n_leaves = 16 * d->Nc;
+    }
+    if (ctx->pc_mask_ms) d->mask = oracle == 0 ? ctx->pc_lm_cw : oracle == 1 ? ctx->pc_hm_cw : (oracle - 2 < (int) ctx->fri_m_off.size() ? ctx->pc_fm + ctx->fri_m_off[oracle - 2] : nullptr);
+    return VP_OK;
+}
+static inline int pc_open_depth(u32 n_leaves) { int depth = 0; while ((1u << depth) < n_leaves) ++depth; return depth; }
+struct PcManyPlan { PcOpenDesc tab[VP_OPEN_MAX_ORACLES]; std::vector<int> plen; u64 bytes = 0; };   // plen[i]: digests of request i's path, 0 = another rank's
+// Validation of a whole list (nothing is launched or written on a refusal).  path_stride < 0: no capacity rule (vp_fri_query packs paths itself).
+static int pc_many_plan(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_t *leaf, int path_stride, PcManyPlan &pl) {
+    int have[VP_OPEN_MAX_ORACLES]; for (int &h : have) h = 0;       // 0 unknown, 1 described
+    pl.plen.assign((size_t) n, 0); pl.bytes = 0;
+    for (auto &t : pl.tab) t = PcOpenDesc{};
+    for (int i = 0; i < n; ++i) {
+        const int o = oracle[i];
+        if (o < 0) return VP_EINVAL;
+        if (o >= VP_OPEN_MAX_ORACLES || !have[o]) { VPCHK(pc_open_desc(ctx, o, &pl.tab[std::min(o, VP_OPEN_MAX_ORACLES - 1)])); have[o] = 1; }
+        const PcOpenDesc &d = pl.tab[o];
+        if (leaf[i] >= d.n_leaves) return VP_EINVAL;
+        const int depth = pc_open_depth(d.n_leaves);
+        if (depth + 1 > VP_OPEN_MAX_PATH) return VP_ELIMIT;
+        if (path_stride >= 0 && path_stride < 32 * (depth + 1)) return VP_EINVAL;
+        if (d.top && !pcs_owns(ctx, leaf[i])) continue;
+        pl.plen[i] = depth + 1;
+        pl.bytes += 130 * sizeof(F) + 32ull * (depth + 1);
+    }
+    return VP_OK;
+}
+// The launches: sink(i, record) receives the answer of every request this rank owns, in request order.
+static int pc_many_run(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_t *leaf, const PcManyPlan &pl, const std::function<void(int, const PcOpenRec &)> &sink) {
+    std::vector<int> mine; mine.reserve((size_t) n);
+    for (int i = 0; i < n; ++i) if (pl.plen[i]) mine.push_back(i);
+    ctx->ev_used = 0;
+    if (mine.empty()) { if (ctx->profiling) prof_collect(ctx); return VP_OK; }
+    VPCHK(pc_many_reserve(ctx, (u32) std::min<size_t>(mine.size(), PC_MANY_PIECE)));
+    const u32 cap = ctx->pc_many_cap;
+    PcOpenDesc *h_tab = reinterpret_cast<PcOpenDesc *>(ctx->h_many);
+    uint2 *h_req = reinterpret_cast<uint2 *>(ctx->h_many + VP_OPEN_MAX_ORACLES * sizeof(PcOpenDesc));
+    const PcOpenRec *h_rec = reinterpret_cast<const PcOpenRec *>(ctx->h_many + pc_many_in_bytes(cap));
+    const PcOpenDesc *d_tab = reinterpret_cast<const PcOpenDesc *>(ctx->pc_many_in);
+    const uint2 *d_req = reinterpret_cast<const uint2 *>(ctx->pc_many_in + VP_OPEN_MAX_ORACLES * sizeof(PcOpenDesc));
+    memcpy(h_tab, pl.tab, sizeof pl.tab);
+    for (size_t at = 0; at < mine.size(); at += PC_MANY_PIECE) {
+        const u32 cnt = (u32) std::min<size_t>(PC_MANY_PIECE, mine.size() - at);
+        u64 bytes = 0;
+        for (u32 j = 0; j < cnt; ++j) {
+            const int i = mine[at + j];
+            h_req[j] = make_uint2((u32) oracle[i], (u32) leaf[i]);
+            bytes += 130 * sizeof(F) + 32ull * pl.plen[i];
+        }
+        HIPCHK(hipMemcpyAsync(ctx->pc_many_in, ctx->h_many, pc_many_in_bytes(cnt), hipMemcpyHostToDevice, ctx->stream));
+        PC_PROF(VP_K_PC_OPEN_MANY, cnt, cnt, bytes, 0,
+                hipLaunchKernelGGL(k_pc_open_many, dim3(cnt), dim3(128), 0, ctx->stream, d_tab, (u32) VP_OPEN_MAX_ORACLES, d_req, cnt, ctx->pc_many_buf));
+        HIPCHK(hipMemcpyAsync(const_cast<PcOpenRec *>(h_rec), ctx->pc_many_buf, (size_t) cnt * sizeof(PcOpenRec), hipMemcpyDeviceToHost, ctx->stream));
+        VPCHK(check_stream(ctx));
+        for (u32 j = 0; j < cnt; ++j) sink(mine[at + j], h_rec[j]);
+    }
+    if (ctx->profiling) prof_collect(ctx);
+    return VP_OK;
+}
 
 
 // ---- the mask slice with content (round 6; kernels: vp_kernels_pc.h "the mask slice WITH CONTENT") ------------------------------------------------------------
@@ -690,6 +788,7 @@ static int pc_warm(vp_ctx *ctx) {
     ctx->pc_dry = false;
     VPCHK(pc_fold0_consts(ctx, lm));
     if (pc_leaf_wg(ctx, (u64) M >> 1)) VPCHK(pc_leaf_prepare(ctx));
+    VPCHK(pc_many_reserve(ctx, 33u * (2 + ln)));             // the query phase's records (vp_fri_query)
     if (!ctx->h_pub) {
         const size_t bytes = sizeof(F) << n;
         if (hipHostMalloc((void **) &ctx->h_pub, bytes, hipHostMallocDefault) == hipSuccess) ctx->h_pub_cap = bytes;
@@ -1039,6 +1138,69 @@ int vp_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_
     HIPCHK(hipMemcpyAsync(path, dpath, 32 * (size_t) (depth + 1), hipMemcpyDeviceToHost, ctx->stream));
     VPCHK(check_stream(ctx));
     *path_len = depth + 1;
+    return VP_OK;
+}
+
+int vp_fri_open_many(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_t *leaf, vp_F *values, uint8_t *paths, int path_stride, int32_t *path_len) {
+    if (!ctx || n < 0) return VP_EINVAL;
+    if (n == 0) return VP_OK;
+    if (!oracle || !leaf || !values || !paths || !path_len || path_stride < 0) return VP_EINVAL;
+    if (n > PC_MANY_MAX) { ctx->err = "vp_fri_open_many: more than 2^16 requests"; return VP_ELIMIT; }
+    VP_ENTER(ctx);
+    PcManyPlan pl;
+    VPCHK(pc_many_plan(ctx, n, oracle, leaf, path_stride, pl));
+    VPCHK(pc_many_run(ctx, n, oracle, leaf, pl, [&](int i, const PcOpenRec &r) {
+        memcpy(values + (size_t) 130 * i, r.v, 130 * sizeof(F));
+        memcpy(paths + (size_t) path_stride * i, r.path, 32 * (size_t) pl.plen[i]);
+    }));
+    for (int i = 0; i < n; ++i) path_len[i] = pl.plen[i];
+    return VP_OK;
+}
+
+// requests of `n_queries` repetitions in vp_fri_query's order: oracle 0, oracle 1, level 0 .. ln - 1 along the leaf chain of host/verifier.cpp
+static int pc_query_requests(vp_ctx *ctx, int n_queries, const uint64_t *leaf0, std::vector<int32_t> &oracle, std::vector<uint64_t> &leaf) {
+    if (ctx->pcs) { ctx->err = "vp_fri_query: not on a sharded commitment (merge vp_fri_open_many over the ranks)"; return VP_EINVAL; }
+    if (ctx->L.empty() || !ctx->pc_public_done) return VP_EINVAL;
+    const int ln = ctx->L[0].bl - 6;
+    if (ctx->fri_step != ln) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
+    if ((u64) n_queries * (u64) (2 + ln) > (u64) PC_MANY_MAX) { ctx->err = "vp_fri_query: more than 2^16 openings"; return VP_ELIMIT; }
+    const u64 M = 1ull << (ctx->L[0].bl - 1);
+    oracle.clear(); leaf.clear();
+    for (int q = 0; q < n_queries; ++q) {
+        const u64 l0 = leaf0 ? leaf0[q] : 0;
+        oracle.push_back(0); leaf.push_back(l0);
+        oracle.push_back(1); leaf.push_back(l0);
+        u64 D = M, t = l0;
+        for (int k = 0; k < ln; ++k) { const u64 Dn = D / 2, lf = t % (Dn / 2); oracle.push_back(2 + k); leaf.push_back(lf); t = lf; D = Dn; }
+    }
+    return VP_OK;
+}
+int vp_fri_query_bytes(vp_ctx *ctx, int n_queries, uint64_t *bytes) {
+    if (!ctx || !bytes || n_queries < 0) return VP_EINVAL;
+    VP_ENTER(ctx);
+    std::vector<int32_t> oracle; std::vector<uint64_t> leaf;
+    VPCHK(pc_query_requests(ctx, n_queries, nullptr, oracle, leaf));
+    PcManyPlan pl;
+    VPCHK(pc_many_plan(ctx, (int) oracle.size(), oracle.data(), leaf.data(), -1, pl));
+    *bytes = pl.bytes;
+    return VP_OK;
+}
+int vp_fri_query(vp_ctx *ctx, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written) {
+    if (!ctx || n_queries < 0 || !n_written || (n_queries > 0 && (!leaf0 || !out))) return VP_EINVAL;
+    VP_ENTER(ctx);
+    std::vector<int32_t> oracle; std::vector<uint64_t> leaf;
+    VPCHK(pc_query_requests(ctx, n_queries, leaf0, oracle, leaf));
+    const int n = (int) oracle.size();
+    PcManyPlan pl;
+    VPCHK(pc_many_plan(ctx, n, oracle.data(), leaf.data(), -1, pl));
+    if (pl.bytes > capacity) { ctx->err = "vp_fri_query: output buffer too small (vp_fri_query_bytes)"; return VP_EINVAL; }
+    std::vector<u64> at((size_t) n + 1, 0);
+    for (int i = 0; i < n; ++i) at[i + 1] = at[i] + 130 * sizeof(F) + 32ull * pl.plen[i];
+    VPCHK(pc_many_run(ctx, n, oracle.data(), leaf.data(), pl, [&](int i, const PcOpenRec &r) {
+        memcpy(out + at[i], r.v, 130 * sizeof(F));
+        memcpy(out + at[i] + 130 * sizeof(F), r.path, 32 * (size_t) pl.plen[i]);
+    }));
+    *n_written = pl.bytes;
     return VP_OK;
 }
 

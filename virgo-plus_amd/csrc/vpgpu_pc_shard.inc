@@ -501,6 +501,30 @@ int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8
     return VP_OK;
 }
 
+// vp_fri_open_many on a sharded commitment: the descriptor of one oracle (refusals as in pcs_fri_open) and who answers a leaf of a position-sharded one
+int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
+    PcShard &s = *ctx->pcs;
+    const int n = ctx->L[0].bl, ln = n - 6;
+    const u32 N = 1u << ln, Nl = N >> s.lw;
+    if (oracle >= 2 && oracle - 2 >= s.n_local - 1) {                       // tail level: whole codeword on every rank
+        const int q = oracle - 2 - (s.n_local - 1);
+        if (s.n_steps == 0 || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        const u32 Nt = (1u << s.lw) >> q;
+        d->cw = s.tail + s.tail_cw_off[q]; d->tree = s.tail_tree + s.tail_tree_off[q]; d->Nc = Nt; d->n_leaves = Nt >= 2 ? 16 * Nt : 16;
+        return VP_OK;
+    }
+    if (oracle == 0) { if (!s.private_done) return VP_EINVAL; d->cw = s.l_loc; d->tree = s.tree_l; d->top = s.top_l; d->Nc = Nl; }
+    else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; d->cw = s.h_loc; d->tree = s.tree_h; d->top = s.top_h; d->Nc = Nl; }
+    else {
+        const int lvl = oracle - 2;
+        if (s.n_steps == 0 || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        d->cw = s.fri_loc + s.fri_off[lvl + 1]; d->tree = s.tree_f + s.tree_f_off[lvl]; d->top = s.top_f + s.top_f_off[lvl]; d->Nc = Nl >> (lvl + 1);
+    }
+    d->n_leaves = (16 * d->Nc) << s.lw; d->n5 = (d->Nc >> 1) << s.lw; d->lw = (u32) s.lw;
+    return VP_OK;
+}
+bool pcs_owns(vp_ctx *ctx, uint64_t leaf) { const PcShard &s = *ctx->pcs; return (int) ((leaf >> 5) & (u64) (s.world - 1)) == s.rank; }
+
 }  // namespace
 
 extern "C" {
@@ -524,7 +548,7 @@ int vp_pc_load_input(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs, int bit
     ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
     ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
     ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
-    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
+    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
     ctx->pc_fri[0] = ctx->pc_fri[1] = nullptr; ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->fri_m_off.clear(); ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
     ctx->evaluated = true;

@@ -460,6 +460,24 @@ void prover::friOpen(int oracle, u64 leaf, std::vector<F> &values, std::vector<h
     check(vp_fri_open(ctx, oracle, leaf, mF(values.data()), path[0].b, 40 * 32, &len), "vp_fri_open");
     path.resize(len);
 }
+void prover::friOpenMany(const std::vector<int32_t> &oracle, const std::vector<u64> &leaf, std::vector<F> &values, std::vector<hhash_digest> &paths, int stride,
+                         std::vector<int32_t> &path_len) {
+    if (oracle.size() != leaf.size()) throw std::runtime_error("friOpenMany: oracle and leaf lists differ in length");
+    const size_t n = oracle.size();
+    values.resize(130 * n); paths.resize((size_t) stride * n); path_len.assign(n, 0);
+    if (!n) return;
+    std::vector<uint64_t> lf(leaf.begin(), leaf.end());
+    check(vp_fri_open_many(ctx, (int) n, oracle.data(), lf.data(), mF(values.data()), paths[0].b, 32 * stride, path_len.data()), "vp_fri_open_many");
+}
+std::vector<uint8_t> prover::friQuery(const std::vector<u64> &leaf0) {
+    uint64_t bytes = 0, written = 0;
+    check(vp_fri_query_bytes(ctx, (int) leaf0.size(), &bytes), "vp_fri_query_bytes");
+    std::vector<uint8_t> out(bytes);
+    std::vector<uint64_t> lf(leaf0.begin(), leaf0.end());
+    check(vp_fri_query(ctx, (int) lf.size(), lf.data(), out.data(), bytes, &written), "vp_fri_query");
+    out.resize(written);
+    return out;
+}
 std::vector<F> prover::fftGkr(int lg, const std::vector<F> &tape) {
     uint64_t nt = 0, nm = 0;
     check(vp_fft_gkr_sizes(lg, &nt, &nm), "vp_fft_gkr_sizes");

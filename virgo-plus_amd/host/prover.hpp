@@ -82,6 +82,12 @@ public:
     std::vector<F> friFinal();                           // 2048 elements, reference layout [i << 7 | slice << 1 | hi]
     // fri::request_init_value_with_merkle (oracle 0 = l, 1 = h) / fri::request_step_commit (oracle 2 + level)
     void friOpen(int oracle, u64 leaf, std::vector<F> &values /* 130 */, std::vector<hhash_digest> &path);
+    // the same for a list of requests in one device pass (vp_fri_open_many): values n x 130, paths at a stride of `stride` digests, path_len per request
+    void friOpenMany(const std::vector<int32_t> &oracle, const std::vector<u64> &leaf, std::vector<F> &values, std::vector<hhash_digest> &paths, int stride,
+                     std::vector<int32_t> &path_len);
+    // the whole query phase (vp_fri_query): leaf0[q] = the leaf of l and h of repetition q; per repetition oracle 0, oracle 1, level 0 .. ln - 1, each the
+    // 130 values followed by the path at its true length
+    std::vector<uint8_t> friQuery(const std::vector<u64> &leaf0);
     // fft_circuit_gkr::fft_gkr (lib/virgo/src/fft_circuit_GKR.cpp:833-849), prover side on the device (vp_fft_gkr): tape = the verifier's
     // draws in the reference's order; returns every prover message (layouts: include/vpgpu.h)
     std::vector<F> fftGkr(int lg, const std::vector<F> &tape);

@@ -375,6 +375,20 @@ vph::hhash_digest dig(const prover::hhash_digest &d) { vph::hhash_digest r; memc
 
 }  // namespace
 
+struct verifier::RecReader {
+    const uint8_t *p; size_t n, at;
+    void bytes(void *dst, size_t k) {
+        if (k > n - at) throw std::runtime_error("record too short");
+        memcpy(dst, p + at, k); at += k;
+    }
+    F elem() {
+        unsigned long long w[2]; bytes(w, 16);
+        if (w[0] >= F::mod || w[1] >= F::mod) throw std::runtime_error("non-canonical field element in the record");
+        F x; x.real = w[0]; x.img = w[1];
+        return x;
+    }
+};
+
 // Recompute the leaf chain from the opened values (fri.cpp:96-124) and walk the path to the root (vpd_verifier.cpp:9-40).
 bool verifier::checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals,
                             const std::vector<prover::hhash_digest> &path) {
@@ -422,7 +436,9 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     poly_prove_timer.start();
     F input_0;
     std::vector<F> all_sum;
-    const prover::hhash_digest root_h_raw = p->commit_public(pub, input_0, all_sum);
+    prover::hhash_digest root_h_raw;
+    if (rec) { rec->bytes(root_h_raw.b, 32); input_0 = rec->elem(); all_sum.resize(65); for (auto &x : all_sum) x = rec->elem(); }
+    else root_h_raw = p->commit_public(pub, input_0, all_sum);
     poly_prove_timer.stop();
     full_tr.insert(full_tr.end(), root_h_raw.b, root_h_raw.b + 32);
     { const uint8_t *b = reinterpret_cast<const uint8_t *>(&input_0); full_tr.insert(full_tr.end(), b, b + 16); }
@@ -447,7 +463,9 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
         for (auto &x : ftape) x = F::random();
         poly_prove_timer.start();
         fft_gkr_timer.start();
-        const std::vector<F> fmsgs = p->fftGkr(ln, ftape);
+        std::vector<F> fmsgs;
+        if (rec) { fmsgs.resize(vph::FftGkrLayout(ln).n_msgs); for (auto &x : fmsgs) x = rec->elem(); }
+        else fmsgs = p->fftGkr(ln, ftape);
         fft_gkr_timer.stop();
         poly_prove_timer.stop();
         fft_gkr_msgs_ = fmsgs;
@@ -460,13 +478,20 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     std::vector<F> fr(ln);
     std::vector<vph::hhash_digest> roots(ln);
     poly_prove_timer.start();
+    std::vector<F> final_code;
+    if (rec) {                  // the same draws; roots and final codeword from the record
+        for (int k = 0; k < ln; ++k) fr[k] = F::random();
+        for (int k = 0; k < ln; ++k) rec->bytes(roots[k].w, 32);
+        final_code.resize(2048); for (auto &x : final_code) x = rec->elem();
+    } else {
     if (fri_batched) {          // same draws in the same order; the device runs the whole commit phase in one pass
         for (int k = 0; k < ln; ++k) fr[k] = F::random();
         const auto ds = p->friCommit(fr);
         for (int k = 0; k < ln; ++k) roots[k] = dig(ds[k]);
     } else
         for (int k = 0; k < ln; ++k) { fr[k] = F::random(); roots[k] = dig(p->friStep(fr[k])); }
-    const std::vector<F> final_code = p->friFinal();
+    final_code = p->friFinal();
+    }
     fri_roots_.clear();
     for (int k = 0; k < ln; ++k) { const uint8_t *b = reinterpret_cast<const uint8_t *>(roots[k].w); fri_roots_.insert(fri_roots_.end(), b, b + 32); }
     fri_final_ = final_code; fri_r_ = fr;
@@ -483,15 +508,39 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     const F w = F::getRootOfUnity(lm), inv2 = F(2ll).inv(), Nf((long long) N);
     std::vector<F> vl, vh, vb;
     std::vector<prover::hhash_digest> pl, ph, pb;
-    for (int rep = 0; rep < reps; ++rep) {
-        // query point x0 = w^(pow/2), pow even in [N, M) (vpd_verifier.cpp:119-123)
-        u64 pw;
-        do { pw = (u64) rand() % M; } while (pw < N || (pw & 1));
-        const u64 s0 = pw / 2;                                   // leaf of the two first oracles; x1 = -x0 sits in the same leaf
+    // query point x0 = w^(pow/2), pow even in [N, M) (vpd_verifier.cpp:119-123); pow / 2 is the leaf of the two first oracles (x1 = -x0 sits in the same leaf)
+    auto draw_leaf = [&]() { u64 pw; do { pw = (u64) rand() % M; } while (pw < N || (pw & 1)); return pw / 2; };
+    // Where the openings come from: one prover::friOpen each (the default), or a block of bytes in vp_fri_query's layout — the answer of ONE
+    // prover::friQuery to all positions (batched_openings), or the record's last section (checkFull).  Either way they are kept for the record.
+    const bool positions_first = rec || batched_openings;
+    std::vector<u64> leaf0((size_t) reps);
+    if (positions_first) for (auto &x : leaf0) x = draw_leaf();
+    openings_.clear();
+    RecReader answer{nullptr, 0, 0}, *src = rec;
+    if (!rec && batched_openings) {
         poly_timer.stop(); open_timer.start();
-        p->friOpen(0, s0, vl, pl);
-        p->friOpen(1, s0, vh, ph);
+        openings_ = p->friQuery(leaf0);
         open_timer.stop(); poly_timer.start();
+        answer = RecReader{openings_.data(), openings_.size(), 0}; src = &answer;
+    }
+    auto open = [&](int oracle, u64 leaf, std::vector<F> &vals, std::vector<prover::hhash_digest> &path) {
+        if (src) {
+            vals.resize(130); for (auto &x : vals) x = src->elem();
+            path.resize((size_t) (oracle < 2 ? n - 1 : n - 2 - (oracle - 2)));
+            src->bytes(path.data(), 32 * path.size());
+            return;
+        }
+        poly_timer.stop(); open_timer.start();
+        p->friOpen(oracle, leaf, vals, path);
+        open_timer.stop(); poly_timer.start();
+        const uint8_t *b = reinterpret_cast<const uint8_t *>(vals.data());
+        openings_.insert(openings_.end(), b, b + 130 * sizeof(F));
+        openings_.insert(openings_.end(), path[0].b, path[0].b + 32 * path.size());
+    };
+    for (int rep = 0; rep < reps; ++rep) {
+        const u64 s0 = positions_first ? leaf0[rep] : draw_leaf();
+        open(0, s0, vl, pl);
+        open(1, s0, vh, ph);
         if (!checkOpening(root_l, s0, vl, pl) || !checkOpening(root_h, s0, vh, ph)) { fprintf(stderr, "commitment: Merkle opening rejected\n"); return false; }
         const F x0 = F::fastPow(w, s0), x1 = F_ZERO - x0;
         const F x0n = F::fastPow(x0, N), x1n = F::fastPow(x1, N);
@@ -511,9 +560,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
             const F inv_mu = F::fastPow(F::fastPow(w, 1ull << k), t).inv();      // (w_D^t)^-1, w_D = w^(2^k)
             const u64 Dn = D / 2;                                // next domain size; the folded value sits at index t
             const u64 leaf = t % (Dn / 2);
-            poly_timer.stop(); open_timer.start();
-            p->friOpen(2 + k, leaf, vb, pb);
-            open_timer.stop(); poly_timer.start();
+            open(2 + k, leaf, vb, pb);
             if (!checkOpening(roots[k], leaf, vb, pb)) { fprintf(stderr, "commitment: FRI Merkle opening rejected (level %d)\n", k); return false; }
             const bool upper = t >= Dn / 2;
             for (int j = 0; j < 64; ++j) {
@@ -527,6 +574,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
             if (cur0[j] != final_val[j] || cur1[j] != final_val[j]) { fprintf(stderr, "Fri final codeword mismatch\n"); return false; }
     }
     poly_timer.stop();
+    if (src == &answer && answer.at != answer.n) { fprintf(stderr, "commitment: the query answer has bytes left over\n"); return false; }
     return true;
 }
 
@@ -547,6 +595,48 @@ bool verifier::verifyFull(int reps) {
     const bool ok = run();
     input_check_by_commitment = false;
     full_tr.insert(full_tr.end(), tr.begin(), tr.end());
+    record_.clear();
     if (!ok) return false;
-    return verifyPoly(root_l, last_claim, reps);
+    if (!verifyPoly(root_l, last_claim, reps)) return false;
+    // the record (vphost.h): header, transcript in the golden layout, fft_gkr messages, FRI roots, final codeword, openings
+    const uint32_t head[4] = {RECORD_MAGIC, RECORD_VERSION, (uint32_t) C.circuit[0].bitLength, (uint32_t) reps};
+    auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); record_.insert(record_.end(), q, q + k); };
+    put(head, sizeof head);
+    put(full_tr.data(), full_tr.size());
+    put(fft_gkr_msgs_.data(), fft_gkr_msgs_.size() * sizeof(F));
+    put(fri_roots_.data(), fri_roots_.size());
+    put(fri_final_.data(), fri_final_.size() * sizeof(F));
+    put(openings_.data(), openings_.size());
+    return true;
+}
+
+bool verifier::checkFull(const std::vector<uint8_t> &record) {
+    record_.clear();
+    const int n = C.circuit[0].bitLength;
+    if (n < 7) return false;
+    RecReader r{record.data(), record.size(), 0};
+    bool ok = false;
+    try {
+        uint32_t head[4];
+        r.bytes(head, sizeof head);
+        if (head[0] != RECORD_MAGIC || head[1] != RECORD_VERSION || head[2] != (uint32_t) n || head[3] < 1 || head[3] > 4096) return false;
+        prover::hhash_digest root_l;
+        r.bytes(root_l.b, 32);
+        // GKR slice: the replay of check(), on the tape redrawn here; it ends where run() stops reading
+        const std::vector<F> tape = drawTape();
+        const std::vector<uint8_t> rest(record.begin() + r.at, record.end());
+        replay = true; rtape = &tape; rtr = &rest; tape_pos = 0; tr_pos = 0; tr.clear();
+        input_check_by_commitment = true;
+        ok = run() && tape_pos == tape.size();
+        input_check_by_commitment = false;
+        if (ok) {
+            r.at += tr_pos;
+            full_tr.assign(root_l.b, root_l.b + 32);
+            full_tr.insert(full_tr.end(), tr.begin(), tr.end());
+            rec = &r;
+            ok = verifyPoly(root_l, last_claim, (int) head[3]) && r.at == r.n;
+        }
+    } catch (const std::runtime_error &) { ok = false; }      // short record / non-canonical element
+    rec = nullptr; input_check_by_commitment = false;
+    return ok;
 }

@@ -26,6 +26,16 @@ public:
     bool verifyFull(int reps = 33);
     prover *pred_dev = nullptr;     // when set, the O(|C|) predicate loops run on the device (prover::predicates) instead of the host
     bool fri_batched = true;        // FRI commit phase as one device pass (prover::friCommit) instead of one friStep per challenge
+    // The query phase as one device pass: all `reps` positions are drawn first (the loop draws nothing else between two positions, so they are the ones
+    // the default path draws), prover::friQuery answers them in one call, the per-repetition checks then run unchanged over the answer.
+    bool batched_openings = false;
+    // Record of the last accepted verifyFull(): everything the prover handed over, in one block of bytes (layout: vphost.h), and its replay with NO
+    // prover: the GKR part as check() does, then verifyPoly reading the prover's side from the record while every challenge and position is drawn
+    // from the same seeded generator as the live run (call F::init() first, as for drawTape()).  A record that is short, long, of another version,
+    // with a non-canonical element or with any byte changed is rejected.
+    const std::vector<uint8_t> &fullRecord() const { return record_; }
+    bool checkFull(const std::vector<uint8_t> &record);
+    static constexpr uint32_t RECORD_MAGIC = 0x52465056u /* "VPFR" */, RECORD_VERSION = 1;
     const std::vector<uint8_t> &fullTranscript() const { return full_tr; }
     // FRI commit phase of the last verifyFull(): Merkle root per fold step (32 bytes each), final codeword (2048), fold challenges
     const std::vector<uint8_t> &friRoots() const { return fri_roots_; }
@@ -100,6 +110,9 @@ private:
     std::vector<F> fft_gkr_msgs_;
     std::vector<uint8_t> full_tr;
     std::vector<uint8_t> fri_roots_; std::vector<F> fri_final_, fri_r_;
+    struct RecReader;                                  // bounds- and canonicity-checked cursor over a record (verifier.cpp)
+    RecReader *rec = nullptr;                          // checkFull(): where verifyPoly reads the prover's side from
+    std::vector<uint8_t> openings_, record_;           // the query phase's answers in vp_fri_query's layout; the whole record
     bool input_check_by_commitment = false;
     F last_claim;
 };

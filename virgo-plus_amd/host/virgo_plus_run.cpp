@@ -1,12 +1,16 @@
 // Command-line driver with the reference's interface (src/main.cpp:145-159):
 //     virgo_plus_run <file.pws> [--blocks B] [--batched | --fs] [--seed S] [--device D] [--dump transcript.bin]
 //     --fs: non-interactive GKR proof (Fiat-Shamir over SHA3-256), then verified from the proof bytes alone
+//     --record FILE: (interactive mode with the commitment) writes the record of the run — everything the prover handed over, layout in vphost.h;
+//         its query phase is then answered in one device pass (verifier::batched_openings)
+//     virgo_plus_run --check-record FILE <file.pws> [--blocks B] [--seed S]: verifies such a record with the host verifier alone, no GPU
 // Loads the circuit, runs the GKR proof on the GPU against the host verifier and prints the
 // reference's result lines (interactive mode runs the whole protocol incl. the Virgo commitment and its verification).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "circuit.hpp"
 #include "prover.hpp"
@@ -14,8 +18,13 @@
 
 int main(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "usage: %s <file.pws> [--blocks B] [--batched | --fs] [--device D] [--dump out.bin]\n", argv[0]); return 2; }
-    int blocks = 1, device = 0; bool batched = false, fsmode = false; const char *dump = nullptr;
-    for (int i = 2; i < argc; ++i) {
+    int blocks = 1, device = 0; bool batched = false, fsmode = false; const char *dump = nullptr, *record = nullptr, *check_record = nullptr;
+    int first = 2;
+    if (!strcmp(argv[1], "--check-record")) {
+        if (argc < 4) { fprintf(stderr, "usage: %s --check-record record.bin <file.pws> [--blocks B] [--seed S]\n", argv[0]); return 2; }
+        check_record = argv[2]; argv[1] = argv[3]; first = 4;
+    }
+    for (int i = first; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--blocks" && i + 1 < argc) blocks = atoi(argv[++i]);
         else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
@@ -23,6 +32,7 @@ int main(int argc, char **argv) {
         else if (a == "--fs") fsmode = true;
         else if (a == "--seed" && i + 1 < argc) srandom((unsigned) atol(argv[++i]));      // witness draw (default: glibc's initial state, as the reference)
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
+        else if (a == "--record" && i + 1 < argc) record = argv[++i];
         else { fprintf(stderr, "bad argument %s\n", argv[i]); return 2; }
     }
     std::vector<DAG_gate> dag;
@@ -31,6 +41,20 @@ int main(int argc, char **argv) {
     layeredCircuit c = vph::DAG_to_layered(dag);
     F::init();
     c.subsetInit();
+    if (check_record) {                              // the host verifier alone: same generator state as the run that wrote the record
+        std::vector<uint8_t> rec;
+        FILE *f = fopen(check_record, "rb");
+        if (!f) { fprintf(stderr, "cannot read %s\n", check_record); return 2; }
+        uint8_t buf[65536];
+        for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) rec.insert(rec.end(), buf, buf + k);
+        fclose(f);
+        bool ok = false;
+        try { verifier v(nullptr, c); ok = v.checkFull(rec); } catch (const std::exception &) { ok = false; }
+        if (!ok) { fprintf(stderr, "Verification fail\n"); return 1; }
+        fprintf(stderr, "Verification pass\n");
+        return 0;
+    }
+    if (record && (batched || fsmode || c.circuit[0].bitLength < 7)) { fprintf(stderr, "--record needs the interactive mode and an input layer of at least 2^7 wires\n"); return 2; }
     try {
         prover p(c, device);
         bool ok;
@@ -52,8 +76,14 @@ int main(int argc, char **argv) {
             vt = v.verifyTime();
         } else if (c.circuit[0].bitLength >= 7) {
             verifier v(&p, c);                       // the reference's flow: commitment on (src/verifier.cpp:134-189)
+            v.batched_openings = record != nullptr;
             ok = v.verifyFull();
             tr = v.fullTranscript();
+            if (ok && record) {
+                FILE *f = fopen(record, "wb");
+                if (!f || fwrite(v.fullRecord().data(), 1, v.fullRecord().size(), f) != v.fullRecord().size()) { fprintf(stderr, "cannot write %s\n", record); if (f) fclose(f); return 2; }
+                fclose(f);
+            }
             vt = v.verifyTime() + v.polyVerifyTime();
             pc_pt = v.polyProveTime();
         } else {

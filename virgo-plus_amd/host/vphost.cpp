@@ -16,6 +16,7 @@ struct vph_session {
     std::unique_ptr<prover> p;
     std::vector<F> tape;
     std::vector<uint8_t> fri_roots; std::vector<F> fri_final, fri_r;      // FRI commit phase of the last complete-protocol run
+    std::vector<uint8_t> full_record;                                     // record of the last accepted complete-protocol run (vph_last_full_record)
     std::vector<F> fft_gkr_msgs; double pc_times[3] = {0, 0, 0};          // fft_gkr messages; {PC prove (reference definition), of which fft_gkr, query answering}
     double t_init = 0, t_round = 0, t_fin = 0;
     std::vector<F> last_point;                                           // r_liu after the last Liu sumcheck of the last complete-protocol run
@@ -283,11 +284,17 @@ int vph_commit_public(vph_session *s, const uint64_t *pub_pairs, uint64_t n_pub,
 
 int vph_prove_and_verify_full(vph_session *s, int reps, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                               double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen) {
+    return vph_prove_and_verify_full_ex(s, reps, 0, transcript, capacity, n_written, gkr_prove_sec, pc_prove_sec, verify_sec, err, errlen);
+}
+int vph_prove_and_verify_full_ex(vph_session *s, int reps, int flags, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
+                                 double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen) {
     try {
         F::init();
         verifier v(s->p.get(), s->circ->c);
+        v.batched_openings = (flags & VPH_VERIFY_BATCHED_OPENINGS) != 0;
         const double t0 = s->p->proveTime();
         const bool ok = v.verifyFull(reps);
+        s->full_record = v.fullRecord();
         s->fri_roots = v.friRoots(); s->fri_final = v.friFinalCode(); s->fri_r = v.friChallenges();
         s->fft_gkr_msgs = v.fftGkrMessages();
         s->pc_times[0] = v.polyProveTime(); s->pc_times[1] = v.fftGkrProveTime(); s->pc_times[2] = v.polyOpenTime();
@@ -304,6 +311,22 @@ int vph_prove_and_verify_full(vph_session *s, int reps, uint8_t *transcript, uin
         set_err(err, errlen, e.what());
         return -2;
     }
+}
+
+int vph_last_full_record(vph_session *s, uint8_t *buf, uint64_t cap, uint64_t *n) {
+    if (!s || !n) return -1;
+    *n = s->full_record.size();
+    if (s->full_record.empty() || !buf || cap < s->full_record.size()) return -1;
+    memcpy(buf, s->full_record.data(), s->full_record.size());
+    return 0;
+}
+int vph_verify_full_record(vph_circuit *c, const uint8_t *record, uint64_t n) {
+    if (!c || !record) return 1;
+    try {
+        F::init();
+        verifier v(nullptr, c->c);
+        return v.checkFull(std::vector<uint8_t>(record, record + n)) ? 0 : 1;
+    } catch (const std::exception &) { return 1; }
 }
 
 // fft_gkr of the last vph_prove_and_verify_full: its messages ({real,img} pairs, layout of vp_fft_gkr); returns their number or -1

@@ -86,6 +86,26 @@ int vph_commit_public(vph_session *, const uint64_t *pub_pairs, uint64_t n_pub, 
  * layout (identical to the reference's up to all_sum); times in seconds.                                  */
 int vph_prove_and_verify_full(vph_session *, int reps, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                               double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen);
+/* The same with flags.  VPH_VERIFY_BATCHED_OPENINGS: the verifier draws all `reps` query positions first and the prover answers them in ONE device
+ * pass (vp_fri_query) instead of 2 + (n - 6) vp_fri_open calls per repetition; same positions, same openings, same checks.                     */
+enum { VPH_VERIFY_BATCHED_OPENINGS = 1 };
+int vph_prove_and_verify_full_ex(vph_session *, int reps, int flags, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
+                                 double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen);
+/* Record of the last ACCEPTED vph_prove_and_verify_full(_ex) of the session: everything the prover handed over, so that the whole verifier can run
+ * again later without a GPU.  All integers little-endian, field elements as {real, img} u64 pairs (canonical), n = bit length of the input layer:
+ *     header       16 bytes   u32 magic 0x52465056 ("VPFR") | u32 version = 1 | u32 n | u32 reps (1 .. 4096)
+ *     transcript              merkle_root_l[32] | GKR slice | merkle_root_h[32] | input_0[16] | all_sum[65 x 16]      (the golden layout)
+ *     fft_gkr      16 x (64 + 3 (2 lg^2 + 2 lg + 6) + 2 + 2 lg) bytes, lg = n - 6                                     (vp_fft_gkr's message layout)
+ *     FRI roots    32 x (n - 6) bytes
+ *     final code   2048 x 16 bytes                                                                                    (vp_fri_final's layout)
+ *     openings     vp_fri_query's bytes for the `reps` positions the verifier drew: per repetition oracle 0, oracle 1, level 0 .. n - 7, each
+ *                  130 values (2080 bytes) + its path at the true length (n - 1 digests for l and h, n - 2 - k for level k)
+ * vph_last_full_record: copies it to buf (*n = its size; -1 if there is none or cap is too small, *n still set).
+ * vph_verify_full_record: no GPU, no session.  F::init(), then verifier::checkFull: the GKR part as vph_verify_transcript, then the commitment's
+ * verifier reading the record while it draws every challenge and query position from the same seeded generator as the live run.  0 = accepted,
+ * 1 = rejected (also: short, long, another version, a non-canonical element, any byte changed).                                               */
+int vph_last_full_record(vph_session *, uint8_t *buf, uint64_t cap, uint64_t *n);
+int vph_verify_full_record(vph_circuit *, const uint8_t *record, uint64_t n);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
