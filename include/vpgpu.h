@@ -289,12 +289,20 @@ int vp_commit_public(vp_ctx *, const vp_F *pub, uint64_t n_pub, vp_F *inner_prod
  * `p->commit_public(pub, ...)`): the caller hands over the opening point (bit_length(layer 0) canonical coordinates) instead of its 2^n-entry
  * eq table, and the device builds eq(point, .) in HBM itself (src/utils.cpp:29-45) — nothing of the public vector crosses PCIe (134 MB at
  * n = 23).  Same outputs, same field elements as vp_commit_public(eq table of the point); an eq table is a tensor by construction, so the one-
- * slice encoding (pc_tensor_pub) applies without its check.  VP_EINVAL on a sharded commitment.                                       */
+ * slice encoding (pc_tensor_pub) applies without its check.  On a sharded commitment (vp_pc_set_shard) every rank passes the point and builds
+ * only what it needs: slice 0 and the 64 slice scalars for the one-slice encoding, and its share of the inner product straight from the two
+ * half tables (no part of the table is stored; with pc_tensor_pub = 0 the rank's own slices are expanded instead).  Collectives and VP_EXCHANGE
+ * as for vp_commit_public; outputs equal it byte for byte on every rank.  A masked commitment is refused.                                */
 int vp_commit_public_eq(vp_ctx *, const vp_F *point, int n_point, vp_F *inner_product_sum, vp_F all_sum[65], uint8_t root_h[32]);
 /* fri::commit_phase_step(r) (lib/virgo/src/fri.cpp:289-424), called n-6 times by poly_commit_prover::commit_phase
  * (vpd_verifier.cpp:44-74): fold the current codewords of all slices by r, hash the new leaves, build the Merkle
  * tree, return its root.  The first call builds the virtual oracle (poly_commit.h:294-318) from the data
- * vp_commit_public left in HBM.  VP_EINVAL once the codeword is down to 32 values per slice.            */
+ * vp_commit_public left in HBM.  VP_EINVAL once the codeword is down to 32 values per slice.
+ * On a sharded commitment (vp_pc_set_shard): every rank is called with the same r and returns the same root, the unsharded one.  Step 0
+ * carries the all-to-all of the virtual oracle; every step k < n_local = (n - 6) - log2(world) ends in one all-gather (the level-5 nodes of
+ * the level; at k = n_local - 1 the 2048 elements the rank is left with); later steps run replicated: 1 + n_local collectives in all.
+ * Without a communicator the call returns VP_EXCHANGE at each collective and is repeated with the same r after the exchange; a repeat
+ * before the exchange returns VP_EXCHANGE again and changes nothing.  Level k may be opened once step k has returned VP_OK.       */
 int vp_fri_step(vp_ctx *, const vp_F *r, uint8_t root[32]);
 /* The same n_steps calls of fri::commit_phase_step in ONE device pass (extension, like vp_prove_gkr: valid because the
  * reference verifier's challenges do not depend on the transcript, fieldElement.cpp:119-124): r[0..n_steps) in, the
@@ -322,10 +330,13 @@ int vp_fri_open(vp_ctx *, int oracle, uint64_t leaf, vp_F values[130], uint8_t *
 int vp_fri_open_many(vp_ctx *, int n, const int32_t *oracle, const uint64_t *leaf, vp_F *values /* n x 130 */, uint8_t *paths, int path_stride,
                      int32_t *path_len /* n */);
 /* The complete answer to n_queries repetitions of the verifier's query (vpd_verifier.cpp:119-306), after the commit phase has finished (VP_EINVAL
- * before; VP_EINVAL on a sharded commitment, whose caller merges vp_fri_open_many).  leaf0[q] is the leaf of the two first oracles (pow / 2); the
+ * before; VP_EINVAL on a sharded commitment after the one-pass vp_fri_commit, whose caller merges vp_fri_open_many).  leaf0[q] is the leaf of the two
+ * first oracles (pow / 2); the
  * leaf of every FRI level follows from it: t = leaf0, D = M = 2^(n-1); per level Dn = D / 2, leaf = t mod (Dn / 2), t = leaf, D = Dn.  Layout of
  * `out`, no headers: per query, in the order oracle 0, oracle 1, level 0 .. n - 7, the 130 values (2080 bytes) followed by that opening's path at
- * its true length (n - 1 digests for l and h, n - 2 - k for level k) in vp_fri_open's order.  vp_fri_query_bytes: the size of that answer.      */
+ * its true length (n - 1 digests for l and h, n - 2 - k for level k) in vp_fri_open's order.  vp_fri_query_bytes: the size of that answer.
+ * On a sharded commitment whose FRI phase ran step by step (vp_fri_step) the layout, the size and *n_written are the same on every rank; a rank writes the openings it owns at their places
+ * (one k_pc_open_many launch) and leaves every other byte of `out` untouched, as vp_fri_open_many does: the ranks' buffers merge into one.    */
 int vp_fri_query_bytes(vp_ctx *, int n_queries, uint64_t *bytes);
 int vp_fri_query(vp_ctx *, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written);
 /* fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp:833-849), prover side: the self-contained GKR over the inverse-FFT +
@@ -393,13 +404,16 @@ int vp_commit_private_state(vp_ctx *, uint64_t *epoch, int *valid);
 
 /* ---- commitment sharded over the GPUs of a node (SURVEY.md §8e "PC sharding"; north_star "FFT subtrees shard") ---------------- */
 /* After vp_pc_set_shard(rank, world) (world a power of two <= 64 with 2^(n-6) >= 2 world) the SAME entry points vp_commit_private /
- * vp_commit_public / vp_fri_commit / vp_fri_final / vp_fri_open work on this rank's share of the commitment: rank r transforms
+ * vp_commit_public / vp_commit_public_eq / vp_fri_step / vp_fri_commit / vp_fri_final / vp_fri_open / vp_fri_open_many / vp_fri_query work on
+ * this rank's share of the commitment: rank r transforms
  * slices [64 r / world, 64 (r+1) / world) (the 64 slices are independent transforms, lib/virgo/src/poly_commit.h:89-107), ONE
  * all-to-all per committed oracle hands every rank the positions a = rank (mod world) of ALL slices (a leaf chains all 64 slices at a
  * position pair, lib/virgo/src/fri.cpp:81-124), the rank hashes its leaves and five tree levels, the level-5 nodes are all-gathered and
  * every rank builds the top of the tree (merkle_tree.cpp:7-51): all ranks return the same root, equal to the unsharded one.  FRI folds
  * stay local (fold partners a, a + N_k/2 share their low bits) until one position per rank is left.  Every rank passes the same `pub`
- * / `r`; vp_fri_commit must be given all n-6 challenges.  vp_fri_open is answered by the owner of the leaf, rank (leaf >> 5) mod world
+ * / `r`; vp_fri_commit must be given all n-6 challenges (vp_fri_step takes them one by one, with one collective per local level).  The context
+ * may also hold a circuit and a round shard (vp_set_round_shard); a round gather and a commitment collective pending at the same time is
+ * VP_EINVAL.  vp_fri_open is answered by the owner of the leaf, rank (leaf >> 5) mod world
  * (VP_EINVAL elsewhere); levels of the last log2(world) folds are replicated.
  * Collectives: over RCCL when vp_comm_init attached a communicator; otherwise a call returns VP_EXCHANGE at each collective and
  * vp_shard_exchange_local(ctxs, world) performs the pending ones among contexts of ONE process (parity tests: W ranks on one GPU).
@@ -407,6 +421,9 @@ int vp_commit_private_state(vp_ctx *, uint64_t *epoch, int *valid);
 int vp_pc_load_input(vp_ctx *, const vp_F *inputs, uint64_t n_inputs, int bit_length);
 int vp_pc_set_shard(vp_ctx *, int rank, int world);
 int vp_shard_exchange_local(vp_ctx **ctxs, int world);
+/* Who answers leaf `leaf` of `oracle` (vp_fri_open's numbering) on a sharded commitment: the rank, or -1 for a level every rank holds whole
+ * (the last log2(world) + 1 FRI levels); 0 on an unsharded context.                                                                  */
+int vp_pc_shard_owner(vp_ctx *, int oracle, uint64_t leaf);
 /* vp_shard_exchange_local and the calls below also serve the gather of round-sharded contexts (vp_set_round_shard): one kind-2 collective.
  * The same pending collectives through a CALLER-SUPPLIED transport — ranks in different processes without RCCL (more ranks than GPUs in a
  * rehearsal, CPU tests over gloo): after VP_EXCHANGE, for i < *n: vp_shard_exchange_info gives kind (1 all-to-all, 2 all-gather) and bytes (per

@@ -154,6 +154,10 @@ def lib_gpu():
         L.vp_commit_public.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp]
         L.vp_commit_public_eq.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
         L.vp_fri_commit.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.vp_fri_step.argtypes = [vp, vp, vp]
+        L.vp_commit_private_masked.argtypes = [vp, vp, ctypes.c_uint64, vp]
+        L.vp_shard_pending.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        L.vp_pc_shard_owner.argtypes = [vp, ctypes.c_int, ctypes.c_uint64]
         L.vp_fri_final.argtypes = [vp, vp]
         L.vp_fri_open.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         L.vp_fri_open_many.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp]
@@ -204,6 +208,12 @@ def lib_host():
         L.vph_session_create_opts.argtypes = [vp, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_session_create_round_sharded.restype = vp
         L.vph_session_create_round_sharded.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_session_create_sharded.restype = vp
+        L.vph_session_create_sharded.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_commit_private_masked.argtypes = [vp, vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
+        L.vph_commit_public_eq.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
+        L.vph_fri_open_many.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_fri_query.argtypes = [vp, ctypes.c_int, vp, vp, u64, ctypes.POINTER(u64), ctypes.c_char_p, ctypes.c_int]
         L.vph_session_rank_ctx.restype = vp
         L.vph_session_rank_ctx.argtypes = [vp, ctypes.c_int]
         L.vph_session_world.argtypes = [vp]
@@ -666,12 +676,19 @@ class Session:
     """One prover on one GPU: circuit resident in HBM, witness evaluated on the device.
 
     devices + round_shard_min_log: the interactive sumchecks of one proof sharded by index over len(devices) ranks (1, 2, 4 or 8; a device may
-    repeat), one context per rank (include/vpgpu.h: vp_set_round_shard).  The prove_* calls work unchanged; `device` is then ignored."""
+    repeat), one context per rank (include/vpgpu.h: vp_set_round_shard).  The prove_* calls work unchanged; `device` is then ignored.
 
-    def __init__(self, circuit, device=0, options=None, devices=None, round_shard_min_log=None):
+    shard_commitment=True (with devices): the Virgo commitment is sharded over the same ranks as well (vp_pc_set_shard) — commit_private / commit_public /
+    commit_public_eq, the FRI commit phase and every opening run on all ranks, so prove_full, prove_and_verify_full, fri_commit, fri_open_many and
+    fri_query work unchanged.  Raises when the input layer is too short for the ranks; masks and prove_protocol are not available on such a session."""
+
+    def __init__(self, circuit, device=0, options=None, devices=None, round_shard_min_log=None, shard_commitment=False):
         err = ctypes.create_string_buffer(512)
         if (devices is None) != (round_shard_min_log is None):
             raise ValueError("Session: devices and round_shard_min_log go together")
+        if shard_commitment and devices is None:
+            raise ValueError("Session: shard_commitment needs devices and round_shard_min_log")
+        self._shard_pc = bool(shard_commitment) and len(devices) > 1
         self.circuit = circuit
         keep = {}
         for k, v in (options.tuning_env() if options is not None else {}).items():          # internal knobs: the library reads them from the environment at vp_create
@@ -683,7 +700,8 @@ class Session:
                 self.h = lib_host().vph_session_create_opts(circuit.h, device, opt, err, len(err))
             else:
                 devs = (ctypes.c_int * max(1, len(devices)))(*devices)
-                self.h = lib_host().vph_session_create_round_sharded(circuit.h, devs, len(devices), int(round_shard_min_log), opt, err, len(err))
+                self.h = lib_host().vph_session_create_sharded(circuit.h, devs, len(devices), int(round_shard_min_log), 1 if shard_commitment else 0, opt,
+                                                               err, len(err))
         finally:
             for k, v in keep.items():
                 if v is None:
@@ -913,12 +931,18 @@ class Session:
             raise RuntimeError("shard_chains failed")
         return owner[:n].copy(), cost[:n].copy()
 
-    def commit_private(self):
-        """prover::commit_private(): (32-byte Merkle root, device milliseconds)."""
+    def commit_private(self, mask=None):
+        """prover::commit_private(): (32-byte Merkle root, device milliseconds).  mask: (k, 2) uint64, the mask vector of lib/virgo's
+        commit_private_array (a non-zero one fills the 65th slice; refused on a sharded commitment)."""
         root = ctypes.create_string_buffer(32)
         ms = ctypes.c_double(0)
         err = ctypes.create_string_buffer(512)
-        rc = lib_host().vph_commit_private(self.h, ctypes.cast(root, ctypes.c_void_p), ctypes.byref(ms), err, len(err))
+        if mask is not None:
+            import numpy as np
+            mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(-1, 2)
+            rc = lib_host().vph_commit_private_masked(self.h, mask.ctypes.data, mask.shape[0], ctypes.cast(root, ctypes.c_void_p), ctypes.byref(ms), err, len(err))
+        else:
+            rc = lib_host().vph_commit_private(self.h, ctypes.cast(root, ctypes.c_void_p), ctypes.byref(ms), err, len(err))
         if rc:
             raise RuntimeError("commit_private failed: " + err.value.decode())
         return root.raw, ms.value
@@ -952,6 +976,12 @@ class Session:
         import numpy as np
         point = np.ascontiguousarray(point, dtype=np.uint64)
         out = ctypes.create_string_buffer(32 + 16 + 65 * 16)
+        if self._shard_pc:                                  # every rank is handed the point
+            ms = ctypes.c_double(0)
+            err = ctypes.create_string_buffer(512)
+            if lib_host().vph_commit_public_eq(self.h, point.ctypes.data, point.shape[0], ctypes.cast(out, ctypes.c_void_p), ctypes.byref(ms), err, len(err)):
+                raise RuntimeError("vp_commit_public_eq failed: " + err.value.decode())
+            return out.raw[:32], out.raw[32:48], out.raw[48:], ms.value
         ctx = lib_host().vph_session_ctx(self.h)
         base = ctypes.addressof(out)
         rc = lib_gpu().vp_commit_public_eq(ctx, point.ctypes.data, point.shape[0], base + 32, base + 48, base)
@@ -1027,6 +1057,18 @@ class Session:
     def fri_open_many(self, requests, path_stride=OPEN_PATH_STRIDE):
         """vp_fri_open_many on this session's commitment: requests = sequence of (oracle, leaf); returns (values (n, 130, 2) uint64,
         paths (n, path_stride) uint8, path_len (n,) int32).  Raises on a refused list."""
+        if self._shard_pc:                                  # asked of every rank and merged
+            import numpy as np
+            n = len(requests)
+            oracle = np.ascontiguousarray([r[0] for r in requests], dtype=np.int32).reshape(n)
+            leaf = np.ascontiguousarray([r[1] for r in requests], dtype=np.uint64).reshape(n)
+            v = np.zeros((max(n, 1), 130, 2), dtype=np.uint64)
+            p = np.zeros((max(n, 1), max(path_stride, 1)), dtype=np.uint8)
+            pl = np.zeros(max(n, 1), dtype=np.int32)
+            err = ctypes.create_string_buffer(512)
+            if lib_host().vph_fri_open_many(self.h, n, oracle.ctypes.data, leaf.ctypes.data, v.ctypes.data, p.ctypes.data, path_stride, pl.ctypes.data, err, len(err)):
+                raise RuntimeError("vp_fri_open_many failed: " + err.value.decode())
+            return v[:n], p[:n], pl[:n]
         ctx = self.gpu_ctx()
         rc, v, p, pl = fri_open_many(ctx, requests, path_stride)
         if rc:
@@ -1035,6 +1077,17 @@ class Session:
 
     def fri_query(self, leaf0):
         """vp_fri_query: the complete answer to len(leaf0) query repetitions as bytes (layout: include/vpgpu.h)."""
+        if self._shard_pc:                                  # every rank fills in the openings it owns
+            import numpy as np
+            leaf0 = np.ascontiguousarray(leaf0, dtype=np.uint64)
+            n_bits = self.circuit.layer_bitlen(0)
+            cap = leaf0.shape[0] * sum(2080 + 32 * d for d in [n_bits - 1, n_bits - 1] + [n_bits - 2 - k for k in range(n_bits - 6)])
+            out = ctypes.create_string_buffer(max(cap, 1))
+            n = ctypes.c_uint64(0)
+            err = ctypes.create_string_buffer(512)
+            if lib_host().vph_fri_query(self.h, leaf0.shape[0], leaf0.ctypes.data, ctypes.cast(out, ctypes.c_void_p), cap, ctypes.byref(n), err, len(err)):
+                raise RuntimeError("vp_fri_query failed: " + err.value.decode())
+            return out.raw[: n.value]
         ctx = self.gpu_ctx()
         rc, out = fri_query(ctx, leaf0)
         if rc:

@@ -92,6 +92,8 @@ struct RoundShard {
 struct PcShard;            // commitment sharded over ranks (vpgpu_pc_shard.inc)
 struct FgkState;           // buffers of vp_fft_gkr (vpgpu_fftgkr.inc)
 struct VpComm;             // RCCL communicator (vpgpu_pc_shard.inc)
+struct vp_ctx;
+bool vp_pc_shard_pending(const vp_ctx *ctx);   // a collective of the sharded commitment waits for its exchange (vpgpu_pc_shard.inc)
 // One in-order chain of the batched proof: its own stream and scratch, so that independent sumchecks
 // (all of them, given the tape, except phase 1 -> phase 2 of the same layer) overlap on the device.
 struct Lane {
@@ -661,6 +663,7 @@ int rs_pack(vp_ctx *ctx) {
     const RsGather g = rs_gather_args(ctx, k);
     const size_t blk = (size_t) g.comps * g.N;
     if (blk > R.cap) { ctx->err = "internal: round-shard gather buffers smaller than the block"; return VP_EINVAL; }      // sized by rs_split
+    if (vp_pc_shard_pending(ctx)) { ctx->err = "round shard: a collective of the sharded commitment is pending on this context"; return VP_EINVAL; }
     hipLaunchKernelGGL(k_rs_pack, dim3(nblk(g.N)), dim3(VP_BLOCK), 0, ctx->stream, g, R.send);
     count_launch(ctx);
     VPCHK(check_stream(ctx));                  // the block is complete before any transport reads it

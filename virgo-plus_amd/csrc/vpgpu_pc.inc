@@ -375,8 +375,13 @@ int pc_merkle(vp_ctx *ctx, Dig *tree, u32 n_leaves) {    // leaves already at tr
 
 // the same entry points on a commitment sharded over ranks (vpgpu_pc_shard.inc)
 int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]);
-int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]);
+int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]);
 int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots);
+int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]);
+bool pcs_private_done(vp_ctx *ctx);
+bool pcs_public_done(vp_ctx *ctx);
+int pcs_fri_done(vp_ctx *ctx);
+bool pcs_fri_one_pass(vp_ctx *ctx);
 int pcs_fri_final(vp_ctx *ctx, vp_F *final_code);
 int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len);
 int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d);
@@ -424,11 +429,11 @@ static int pc_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     return VP_OK;
 }
 static inline int pc_open_depth(u32 n_leaves) { int depth = 0; while ((1u << depth) < n_leaves) ++depth; return depth; }
-struct PcManyPlan { PcOpenDesc tab[VP_OPEN_MAX_ORACLES]; std::vector<int> plen; u64 bytes = 0; };   // plen[i]: digests of request i's path, 0 = another rank's
+struct PcManyPlan { PcOpenDesc tab[VP_OPEN_MAX_ORACLES]; std::vector<int> plen, dlen; u64 bytes = 0, layout = 0; };   // plen[i]: digests of request i's path, 0 = another rank's; dlen[i]: whoever answers; bytes: this rank's answers, layout: all
 // Validation of a whole list (nothing is launched or written on a refusal).  path_stride < 0: no capacity rule (vp_fri_query packs paths itself).
 static int pc_many_plan(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_t *leaf, int path_stride, PcManyPlan &pl) {
     int have[VP_OPEN_MAX_ORACLES]; for (int &h : have) h = 0;       // 0 unknown, 1 described
-    pl.plen.assign((size_t) n, 0); pl.bytes = 0;
+    pl.plen.assign((size_t) n, 0); pl.dlen.assign((size_t) n, 0); pl.bytes = pl.layout = 0;
     for (auto &t : pl.tab) t = PcOpenDesc{};
     for (int i = 0; i < n; ++i) {
         const int o = oracle[i];
@@ -439,6 +444,8 @@ static int pc_many_plan(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_
         const int depth = pc_open_depth(d.n_leaves);
         if (depth + 1 > VP_OPEN_MAX_PATH) return VP_ELIMIT;
         if (path_stride >= 0 && path_stride < 32 * (depth + 1)) return VP_EINVAL;
+        pl.dlen[i] = depth + 1;
+        pl.layout += 130 * sizeof(F) + 32ull * (depth + 1);
         if (d.top && !pcs_owns(ctx, leaf[i])) continue;
         pl.plen[i] = depth + 1;
         pl.bytes += 130 * sizeof(F) + 32ull * (depth + 1);
@@ -797,7 +804,7 @@ static int pc_warm(vp_ctx *ctx) {
     return VP_OK;
 }
 static int pc_commit_public_host(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32], const vp_F *pub_mask, uint64_t n_pub_mask) {
-    if (ctx->pcs) { if (pub_mask) { ctx->err = "masked commitment: not on a sharded commitment"; return VP_EINVAL; } return pcs_commit_public(ctx, pub, n_pub, inner, all_sum, root_h); }
+    if (ctx->pcs) { if (pub_mask) { ctx->err = "masked commitment: not on a sharded commitment"; return VP_EINVAL; } return pcs_commit_public(ctx, pub, n_pub, nullptr, inner, all_sum, root_h); }
     if (!ctx->pc_private_done) return VP_EINVAL;
     const int n = ctx->L[0].bl;
     if (n_pub != (1ull << n)) return VP_EINVAL;
@@ -835,12 +842,13 @@ int vp_commit_public_masked(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const 
 int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
     if (!ctx || !ctx->evaluated || !point || !inner || !all_sum || !root_h) return VP_EINVAL;
     VP_ENTER_Q(ctx);
-    if (ctx->pcs) { ctx->err = "vp_commit_public_eq: not available on a sharded commitment (hand the eq table to vp_commit_public)"; return VP_EINVAL; }
     if (ctx->pc_mask_ms) { ctx->err = "vp_commit_public_eq: the private commitment carries a mask (vp_commit_public_masked)"; return VP_EINVAL; }
-    if (!ctx->pc_private_done) return VP_EINVAL;
+    if (!(ctx->pcs ? pcs_private_done(ctx) : ctx->pc_private_done)) return VP_EINVAL;
     const int n = ctx->L[0].bl;
     if (n_point != n) return VP_EINVAL;
     for (int i = 0; i < n; ++i) if (point[i].real >= P61 || point[i].img >= P61) { ctx->err = "vp_commit_public_eq: non-canonical coordinate"; return VP_EINVAL; }
+    // a sharded commitment: every rank is handed the point and builds what it needs of the table itself (pcs_commit_public)
+    if (ctx->pcs) { VPCHK(flush_pending(ctx, (size_t) -1)); return pcs_commit_public(ctx, nullptr, 0, point, inner, all_sum, root_h); }
     const u32 N = 1u << (n - 6);
     VPCHK(pc_public_alloc(ctx));
     // the public vector never crosses PCIe: eq(point, .) is built where it is consumed (two half tables by one workgroup, then one
@@ -876,8 +884,9 @@ int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner
 }
 
 int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
-    if (ctx && ctx->pcs) { ctx->err = "sharded commitment: the FRI commit phase runs as one pass (vp_fri_commit)"; return VP_EINVAL; }
-    if (!ctx || !ctx->pc_public_done || !r || !root) return VP_EINVAL;
+    if (!ctx || !r || !root) return VP_EINVAL;
+    if (ctx->pcs) { VP_ENTER(ctx); return pcs_fri_step(ctx, r, root); }
+    if (!ctx->pc_public_done) return VP_EINVAL;
     VP_ENTER(ctx);
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
@@ -1159,10 +1168,12 @@ int vp_fri_open_many(vp_ctx *ctx, int n, const int32_t *oracle, const uint64_t *
 
 // requests of `n_queries` repetitions in vp_fri_query's order: oracle 0, oracle 1, level 0 .. ln - 1 along the leaf chain of host/verifier.cpp
 static int pc_query_requests(vp_ctx *ctx, int n_queries, const uint64_t *leaf0, std::vector<int32_t> &oracle, std::vector<uint64_t> &leaf) {
-    if (ctx->pcs) { ctx->err = "vp_fri_query: not on a sharded commitment (merge vp_fri_open_many over the ranks)"; return VP_EINVAL; }
-    if (ctx->L.empty() || !ctx->pc_public_done) return VP_EINVAL;
+    // a sharded commitment: the drop-in state machine (vp_fri_step) is answered here; after the one-pass vp_fri_commit the calling pattern stays the
+    // one-pass one, whose caller merges vp_fri_open_many over the ranks, as before
+    if (ctx->pcs && pcs_fri_one_pass(ctx)) { ctx->err = "vp_fri_query: not after vp_fri_commit on a sharded commitment (merge vp_fri_open_many over the ranks)"; return VP_EINVAL; }
+    if (ctx->L.empty() || !(ctx->pcs ? pcs_public_done(ctx) : ctx->pc_public_done)) return VP_EINVAL;
     const int ln = ctx->L[0].bl - 6;
-    if (ctx->fri_step != ln) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
+    if ((ctx->pcs ? pcs_fri_done(ctx) : ctx->fri_step) != ln) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
     if ((u64) n_queries * (u64) (2 + ln) > (u64) PC_MANY_MAX) { ctx->err = "vp_fri_query: more than 2^16 openings"; return VP_ELIMIT; }
     const u64 M = 1ull << (ctx->L[0].bl - 1);
     oracle.clear(); leaf.clear();
@@ -1182,7 +1193,7 @@ int vp_fri_query_bytes(vp_ctx *ctx, int n_queries, uint64_t *bytes) {
     VPCHK(pc_query_requests(ctx, n_queries, nullptr, oracle, leaf));
     PcManyPlan pl;
     VPCHK(pc_many_plan(ctx, (int) oracle.size(), oracle.data(), leaf.data(), -1, pl));
-    *bytes = pl.bytes;
+    *bytes = pl.layout;
     return VP_OK;
 }
 int vp_fri_query(vp_ctx *ctx, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written) {
@@ -1193,14 +1204,16 @@ int vp_fri_query(vp_ctx *ctx, int n_queries, const uint64_t *leaf0, uint8_t *out
     const int n = (int) oracle.size();
     PcManyPlan pl;
     VPCHK(pc_many_plan(ctx, n, oracle.data(), leaf.data(), -1, pl));
-    if (pl.bytes > capacity) { ctx->err = "vp_fri_query: output buffer too small (vp_fri_query_bytes)"; return VP_EINVAL; }
+    // the layout is the unsharded one on every rank of a sharded commitment: a rank writes the openings it owns at their places and leaves the
+    // other bytes alone (the rule of vp_fri_open_many), so the ranks' buffers merge into one
+    if (pl.layout > capacity) { ctx->err = "vp_fri_query: output buffer too small (vp_fri_query_bytes)"; return VP_EINVAL; }
     std::vector<u64> at((size_t) n + 1, 0);
-    for (int i = 0; i < n; ++i) at[i + 1] = at[i] + 130 * sizeof(F) + 32ull * pl.plen[i];
+    for (int i = 0; i < n; ++i) at[i + 1] = at[i] + 130 * sizeof(F) + 32ull * pl.dlen[i];
     VPCHK(pc_many_run(ctx, n, oracle.data(), leaf.data(), pl, [&](int i, const PcOpenRec &r) {
         memcpy(out + at[i], r.v, 130 * sizeof(F));
         memcpy(out + at[i] + 130 * sizeof(F), r.path, 32 * (size_t) pl.plen[i]);
     }));
-    *n_written = pl.bytes;
+    *n_written = pl.layout;
     return VP_OK;
 }
 

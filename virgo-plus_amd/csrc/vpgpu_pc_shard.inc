@@ -15,6 +15,7 @@
 //     tree: all ranks know the root, any rank can answer the upper part of an opening;
 //   * the FRI commit phase folds locally until one position per rank is left, all-gathers that 64 x 32 x W tail together
 //     with the level-5 nodes of every level, and finishes the last log2 W levels redundantly on every rank.
+//     vp_fri_step takes the challenges one by one instead (pcs_fri_step): the same folds and hashes, one all-gather per local level.
 // Bytes on the wire for an input layer of 2^n wires: each all-to-all moves 64*2^(n-1)*16 B in total ((W-1)/W of it leaves
 // its GPU): n = 23, W = 8: 4.3 GB per oracle, 67 MB per ordered pair of GPUs; the all-gathers move 2^(n-7)*32 B (2 MB at n = 23).
 //
@@ -42,6 +43,10 @@ struct PcShard {
     unsigned char *ag_send = nullptr, *ag_recv = nullptr; size_t ag_cap = 0;
     Dig *d_roots = nullptr;
     int n_local = 0, n_steps = 0;
+    int f_done = 0, f_mode = 0;                             // FRI levels committed (openable); how: 0 none yet, 1 one pass (vp_fri_commit), 2 step by step (vp_fri_step)
+    F step_r;                                               // the vp_fri_step in flight: its challenge
+    float acc_ms = 0;                                       // the call in flight: device time of its parts before the collectives it stopped at
+    F *eq = nullptr; F pt[32];                              // vp_commit_public_eq: point | two eq half tables on the device; the point of the call in flight
     std::vector<F> fri_r;
     bool private_done = false, public_done = false;
     // tensor public vector (round 4; vpgpu_pc.inc: pc_commit_public_body): slice 0 | this rank's slices on the device for the exact check, the ONE
@@ -71,6 +76,7 @@ struct VpComm {
 extern "C" bool vp_comm_attached(const vp_ctx *ctx) { return ctx && ctx->cm && ctx->cm->comm; }
 extern "C" bool vp_comm_matches(const vp_ctx *ctx, int rank, int world) { return ctx && ctx->cm && ctx->cm->comm && ctx->cm->rank == rank && ctx->cm->world == world; }
 void vp_free_shard_state(vp_ctx *ctx) { delete ctx->pcs; ctx->pcs = nullptr; }
+bool vp_pc_shard_pending(const vp_ctx *ctx) { return ctx->pcs && ctx->pcs->nx; }
 void vp_free_comm(vp_ctx *ctx) {
     if (ctx->cm) { if (ctx->cm->comm && ctx->cm->fn_comm_destroy) ctx->cm->fn_comm_destroy(ctx->cm->comm); delete ctx->cm; ctx->cm = nullptr; }
 }
@@ -103,6 +109,47 @@ __global__ void __launch_bounds__(VP_BLOCK) k_pc_sum_gathered(const F *__restric
     F s = f_zero();
     for (u32 r = 0; r < n; ++r) s = f_add(s, in[(size_t) r * stride]);
     *out = s;
+}
+
+// vp_commit_public_eq on a shard: entries [base, base + count) of the eq table from its two half tables (k_beta_expand with an offset) ...
+__global__ void __launch_bounds__(VP_BLOCK) k_pc_eq_range(const F *__restrict__ bf, const F *__restrict__ bs, int h1, u64 base, u32 count, F *__restrict__ out) {
+    const u32 mask = (1u << h1) - 1;
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        const u64 g = base + i;
+        out[i] = f_mul(bf[(u32) g & mask], bs[(u32) (g >> h1)]);
+    }
+}
+// ... and k_pc_dot against that range without storing it: x streams from HBM, the half tables (2^(n/2) entries each) stay in L2
+__global__ void __launch_bounds__(VP_BLOCK) k_pc_dot_eq(const F *__restrict__ x, const F *__restrict__ bf, const F *__restrict__ bs, int h1, u64 base, u32 n, F *part) {
+    __shared__ F lds[4];
+    const u32 mask = (1u << h1) - 1;
+    F acc[1] = {f_zero()};
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const u64 g = base + i;
+        acc[0] = f_add(acc[0], f_mul(x[i], f_mul(bf[(u32) g & mask], bs[(u32) (g >> h1)])));
+    }
+    block_sum<1>(acc, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
+}
+
+// a pending gather of the round shard (vp_set_round_shard) and a commitment collective cannot both be open on one context
+int pcs_guard(vp_ctx *ctx) {
+    if (ctx->rsh && ctx->rsh->nx) { ctx->err = "sharded commitment: a round-shard gather is pending on this context"; return VP_EINVAL; }
+    return VP_OK;
+}
+
+// A call stops at a collective the caller performs (VP_EXCHANGE): the device time of the part that ends here counts towards vp_commit_stats, the wait for
+// the exchange (with several ranks on one GPU: the other ranks' work) does not.  pcs_resume starts the next part's clock.
+int pcs_pause(vp_ctx *ctx) {
+    HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+    VPCHK(check_stream(ctx));
+    float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->pcs->acc_ms += ms;
+    return VP_OK;
+}
+int pcs_resume(vp_ctx *ctx) {
+    if (ctx->pcs->stage == 0) ctx->pcs->acc_ms = 0;
+    else HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+    return VP_OK;
 }
 
 // five tree levels above the local leaves (local leaf order 32a' + b: the 32 cosets of a position are one subtree)
@@ -148,6 +195,7 @@ int pcs_alloc(vp_ctx *ctx, int ln, int lm) {
     VPCHK(dalloc(ctx, &s.pub0, (S + 1) * N));                 // [slice 0][own slices]: s.pub points behind slice 0
     s.pub = s.pub0 + N;
     VPCHK(dalloc(ctx, &s.q0cw, 32 * N)); VPCHK(dalloc(ctx, &s.qscal, (size_t) 64)); VPCHK(dalloc(ctx, &s.flag, (size_t) 1));
+    VPCHK(dalloc(ctx, &s.eq, (size_t) 32 + 2 * ((size_t) 1 << ((ln + 6 + 1) / 2))));       // point | two eq half tables (as pc_public_alloc)
     VPCHK(dalloc(ctx, &s.send, S * 32 * N)); s.send_cap = S * 32 * N;
     VPCHK(dalloc(ctx, &s.l_loc, 64 * 32 * Nl)); VPCHK(dalloc(ctx, &s.h_loc, 64 * 32 * Nl)); VPCHK(dalloc(ctx, &s.fri_loc, 2 * 64 * 32 * Nl));
     VPCHK(dalloc(ctx, &s.tree_l, 32 * Nl)); VPCHK(dalloc(ctx, &s.tree_h, 32 * Nl)); VPCHK(dalloc(ctx, &s.tree_f, 32 * Nl));       // 2 * n_leaves_local, n_leaves_local = 16 Nl
@@ -186,7 +234,9 @@ int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]) {
     PcShard &s = *ctx->pcs;
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, Nl = N >> s.lw;
+    VPCHK(pcs_guard(ctx));
     if (s.op != 1) { s.op = 1; s.stage = 0; }
+    VPCHK(pcs_resume(ctx));
     for (;;) {
         if (s.stage == 0) {
             VPCHK(pc_root_table(ctx, lm));
@@ -200,36 +250,50 @@ int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]) {
             s.x[0] = {1, s.send, s.l_loc, (size_t) s.S * 32 * Nl * sizeof(F)}; s.nx = 1;
             s.stage = 1;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else if (s.stage == 1) {
             VPCHK(pcs_hash_local(ctx, s.l_loc, Nl, s.tree_l, 0));
             s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) (Nl >> 1) * 32}; s.nx = 1;
             s.stage = 2;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else {
             VPCHK(pcs_top(ctx, s.ag_recv, (size_t) (Nl >> 1) * 32, 0, Nl, s.top_l));
             HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
             HIPCHK(hipMemcpyAsync(root, s.top_l + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
             VPCHK(check_stream(ctx));
             if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = ms;
+            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
             s.op = 0; s.stage = 0; s.private_done = true;
             return VP_OK;
         }
     }
 }
 
-int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
+// vp_commit_public (pub: the whole vector on the host) or vp_commit_public_eq (pub == nullptr, point: n coordinates, checked by the caller).  With a point
+// nothing of the public vector crosses PCIe and none of it is stored: an eq table is a tensor by construction, so the rank needs slice 0 (the first N
+// entries, expanded from the two half tables), the 64 scalars eq(r_hi, i) / eq(r_hi, 0) (formed on the host from the point) and its share of
+// <V_0, eq(point, .)>, which k_pc_dot_eq takes from the half tables entry by entry.  The outputs are the field elements vp_commit_public gives for the table.
+int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
     PcShard &s = *ctx->pcs;
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
-    if (!s.private_done || n_pub != (1ull << n)) return VP_EINVAL;
+    if (!s.private_done || (pub && n_pub != (1ull << n))) return VP_EINVAL;
+    VPCHK(pcs_guard(ctx));
     if (s.op != 2) { s.op = 2; s.stage = 0; }
+    VPCHK(pcs_resume(ctx));
     const size_t sums_at = (size_t) (Nl >> 1) * 32;                      // staging layout of stage 1: [level-5 nodes][66 sums]
     for (;;) {
         if (s.stage == 0) {
-            HIPCHK(hipMemcpyAsync(s.pub, reinterpret_cast<const F *>(pub) + (size_t) s.rank * S * N, (size_t) S * N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+            s.f_done = 0; s.f_mode = 0; s.n_steps = 0;                   // the FRI phase of an earlier public vector is gone
+            const int h1 = n >> 1;
+            F *dr = s.eq, *dbf = s.eq + 32, *dbs = dbf + ((size_t) 1 << ((n + 1) / 2));
+            if (pub) HIPCHK(hipMemcpyAsync(s.pub, reinterpret_cast<const F *>(pub) + (size_t) s.rank * S * N, (size_t) S * N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+            else {
+                for (int i = 0; i < n; ++i) s.pt[i] = f_make(point[i].real, point[i].img);
+                s.pt[n] = f_one();
+                HIPCHK(hipMemcpyAsync(dr, s.pt, (size_t) (n + 1) * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+            }
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
             F *P = s.tmp, *ST = s.tmp + (size_t) 2 * S * N, *H = s.tmp + (size_t) 4 * S * N;
@@ -237,27 +301,51 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner,
             // partial inner product over this rank's slices (slice i = input wires [i N, (i+1) N))
             const u64 lo = (u64) s.rank * S * N, used = ctx->L[0].size > lo ? std::min<u64>(ctx->L[0].size - lo, (u64) S * N) : 0;
             const u32 g = std::max<u32>(1, std::min<u32>(1024, nblk(used)));
-            hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, s.pub, (u32) used, parts);
+            if (pub) hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, s.pub, (u32) used, parts);
+            else {
+                hipLaunchKernelGGL(k_beta_half, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dr, n, (const F *) (dr + n), dbf, dbs);
+                PC_PROF(VP_K_PC_POINTWISE, g, 1, 16ull * used, used,
+                        hipLaunchKernelGGL(k_pc_dot_eq, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, (const F *) dbf, (const F *) dbs, h1, lo, (u32) used, parts));
+            }
             hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, parts, g, d_inner);
             // The protocol's public vector is a tensor (eq table of the opening point, src/verifier.cpp:368-369): slice i = c_i x slice 0.  Checked
             // exactly on the device for THIS rank's slices against slice 0 (pub[i N + k] pub[0] == pub[i N] pub[k]); when it holds, only slice 0 is
             // encoded (on every rank: 32 transforms instead of 32 S) and q_i = c_i q_0 is formed where it is consumed.  The ranks need not agree:
             // either way a rank's slices come out as the same field elements.
             const F *hp = reinterpret_cast<const F *>(pub);
-            s.q_tensor = false;
-            if (ctx->opt.pc_tensor_pub && (hp[0].re | hp[0].im) != 0 && hp[0].re < P61 && hp[0].im < P61) {
-                HIPCHK(hipMemcpyAsync(s.pub0, hp, (size_t) N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(hipMemsetAsync(s.flag, 0, sizeof(int), ctx->stream));
-                hipLaunchKernelGGL(k_pc_rank1_check, dim3(nblk((u64) (S + 1) * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) s.pub0, N, S + 1, s.flag);
-                int bad = 1;
-                HIPCHK(hipMemcpyAsync(&bad, s.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));
-                s.q_tensor = bad == 0;
+            F corner[64];                                                // corner[i] = pub[i N]; of an eq table: the host's own product (vp_commit_public_eq)
+            if (pub) for (int i = 0; i < 64; ++i) corner[i] = hp[(size_t) i * N];
+            else {
+                F low = f_one();
+                for (int k = 0; k < ln; ++k) low = f_mul(low, f_sub(f_one(), s.pt[k]));
+                for (int i = 0; i < 64; ++i) {
+                    F v = low;
+                    for (int k = 0; k < 6; ++k) v = f_mul(v, ((i >> k) & 1) ? s.pt[ln + k] : f_sub(f_one(), s.pt[ln + k]));
+                    corner[i] = v;
+                }
             }
+            s.q_tensor = false;
+            if (ctx->opt.pc_tensor_pub && (corner[0].re | corner[0].im) != 0 && corner[0].re < P61 && corner[0].im < P61) {
+                if (pub) {
+                    HIPCHK(hipMemcpyAsync(s.pub0, hp, (size_t) N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+                    HIPCHK(hipMemsetAsync(s.flag, 0, sizeof(int), ctx->stream));
+                    hipLaunchKernelGGL(k_pc_rank1_check, dim3(nblk((u64) (S + 1) * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) s.pub0, N, S + 1, s.flag);
+                    int bad = 1;
+                    HIPCHK(hipMemcpyAsync(&bad, s.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+                    HIPCHK(hipStreamSynchronize(ctx->stream));
+                    s.q_tensor = bad == 0;
+                } else {
+                    hipLaunchKernelGGL(k_beta_expand, dim3(grid_for(N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, N, s.pub0);
+                    s.q_tensor = true;
+                }
+            }
+            if (!pub && !s.q_tensor)                                     // every slice of this rank, as a vector handed in would be
+                PC_PROF(VP_K_PC_POINTWISE, grid_for((u64) S * N), 1, 16ull * S * N, (u64) S * N,
+                        hipLaunchKernelGGL(k_pc_eq_range, dim3(grid_for((u64) S * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, lo, S * N, s.pub));
             if (s.q_tensor) {
                 F sc[64];
-                const F inv0 = host_pow(hp[0], (unsigned __int128) P61 * P61 - 2);
-                for (int i = 0; i < 64; ++i) sc[i] = f_mul(hp[(size_t) i * N], inv0);
+                const F inv0 = host_pow(corner[0], (unsigned __int128) P61 * P61 - 2);
+                for (int i = 0; i < 64; ++i) sc[i] = f_mul(corner[i], inv0);
                 HIPCHK(hipMemcpyAsync(s.qscal, sc, sizeof sc, hipMemcpyHostToDevice, ctx->stream));
                 HIPCHK(hipStreamSynchronize(ctx->stream));                        // sc lives on this frame
                 VPCHK(pc_launch_ntt(ctx, s.pub0, s.coef, ln, lm, 1, 1, 1, N));
@@ -277,7 +365,7 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner,
             s.x[0] = {1, s.send, s.h_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
             s.stage = 1;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else if (s.stage == 1) {
             VPCHK(pcs_hash_local(ctx, s.h_loc, Nl, s.tree_h, 0));
             // this rank's all_sum entries and its share of the inner product ride on the same all-gather
@@ -286,7 +374,7 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner,
             s.x[0] = {2, s.ag_send, s.ag_recv, sums_at + (size_t) (S + 1) * sizeof(F)}; s.nx = 1;
             s.stage = 2;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else {
             const size_t stride = sums_at + (size_t) (S + 1) * sizeof(F);
             VPCHK(pcs_top(ctx, s.ag_recv, stride, 0, Nl, s.top_h));
@@ -302,7 +390,7 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, vp_F *inner,
             HIPCHK(hipMemcpyAsync(all_sum, g_all, 65 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
             VPCHK(check_stream(ctx));
             if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = ms;
+            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
             s.op = 0; s.stage = 0; s.public_done = true;
             return VP_OK;
         }
@@ -314,11 +402,15 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
     if (!s.public_done || n_steps != ln) { ctx->err = "sharded vp_fri_commit: all n-6 steps in one call, after vp_commit_public"; return VP_EINVAL; }
+    if (s.f_mode == 2) { ctx->err = "vp_fri_commit after vp_fri_step"; return VP_EINVAL; }
+    VPCHK(pcs_guard(ctx));
     if (s.op != 3) { s.op = 3; s.stage = 0; }
+    VPCHK(pcs_resume(ctx));
     const int n_local = ln - s.lw;                                        // folds whose partners are on this rank: N_k -> N_k/2 while N_k >= 2W
     for (;;) {
         if (s.stage == 0) {
             s.fri_r.assign(reinterpret_cast<const F *>(r), reinterpret_cast<const F *>(r) + n_steps);
+            s.f_done = 0;
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
             // virtual oracle of the own slices (in place over q), then to position ownership
@@ -329,7 +421,7 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
             s.stage = 1;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else if (s.stage == 1) {
             // local folds; level k's output has Nl >> (k+1) positions per coset here
             s.fri_off.assign(1, 0); s.tree_f_off.clear();
@@ -374,7 +466,7 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             s.n_local = n_local; s.n_steps = n_steps;
             s.stage = 2;
             const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(check_stream(ctx)); return rc; }
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else {
             // top trees of the locally hashed levels
             size_t at = 0, stride = 0;
@@ -427,16 +519,132 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             HIPCHK(hipMemcpyAsync(roots, s.d_roots, (size_t) 32 * n_steps, hipMemcpyDeviceToHost, ctx->stream));
             VPCHK(check_stream(ctx));
             if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = ms;
-            s.op = 0; s.stage = 0;
+            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
+            s.op = 0; s.stage = 0; s.f_done = n_steps; s.f_mode = 1;
             return VP_OK;
         }
     }
 }
 
+// vp_fri_step on a sharded commitment: pcs_fri_commit cut along its levels, one call per fold challenge (the drop-in's commit_phase loop,
+// vpd_verifier.cpp:44-74).  Step k commits level k and returns its root, the unsharded one, on every rank:
+//   * step 0 begins with the virtual oracle and its all-to-all to position ownership;
+//   * a step k < n_local = (n - 6) - log2 W folds locally and ends in ONE all-gather: the level-5 nodes of the level while the rank keeps at least two
+//     positions per coset, the 2048 tail elements at the last local step (k = n_local - 1), whose level every rank then holds whole and hashes itself;
+//   * a step k >= n_local folds and hashes the replicated tail: no collective.
+// 1 + n_local collectives in all (the one-pass form needs 2: it knows every challenge and gathers all levels at once).  Without a communicator the call
+// stops at each collective with VP_EXCHANGE and is repeated with the same r after the exchange; a repeat before the exchange changes nothing.
+int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
+    PcShard &s = *ctx->pcs;
+    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
+    const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
+    if (!s.public_done) { ctx->err = "vp_fri_step: vp_commit_public first"; return VP_EINVAL; }
+    if (s.op != 0 && s.op != 4) { ctx->err = "vp_fri_step: another call of the sharded commitment is unfinished"; return VP_EINVAL; }
+    if (s.f_mode == 1) { ctx->err = "vp_fri_step after vp_fri_commit"; return VP_EINVAL; }
+    VPCHK(pcs_guard(ctx));
+    if (s.op == 4 && s.nx) return VP_EXCHANGE;                            // the collective this step waits for has not been performed
+    const int n_local = ln - s.lw, k = s.f_done;
+    if (s.op != 4) {
+        if (k >= ln) { ctx->err = "FRI commit phase already finished"; return VP_EINVAL; }
+        memcpy(&s.step_r, r, sizeof(F));
+        s.acc_ms = 0; ctx->ev_used = 0;
+        if (k == 0) {
+            s.f_mode = 2; s.n_steps = ln; s.n_local = n_local;
+            s.fri_off.assign(1, 0); s.tree_f_off.clear(); s.top_f_off.clear(); s.tail_cw_off.clear(); s.tail_tree_off.clear();
+        }
+        s.op = 4; s.stage = k == 0 ? 0 : k < n_local ? 1 : 3;
+    }
+    HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+    // a part of the step ends: at a collective the caller has to perform, or with the level's root
+    auto part_end = [&](const Dig *d_root) -> int {
+        HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+        if (d_root) HIPCHK(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, ctx->stream));
+        VPCHK(check_stream(ctx));
+        float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); s.acc_ms += ms;
+        return VP_OK;
+    };
+    const u32 Nk = k < n_local ? Nl >> k : 0, No = Nk >> 1;               // local step: positions per coset on this rank before / after the fold
+    Dig *d_root = nullptr;
+    for (;;) {
+        if (s.stage == 0) {
+            // virtual oracle of the own slices (in place over q), then to position ownership
+            hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, s.hcw, s.small + 1025 + 80, N,
+                               ctx->pc_rt, M >> 1, f_make(N, 0), S, (const F *) (s.q_tensor ? s.q0cw : nullptr),
+                               (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
+            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.qcw, s.send, N, s.lw, S * 32);
+            s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
+            s.stage = 1;
+            const int rc = pcs_collectives(ctx);
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
+        } else if (s.stage == 1) {
+            const F *in = s.fri_loc + s.fri_off[k];
+            const size_t off = s.fri_off[k] + (size_t) 64 * 32 * Nk;
+            F *out = s.fri_loc + off;
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, s.step_r,
+                                       host_inv_real(2), s.lw, (u32) s.rank));
+            if ((int) s.fri_off.size() == k + 1) s.fri_off.push_back(off);
+            if (No >= 2) {                                                // leaves pair (a', a' + No/2): local; the level-5 nodes go to every rank
+                size_t toff = 0;
+                for (int q = 0; q < k; ++q) toff += (size_t) 32 * (Nl >> (q + 1));
+                if ((int) s.tree_f_off.size() == k) s.tree_f_off.push_back(toff);
+                VPCHK(pcs_hash_local(ctx, out, No, s.tree_f + toff, 0));
+                s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) (No >> 1) * 32}; s.nx = 1;
+            } else {                                                       // the one position per coset this rank is left with
+                HIPCHK(hipMemcpyAsync(s.ag_send, out, (size_t) 2048 * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
+                s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) 2048 * sizeof(F)}; s.nx = 1;
+            }
+            s.stage = 2;
+            const int rc = pcs_collectives(ctx);
+            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
+        } else if (s.stage == 2) {
+            if (No >= 2) {
+                size_t toff = 0;
+                for (int q = 0; q < k; ++q) toff += (size_t) 2 * (((Nl >> (q + 1)) >> 1) << s.lw);
+                if ((int) s.top_f_off.size() == k) s.top_f_off.push_back(toff);
+                VPCHK(pcs_top(ctx, s.ag_recv, (size_t) (No >> 1) * 32, 0, No, s.top_f + toff));
+                d_root = s.top_f + toff + 1;                               // heap layout: the root is node 1
+            } else {
+                // level k = n_local - 1 whole on every rank (W positions per coset): the first level of the replicated tail
+                hipLaunchKernelGGL(k_pc_interleave_tail, dim3(nblk(2048u << s.lw)), dim3(VP_BLOCK), 0, ctx->stream, reinterpret_cast<const F *>(s.ag_recv), s.tail, s.lw);
+                s.tail_cw_off.assign(1, 0); s.tail_tree_off.assign(1, 0);
+                const u32 Nt = 1u << s.lw, n_leaves = Nt >= 2 ? 16 * Nt : 16;
+                if (Nt >= 2) pc_launch_leaf_hash(ctx, s.tail, Nt, s.tail_tree + n_leaves);
+                else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, s.tail, 64, s.tail_tree + n_leaves);
+                VPCHK(pc_merkle(ctx, s.tail_tree, n_leaves));
+                d_root = s.tail_tree + 1;
+            }
+            break;
+        } else {
+            // replicated step: level k - 1 (Nt positions per coset, whole on every rank) folds to level k, which is hashed here
+            const int q = k - (n_local - 1);                              // index of level k among the tail levels, >= 1
+            if ((int) s.tail_cw_off.size() != q || (int) s.tail_tree_off.size() != q) { ctx->err = "internal: sharded FRI tail out of step"; return VP_EINVAL; }
+            const u32 Nt = (1u << s.lw) >> (q - 1), Nn = Nt >> 1, leaves_in = 16 * Nt, n_leaves = Nn >= 2 ? 16 * Nn : 16;
+            const F *cw = s.tail + s.tail_cw_off[q - 1];
+            const size_t coff = s.tail_cw_off[q - 1] + (size_t) 64 * 32 * Nt, ttoff = s.tail_tree_off[q - 1] + (size_t) 2 * leaves_in;
+            F *out = s.tail + coff;
+            Dig *tree = s.tail_tree + ttoff;
+            hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * Nn)), dim3(VP_BLOCK), 0, ctx->stream, cw, out, Nt, k, ctx->pc_rt, M >> 1,
+                               s.step_r, host_inv_real(2), 0, 0u);
+            if (Nn >= 2) pc_launch_leaf_hash(ctx, out, Nn, tree + n_leaves);
+            else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, out, 64, tree + n_leaves);
+            VPCHK(pc_merkle(ctx, tree, n_leaves));
+            s.tail_cw_off.push_back(coff); s.tail_tree_off.push_back(ttoff);
+            d_root = tree + 1;
+            break;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(s.d_roots + k, d_root, 32, hipMemcpyDeviceToDevice, ctx->stream));
+    VPCHK(part_end(d_root));
+    if (ctx->profiling) prof_collect(ctx);
+    ctx->commit_ms = s.acc_ms;
+    s.op = 0; s.stage = 0; s.f_done = k + 1;
+    return VP_OK;
+}
+
 int pcs_fri_final(vp_ctx *ctx, vp_F *final_code) {
     PcShard &s = *ctx->pcs;
-    if (s.tail_cw_off.empty() || s.n_steps == 0) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
+    if (s.tail_cw_off.empty() || s.n_steps == 0 || s.f_done != s.n_steps) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
     std::vector<F> cw(64 * 32);
     HIPCHK(hipMemcpy(cw.data(), s.tail + s.tail_cw_off.back(), cw.size() * sizeof(F), hipMemcpyDeviceToHost));
     F *o = reinterpret_cast<F *>(final_code);
@@ -472,7 +680,7 @@ int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8
     u32 n_leaves;
     if (oracle >= 2 && oracle - 2 >= s.n_local - 1) {                       // tail level: whole codeword on every rank
         const int q = oracle - 2 - (s.n_local - 1);
-        if (s.n_steps == 0 || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        if (oracle - 2 >= s.f_done || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
         const u32 Nt = (1u << s.lw) >> q;
         n_leaves = Nt >= 2 ? 16 * Nt : 16;
         if (leaf >= n_leaves) return VP_EINVAL;
@@ -484,7 +692,7 @@ int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8
         else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; cw = s.h_loc; tl = s.tree_h; top = s.top_h; Nc = Nl; }
         else {
             const int lvl = oracle - 2;
-            if (s.n_steps == 0 || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+            if (lvl >= s.f_done || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
             cw = s.fri_loc + s.fri_off[lvl + 1]; tl = s.tree_f + s.tree_f_off[lvl]; top = s.top_f + s.top_f_off[lvl]; Nc = Nl >> (lvl + 1);
         }
         n_leaves = (16 * Nc) << s.lw;
@@ -508,7 +716,7 @@ int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     const u32 N = 1u << ln, Nl = N >> s.lw;
     if (oracle >= 2 && oracle - 2 >= s.n_local - 1) {                       // tail level: whole codeword on every rank
         const int q = oracle - 2 - (s.n_local - 1);
-        if (s.n_steps == 0 || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        if (oracle - 2 >= s.f_done || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
         const u32 Nt = (1u << s.lw) >> q;
         d->cw = s.tail + s.tail_cw_off[q]; d->tree = s.tail_tree + s.tail_tree_off[q]; d->Nc = Nt; d->n_leaves = Nt >= 2 ? 16 * Nt : 16;
         return VP_OK;
@@ -517,12 +725,16 @@ int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; d->cw = s.h_loc; d->tree = s.tree_h; d->top = s.top_h; d->Nc = Nl; }
     else {
         const int lvl = oracle - 2;
-        if (s.n_steps == 0 || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        if (lvl >= s.f_done || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
         d->cw = s.fri_loc + s.fri_off[lvl + 1]; d->tree = s.tree_f + s.tree_f_off[lvl]; d->top = s.top_f + s.top_f_off[lvl]; d->Nc = Nl >> (lvl + 1);
     }
     d->n_leaves = (16 * d->Nc) << s.lw; d->n5 = (d->Nc >> 1) << s.lw; d->lw = (u32) s.lw;
     return VP_OK;
 }
+bool pcs_private_done(vp_ctx *ctx) { return ctx->pcs->private_done; }
+bool pcs_public_done(vp_ctx *ctx) { return ctx->pcs->public_done; }
+int pcs_fri_done(vp_ctx *ctx) { return ctx->pcs->f_done; }
+bool pcs_fri_one_pass(vp_ctx *ctx) { return ctx->pcs->f_mode == 1; }
 bool pcs_owns(vp_ctx *ctx, uint64_t leaf) { const PcShard &s = *ctx->pcs; return (int) ((leaf >> 5) & (u64) (s.world - 1)) == s.rank; }
 
 }  // namespace
@@ -574,6 +786,7 @@ int vp_pc_set_shard(vp_ctx *ctx, int rank, int world) {
     if (world == 1 && !(ctx->cm && ctx->cm->comm && ctx->cm->world == 1)) return VP_OK;
     ctx->pcs = new PcShard();
     ctx->pcs->rank = rank; ctx->pcs->world = world; ctx->pcs->lw = lw; ctx->pcs->S = 64 / world;
+    ctx->pcs->n_local = ln - lw;                // known before the FRI phase: vp_pc_shard_owner tells the replicated levels by it
     return VP_OK;
 }
 

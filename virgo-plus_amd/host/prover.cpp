@@ -8,6 +8,7 @@
 #include <thread>
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <cstdlib>
 
 #include <cstdio>
@@ -80,7 +81,7 @@ int prover::onRanks(const std::function<int(int, vp_ctx *)> &fn, const char *wha
 
 prover::prover(const layeredCircuit &cir, int device, const vp_options *options) : C(cir) { upload({device}, options); }
 
-prover::prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options) : C(cir) {
+prover::prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options, bool shard_commitment) : C(cir) {
     if (devices.empty() || devices.size() > 8 || (devices.size() & (devices.size() - 1)))
         throw std::invalid_argument("round-sharded prover: 1, 2, 4 or 8 ranks");
     // Ranks that share a device run without the resident round kernel: it holds the hardware queue it was launched on until its phase ends, and
@@ -100,6 +101,17 @@ prover::prover(const layeredCircuit &cir, const std::vector<int> &devices, int m
         for (size_t r = 0; r < rk.size(); ++r) {
             const int rc = vp_set_round_shard(rk[r], (int) r, (int) rk.size(), min_log);
             if (rc != VP_OK) throw std::runtime_error("vp_set_round_shard failed (" + std::to_string(rc) + "): " + vp_last_error(rk[r]));
+        }
+        if (shard_commitment && rk.size() > 1) {
+            const int n = C.circuit[0].bitLength;
+            if (n < 7 || (1ull << (n - 6)) < 2 * rk.size())
+                throw std::runtime_error("sharded commitment: an input layer of 2^" + std::to_string(n) + " wires has 2^" + std::to_string(n - 6) +
+                                         " positions per slice, fewer than the 2 per rank that " + std::to_string(rk.size()) + " ranks need");
+            for (size_t r = 0; r < rk.size(); ++r) {
+                const int rc = vp_pc_set_shard(rk[r], (int) r, (int) rk.size());
+                if (rc != VP_OK) throw std::runtime_error("vp_pc_set_shard failed (" + std::to_string(rc) + "): " + vp_last_error(rk[r]));
+            }
+            shard_pc = true;
         }
     } catch (...) {
         pool.reset();
@@ -379,8 +391,36 @@ void prover::finalizeAll(const F &previousRandom, F *claims, int n, const char *
     for (int q = 0; q < n; ++q) claims[q] = cl[0][q];
 }
 
+void prover::pcRanks(const std::function<int(int, vp_ctx *)> &fn, const char *what) {
+    for (int pass = 0; pass < 8; ++pass) {                 // no call of the commitment stops at more than two collectives
+        if (onRanks(fn, what) == VP_OK) return;
+        check(vp_shard_exchange_local(rk.data(), (int) rk.size()), "vp_shard_exchange_local");
+    }
+    throw std::runtime_error(std::string(what) + ": still at a collective after its exchanges");
+}
+namespace {
+struct PubOut { prover::hhash_digest d; F inner; std::vector<F> all = std::vector<F>(65); };
+// root_h, input_0 and all_sum of a sharded commit_public: the ranks must agree
+void same_public(const std::vector<PubOut> &o, const char *what) {
+    for (size_t r = 1; r < o.size(); ++r)
+        if (memcmp(o[r].d.b, o[0].d.b, 32) || o[r].inner != o[0].inner || o[r].all != o[0].all)
+            throw std::runtime_error(std::string(what) + ": rank " + std::to_string(r) + " returned a different root_h / input_0 / all_sum than rank 0");
+}
+void same_roots(const std::vector<std::vector<prover::hhash_digest>> &d, const char *what) {
+    for (size_t r = 1; r < d.size(); ++r)
+        if (memcmp(d[r].data(), d[0].data(), d[0].size() * sizeof(prover::hhash_digest)))
+            throw std::runtime_error(std::string(what) + ": rank " + std::to_string(r) + " returned a different root than rank 0");
+}
+}  // namespace
+
 prover::hhash_digest prover::commit_private() {      // src/prover.cpp:524-530 (mask = one zero element)
     masked = false;
+    if (shard_pc) {
+        std::vector<std::vector<hhash_digest>> d(rk.size(), std::vector<hhash_digest>(1));
+        pcRanks([&](int r, vp_ctx *c) { return vp_commit_private(c, d[r][0].b); }, "vp_commit_private");
+        same_roots(d, "vp_commit_private");
+        return d[0][0];
+    }
     hhash_digest d;
     check(vp_commit_private(ctx, d.b), "vp_commit_private");
     return d;
@@ -388,6 +428,13 @@ prover::hhash_digest prover::commit_private() {      // src/prover.cpp:524-530 (
 prover::hhash_digest prover::commit_public(std::vector<F> &pub, F &inner_product_sum, std::vector<F> &all_sum) {
     hhash_digest d;
     all_sum.resize(65);
+    if (shard_pc) {
+        std::vector<PubOut> o(rk.size());
+        pcRanks([&](int r, vp_ctx *c) { return vp_commit_public(c, cF(pub.data()), pub.size(), mF(&o[r].inner), mF(o[r].all.data()), o[r].d.b); }, "vp_commit_public");
+        same_public(o, "vp_commit_public");
+        inner_product_sum = o[0].inner; all_sum = o[0].all;
+        return o[0].d;
+    }
     check(vp_commit_public(ctx, cF(pub.data()), pub.size(), mF(&inner_product_sum), mF(all_sum.data()), d.b), "vp_commit_public");
     return d;
 }
@@ -395,6 +442,7 @@ static bool all_zero(const std::vector<F> &v) { for (auto &x : v) if (x.real | x
 prover::hhash_digest prover::commit_private(const std::vector<F> &mask) {      // poly_commit.h:41-124 with its mask argument
     if (mask.empty() || all_zero(mask)) { masked = false; return commit_private(); }
     hhash_digest d;
+    // (on a sharded commitment the library refuses the mask: its message is the exception's)
     check(vp_commit_private_masked(ctx, cF(mask.data()), mask.size(), d.b), "vp_commit_private_masked");
     masked = true;
     return d;
@@ -416,6 +464,13 @@ std::vector<F> prover::friFinalMask() {
 prover::hhash_digest prover::commit_public_eq(const std::vector<F> &point, F &inner_product_sum, std::vector<F> &all_sum) {
     hhash_digest d;
     all_sum.resize(65);
+    if (shard_pc) {
+        std::vector<PubOut> o(rk.size());
+        pcRanks([&](int r, vp_ctx *c) { return vp_commit_public_eq(c, cF(point.data()), (int) point.size(), mF(&o[r].inner), mF(o[r].all.data()), o[r].d.b); }, "vp_commit_public_eq");
+        same_public(o, "vp_commit_public_eq");
+        inner_product_sum = o[0].inner; all_sum = o[0].all;
+        return o[0].d;
+    }
     check(vp_commit_public_eq(ctx, cF(point.data()), (int) point.size(), mF(&inner_product_sum), mF(all_sum.data()), d.b), "vp_commit_public_eq");
     return d;
 }
@@ -440,16 +495,37 @@ F prover::layerMle(int layer, const std::vector<F> &r, int n) {
 }
 prover::hhash_digest prover::friStep(const F &r) {
     hhash_digest d;
+    if (shard_pc) {
+        std::vector<std::vector<hhash_digest>> ds(rk.size(), std::vector<hhash_digest>(1));
+        pcRanks([&](int q, vp_ctx *c) { return vp_fri_step(c, cF(&r), ds[q][0].b); }, "vp_fri_step");
+        fri_one_pass = false;
+        same_roots(ds, "vp_fri_step");
+        return ds[0][0];
+    }
     check(vp_fri_step(ctx, cF(&r), d.b), "vp_fri_step");
     return d;
 }
 std::vector<prover::hhash_digest> prover::friCommit(const std::vector<F> &r) {
     std::vector<hhash_digest> d(r.size());
+    if (shard_pc) {
+        std::vector<std::vector<hhash_digest>> ds(rk.size(), std::vector<hhash_digest>(std::max<size_t>(1, r.size())));
+        pcRanks([&](int q, vp_ctx *c) { return vp_fri_commit(c, cF(r.data()), (int) r.size(), ds[q][0].b); }, "vp_fri_commit");
+        fri_one_pass = true;
+        same_roots(ds, "vp_fri_commit");
+        ds[0].resize(r.size());
+        return ds[0];
+    }
     check(vp_fri_commit(ctx, cF(r.data()), (int) r.size(), d[0].b), "vp_fri_commit");
     return d;
 }
 std::vector<F> prover::friFinal() {
     std::vector<F> out(2048);
+    if (shard_pc) {                                         // the last codeword is whole on every rank
+        std::vector<std::vector<F>> o(rk.size(), std::vector<F>(2048));
+        onRanks([&](int r, vp_ctx *c) { return vp_fri_final(c, mF(o[r].data())); }, "vp_fri_final");
+        for (size_t r = 1; r < o.size(); ++r) if (o[r] != o[0]) throw std::runtime_error("vp_fri_final: rank " + std::to_string(r) + " returned a different codeword than rank 0");
+        return o[0];
+    }
     check(vp_fri_final(ctx, mF(out.data())), "vp_fri_final");
     return out;
 }
@@ -457,7 +533,10 @@ void prover::friOpen(int oracle, u64 leaf, std::vector<F> &values, std::vector<h
     values.resize(130);
     path.resize(40);
     int len = 0;
-    check(vp_fri_open(ctx, oracle, leaf, mF(values.data()), path[0].b, 40 * 32, &len), "vp_fri_open");
+    vp_ctx *who = ctx;
+    if (shard_pc) { const int owner = vp_pc_shard_owner(ctx, oracle, leaf); who = rk[owner < 0 ? 0 : owner]; }      // -1: a replicated level, any rank answers
+    const int rc = vp_fri_open(who, oracle, leaf, mF(values.data()), path[0].b, 40 * 32, &len);
+    if (rc != VP_OK) throw std::runtime_error("vp_fri_open failed (" + std::to_string(rc) + "): " + vp_last_error(who));
     path.resize(len);
 }
 void prover::friOpenMany(const std::vector<int32_t> &oracle, const std::vector<u64> &leaf, std::vector<F> &values, std::vector<hhash_digest> &paths, int stride,
@@ -467,13 +546,78 @@ void prover::friOpenMany(const std::vector<int32_t> &oracle, const std::vector<u
     values.resize(130 * n); paths.resize((size_t) stride * n); path_len.assign(n, 0);
     if (!n) return;
     std::vector<uint64_t> lf(leaf.begin(), leaf.end());
+    if (shard_pc) {
+        // every rank answers what it owns into buffers of its own; a request's answer is taken from a rank that reports a path for it
+        struct Ans { std::vector<F> v; std::vector<hhash_digest> p; std::vector<int32_t> len; };
+        std::vector<Ans> a(rk.size());
+        for (auto &x : a) { x.v.resize(130 * n); x.p.resize((size_t) stride * n); x.len.assign(n, 0); }
+        onRanks([&](int r, vp_ctx *c) { return vp_fri_open_many(c, (int) n, oracle.data(), lf.data(), mF(a[r].v.data()), a[r].p[0].b, 32 * stride, a[r].len.data()); },
+                "vp_fri_open_many");
+        for (size_t i = 0; i < n; ++i) {
+            size_t r = 0;
+            while (r < rk.size() && a[r].len[i] <= 0) ++r;
+            if (r == rk.size()) throw std::runtime_error("vp_fri_open_many: no rank answered request " + std::to_string(i));
+            std::copy(a[r].v.begin() + 130 * i, a[r].v.begin() + 130 * (i + 1), values.begin() + 130 * i);
+            std::copy(a[r].p.begin() + (size_t) stride * i, a[r].p.begin() + (size_t) stride * i + a[r].len[i], paths.begin() + (size_t) stride * i);
+            path_len[i] = a[r].len[i];
+        }
+        return;
+    }
     check(vp_fri_open_many(ctx, (int) n, oracle.data(), lf.data(), mF(values.data()), paths[0].b, 32 * stride, path_len.data()), "vp_fri_open_many");
 }
 std::vector<uint8_t> prover::friQuery(const std::vector<u64> &leaf0) {
+    if (shard_pc && fri_one_pass) {
+        // after the one-pass friCommit a sharded commitment answers lists of openings only: the same requests in vp_fri_query's order through
+        // friOpenMany, packed into its layout (values, then the path at its true length)
+        const int n = C.circuit[0].bitLength, ln = n - 6;
+        std::vector<int32_t> oracle, len;
+        std::vector<u64> leaf;
+        for (u64 l0 : leaf0) {
+            oracle.push_back(0); leaf.push_back(l0);
+            oracle.push_back(1); leaf.push_back(l0);
+            u64 D = 1ull << (n - 1), t = l0;
+            for (int k = 0; k < ln; ++k) { const u64 Dn = D / 2, lf = t % (Dn / 2); oracle.push_back(2 + k); leaf.push_back(lf); t = lf; D = Dn; }
+        }
+        std::vector<F> values;
+        std::vector<hhash_digest> paths;
+        const int stride = n - 1;                           // digests of the longest path
+        friOpenMany(oracle, leaf, values, paths, stride, len);
+        std::vector<uint8_t> out;
+        for (size_t i = 0; i < oracle.size(); ++i) {
+            const uint8_t *v = reinterpret_cast<const uint8_t *>(values.data() + 130 * i);
+            out.insert(out.end(), v, v + 130 * sizeof(F));
+            out.insert(out.end(), paths[(size_t) stride * i].b, paths[(size_t) stride * i].b + 32 * (size_t) len[i]);
+        }
+        return out;
+    }
     uint64_t bytes = 0, written = 0;
     check(vp_fri_query_bytes(ctx, (int) leaf0.size(), &bytes), "vp_fri_query_bytes");
     std::vector<uint8_t> out(bytes);
     std::vector<uint64_t> lf(leaf0.begin(), leaf0.end());
+    if (shard_pc) {
+        // the layout is the same on every rank and a rank fills in the openings it owns: walk the requests in vp_fri_query's order (host/verifier.cpp's
+        // leaf chain) and take each opening from its owner's buffer
+        std::vector<std::vector<uint8_t>> o(rk.size(), std::vector<uint8_t>(bytes));
+        std::vector<uint64_t> wr(rk.size(), 0);
+        onRanks([&](int r, vp_ctx *c) { return vp_fri_query(c, (int) lf.size(), lf.data(), o[r].data(), bytes, &wr[r]); }, "vp_fri_query");
+        for (size_t r = 0; r < rk.size(); ++r) if (wr[r] != bytes) throw std::runtime_error("vp_fri_query: rank " + std::to_string(r) + " reports another answer size than vp_fri_query_bytes");
+        const int n = C.circuit[0].bitLength, ln = n - 6;
+        size_t at = 0;
+        auto take = [&](int oracle, uint64_t leaf, int path_digests) {
+            const int owner = vp_pc_shard_owner(ctx, oracle, leaf);
+            const size_t len = 130 * sizeof(F) + 32 * (size_t) path_digests;
+            if (at + len > bytes) throw std::runtime_error("vp_fri_query: the answer is shorter than its layout");
+            memcpy(out.data() + at, o[owner < 0 ? 0 : owner].data() + at, len);
+            at += len;
+        };
+        for (uint64_t l0 : lf) {
+            take(0, l0, n - 1); take(1, l0, n - 1);
+            uint64_t D = 1ull << (n - 1), t = l0;
+            for (int k = 0; k < ln; ++k) { const uint64_t Dn = D / 2, leaf = t % (Dn / 2); take(2 + k, leaf, n - 2 - k); t = leaf; D = Dn; }
+        }
+        if (at != bytes) throw std::runtime_error("vp_fri_query: the answer is longer than its layout");
+        return out;
+    }
     check(vp_fri_query(ctx, (int) lf.size(), lf.data(), out.data(), bytes, &written), "vp_fri_query");
     out.resize(written);
     return out;

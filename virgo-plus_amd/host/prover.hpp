@@ -32,8 +32,14 @@ public:
     explicit prover(const layeredCircuit &cir, int device = 0, const vp_options *options = nullptr);   // options: include/vpgpu.h (NULL = shipped defaults)
     // One proof's interactive sumchecks sharded by index over W = devices.size() ranks (vp_set_round_shard, min_log): one context per rank, the same
     // device may be listed several times.  Every sumcheck method runs on all ranks at once (one worker thread per rank), sums the partial round
-    // polynomials mod p, performs the gather when a rank stops at it, and checks that the ranks' claims agree.  Vres and the commitment run on rank 0.
-    prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options = nullptr);
+    // polynomials mod p, performs the gather when a rank stops at it, and checks that the ranks' claims agree.  Vres's message is rank 0's.
+    // shard_commitment = false: the commitment runs on rank 0.  true: it is sharded over the same ranks (vp_pc_set_shard) — commit_private, commit_public,
+    // commit_public_eq, friStep, friCommit, friFinal and the openings run on every rank through the same worker pool; when all ranks stop at a collective
+    // (VP_EXCHANGE) it is performed by vp_shard_exchange_local and the call repeated; roots, input_0 and all_sum must agree across the ranks; friOpen asks
+    // the owner of the leaf, friOpenMany and friQuery merge the ranks' answers (friQuery after friCommit: through friOpenMany, since vp_fri_query on a shard
+    // serves the step-wise phase only).  Masks are refused on a sharded commitment.  A request that cannot be met
+    // (fewer than 2 W positions per slice) throws here with the reason: there is no silent fall-back to rank 0.
+    prover(const layeredCircuit &cir, const std::vector<int> &devices, int min_log, const vp_options *options = nullptr, bool shard_commitment = false);
     ~prover();
     prover(const prover &) = delete;
     prover &operator=(const prover &) = delete;
@@ -114,6 +120,7 @@ public:
     std::vector<F> layerValues(int layer);
     vp_ctx *context() { return ctx; }
     int world() const { return (int) rk.size(); }
+    bool commitmentSharded() const { return shard_pc; }
     vp_ctx *rankContext(int r) { return (r >= 0 && r < (int) rk.size()) ? rk[r] : nullptr; }
     // round-sharded prover: every rank's partial polynomial of every round since the last clearPartials (test and profiling aid), and a rank whose
     // partial is left out of the sum (-1: none; a test of the verifier's sumcheck check)
@@ -130,6 +137,10 @@ private:
     // run fn(rank, context) on every rank concurrently and throw on the first failure (VP_EXCHANGE is returned to the caller when every rank stopped there)
     int onRanks(const std::function<int(int, vp_ctx *)> &fn, const char *what);
     void finalizeAll(const F &previousRandom, F *claims, int n, const char *what);
+    // a call of the sharded commitment on every rank, repeated after each collective the ranks stop at
+    void pcRanks(const std::function<int(int, vp_ctx *)> &fn, const char *what);
+    bool shard_pc = false;
+    bool fri_one_pass = false;                           // the standing FRI phase came from friCommit: vp_fri_query is not answered on a shard then, friQuery merges friOpenMany
     struct Pool;
     std::unique_ptr<Pool> pool;
     std::vector<vp_ctx *> rk;                            // every rank's context (rk[0] == ctx)

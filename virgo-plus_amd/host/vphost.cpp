@@ -99,11 +99,14 @@ vph_session *vph_session_create_opts(vph_circuit *c, int device, const vp_option
     }
 }
 vph_session *vph_session_create_round_sharded(vph_circuit *c, const int *devices, int world, int min_log, const vp_options *opt, char *err, int errlen) {
+    return vph_session_create_sharded(c, devices, world, min_log, 0, opt, err, errlen);
+}
+vph_session *vph_session_create_sharded(vph_circuit *c, const int *devices, int world, int min_log, int shard_commitment, const vp_options *opt, char *err, int errlen) {
     if (!c || !devices || world < 1) { set_err(err, errlen, "null circuit / device list"); return nullptr; }
     try {
         std::unique_ptr<vph_session> s(new vph_session());
         s->circ = c;
-        s->p.reset(new prover(c->c, std::vector<int>(devices, devices + world), min_log, opt));
+        s->p.reset(new prover(c->c, std::vector<int>(devices, devices + world), min_log, opt, shard_commitment != 0));
         return s.release();
     } catch (const std::exception &e) {
         set_err(err, errlen, e.what());
@@ -282,6 +285,71 @@ int vph_commit_public(vph_session *s, const uint64_t *pub_pairs, uint64_t n_pub,
     }
 }
 
+int vph_commit_private_masked(vph_session *s, const uint64_t *mask_pairs, uint64_t n_mask, uint8_t root[32], double *ms, char *err, int errlen) {
+    try {
+        std::vector<F> mask(n_mask);
+        for (u64 i = 0; i < n_mask; ++i) { mask[i].real = mask_pairs[2 * i]; mask[i].img = mask_pairs[2 * i + 1]; }
+        prover::hhash_digest d = s->p->commit_private(mask);
+        memcpy(root, d.b, 32);
+        if (ms) *ms = s->p->commitDeviceMs();
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
+int vph_commit_public_eq(vph_session *s, const uint64_t *point_pairs, int n_point, uint8_t *out, double *ms, char *err, int errlen) {
+    try {
+        std::vector<F> point((size_t) std::max(0, n_point)), all_sum;
+        for (int i = 0; i < n_point; ++i) { point[i].real = point_pairs[2 * i]; point[i].img = point_pairs[2 * i + 1]; }
+        F inner;
+        prover::hhash_digest d = s->p->commit_public_eq(point, inner, all_sum);
+        memcpy(out, d.b, 32);
+        memcpy(out + 32, &inner, 16);
+        memcpy(out + 48, all_sum.data(), 65 * 16);
+        if (ms) *ms = s->p->commitDeviceMs();
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
+int vph_fri_open_many(vph_session *s, int n, const int32_t *oracle, const uint64_t *leaf, uint64_t *values_pairs, uint8_t *paths, int path_stride,
+                      int32_t *path_len, char *err, int errlen) {
+    try {
+        if (n < 0 || path_stride < 0 || path_stride % 32) throw std::runtime_error("vph_fri_open_many: path_stride must be a multiple of 32 bytes");
+        std::vector<int32_t> o(oracle, oracle + n), len;
+        std::vector<u64> lf(leaf, leaf + n);
+        std::vector<F> values;
+        std::vector<prover::hhash_digest> pt;
+        s->p->friOpenMany(o, lf, values, pt, path_stride / 32, len);
+        for (int i = 0; i < n; ++i) {
+            memcpy(values_pairs + (size_t) 260 * i, values.data() + (size_t) 130 * i, 130 * sizeof(F));
+            memcpy(paths + (size_t) path_stride * i, pt.data() + (size_t) (path_stride / 32) * i, 32 * (size_t) len[i]);
+            path_len[i] = len[i];
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
+int vph_fri_query(vph_session *s, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written, char *err, int errlen) {
+    try {
+        const std::vector<uint8_t> a = s->p->friQuery(std::vector<u64>(leaf0, leaf0 + std::max(0, n_queries)));
+        if (n_written) *n_written = a.size();
+        if (a.size() > capacity) { set_err(err, errlen, "vph_fri_query: output buffer too small"); return -1; }
+        memcpy(out, a.data(), a.size());
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
 int vph_prove_and_verify_full(vph_session *s, int reps, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                               double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen) {
     return vph_prove_and_verify_full_ex(s, reps, 0, transcript, capacity, n_written, gkr_prove_sec, pc_prove_sec, verify_sec, err, errlen);
@@ -368,7 +436,24 @@ void vph_test_sha3(const uint8_t *in, uint8_t *out, uint64_t n) {
     }
 }
 
+// the two FRI commit calls on a session whose commitment is sharded: through the prover, which runs every rank
+static int fri_commit_sharded(vph_session *s, const uint64_t *r_pairs, int n_steps, uint8_t *roots, uint64_t *final_pairs, bool batched, char *err, int errlen) {
+    try {
+        std::vector<F> r((size_t) n_steps);
+        for (int k = 0; k < n_steps; ++k) { r[k].real = r_pairs[2 * k]; r[k].img = r_pairs[2 * k + 1]; }
+        if (batched) { const auto d = s->p->friCommit(r); memcpy(roots, d.data(), 32 * d.size()); }
+        else for (int k = 0; k < n_steps; ++k) { const auto d = s->p->friStep(r[k]); memcpy(roots + 32 * k, d.b, 32); }
+        const std::vector<F> fin = s->p->friFinal();
+        memcpy(final_pairs, fin.data(), fin.size() * sizeof(F));
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
 int vph_fri_commit(vph_session *s, const uint64_t *r_pairs, int n_steps, uint8_t *roots, uint64_t *final_pairs, char *err, int errlen) {
+    if (s->p->commitmentSharded()) return fri_commit_sharded(s, r_pairs, n_steps, roots, final_pairs, false, err, errlen);
     vp_ctx *ctx = s->p->context();
     for (int k = 0; k < n_steps; ++k) {
         vp_F r; r.real = r_pairs[2 * k]; r.img = r_pairs[2 * k + 1];
@@ -381,6 +466,7 @@ int vph_fri_commit(vph_session *s, const uint64_t *r_pairs, int n_steps, uint8_t
 }
 
 int vph_fri_commit_batched(vph_session *s, const uint64_t *r_pairs, int n_steps, uint8_t *roots, uint64_t *final_pairs, char *err, int errlen) {
+    if (s->p->commitmentSharded()) return fri_commit_sharded(s, r_pairs, n_steps, roots, final_pairs, true, err, errlen);
     vp_ctx *ctx = s->p->context();
     int rc = vp_fri_commit(ctx, reinterpret_cast<const vp_F *>(r_pairs), n_steps, roots);
     if (rc != VP_OK) { set_err(err, errlen, std::string("vp_fri_commit: ") + vp_last_error(ctx)); return rc; }
@@ -457,6 +543,7 @@ int vph_draw_protocol_tape(vph_session *s) {
 // (vph_last_fft_gkr), the FRI data too (vph_last_fri).  0 = done, < 0 = error.
 int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
                           uint64_t *final_pairs, double sec[6], int flags, char *err, int errlen) {
+    if (s->p->commitmentSharded()) { set_err(err, errlen, "vph_prove_protocol: not on a session with a sharded commitment (vph_prove_and_verify_full runs it)"); return -1; }
     vp_ctx *ctx = s->p->context();
     const bool defer = (flags & VPH_PASS_DEFERRED) != 0, queue_next = defer && (flags & VPH_PASS_QUEUE_NEXT) != 0;
     // a run of fft_gkr that is begun and not collected when this function leaves, for whatever reason, is dropped (it would make every later pass of the

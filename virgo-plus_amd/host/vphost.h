@@ -51,6 +51,13 @@ void *vph_session_ctx(vph_session *);
  * of `devices` (the same device may repeat).  vph_prove_interactive, vph_prove_full and vph_prove_and_verify_full work on it unchanged; the prover
  * sums the ranks' partial round polynomials.  vph_session_ctx is rank 0's context, vph_session_rank_ctx(s, r) rank r's (per-rank stats). */
 vph_session *vph_session_create_round_sharded(vph_circuit *, const int *devices, int world, int min_log, const vp_options *opt, char *err, int errlen);
+/* The same with a switch for the commitment: shard_commitment = 0 is vph_session_create_round_sharded; non-zero also shards the Virgo commitment
+ * over the ranks (vp_pc_set_shard), so that vph_commit_private / vph_commit_public, vph_fri_commit(_batched), vph_prove_full and
+ * vph_prove_and_verify_full run commit_private, commit_public, the FRI commit phase and every opening on all ranks (collectives among the
+ * contexts by vp_shard_exchange_local).  Fails with the reason when the input layer is too short for the ranks (2^(n-6) < 2 world): there
+ * is no fall-back to rank 0.  Masks and the one-pass vph_prove_protocol are not available on such a session.                                  */
+vph_session *vph_session_create_sharded(vph_circuit *, const int *devices, int world, int min_log, int shard_commitment, const vp_options *opt,
+                                        char *err, int errlen);
 void *vph_session_rank_ctx(vph_session *, int rank);
 int vph_session_world(vph_session *);
 /* round-sharded session: every rank's partial polynomial of every round since the last clear (rank-major per round, 3 elements each; returns the
@@ -127,6 +134,16 @@ void vph_test_sha3(const uint8_t *in, uint8_t *out, uint64_t n);
 int vph_fri_commit(vph_session *, const uint64_t *r_pairs, int n_steps, uint8_t *roots, uint64_t *final_pairs, char *err, int errlen);
 /* same through vp_fri_commit: every step in one device pass */
 int vph_fri_commit_batched(vph_session *, const uint64_t *r_pairs, int n_steps, uint8_t *roots, uint64_t *final_pairs, char *err, int errlen);
+/* The commitment calls below go through the session's prover, so on a session with a sharded commitment (vph_session_create_sharded) they run on
+ * every rank and return the merged answer; on any other session they are the calls of include/vpgpu.h on its one context.  0 = done, -2 = error (err).
+ * vph_commit_private_masked: prover::commit_private(mask) (an all-zero mask is vph_commit_private; a non-zero one is refused on a sharded commitment).
+ * vph_commit_public_eq: prover::commit_public_eq, out = root_h | input_0 | all_sum[65].  vph_fri_open_many / vph_fri_query: vp_fri_open_many /
+ * vp_fri_query with their layouts (path_stride in bytes, a multiple of 32).                                                                      */
+int vph_commit_private_masked(vph_session *, const uint64_t *mask_pairs, uint64_t n_mask, uint8_t root[32], double *ms, char *err, int errlen);
+int vph_commit_public_eq(vph_session *, const uint64_t *point_pairs, int n_point, uint8_t out[32 + 16 + 65 * 16], double *ms, char *err, int errlen);
+int vph_fri_open_many(vph_session *, int n, const int32_t *oracle, const uint64_t *leaf, uint64_t *values_pairs, uint8_t *paths, int path_stride,
+                      int32_t *path_len, char *err, int errlen);
+int vph_fri_query(vph_session *, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written, char *err, int errlen);
 /* The whole protocol of verifier::verify() up to commit_public (src/verifier.cpp:134-169,363-379), interactive
  * GKR: writes merkle_root_l | GKR slice | merkle_root_h | input_0 | all_sum[65] — the golden layout.   */
 int vph_prove_full(vph_session *, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, int batched, char *err,
