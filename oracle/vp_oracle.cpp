@@ -1409,13 +1409,10 @@ int64_t orc_prove_full(orc_circuit *oc, uint8_t *transcript, int64_t capacity, o
 
 }  // extern "C"
 
-extern "C" int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code) {
-    if (n_bits < 7) return -1;
-    const u64 n = 1ull << n_bits;
-    vector<F> in(n), pb(n), vo;
-    for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
-    PublicOut po;
-    commit_public_core(in, pb, n_bits, n, po, &vo);
+// fri::commit_phase_step (fri.cpp:289-424) looped over the n_bits-6 challenges on the virtual oracle vo [64][2^(n_bits-1)], then
+// fri::commit_phase_final's layout: the loop behind orc_fri_commit and orc_commitment_array.
+namespace {
+void fri_commit_loop(const vector<F> &vo, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code) {
     u64 M = 1ull << (n_bits - 1);
     const int steps = n_bits - 6;
     const F inv2 = finv(F(2ll));
@@ -1451,6 +1448,38 @@ extern "C" int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, 
                 orc_F &o = final_code[(i << 7) | (s << 1) | hi];
                 o.real = x.re; o.img = x.im;
             }
+}
+}  // namespace
+
+extern "C" int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code) {
+    if (n_bits < 7) return -1;
+    const u64 n = 1ull << n_bits;
+    vector<F> in(n), pb(n), vo;
+    for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
+    PublicOut po;
+    commit_public_core(in, pb, n_bits, n, po, &vo);
+    fri_commit_loop(vo, n_bits, r, roots, final_code);
+    return 0;
+}
+
+extern "C" int orc_commitment_array(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, uint8_t root_l[32],
+                                    orc_F *inner, orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots, orc_F *final_code) {
+    if (n_bits < 7 || n_used > (1ull << n_bits)) return -1;
+    const u64 n = 1ull << n_bits;
+    vector<F> in(n), pb(n), vo;
+    for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
+    {   // merkle_root_l, as orc_commit_private
+        vector<F> l_eval; u64 slice_size;
+        commit_private_evals(in, n_bits, l_eval, slice_size);
+        Digest d = merkle_root(leaf_hashes(l_eval, slice_size));
+        memcpy(root_l, d.w, 32);
+    }
+    PublicOut po;
+    commit_public_core(in, pb, n_bits, n_used, po, &vo);
+    inner->real = po.inner.re; inner->img = po.inner.im;
+    for (int i = 0; i < 65; ++i) { all_sum[i].real = po.all_sum[i].re; all_sum[i].img = po.all_sum[i].im; }
+    memcpy(root_h, po.root_h.w, 32);
+    fri_commit_loop(vo, n_bits, r, roots, final_code);
     return 0;
 }
 

@@ -136,6 +136,12 @@ int orc_commit_public(const orc_F *input, const orc_F *pub, int n_bits, uint64_t
 /* The point the input layer is opened at (r_liu after the last Liu sumcheck) of the last orc_prove_full run.  */
 int orc_last_point(const orc_circuit *, orc_F *out, int n);
 int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code);
+/* The whole commitment on caller-supplied arrays in one pass: commit_private_array's root (merkle_root_l), commit_public_array's outputs as
+ * orc_commit_public gives them (inner product over the first n_used entries) and the FRI commit phase as orc_fri_commit gives it.  input and pub
+ * have 2^n_bits entries (input zero from n_used on, as the padded input layer is); r the n_bits-6 fold challenges; roots 32 (n_bits-6) bytes;
+ * final_code 2048 elements.  A composition of the functions above: no arithmetic of its own.                                              */
+int orc_commitment_array(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, uint8_t root_l[32], orc_F *inner,
+                         orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots, orc_F *final_code);
 
 #ifdef __cplusplus
 }

@@ -794,30 +794,35 @@ def test_fri_commit_phase_randomize(vp, golden):
 
 
 def test_commitment_with_split_transforms_vs_oracle(vp, ob, pws_path):
-    """128 blocks: slices of 2^14 elements, beyond the in-LDS transform -> split path.  No golden at this size:
-    compare commit_private / commit_public with the oracle's restatement on the same witness and public vector."""
+    """128 blocks: slices of 2^14 elements, beyond the in-LDS transform -> split path (k_ntt_split -> k_ntt_lds, ntt_r8 = 0) and, as shipped, the radix-8
+    pair.  No golden at this size: compare commit_private / commit_public of both with the oracle's restatement on the same witness and public vector."""
     c = vp.Circuit.from_pws(pws_path, 128, seed=3)
     oc = ob.Circuit.from_pws(pws_path, 128, seed=3)
     assert c.hash() == oc.hash()
-    s = vp.Session(c)
-    root, _ = s.commit_private()
     L = ob.lib()
     L.orc_commit_private.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
     er = ctypes.create_string_buffer(32)
     assert L.orc_commit_private(oc.h, er) == 0
-    assert root == er.raw
     n_bits = c.layer_bitlen(0)
     assert n_bits - 6 == 14
     rng = np.random.default_rng(8)
     pub = rng.integers(0, P, size=(1 << n_bits, 2), dtype=np.uint64)
-    root_h, inner, all_sum, _ = s.commit_public(pub)
     inp = np.zeros((1 << n_bits, 2), dtype=np.uint64)
     L.orc_circuit_inputs(oc.h, inp.ctypes.data)
     e_inner = np.zeros(2, dtype=np.uint64); e_all = np.zeros((65, 2), dtype=np.uint64); e_root = ctypes.create_string_buffer(32)
     L.orc_commit_public.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p]
     assert L.orc_commit_public(inp.ctypes.data, pub.ctypes.data, n_bits, oc.layer_size(0), e_inner.ctypes.data, e_all.ctypes.data, e_root) == 0
-    assert inner == e_inner.tobytes() and all_sum == e_all.tobytes() and root_h == e_root.raw
-    s.close(); c.close(); oc.close()
+    for options in (vp.Options(ntt_r8=0), None):
+        s = vp.Session(c, options=options)
+        s.set_profiling(1)
+        root, _ = s.commit_private()
+        assert ("k_ntt_split" in {e["kernel"] for e in s.launch_stats()}) == (options is not None)       # the split path runs when asked for, and only then
+        s.set_profiling(0)
+        assert root == er.raw
+        root_h, inner, all_sum, _ = s.commit_public(pub)
+        assert inner == e_inner.tobytes() and all_sum == e_all.tobytes() and root_h == e_root.raw
+        s.close()
+    c.close(); oc.close()
 
 
 def test_sha256_x128_vs_oracle(vp, ob, pws_path):

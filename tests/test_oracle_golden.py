@@ -240,6 +240,44 @@ def test_oracle_full_transcript_and_fri_randomize(ob, golden):
     c.close()
 
 
+def test_oracle_commitment_array_vs_reference_x1(ob, golden, pws_path):
+    """orc_commitment_array (commit_private, commit_public and the FRI commit phase on caller-supplied arrays, in one pass) on sha256_x1's input layer, the eq
+    table of its opening point and the challenges the real reference recorded: every output is what the reference's golden transcript and FRI record hold."""
+    import pc_array_inputs as pai
+    from conftest import GOLDEN
+    L = ob.lib()
+    L.orc_prove_full.restype = ctypes.c_int64
+    L.orc_prove_full.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    L.orc_last_point.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    g = golden["sha256_x1"]
+    gold = open(os.path.join(GOLDEN, g["transcript"]), "rb").read()
+    fri = open(os.path.join(GOLDEN, g["fri"]), "rb").read()
+    c = ob.Circuit.from_pws(pws_path, 1, seed=1)
+    buf = ctypes.create_string_buffer(1 << 20)
+    assert L.orc_prove_full(c.h, buf, len(buf), None) == len(gold)           # (leaves the opening point behind)
+    nb = L.orc_circuit_layer_bitlen(c.h, 0)
+    st = g["fri_steps"]
+    assert st == nb - 6
+    pt = np.zeros((nb, 2), np.uint64)
+    assert L.orc_last_point(c.h, pt.ctypes.data, nb) == 0
+    one = np.array([1, 0], np.uint64)
+    pub = np.zeros((1 << nb, 2), np.uint64)
+    L.orc_beta_table(pt.ctypes.data, nb, one.ctypes.data, pub.ctypes.data)
+    inp = np.zeros((1 << nb, 2), np.uint64)
+    L.orc_circuit_inputs(c.h, inp.ctypes.data)
+    rec = np.frombuffer(fri[:48 * st], dtype=np.uint64).reshape(st, 6)
+    r = np.ascontiguousarray(rec[:, :2])
+    assert c.layer_size(0) < 1 << nb                                         # the inner product stops before the padding
+    out = pai.split_record(pai.oracle_record(L, inp, c.layer_size(0), pub, nb, r), nb)
+    tail = 16 + 65 * 16
+    assert out["root_l"] == gold[:32]
+    assert out["root_h"] == gold[-tail - 32:-tail]
+    assert out["public"] == gold[-tail:]                                     # input_0 | all_sum[65]
+    assert out["roots"] == [rec[k, 2:].tobytes() for k in range(st)]
+    assert out["final"] == fri[48 * st:48 * st + 2048 * 16]
+    c.close()
+
+
 @pytest.mark.parametrize("name", ["custom_a", "custom_b"])
 def test_oracle_on_all_gate_types_and_asserts_vs_reference(ob, golden, name):
     """Circuits using every gate type + assert gates, proved by the REAL reference (ref_run --custom): the oracle must
@@ -385,6 +423,41 @@ def test_masked_commitment_goldens_are_the_recorded_files():
             assert fri[-32 * 16:] == bytes(32 * 16) and rec[64 + 64 * 16:64 + 65 * 16] == bytes(16)          # zero mask: all_sum[64] = 0, mask codeword 0
         else:
             assert fri[-32 * 16:] != bytes(32 * 16) and rec[64 + 64 * 16:64 + 65 * 16] != bytes(16)
+
+
+def test_commitment_array_goldens_are_the_recorded_files():
+    """tests/golden/pc_array_n18.bin / _n20.bin (the oracle's orc_commitment_array on the uniform input set, make_pc_array.py): the files are the ones the index
+    was written for, they have the record's layout, and the inputs the GPU test regenerates are the ones they were recorded with."""
+    import json
+    import pc_array_inputs as pai
+    from conftest import GOLDEN
+    meta = json.load(open(os.path.join(GOLDEN, "pc_array.json")))
+    assert sorted(meta) == ["n18", "n20"]
+    for m in meta.values():
+        rec = open(os.path.join(GOLDEN, m["record"]), "rb").read()
+        assert hashlib.sha256(rec).hexdigest() == m["record_sha256"] and len(rec) == pai.record_bytes(m["n"])
+        assert m["seed"] == pai.seed_of(m["set"], m["n"])
+        x = pai.inputs(m["set"], m["n"], seed=m["seed"])
+        assert x["n_used"] == m["n_used"] == (1 << m["n"]) - 3
+        for k, v in pai.digests(x).items():
+            assert m[k] == v, "input generator differs: " + k
+        f = pai.split_record(rec, m["n"])
+        assert len(set(f["roots"] + [f["root_l"], f["root_h"]])) == m["n"] - 4 and f["public"][-16:] == bytes(16)      # all_sum[64]: the zero mask
+
+
+def test_commitment_array_input_sets_have_their_edges():
+    """the three input sets of the commitment ladder are what its cases name: canonical limbs, the unused tail, the all-zero slices, the five-wire witness"""
+    import pc_array_inputs as pai
+    for n in (7, 12):
+        sl = 1 << (n - 6)
+        a, b, c = (pai.inputs(k, n) for k in pai.SETS)
+        assert a["n_used"] == (1 << n) - 3 and not a["values"][-3:].any() and a["values"][-4].any() and a["values"][:, 1].any()
+        assert b["n_used"] == 1 << n and set(np.unique(b["values"])) <= set(pai.EDGES) and set(np.unique(b["pub"])) <= set(pai.EDGES)
+        assert not b["values"][5 * sl:6 * sl].any() and not b["values"][63 * sl:].any() and not b["pub"][7 * sl:8 * sl].any() and not b["pub"][0].any()
+        assert b["values"][4 * sl:5 * sl].any() and b["values"][62 * sl:63 * sl].any() and b["pub"][6 * sl:7 * sl].any()
+        assert c["n_used"] == 5 and c["values"][:5, 0].all() and not c["values"][5:].any() and not c["values"][:, 1].any()
+        for x in (a, b, c):
+            assert x["r"].shape == (n - 6, 2) and int(max(x["values"].max(), x["pub"].max(), x["r"].max())) < pai.P61
 
 
 @pytest.mark.parametrize("name", ["n13_m5", "n13_m64", "n16_m100", "n13_m300", "n13_m2000"])
