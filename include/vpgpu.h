@@ -397,6 +397,17 @@ int vp_commit_stats(vp_ctx *, double *commit_ms);
 int vp_set_deferred(vp_ctx *, int on);
 int vp_flush(vp_ctx *, int count);
 int vp_pending(vp_ctx *, int *n);
+/* Postponed hashing: one leaf-hash launch and one sequence of Merkle launches for the l, h and FRI oracles of a prover pass.  Nothing in the pass reads a
+ * root on the device (the folds read codewords and challenges), so with vp_pc_hash_late(ctx, 1) the unmasked, unsharded vp_commit_private, vp_commit_public
+ * and vp_commit_public_eq queue their transforms and stop: the oracle is "codeword complete, not hashed", the root pointer is remembered and NOT written
+ * (input_0 and all_sum are delivered as always).  The one-pass vp_fri_commit then puts every such oracle in front of its own levels: one launch hashes all
+ * leaves (an l or h codeword is a list entry like a level's, same digests), the trees are built together, and the roots are written, each where its call
+ * asked for it, when vp_fri_commit completes (at once, or in vp_flush under vp_set_deferred).  The root buffers must stay valid until then.
+ * No call sequence sees a missing tree: vp_fri_open / _open_many / _query(_bytes), vp_fri_step (and the masked vp_fri_commit), another vp_commit_private or
+ * vp_commit_public(_eq), the masked commits, vp_evaluate, vp_circuit_upload, vp_pc_load_input, vp_pc_set_shard, vp_destroy, and vp_flush once the mode is
+ * off, first hash what is outstanding with the single-oracle launches of the synchronous calls, wait, and write the same root bytes.  Masked and sharded
+ * commitments ignore the mode.  vp_pc_hash_late(ctx, 0) itself leaves what is unhashed unhashed; vp_pending's counts are those of the mode off. */
+int vp_pc_hash_late(vp_ctx *, int on);
 /* device time in ms of the last finished vp_commit_private | vp_prove_gkr | vp_commit_public(_eq) | vp_fri_commit | vp_fri_final of the context */
 int vp_phase_ms(vp_ctx *, double out[5]);
 /* how many vp_commit_private calls the context has queued so far, and whether the latest one still stands (no upload / evaluate / vp_pc_load_input since) */

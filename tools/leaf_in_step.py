@@ -7,7 +7,8 @@ Needs the diagnostic build of the library (stamps in the leaf-hash kernels only,
 Every workgroup of k_leaf_hash / k_leaf_hash_multi stamps {s_memtime, s_memrealtime} before and after its 65-step chains.  Per launch this prints the
 launch's duration by the 100 MHz real-time counter (first workgroup in -> last workgroup out), the median duration of one workgroup in shader
 cycles (work: it does not depend on the clock) and the median effective shader clock d(memtime) / d(memrealtime) x 100 MHz of its workgroups —
-(a) inside the protocol step (commit_private -> GKR -> commit_public -> fft_gkr -> FRI), after >= 2 s of back-to-back steps;
+(a) inside the protocol step (commit_private -> GKR -> commit_public -> fft_gkr -> FRI; one launch for l, h and the FRI levels), after >= 2 s of
+    back-to-back steps; (a-) the same with every commit hashing its own oracle (three launches);
 (b) the same launch alone, back to back, after >= 2 s of itself;
 (c) the step again with idle gaps in front of it (the clock a cold chip gives the first kernels).
 If (a) and (b) differ in clock at equal cycles per workgroup, the step loses to the clock; if the cycles differ, to the memory side."""
@@ -117,6 +118,18 @@ a = launches(sa)
 show("(a) in step", a[:6])
 octiles("(a) in step", sa, (0, 1, 2, 3, 4, 5))
 summary("(a) in step", a)
+
+# (a-) the pass in its earlier form: every commit hashes its own oracle (three launches of 2048 workgroups instead of the one of 6144 above)
+t = time.time()
+while time.time() - t < 2.5:
+    s.prove_protocol(hash_per_call=True)
+stamps()
+for _ in range(5):
+    s.prove_protocol(hash_per_call=True)
+so = stamps()
+show("(a-) in step, hash per call", launches(so)[:6])
+octiles("(a-) hash per call", so, (0, 1, 2, 3, 4, 5))
+summary("(a-) in step, hash per call", launches(so))
 
 # (b) alone, back to back
 t = time.time()

@@ -131,6 +131,7 @@ def lib_gpu():
         L.vp_warm.argtypes = [vp, ctypes.c_uint32]
         L.vp_flush.argtypes = [vp, ctypes.c_int]
         L.vp_pending.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        L.vp_pc_hash_late.argtypes = [vp, ctypes.c_int]
         L.vp_phase_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.vp_commit_private.argtypes = [vp, vp]
         L.vp_fft_gkr_sizes.argtypes = [ctypes.c_int, vp, vp]
@@ -1000,13 +1001,14 @@ class Session:
         if lib_host().vph_draw_protocol_tape(self.h):
             raise RuntimeError("draw_protocol_tape: the commitment needs an input layer of at least 2^7 wires")
 
-    def prove_protocol(self, deferred=False, queue_next=False):
+    def prove_protocol(self, deferred=False, queue_next=False, hash_per_call=False):
         """The prover side of the complete protocol in one pass (no verifier work): commit_private -> batched GKR -> commit_public on
         eq(r_liu, .) -> fft_gkr -> FRI commit phase.  Returns (transcript in the golden layout, FRI roots bytes, final codeword (2048, 2),
         seconds dict {total, commit_private, gkr, commit_public, fft_gkr, fri_commit}).
         deferred: the calls are queued back to back and collected at the end (vp_set_deferred: no idle device between them); the per-call seconds are then
         device times.  queue_next: the pass also queues the next pass's commit_private behind its own folds (vphost.h, VPH_PASS_QUEUE_NEXT): for a
-        session that proves back to back; this pass's commitment cannot be opened afterwards."""
+        session that proves back to back; this pass's commitment cannot be opened afterwards.  hash_per_call: every commit hashes its own oracle (three
+        leaf-hash launches) instead of the one launch behind the FRI folds (vphost.h, VPH_PASS_HASH_PER_CALL): same bytes, the A/B partner."""
         import numpy as np
         if not hasattr(self, "_pp"):
             cap = self._cap + 32 + 32 + 16 + 65 * 16
@@ -1014,7 +1016,7 @@ class Session:
                         (ctypes.c_double * 6)(), ctypes.c_uint64(0), ctypes.create_string_buffer(512))
         buf, cap, roots, fin, sec, n, err = self._pp
         rc = lib_host().vph_prove_protocol_ex(self.h, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n), ctypes.cast(roots, ctypes.c_void_p), len(roots),
-                                              fin.ctypes.data, sec, (1 if deferred or queue_next else 0) | (2 if queue_next else 0), err, len(err))
+                                              fin.ctypes.data, sec, (1 if deferred or queue_next else 0) | (2 if queue_next else 0) | (4 if hash_per_call else 0), err, len(err))
         if rc:
             raise RuntimeError("prove_protocol failed: " + err.value.decode())
         st = self.circuit.layer_bitlen(0) - 6

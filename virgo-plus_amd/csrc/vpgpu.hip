@@ -254,6 +254,13 @@ struct vp_ctx {
     bool pc_dry = false;                                                    // vp_warm: the transform helpers set up their tables and scratch and launch nothing
     unsigned char *h_pub = nullptr; size_t h_pub_cap = 0;                   // vp_warm: pinned staging of vp_commit_public's vector (uploaded from here in chunks)
     u64 private_epoch = 0;                                                  // vp_commit_private calls queued on this context so far
+    // Postponed hashing (vp_pc_hash_late): the unmasked, unsharded vp_commit_private / vp_commit_public(_eq) stop behind their transforms; vp_fri_commit hashes
+    // what they left together with its own levels (one leaf-hash launch, one sequence of Merkle launches).  pc_unhashed: bit 0 = l, bit 1 = h — codeword
+    // complete, leaf chains and tree not queued yet; late_root: where that call's caller wants the root.  Whatever reads a tree or replaces a codeword first
+    // hashes what is outstanding with the single-oracle launches (pc_hash_outstanding).
+    int hash_late = 0;
+    unsigned pc_unhashed = 0;
+    uint8_t *late_root[2] = {nullptr, nullptr};
 
     PcShard *pcs = nullptr;              // non-null while the commitment is sharded over ranks (vp_pc_set_shard, world > 1)
     FgkState *fgk = nullptr;             // vp_fft_gkr: circuit layers and sumcheck tables of the last size used
@@ -343,6 +350,7 @@ struct CtxLock {
 };
 #define VP_LOCK(ctx) CtxLock vp_ctx_lock_(ctx, false)
 int flush_pending(vp_ctx *ctx, size_t count);
+int pc_hash_outstanding(vp_ctx *ctx, unsigned which);          // vpgpu_pc.inc
 // VP_ENTER_Q: the entry points that can leave their completion pending (deferred mode); everything else finishes what is pending first
 #define VP_ENTER_Q(ctx) CtxLock vp_ctx_lock_(ctx, true); do { HIPCHK(hipSetDevice((ctx)->device)); if ((ctx)->tail_active) (void) tail_quit(ctx); (ctx)->tail_suspended = false; (ctx)->tail_lost = false; (ctx)->ring_call = 0; } while (0)
 #define VP_ENTER(ctx) VP_ENTER_Q(ctx); do { if (!(ctx)->pending.empty()) VPCHK(flush_pending((ctx), (size_t) -1)); } while (0)
@@ -1189,6 +1197,7 @@ void vp_destroy(vp_ctx *ctx) {
     (void) hipSetDevice(ctx->device);
     if (ctx->tail_active) (void) tail_quit(ctx);
     (void) hipStreamSynchronize(ctx->stream);
+    (void) pc_hash_outstanding(ctx, 3u);                      // a root that a commit under vp_pc_hash_late still owes its caller
     vp_free_shard_state(ctx);
     rs_free(ctx);
     vp_free_comm(ctx);
@@ -1223,6 +1232,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     if (n_layers > VP_MAX_TAB) { ctx->err = "too many layers"; return VP_ELIMIT; }
     RandKeep keep_callers_random_stream;                               // rocPRIM / first-use module loads: see vp_create_with_options
     VP_ENTER(ctx);
+    VPCHK(pc_hash_outstanding(ctx, 3u));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->gkr_graph) { (void) hipGraphExecDestroy(ctx->gkr_graph); ctx->gkr_graph = nullptr; }
     ctx->graph_failed = false; ctx->plan_tuned = false; ctx->plan_tune_cached = false;
@@ -1443,6 +1453,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
 int vp_evaluate(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs) {
     if (!ctx || !inputs || ctx->n_layers < 2 || n_inputs != ctx->L[0].size) return VP_EINVAL;
     VP_ENTER(ctx);
+    VPCHK(pc_hash_outstanding(ctx, 3u));
     LayerDev &L0 = ctx->L[0];
     ctx->pc_private_done = false; ctx->pc_public_done = false; ctx->pc_mask_ms = 0;          // a commitment to the previous witness does not stand for this one
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
@@ -2015,7 +2026,14 @@ int vp_pending(vp_ctx *ctx, int *n) {
 int vp_flush(vp_ctx *ctx, int count) {
     if (!ctx) return VP_EINVAL;
     VP_ENTER_Q(ctx);
-    return flush_pending(ctx, count < 0 ? (size_t) -1 : (size_t) count);
+    VPCHK(flush_pending(ctx, count < 0 ? (size_t) -1 : (size_t) count));
+    return ctx->hash_late ? VP_OK : pc_hash_outstanding(ctx, 3u);     // mode switched off with a hash still owed: no vp_fri_commit is coming for it
+}
+int vp_pc_hash_late(vp_ctx *ctx, int on) {
+    if (!ctx) return VP_EINVAL;
+    VP_ENTER_Q(ctx);
+    ctx->hash_late = on ? 1 : 0;                              // (what is unhashed stays so: vp_fri_commit, vp_flush with the mode off, or whatever needs a tree hashes it)
+    return VP_OK;
 }
 int vp_phase_ms(vp_ctx *ctx, double out[5]) {
     if (!ctx || !out) return VP_EINVAL;

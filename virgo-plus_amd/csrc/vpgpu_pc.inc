@@ -373,6 +373,30 @@ int pc_merkle(vp_ctx *ctx, Dig *tree, u32 n_leaves) {    // leaves already at tr
     return VP_OK;
 }
 
+// vp_pc_hash_late: the leaf chains and trees that vp_commit_private / vp_commit_public(_eq) left for vp_fri_commit (vp_ctx::pc_unhashed; which: bit 0 = l,
+// bit 1 = h), by the single-oracle launches of the synchronous calls, finished here; each root goes where its call was asked to put it.  Called by everything
+// that reads a tree, replaces a codeword or ends the context before a vp_fri_commit has merged them.
+int pc_hash_outstanding(vp_ctx *ctx, unsigned which) {
+    which &= ctx->pc_unhashed;
+    if (!which) return VP_OK;
+    if (ctx->L.empty() || !ctx->pc_cw || !ctx->pc_tree) { ctx->pc_unhashed = 0; ctx->err = "internal: unhashed oracle without its codeword"; return VP_EINVAL; }
+    const int n = ctx->L[0].bl;
+    const u32 N = 1u << (n - 6), n_leaves = 1u << (n - 2);
+    uint8_t got[2][32];
+    for (int o = 0; o < 2; ++o) {
+        if (!(which >> o & 1)) continue;
+        const F *cw = o ? ctx->pc_hcw : ctx->pc_cw;
+        Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
+        PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65, pc_launch_leaf_hash(ctx, cw, N, tree + n_leaves));
+        VPCHK(pc_merkle(ctx, tree, n_leaves));
+        HIPCHK(hipMemcpyAsync(got[o], tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ctx->pc_unhashed &= ~which;
+    VPCHK(check_stream(ctx));
+    for (int o = 0; o < 2; ++o) if ((which >> o & 1) && ctx->late_root[o]) { memcpy(ctx->late_root[o], got[o], 32); ctx->late_root[o] = nullptr; }
+    return VP_OK;
+}
+
 // the same entry points on a commitment sharded over ranks (vpgpu_pc_shard.inc)
 int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]);
 int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]);
@@ -415,6 +439,7 @@ static int pc_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     if (oracle < 0 || ctx->L.empty()) return VP_EINVAL;
     if (oracle >= VP_OPEN_MAX_ORACLES) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
     if (ctx->pcs) return pcs_open_desc(ctx, oracle, d);
+    VPCHK(pc_hash_outstanding(ctx, 3u));
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
     if (oracle == 0) { if (!ctx->pc_private_done) return VP_EINVAL; d->cw = ctx->pc_cw; d->tree = ctx->pc_tree; d->Nc = N; d->n_leaves = M >> 1; }
@@ -583,6 +608,8 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
                           const vp_F *pub_mask = nullptr, uint64_t n_pub_mask = 0) {
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
+    VPCHK(pc_hash_outstanding(ctx, 2u));                  // an h of an earlier call that no vp_fri_commit has hashed: its codeword is replaced below
+    const bool late = ctx->hash_late && !pub_mask;        // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels
     F *P = ctx->pc_tmp, *ST = ctx->pc_tmp + (size_t) 128 * N, *H = ctx->pc_tmp + (size_t) 256 * N;
     F *parts = ctx->pc_small, *d_inner = ctx->pc_small + 1024, *d_all = ctx->pc_small + 1025;
     // input_0 = <circuitValue[0], pub>
@@ -644,17 +671,19 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
         hipLaunchKernelGGL(k_mask_hcoef, dim3(nblk((u64) B)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (t + 4 * B), ms, (u32) B, f_make(ms, 0), t, S0m, d_all + 64);
         VPCHK(pc_mask_encode(ctx, t, ms, ctx->pc_hm_cw));
         pc_launch_leaf_hash_masked(ctx, ctx->pc_hcw, N, ctx->pc_hm_cw, ctx->pc_tree_h + n_leaves);
-    } else
+    } else if (!late)
     PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
             pc_launch_leaf_hash(ctx, ctx->pc_hcw, N, ctx->pc_tree_h + n_leaves));
-    VPCHK(pc_merkle(ctx, ctx->pc_tree_h, n_leaves));
+    if (!late) VPCHK(pc_merkle(ctx, ctx->pc_tree_h, n_leaves));
     unsigned char *st = nullptr;                          // root_h | inner | all_sum[65]
     VPCHK(ring_alloc(ctx, 32 + 66 * sizeof(F), (void **) &st));
-    HIPCHK(hipMemcpyAsync(st, ctx->pc_tree_h + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (!late) HIPCHK(hipMemcpyAsync(st, ctx->pc_tree_h + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(st + 32, d_inner, 66 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));        // d_all = d_inner + 1
     ctx->pc_public_done = true; ctx->fri_step = -1;
-    return defer_end(ctx, ev_a, VP_PH_PUBLIC, [ctx, st, root_h, inner, all_sum](float ms) {
-        memcpy(root_h, st, 32); memcpy(inner, st + 32, sizeof(F)); memcpy(all_sum, st + 32 + sizeof(F), 65 * sizeof(F));
+    if (late) { ctx->pc_unhashed |= 2u; ctx->late_root[1] = root_h; }
+    return defer_end(ctx, ev_a, VP_PH_PUBLIC, [ctx, st, root_h, inner, all_sum, late](float ms) {
+        if (!late) memcpy(root_h, st, 32);
+        memcpy(inner, st + 32, sizeof(F)); memcpy(all_sum, st + 32 + sizeof(F), 65 * sizeof(F));
         ctx->commit_ms = ms;
         return VP_OK;
     });
@@ -672,6 +701,8 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
     if (n > PC_MAX_N) { ctx->err = "input layer of more than 2^25 wires: the reference's commitment indexes its codeword with int (poly_commit.h:87-166), "
                                    "which overflows at 2^26 wires"; return VP_ELIMIT; }
     const u32 N = 1u << ln, M = 1u << lm;
+    VPCHK(pc_hash_outstanding(ctx, 3u));                  // an earlier commitment under vp_pc_hash_late whose codeword this call replaces
+    const bool late = ctx->hash_late && !mask;            // vp_pc_hash_late: the transforms only; vp_fri_commit hashes l with h and its own levels
     u32 ms = 0;
     if (mask) { VPCHK(pc_mask_geometry(ctx, n_mask, &ms)); VPCHK(flush_pending(ctx, (size_t) -1)); }
     VPCHK(pc_root_table(ctx, lm));
@@ -703,6 +734,11 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
         VPCHK(pc_mask_lde(ctx, mask, n_mask, ms, ctx->pc_lm_cw));
         pc_launch_leaf_hash_masked(ctx, ctx->pc_cw, N, ctx->pc_lm_cw, ctx->pc_tree + n_leaves);
         ctx->pc_mask_ms = ms;
+    } else if (late) {
+        ctx->pc_unhashed |= 1u; ctx->late_root[0] = root;
+        ctx->pc_private_done = true; ++ctx->private_epoch;
+        ctx->pc_public_done = false;
+        return defer_end(ctx, ev_a, VP_PH_PRIVATE, [ctx](float ms) { ctx->commit_ms = ms; return VP_OK; });
     } else
     PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
             pc_launch_leaf_hash(ctx, ctx->pc_cw, N, ctx->pc_tree + n_leaves));
@@ -888,6 +924,7 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
     if (ctx->pcs) { VP_ENTER(ctx); return pcs_fri_step(ctx, r, root); }
     if (!ctx->pc_public_done) return VP_EINVAL;
     VP_ENTER(ctx);
+    VPCHK(pc_hash_outstanding(ctx, 3u));                  // (vp_pc_hash_late: only the one-pass vp_fri_commit merges)
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
     if (!ctx->pc_fri_all) {
@@ -969,6 +1006,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     if (n_steps > ln || n_steps > VP_FRI_MAX) { ctx->err = "too many FRI steps"; return VP_EINVAL; }
     if (ctx->pc_mask_ms) {             // a commitment with a mask slice: the per-step path carries the 65th slice (the fused first folds and the all-level leaf launch do not)
         VPCHK(flush_pending(ctx, (size_t) -1));
+        VPCHK(pc_hash_outstanding(ctx, 3u));
         double ms_sum = 0;
         for (int k = 0; k < n_steps; ++k) { VPCHK(vp_fri_step(ctx, r + k, roots + 32 * (size_t) k)); ms_sum += ctx->commit_ms; }
         ctx->commit_ms = ms_sum;
@@ -991,6 +1029,22 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     // folds of every level, back to back
     FriLeafArgs la{}; MerkleArgs ma{};
     u32 blocks = 0; size_t cw_off = 0;
+    // vp_pc_hash_late: the oracles whose commit stopped behind its transforms go IN FRONT of the levels in the same lists — an l or h codeword is an entry
+    // with N values per coset and 16 N leaves like a level's.  VP_FRI_MAX covers n_steps + 2 (n <= 25: 21 entries) and the u32 leaf offsets 3 x 2^23 leaves.
+    if (n_steps + 2 > VP_FRI_MAX) VPCHK(pc_hash_outstanding(ctx, 3u));
+    const unsigned merged = ctx->pc_unhashed;
+    uint8_t *late_root[2] = {nullptr, nullptr};
+    int ne = 0;
+    for (int o = 0; o < 2; ++o) {
+        if (!(merged >> o & 1)) continue;
+        Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
+        const u32 n_leaves = M >> 1;
+        ma.tree[ne] = tree; ma.count[ne] = n_leaves;
+        la.cw[la.n] = o ? ctx->pc_hcw : ctx->pc_cw; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = N; blocks += nblk(n_leaves); ++la.n;
+        late_root[ne] = ctx->late_root[o];
+        ++ne;
+    }
+    const int nt = ne + n_steps;                          // trees of this call
     // folds 0, 1, 2 in one pass (k_fri_fold0_vo3): every challenge is here before the first fold starts
     const bool fold3 = n_steps >= 3 && ln >= 9;       // (E = N / 8 >= 64: a wave per offset)
     for (int k = 0; k < n_steps; ++k) {
@@ -1043,7 +1097,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                                    host_inv_real(2), 0, 0u));
         const u32 n_leaves = 16 * No;
         Dig *tree = ctx->pc_fri_tree + ctx->fri_tree_used;
-        ma.tree[k] = tree; ma.count[k] = n_leaves;
+        ma.tree[ne + k] = tree; ma.count[ne + k] = n_leaves;
         {   // every level, the single-value last one included, goes into the one leaf-hash launch (the chain of 65 Keccak-f is
             // a fixed ~1 ms latency however few leaves there are)
             la.cw[la.n] = out; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
@@ -1052,12 +1106,13 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         ctx->fri_tree_used += 2 * (size_t) n_leaves;
     }
     u64 all_leaves = 0;
-    for (int k = 0; k < n_steps; ++k) all_leaves += ma.count[k];
+    for (int k = 0; k < nt; ++k) all_leaves += ma.count[k];
     if (la.n) PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65, pc_launch_leaf_hash_multi(ctx, la));
-    // Merkle trees of all levels, one launch per height while some tree still has more than 512 nodes at it
+    if (merged) { ctx->pc_unhashed = 0; ctx->late_root[0] = ctx->late_root[1] = nullptr; }      // queued: whatever follows in stream order finds the trees
+    // Merkle trees of all levels (and of the merged oracles), one launch per height while some tree still has more than 512 nodes at it
     for (;;) {
         MerkleArgs lv{}; u32 b = 0;
-        for (int k = 0; k < n_steps; ++k) {
+        for (int k = 0; k < nt; ++k) {
             const u32 c = ma.count[k] >> 1;
             if (c <= 512) continue;
             lv.tree[lv.n] = ma.tree[k]; lv.count[lv.n] = c; lv.blk_start[lv.n] = b; b += nblk(c); ++lv.n;
@@ -1069,17 +1124,24 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         for (int q = 0; q < lv.n; ++q) hs += lv.count[q];
         PC_PROF(VP_K_MERKLE, b, lv.n, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_level_multi, dim3(b), dim3(VP_BLOCK), 0, ctx->stream, lv));
     }
-    ma.n = n_steps;
+    ma.n = nt;
     {
         u64 hs = 0;
-        for (int k = 0; k < n_steps; ++k) hs += ma.count[k] ? ma.count[k] - 1 : 0;
-        PC_PROF(VP_K_MERKLE, n_steps, n_steps, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_top_multi, dim3(n_steps), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots));
+        for (int k = 0; k < nt; ++k) hs += ma.count[k] ? ma.count[k] - 1 : 0;
+        PC_PROF(VP_K_MERKLE, nt, nt, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_top_multi, dim3(nt), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots));
     }
-    void *st = nullptr;
-    VPCHK(ring_alloc(ctx, (size_t) 32 * n_steps, &st));
-    HIPCHK(hipMemcpyAsync(st, d_roots, (size_t) 32 * n_steps, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned char *st = nullptr;                          // the merged oracles' roots | the levels' roots: one pinned copy
+    VPCHK(ring_alloc(ctx, (size_t) 32 * nt, (void **) &st));
+    HIPCHK(hipMemcpyAsync(st, d_roots, (size_t) 32 * nt, hipMemcpyDeviceToHost, ctx->stream));
     ctx->fri_step = n_steps;
-    return defer_end(ctx, ev_a, VP_PH_FRI, [ctx, st, roots, n_steps](float ms) { memcpy(roots, st, (size_t) 32 * n_steps); ctx->commit_ms = ms; return VP_OK; });
+    uint8_t *lr0 = late_root[0], *lr1 = late_root[1];
+    return defer_end(ctx, ev_a, VP_PH_FRI, [ctx, st, roots, n_steps, ne, lr0, lr1](float ms) {
+        if (ne > 0 && lr0) memcpy(lr0, st, 32);
+        if (ne > 1 && lr1) memcpy(lr1, st + 32, 32);
+        memcpy(roots, st + 32 * (size_t) ne, (size_t) 32 * n_steps);
+        ctx->commit_ms = ms;
+        return VP_OK;
+    });
 }
 
 int vp_fri_final(vp_ctx *ctx, vp_F *final_code) {
@@ -1124,6 +1186,7 @@ int vp_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_
     if (!ctx || !values || !path || !path_len || oracle < 0) return VP_EINVAL;
     VP_ENTER(ctx);
     if (ctx->pcs) return pcs_fri_open(ctx, oracle, leaf, values, path, path_capacity, path_len);
+    VPCHK(pc_hash_outstanding(ctx, 3u));
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
     const F *cw; const Dig *tree; u32 Nc, n_leaves;

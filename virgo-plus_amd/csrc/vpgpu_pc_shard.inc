@@ -744,6 +744,7 @@ extern "C" {
 int vp_pc_load_input(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs, int bit_length) {
     if (!ctx || !inputs || bit_length < 7 || bit_length > 30 || n_inputs == 0 || n_inputs > (1ull << bit_length)) return VP_EINVAL;
     VP_ENTER(ctx);
+    VPCHK(pc_hash_outstanding(ctx, 3u));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->gkr_graph) { (void) hipGraphExecDestroy(ctx->gkr_graph); ctx->gkr_graph = nullptr; }
     free_plan(ctx);
@@ -779,6 +780,7 @@ int vp_pc_set_shard(vp_ctx *ctx, int rank, int world) {
     if (world > 1 && ln - lw < 1) { ctx->err = "vp_pc_set_shard: slice too short for this many ranks"; return VP_ELIMIT; }
     if (world > 1 && ln > PC_MAX_LN_LONG) { ctx->err = "vp_pc_set_shard: input layer of more than 2^25 wires"; return VP_ELIMIT; }
     VP_ENTER(ctx);
+    VPCHK(pc_hash_outstanding(ctx, 3u));        // (vp_pc_hash_late: a sharded commitment hashes at once, and what the unsharded one still owes is hashed first)
     HIPCHK(hipStreamSynchronize(ctx->stream));
     vp_free_shard_state(ctx);                   // its device arrays stay with the context until the next upload
     // world 1 is the unsharded commitment — unless a one-rank communicator is attached: then the sharded code path runs with a single

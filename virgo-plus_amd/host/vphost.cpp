@@ -538,6 +538,7 @@ int vph_draw_protocol_tape(vph_session *s) {
 // flags (vphost.h): VPH_PASS_DEFERRED — the calls are queued back to back without a host wait between them (vp_set_deferred) and collected at the end;
 // VPH_PASS_QUEUE_NEXT — before it waits, the pass queues the HEAD of the next one (commit_private of the same witness) behind its own folds, so
 // that the device goes from this proof's last kernel straight into the next proof's first (the next pass finds it and starts at the GKR part).
+// The pass hashes once (vphost.h): sec[1] and sec[3] are the transforms of the two commits, sec[5] holds the leaf chains and trees of l, h and the FRI levels.
 // sec[6] = whole pass (host wall clock) | commit_private | GKR | commit_public | fft_gkr (host time of its begin + end) | FRI commit phase + final;
 // synchronous: host wall clock of each call, deferred: device time of each call (vp_phase_ms).  The fft_gkr messages stay with the session
 // (vph_last_fft_gkr), the FRI data too (vph_last_fri).  0 = done, < 0 = error.
@@ -560,11 +561,16 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
         const auto t0 = clk::now();
         static const bool fft_sync = getenv("VPH_FFT_GKR_SYNC") != nullptr;
+        static const bool hash_per_call_env = getenv("VPH_HASH_PER_CALL") != nullptr;
+        const bool hash_once = !hash_per_call_env && !(flags & VPH_PASS_HASH_PER_CALL);
         u64 nt = 0, nb = 0;
         s->p->gkrSizes(nt, nb);
         if (s->tape.size() != nt) throw std::runtime_error("the tape has the wrong length");
         s->pp_gkr.resize(nb); s->pp_all.resize(65); s->pp_roots.resize((size_t) 32 * ln); s->pp_final.resize(2048);
         chk(vp_set_deferred(ctx, defer ? 1 : 0), "vp_set_deferred");
+        // the pass hashes once: commit_private and commit_public_eq stop behind their transforms, vp_fri_commit hashes l, h and its levels in one launch and
+        // writes pp_root_l / pp_root_h with its own roots (VPH_PASS_HASH_PER_CALL / VPH_HASH_PER_CALL: every call hashes its own oracle, as before)
+        chk(vp_pc_hash_late(ctx, hash_once ? 1 : 0), "vp_pc_hash_late");
         // ---- head: fft_gkr (depends on the verifier's draws only: queued on its own stream, its small launches run in the gaps of everything below;
         // VPH_FFT_GKR_SYNC=1: in the reference's place, between commit_public and the FRI folds) and commit_private (src/verifier.cpp:137) —
         // unless the previous pass queued them for this one and that commitment still stands
@@ -602,6 +608,7 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         chk(vp_fri_commit(ctx, reinterpret_cast<const vp_F *>(s->ptape_fri.data()), ln, s->pp_roots.data()), "vp_fri_commit");
         chk(vp_fri_final(ctx, reinterpret_cast<vp_F *>(s->pp_final.data())), "vp_fri_final");
         s_fri = since(t);
+        chk(vp_pc_hash_late(ctx, 0), "vp_pc_hash_late");      // the mode belongs to this pass's own calls: the next pass's head below is a complete commit_private
         int n_mine = 0;
         chk(vp_pending(ctx, &n_mine), "vp_pending");
         if (queue_next) {
@@ -638,6 +645,7 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         if (sec) { sec[0] = since(t0); sec[1] = s_priv; sec[2] = s_gkr; sec[3] = s_pub; sec[4] = s_fft; sec[5] = s_fri; }
         return 0;
     } catch (const std::exception &e) {
+        (void) vp_pc_hash_late(ctx, 0);                  // (first: the flush then also hashes what the failed pass left unhashed)
         (void) vp_flush(ctx, -1);                        // nothing of a failed pass stays queued
         (void) vp_set_deferred(ctx, 0);
         s->head_queued = false;

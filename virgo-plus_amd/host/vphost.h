@@ -162,8 +162,14 @@ int vph_prove_protocol(vph_session *, uint8_t *transcript, uint64_t capacity, ui
  *   runs the following milliseconds at a lower clock); sec[1..5]: device time per call;
  * | VPH_PASS_QUEUE_NEXT = before it waits, the pass queues the next pass's head (commit_private of the same witness) behind its own FRI folds, and
  *   the next vph_prove_protocol_ex of the session starts at its GKR part: no idle device between two proofs of a session that proves back to back.  The
- *   openings of THIS pass's commitment are gone once that head runs (it overwrites the codeword); a pass that will be opened is made without the flag. */
-enum { VPH_PASS_DEFERRED = 1, VPH_PASS_QUEUE_NEXT = 2 };
+ *   openings of THIS pass's commitment are gone once that head runs (it overwrites the codeword); a pass that will be opened is made without the flag.
+ * In every combination the pass hashes ONCE (vp_pc_hash_late, include/vpgpu.h): commit_private and commit_public queue their transforms only, and the FRI
+ * commit call hashes the leaves of l, h and all FRI levels in one launch and builds their trees together (a head queued by the previous pass is a complete
+ * commit_private: such a pass merges h and the levels).  Same transcript, same layout; sec[1] and sec[3] are then the transforms alone and sec[5] carries
+ * all of the hashing — their sum, the reference's "prove time", keeps its meaning.
+ * | VPH_PASS_HASH_PER_CALL = the earlier form, every call hashing its own oracle (three leaf-hash launches, three tree chains): the partner of A/B
+ *   comparisons in one process (tools/pass_modes.py); the environment variable VPH_HASH_PER_CALL, read once, selects it for every pass. */
+enum { VPH_PASS_DEFERRED = 1, VPH_PASS_QUEUE_NEXT = 2, VPH_PASS_HASH_PER_CALL = 4 };
 int vph_prove_protocol_ex(vph_session *, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
                           uint64_t *final_pairs, double sec[6], int flags, char *err, int errlen);
 /* No GPU needed: F::init(), draw the tape for `circuit`, replay the host verifier over `transcript`
