@@ -228,11 +228,30 @@ def test_stepwise_fri_matches_reference(vp, case, name, world):
     rk.close()
 
 
+def _check_openings_at_cut(rk, n, roots):
+    """every oracle (l, h, each FRI level; roots: the unsharded run's): leaf 0, one in the middle and the last verify on the owning rank (rank 0 for a
+    replicated level), and a rank that does not own the leaf answers VP_EINVAL"""
+    W, st = rk.world, n - 6
+    lw = W.bit_length() - 1
+    for oracle in range(2 + st):
+        n_leaves = 1 << (n - 2) if oracle < 2 else 1 << (n - 3 - (oracle - 2))
+        replicated = oracle >= 2 and oracle - 2 >= st - lw - 1
+        for leaf in sorted({0, n_leaves // 2 + min(33, n_leaves // 4), n_leaves - 1}):
+            owner = 0 if replicated else (leaf >> 5) % W
+            assert rk.L.vp_pc_shard_owner(rk.ctx[0], oracle, leaf) == (-1 if replicated else owner)
+            rc, vals, path = rk.open(oracle, leaf, owner)
+            assert rc == 0, (oracle, leaf, rk.err(owner))
+            assert _opening_ok(roots[oracle], leaf, vals, path), "n %d world %d oracle %d leaf %d: opening does not verify" % (n, W, oracle, leaf)
+            if not replicated:
+                assert rk.open(oracle, leaf, (owner + 1) % W)[0] == VP_EINVAL, "a rank that does not own the leaf answered"
+
+
 @pytest.mark.parametrize("n,world", [(8, 2), (9, 2), (9, 4), (10, 4)])
 def test_level_cut_edges_against_unsharded(vp, n, world):
     """The smallest shapes of the level cut — one local step and no locally hashed level (n = 8, W = 2), one locally hashed level with a single
     level-5 node per rank (n = 9, W = 2), and their W = 4 neighbours — with complex inputs and a public vector that is no tensor: the same calls on
-    an unsharded context give the expected bytes."""
+    an unsharded context give the expected bytes.  Every oracle of the sharded ranks then opens against the unsharded roots, after the step-wise phase
+    and again after the one-pass vp_fri_commit on the same ranks, whose roots are the step-wise ones."""
     rng = np.random.default_rng(1000 * n + world)
     inputs = rng.integers(0, P, size=((1 << n) - 3, 2), dtype=np.uint64)
     pub = rng.integers(0, P, size=(1 << n, 2), dtype=np.uint64)
@@ -244,11 +263,20 @@ def test_level_cut_edges_against_unsharded(vp, n, world):
         out += [rk.step(r[k])[0] for k in range(n - 6)]
         out.append(rk.final().tobytes())
         assert rk.step_rc(r[0]) == [VP_EINVAL] * w                    # step n - 6 + 1
-        rk.close()
         got.append(out)
+        if w == 1:
+            rk.close()
     names = ["root_l", "root_h | input_0 | all_sum"] + ["root of step %d" % k for k in range(n - 6)] + ["final codeword"]
     for what, a, b in zip(names, got[0], got[1]):
         assert a == b, what
+    roots = [got[0][0], got[0][1][:32]] + got[0][2:2 + n - 6]        # per oracle, of the unsharded run
+    _check_openings_at_cut(rk, n, roots)
+    assert rk.commit_public(pub) == got[0][1]
+    one_pass = rk.fri_commit(r)
+    assert [one_pass[32 * k:32 * k + 32] for k in range(n - 6)] == got[1][2:2 + n - 6], "one-pass roots differ from the step-wise ones"
+    assert rk.final().tobytes() == got[0][-1]
+    _check_openings_at_cut(rk, n, roots)
+    rk.close()
 
 
 def test_collective_count_and_repeat_rule(vp, case):

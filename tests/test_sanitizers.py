@@ -42,3 +42,18 @@ def test_host_library_under_asan_ubsan(vp, pws_path):
     r = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "host_asan ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+
+
+def test_fri_layout_under_asan_ubsan():
+    """csrc/vp_fri_layout.h (where a FRI level lives, as closed forms) against the drivers' incremental recurrences, for every slice length and rank
+    count: tests/sanitize/fri_layout_main.cpp, plain g++ with the sanitizers, nothing but the header under test."""
+    out_dir = os.path.join(ROOT, "tests", "sanitize", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "fri_layout_asan")
+    src = os.path.join(ROOT, "tests", "sanitize", "fri_layout_main.cpp")
+    deps = [src, os.path.join(ROOT, "virgo-plus_amd", "csrc", "vp_fri_layout.h")]
+    if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
+        subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror"] + SAN + ["-o", exe, src], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=ENV)
+    assert r.returncode == 0 and "fri_layout ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-3000:]

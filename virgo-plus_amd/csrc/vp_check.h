@@ -6,7 +6,7 @@
 //   sites:  1 operand gather of an init contribution (layer, index)      2 V gather of a phase-2 slot (layer, index)      3 row pointers of a target-sorted list
 //           4 Liu gather list (row pointers, half-table selector)        5 store of a folded table entry beyond the buffers' capacity
 //           6 LDS slot of a transform tile                               7 codeword position of a leaf
-//           8 table entry of a round-sharded gather (pack / unpack)               9 request of a batched opening (oracle, leaf, bound)
+//           8 table entry of a round-sharded gather (pack / unpack)               9 request of an opening (oracle, leaf, bound)
 #pragma once
 
 namespace vp {

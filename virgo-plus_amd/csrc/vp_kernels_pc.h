@@ -769,53 +769,20 @@ __global__ void __launch_bounds__(VP_BLOCK) k_ntt_split(SplitArgs a) {
 
 // ---- openings (fri::request_init_value_with_merkle, fri.cpp:148-205; fri::request_step_commit, :229-287) ----
 namespace vp {
-// One leaf of a committed oracle: the 64 slice pairs + the (zero) mask pair, and the Merkle path from the leaf up.
-// Coset-major codeword with Nc values per coset: leaf i = 32a + b holds (cw[s][b][a], cw[s][b][a + Nc/2]); for Nc == 1
-// (last FRI level) leaf j < 16 holds (cw[s][j], cw[s][j + 16]).
-__global__ void k_pc_open(const F *__restrict__ cw, u32 Nc, const Dig *__restrict__ tree, u32 n_leaves, u32 leaf,
-                          F *__restrict__ vals /* 65*2 */, Dig *__restrict__ path /* depth+1 */, const F *__restrict__ mask /* the mask slice at this level (coset-major), or nullptr: zeros */) {
-    const u32 t = threadIdx.x;
-    if (t < 64) {
-        F x, y;
-        if (Nc >= 2) { const u32 a = leaf >> 5, b = leaf & 31; const F *row = cw + ((size_t) t * 32 + b) * Nc; x = row[a]; y = row[a + (Nc >> 1)]; }
-        else { x = cw[(size_t) t * 32 + leaf]; y = cw[(size_t) t * 32 + leaf + 16]; }
-        vals[2 * t] = x; vals[2 * t + 1] = y;
-    } else if (t == 64) {
-        F x = f_zero(), y = f_zero();
-        if (mask) {
-            if (Nc >= 2) { const u32 a = leaf >> 5, b = leaf & 31; x = mask[(size_t) b * Nc + a]; y = mask[(size_t) b * Nc + a + (Nc >> 1)]; }
-            else { x = mask[leaf]; y = mask[leaf + 16]; }
-        }
-        vals[128] = x; vals[129] = y;
-    }
-    // path[k] = sibling at height k (k < depth), path[depth] = the leaf digest itself (the reference's com_hhash layout)
-    u32 depth = 0;
-    while ((1u << depth) < n_leaves) ++depth;
-    if (t <= depth) {
-        if (t == depth) path[t] = tree[n_leaves + leaf];
-        else path[t] = tree[((n_leaves + leaf) >> t) ^ 1];
-    }
-}
-
-// The whole query phase in one launch (vp_fri_open_many / vp_fri_query): workgroup r answers request r = (oracle, leaf) from a table of per-oracle
-// descriptors (oracle 0 = l, 1 = h, 2 + k = FRI level k) and writes one fixed-stride record: the 130 values, then the path in k_pc_open's layout.
-// top == nullptr: the whole codeword (Nc values per coset) and the whole tree are here (k_pc_open's cases: Nc >= 2, the last level's Nc == 1, a mask
-// slice or zeros).  top != nullptr: a position-sharded oracle (k_pc_open_sh's case): Nc is the LOCAL number of values per coset, tree the local tree
-// (five lowest siblings), top the replicated tree above it with n5 leaves, lw = log2(world).  The host has validated every request; the checked
-// build checks them again (site 9) and the positions they lead to (site 7).
+// One leaf of a committed oracle: the 64 slice pairs + the mask pair (zeros without a mask slice), and the Merkle path from the leaf up: path[k] = sibling
+// at height k (k < depth), path[depth] = the leaf digest itself (the reference's com_hhash layout).  PcOpenDesc says where the oracle is (the host resolves
+// an oracle number — 0 = l, 1 = h, 2 + k = FRI level k — to it: pc_open_desc).
+// top == nullptr: the whole codeword and the whole tree are here.  Coset-major codeword with Nc values per coset: leaf i = 32a + b holds (cw[s][b][a],
+// cw[s][b][a + Nc/2]); for Nc == 1 (last FRI level) leaf j < 16 holds (cw[s][j], cw[s][j + 16]); mask: the mask slice at this level, laid out likewise.
+// top != nullptr: a position-sharded oracle, answered by the rank that owns position a (a mod W): Nc is the LOCAL number of values per coset, tree the local
+// tree (local leaf order 32 (a / W) + b: the five lowest siblings), top the replicated tree above it with n5 leaves, lw = log2 W.
+// The host has validated every request; the checked build checks them again (site 9, in the kernels) and the positions they lead to (site 7).
 #define VP_OPEN_MAX_ORACLES 21            // l, h and the 19 levels of an input layer of 2^25 wires
 #define VP_OPEN_MAX_PATH 26
 struct PcOpenDesc { const F *cw; const F *mask; const Dig *tree; const Dig *top; u32 Nc, n_leaves, n5, lw; };
 struct PcOpenRec { F v[130]; Dig path[VP_OPEN_MAX_PATH]; };
-__global__ void __launch_bounds__(128)
-k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *__restrict__ req, u32 n_req, PcOpenRec *__restrict__ out) {
-    const u32 r = blockIdx.x, t = threadIdx.x;
-    if (r >= n_req) return;
-    const u32 o = req[r].x, leaf = req[r].y;
-    if (!VP_CHK(o < n_oracles, 9, o, leaf, n_oracles)) return;
-    const PcOpenDesc d = tab[o];
-    if (!VP_CHK(leaf < d.n_leaves, 9, o, leaf, d.n_leaves)) return;
-    PcOpenRec &rec = out[r];
+__device__ __forceinline__ void pc_open_leaf(const PcOpenDesc &d, u32 leaf, F *__restrict__ vals /* 65*2 */, Dig *__restrict__ path /* depth+1 */) {
+    const u32 t = threadIdx.x;                            // one workgroup of 128 threads
     u32 depth = 0;
     while ((1u << depth) < d.n_leaves) ++depth;
     if (d.top) {
@@ -823,11 +790,11 @@ k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *_
         if (!VP_CHK(al + (d.Nc >> 1) < d.Nc && a < d.n5, 7, a, b, d.Nc)) return;
         if (t < 64) {
             const F *row = d.cw + ((size_t) t * 32 + b) * d.Nc;
-            rec.v[2 * t] = row[al]; rec.v[2 * t + 1] = row[al + (d.Nc >> 1)];
-        } else if (t == 64) { rec.v[128] = f_zero(); rec.v[129] = f_zero(); }
-        if (t == depth) rec.path[t] = d.tree[nl + leaf_loc];
-        else if (t < 5) rec.path[t] = d.tree[((nl + leaf_loc) >> t) ^ 1];
-        else if (t < depth) rec.path[t] = d.top[((d.n5 + a) >> (t - 5)) ^ 1];
+            vals[2 * t] = row[al]; vals[2 * t + 1] = row[al + (d.Nc >> 1)];
+        } else if (t == 64) { vals[128] = f_zero(); vals[129] = f_zero(); }
+        if (t == depth) path[t] = d.tree[nl + leaf_loc];
+        else if (t < 5) path[t] = d.tree[((nl + leaf_loc) >> t) ^ 1];
+        else if (t < depth) path[t] = d.top[((d.n5 + a) >> (t - 5)) ^ 1];
         return;
     }
     const u32 Nc = d.Nc, a = leaf >> 5, b = leaf & 31;
@@ -836,17 +803,34 @@ k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *_
         F x, y;
         if (Nc >= 2) { const F *row = d.cw + ((size_t) t * 32 + b) * Nc; x = row[a]; y = row[a + (Nc >> 1)]; }
         else { x = d.cw[(size_t) t * 32 + leaf]; y = d.cw[(size_t) t * 32 + leaf + 16]; }
-        rec.v[2 * t] = x; rec.v[2 * t + 1] = y;
+        vals[2 * t] = x; vals[2 * t + 1] = y;
     } else if (t == 64) {
         F x = f_zero(), y = f_zero();
         if (d.mask) {
             if (Nc >= 2) { x = d.mask[(size_t) b * Nc + a]; y = d.mask[(size_t) b * Nc + a + (Nc >> 1)]; }
             else { x = d.mask[leaf]; y = d.mask[leaf + 16]; }
         }
-        rec.v[128] = x; rec.v[129] = y;
+        vals[128] = x; vals[129] = y;
     }
-    if (t == depth) rec.path[t] = d.tree[d.n_leaves + leaf];
-    else if (t < depth) rec.path[t] = d.tree[((d.n_leaves + leaf) >> t) ^ 1];
+    if (t == depth) path[t] = d.tree[d.n_leaves + leaf];
+    else if (t < depth) path[t] = d.tree[((d.n_leaves + leaf) >> t) ^ 1];
+}
+// vp_fri_open: one opening, the descriptor in the kernel's arguments (oracle: what d was resolved from, for the checked build's report only)
+__global__ void __launch_bounds__(128) k_pc_open(const PcOpenDesc d, u32 oracle, u32 leaf, F *__restrict__ vals, Dig *__restrict__ path) {
+    if (!VP_CHK(leaf < d.n_leaves, 9, oracle, leaf, d.n_leaves)) return;
+    pc_open_leaf(d, leaf, vals, path);
+}
+// The whole query phase in one launch (vp_fri_open_many / vp_fri_query): workgroup r answers request r = (oracle, leaf) from a table of per-oracle
+// descriptors and writes one fixed-stride record: the 130 values, then the path.
+__global__ void __launch_bounds__(128)
+k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *__restrict__ req, u32 n_req, PcOpenRec *__restrict__ out) {
+    const u32 r = blockIdx.x;
+    if (r >= n_req) return;
+    const u32 o = req[r].x, leaf = req[r].y;
+    if (!VP_CHK(o < n_oracles, 9, o, leaf, n_oracles)) return;
+    const PcOpenDesc d = tab[o];
+    if (!VP_CHK(leaf < d.n_leaves, 9, o, leaf, d.n_leaves)) return;
+    pc_open_leaf(d, leaf, out[r].v, out[r].path);
 }
 
 // ---- the mask slice WITH CONTENT (round 6; lib/virgo/src/poly_commit.h:42,55-86,138-161,187-191, fri.cpp:96-124,366-386,403-411) --------------------------------

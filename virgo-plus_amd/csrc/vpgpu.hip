@@ -19,6 +19,7 @@
 
 #include "../../include/vpgpu.h"
 #include "vp_kernels.h"
+#include "vp_fri_layout.h"
 
 using namespace vp;
 
@@ -227,14 +228,14 @@ struct vp_ctx {
     F *pc_q0 = nullptr, *pc_eq = nullptr, *pc_cbuf = nullptr; int pc_cbuf_lm = -1; int *pc_flag = nullptr; bool pc_q_tensor = false;   // tensor public vector: its one encoded slice (commit_public)
     F *pc_pub = nullptr, *pc_qcw = nullptr, *pc_hcw = nullptr, *pc_tmp = nullptr, *pc_small = nullptr; Dig *pc_tree_h = nullptr; bool pc_private_done = false;
     F *pc_scr = nullptr; size_t pc_scr_cap = 0;
-    F *pc_fri_all = nullptr; std::vector<size_t> fri_cw_off, fri_tree_off; F *pc_open_buf = nullptr;
+    F *pc_fri_all = nullptr, *pc_open_buf = nullptr;     // every FRI level's codeword, end to end (where: FriLayout, vp_fri_layout.h)
     // vp_fri_open_many / vp_fri_query: records on the device, descriptor table + request list on the device, pinned staging of both directions
     PcOpenRec *pc_many_buf = nullptr; unsigned char *pc_many_in = nullptr; u32 pc_many_cap = 0; unsigned char *h_many = nullptr; size_t h_many_cap = 0;
     Dig *pc_fri_roots = nullptr;
-    F *pc_fri[2] = {nullptr, nullptr}; Dig *pc_fri_tree = nullptr; int fri_step = -1; size_t fri_tree_used = 0; bool pc_public_done = false;
+    Dig *pc_fri_tree = nullptr; int fri_step = -1; bool pc_public_done = false;       // fri_step: FRI levels committed (openable); -1: no FRI phase begun
     // the mask slice with content (vp_commit_private_masked / vp_commit_public_masked; 0 = the protocol's zero mask, nothing below is touched): padded mask length,
-    // the slice's l / q / h codewords and its FRI levels end to end (M elements each, coset-major), scratch of its small transforms, per-level offsets
-    u32 pc_mask_ms = 0; F *pc_lm_cw = nullptr, *pc_qm_cw = nullptr, *pc_hm_cw = nullptr, *pc_fm = nullptr, *pc_mtmp = nullptr; std::vector<size_t> fri_m_off;
+    // the slice's l / q / h codewords and its FRI levels end to end (M elements each, coset-major), scratch of its small transforms
+    u32 pc_mask_ms = 0; F *pc_lm_cw = nullptr, *pc_qm_cw = nullptr, *pc_hm_cw = nullptr, *pc_fm = nullptr, *pc_mtmp = nullptr;
     size_t pc_mtmp_cap = 0, pc_mB = 0;                 // scratch capacity; B = max(ms, N): the scratch is laid out in blocks of B elements (pc_mask_scratch)
 
     // Deferred completion (vp_set_deferred / vp_flush; round 5).  A GPU that goes idle for a fraction of a millisecond — a host synchronisation between two
@@ -374,6 +375,15 @@ int dupload(vp_ctx *ctx, T **p, const std::vector<T> &h) {
 void free_all(vp_ctx *ctx) {
     for (void *p : ctx->allocs) (void) hipFree(p);
     ctx->allocs.clear();
+}
+// the commitment's device arrays went with free_all: forget them and whatever was committed (a new circuit, or a new input layer of vp_pc_load_input)
+void pc_forget(vp_ctx *ctx) {
+    ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
+    ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
+    ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
+    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0;
+    ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
+    ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
 }
 
 inline u32 nblk(u64 n) { return (u32) ((n + VP_BLOCK - 1) / VP_BLOCK); }
@@ -1245,12 +1255,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     ctx->chain_owner.clear(); ctx->chain_cost.clear();
     ctx->chunk_cap = 0;
     ctx->pred_r = ctx->pred_pool = ctx->pred_part = ctx->pred_out = nullptr; ctx->pred_jobs = nullptr; ctx->pred_dot = nullptr; ctx->pred_map = nullptr;
-    ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
-    ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
-    ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
-    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
-    ctx->pc_fri[0] = ctx->pc_fri[1] = nullptr; ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
-    ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->fri_m_off.clear(); ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
+    pc_forget(ctx);
     int max_bl = 0;
     for (int i = 0; i < n_layers; ++i) {
         if (ld[i].size == 0 || ld[i].size > (1ull << 30) || ld[i].bit_length < 0 || ld[i].bit_length > 30 ||

@@ -407,7 +407,6 @@ bool pcs_public_done(vp_ctx *ctx);
 int pcs_fri_done(vp_ctx *ctx);
 bool pcs_fri_one_pass(vp_ctx *ctx);
 int pcs_fri_final(vp_ctx *ctx, vp_F *final_code);
-int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len);
 int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d);
 bool pcs_owns(vp_ctx *ctx, uint64_t leaf);
 
@@ -433,7 +432,8 @@ static int pc_many_reserve(vp_ctx *ctx, u32 want) {        // buffers for `want`
     ctx->pc_many_cap = cap;
     return VP_OK;
 }
-// descriptor of one oracle, refused exactly where vp_fri_open refuses it
+// Which buffers an oracle number means (0 = l, 1 = h, 2 + k = FRI level k), or why it cannot be opened: the one place that decides it, for vp_fri_open and
+// for every request of vp_fri_open_many / vp_fri_query
 static int pc_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     *d = PcOpenDesc{};
     if (oracle < 0 || ctx->L.empty()) return VP_EINVAL;
@@ -446,11 +446,13 @@ static int pc_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     else if (oracle == 1) { if (!ctx->pc_public_done) return VP_EINVAL; d->cw = ctx->pc_hcw; d->tree = ctx->pc_tree_h; d->Nc = N; d->n_leaves = M >> 1; }
     else {
         const int lvl = oracle - 2;
-        if (lvl >= ctx->fri_step || lvl >= (int) ctx->fri_cw_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-        d->cw = ctx->pc_fri_all + ctx->fri_cw_off[lvl]; d->tree = ctx->pc_fri_tree + ctx->fri_tree_off[lvl];
-        d->Nc = N >> (lvl + 1); d->n_leaves = 16 * d->Nc;
+        if (lvl >= ctx->fri_step) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+        const FriLayout fl(ln, 0);
+        d->cw = ctx->pc_fri_all + fl.cw(lvl); d->tree = ctx->pc_fri_tree + fl.tree(lvl);
+        d->Nc = (u32) fl.per_coset(lvl); d->n_leaves = (u32) fl.leaves(lvl);
+        if (ctx->pc_mask_ms) d->mask = ctx->pc_fm + fl.mask(lvl);
     }
-    if (ctx->pc_mask_ms) d->mask = oracle == 0 ? ctx->pc_lm_cw : oracle == 1 ? ctx->pc_hm_cw : (oracle - 2 < (int) ctx->fri_m_off.size() ? ctx->pc_fm + ctx->fri_m_off[oracle - 2] : nullptr);
+    if (ctx->pc_mask_ms && oracle < 2) d->mask = oracle == 0 ? ctx->pc_lm_cw : ctx->pc_hm_cw;   // the mask slice's codeword of this oracle (zeros otherwise)
     return VP_OK;
 }
 static inline int pc_open_depth(u32 n_leaves) { int depth = 0; while ((1u << depth) < n_leaves) ++depth; return depth; }
@@ -578,6 +580,20 @@ static int pc_mask_lde(vp_ctx *ctx, const vp_F *mask, uint64_t n_mask, u32 ms, F
 static inline void pc_launch_leaf_hash_masked(vp_ctx *ctx, const F *cw, u32 N, const F *mask, Dig *leaves) {      // N = 1: the last FRI level
     const u32 n_leaves = N >= 2 ? 16 * N : 16u;
     hipLaunchKernelGGL(k_leaf_hash_cm, dim3(nblk(n_leaves)), dim3(VP_BLOCK), 0, ctx->stream, cw, N, 64, mask, leaves);
+}
+
+// One whole FRI level, unprofiled: its leaf chains (Nc == 1: the 16 leaves of the last level; mask: the mask slice's pair closes every chain) and the tree
+static int pc_hash_level(vp_ctx *ctx, const F *cw, u32 Nc, const F *mask, Dig *tree) {
+    const u32 n_leaves = 16 * Nc;
+    if (mask) pc_launch_leaf_hash_masked(ctx, cw, Nc, mask, tree + n_leaves);
+    else if (Nc >= 2) pc_launch_leaf_hash(ctx, cw, Nc, tree + n_leaves);
+    else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, cw, 64, tree + n_leaves);
+    return pc_merkle(ctx, tree, n_leaves);
+}
+// the last level's codeword ([slice][32], one value per coset) in the reference's order: out[(i << 7) | (slice << 1) | hi] = value at position i + 16 hi
+static void pc_final_order(const F *cw, vp_F *final_code) {
+    F *o = reinterpret_cast<F *>(final_code);
+    for (u32 i = 0; i < 16; ++i) for (u32 s = 0; s < 64; ++s) for (u32 hi = 0; hi < 2; ++hi) o[(i << 7) | (s << 1) | hi] = cw[s * 32 + i + 16 * hi];
 }
 
 // buffers of commit_public and of the FRI commit phase (every level's codeword is kept for the openings): allocated with the commitment,
@@ -937,44 +953,33 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) 64 * M)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw,
                            ctx->pc_hcw, ctx->pc_small + 1025 + 80, N, ctx->pc_rt, M >> 1, f_make(N, 0), 64u,
                            (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr));
-        ctx->fri_step = 0; ctx->fri_tree_used = 0;
-        ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear(); ctx->fri_m_off.clear();
+        ctx->fri_step = 0;
         if (ctx->pc_mask_ms)      // the mask slice's virtual oracle, in place over its q codeword (poly_commit.h:225-245)
             hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
                                (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw);
     }
     const int k = ctx->fri_step;
     if (k >= ln) { ctx->err = "FRI commit phase already finished"; return VP_EINVAL; }
+    const FriLayout fl(ln, 0);
     const u32 Nk = N >> k, No = Nk >> 1;
-    size_t cw_off = 0;
-    for (int q = 0; q < k; ++q) cw_off += (size_t) 64 * 32 * (N >> (q + 1));
-    const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + ctx->fri_cw_off[k - 1];
-    F *out = ctx->pc_fri_all + cw_off;
-    ctx->fri_cw_off.push_back(cw_off);
-    ctx->fri_tree_off.push_back(ctx->fri_tree_used);
+    const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + fl.cw(k - 1);
+    F *out = ctx->pc_fri_all + fl.cw(k);
     F rf; memcpy(&rf, r, sizeof(F));
     hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
                        host_inv_real(2), 0, 0u);
     // leaves of the folded codeword (M_{k+1} / 2 of them) + tree
-    const u32 n_leaves = 16 * No;
-    Dig *tree = ctx->pc_fri_tree + ctx->fri_tree_used;
+    Dig *tree = ctx->pc_fri_tree + fl.tree(k);
+    F *out_m = nullptr;
     if (ctx->pc_mask_ms) {
         // the mask slice folds like the others (fri.cpp:366-374) and its pair closes every leaf chain of the level (:403-411)
-        size_t m_off = 0;
-        for (int q = 0; q < k; ++q) m_off += (size_t) 32 * (N >> (q + 1));
-        const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + ctx->fri_m_off[k - 1];
-        F *out_m = ctx->pc_fm + m_off;
-        ctx->fri_m_off.push_back(m_off);
+        const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
+        out_m = ctx->pc_fm + fl.mask(k);
         hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, rf, host_inv_real(2));
-        pc_launch_leaf_hash_masked(ctx, out, No, out_m, tree + n_leaves);
-    } else
-    if (No >= 2) pc_launch_leaf_hash(ctx, out, No, tree + n_leaves);
-    else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, out, 64, tree + n_leaves);
-    VPCHK(pc_merkle(ctx, tree, n_leaves));
+    }
+    VPCHK(pc_hash_level(ctx, out, No, out_m, tree));
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     HIPCHK(hipMemcpyAsync(root, tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
     VPCHK(check_stream(ctx));
-    ctx->fri_tree_used += 2 * (size_t) n_leaves;
     ctx->fri_step = k + 1;
     float ms = 0;
     hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
@@ -1024,11 +1029,11 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     VPCHK(defer_begin(ctx, &ev_a));
     EvGuard ev_guard{ctx, &ev_a};
     // the virtual oracle (poly_commit.h:294-318) is consumed by the first fold only: fused into it (k_fri_fold0_vo / k_fri_fold0_vo3)
-    ctx->fri_step = 0; ctx->fri_tree_used = 0;
-    ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
+    ctx->fri_step = 0;
     // folds of every level, back to back
+    const FriLayout fl(ln, 0);
     FriLeafArgs la{}; MerkleArgs ma{};
-    u32 blocks = 0; size_t cw_off = 0;
+    u32 blocks = 0;
     // vp_pc_hash_late: the oracles whose commit stopped behind its transforms go IN FRONT of the levels in the same lists — an l or h codeword is an entry
     // with N values per coset and 16 N leaves like a level's.  VP_FRI_MAX covers n_steps + 2 (n <= 25: 21 entries) and the u32 leaf offsets 3 x 2^23 leaves.
     if (n_steps + 2 > VP_FRI_MAX) VPCHK(pc_hash_outstanding(ctx, 3u));
@@ -1049,10 +1054,8 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     const bool fold3 = n_steps >= 3 && ln >= 9;       // (E = N / 8 >= 64: a wave per offset)
     for (int k = 0; k < n_steps; ++k) {
         const u32 Nk = N >> k, No = Nk >> 1;
-        const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + ctx->fri_cw_off[k - 1];
-        F *out = ctx->pc_fri_all + cw_off;
-        ctx->fri_cw_off.push_back(cw_off);
-        ctx->fri_tree_off.push_back(ctx->fri_tree_used);
+        const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + fl.cw(k - 1);
+        F *out = ctx->pc_fri_all + fl.cw(k);
         F rf; memcpy(&rf, r + k, sizeof(F));
         if (fold3 && k < 3) {
             if (k == 0) {
@@ -1060,7 +1063,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 VPCHK(pc_circle_roots(ctx, lm, ln, &rtn));
                 VPCHK(pc_fold0_consts(ctx, lm));
                 F r1, r2; memcpy(&r1, r + 1, sizeof(F)); memcpy(&r2, r + 2, sizeof(F));
-                F *o1 = out, *o2 = o1 + (size_t) 64 * 32 * No, *o3 = o2 + (size_t) 64 * 32 * (No >> 1);       // the levels lie end to end (cw_off below)
+                F *o1 = out, *o2 = o1 + (size_t) 64 * 32 * No, *o3 = o2 + (size_t) 64 * 32 * (No >> 1);       // the levels lie end to end (FriLayout::cw)
                 const u32 E = N >> 3;
                 // VP_VO_GRP slice groups per workgroup where that still leaves >= 2048 workgroups (N >= 2^14), one group per workgroup below
                 const bool grouped = (64 / VP_VO_SPT / VP_VO_GRP) * 32 * (E >> 6) >= 2048;
@@ -1096,14 +1099,12 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
                                    host_inv_real(2), 0, 0u));
         const u32 n_leaves = 16 * No;
-        Dig *tree = ctx->pc_fri_tree + ctx->fri_tree_used;
+        Dig *tree = ctx->pc_fri_tree + fl.tree(k);
         ma.tree[ne + k] = tree; ma.count[ne + k] = n_leaves;
         {   // every level, the single-value last one included, goes into the one leaf-hash launch (the chain of 65 Keccak-f is
             // a fixed ~1 ms latency however few leaves there are)
             la.cw[la.n] = out; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
         }
-        cw_off += (size_t) 64 * 32 * No;
-        ctx->fri_tree_used += 2 * (size_t) n_leaves;
     }
     u64 all_leaves = 0;
     for (int k = 0; k < nt; ++k) all_leaves += ma.count[k];
@@ -1156,12 +1157,8 @@ int vp_fri_final(vp_ctx *ctx, vp_F *final_code) {
     EvGuard ev_guard{ctx, &ev_a};
     F *cw = nullptr;
     VPCHK(ring_alloc(ctx, 64 * 32 * sizeof(F), (void **) &cw));
-    HIPCHK(hipMemcpyAsync(cw, ctx->pc_fri_all + ctx->fri_cw_off[ln - 1], 64 * 32 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-    return defer_end(ctx, ev_a, VP_PH_FRI_FINAL, [cw, final_code](float) {         // (commit_ms stays the commit phase's)
-        F *o = reinterpret_cast<F *>(final_code);
-        for (u32 i = 0; i < 16; ++i) for (u32 s = 0; s < 64; ++s) for (u32 hi = 0; hi < 2; ++hi) o[(i << 7) | (s << 1) | hi] = cw[s * 32 + i + 16 * hi];
-        return VP_OK;
-    });
+    HIPCHK(hipMemcpyAsync(cw, ctx->pc_fri_all + FriLayout(ln, 0).cw(ln - 1), 64 * 32 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
+    return defer_end(ctx, ev_a, VP_PH_FRI_FINAL, [cw, final_code](float) { pc_final_order(cw, final_code); return VP_OK; });      // (commit_ms stays the commit phase's)
 }
 
 // The mask slice's last codeword (fri::cpd.rs_codeword_msk[last], read by vpd_verifier.cpp:321-325): 32 values in the reference's interleaved order
@@ -1176,7 +1173,7 @@ int vp_fri_final_mask(vp_ctx *ctx, vp_F out[32]) {
     memset(out, 0, 32 * sizeof(vp_F));
     if (!ctx->pc_mask_ms) return VP_OK;
     F v[32];
-    HIPCHK(hipMemcpyAsync(v, ctx->pc_fm + ctx->fri_m_off[ln - 1], sizeof v, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(v, ctx->pc_fm + FriLayout(ln, 0).mask(ln - 1), sizeof v, hipMemcpyDeviceToHost, ctx->stream));
     VPCHK(check_stream(ctx));
     for (u32 i = 0; i < 16; ++i) for (u32 hi = 0; hi < 2; ++hi) { out[2 * i + hi].real = v[i + 16 * hi].re; out[2 * i + hi].img = v[i + 16 * hi].im; }
     return VP_OK;
@@ -1185,27 +1182,15 @@ int vp_fri_final_mask(vp_ctx *ctx, vp_F out[32]) {
 int vp_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len) {
     if (!ctx || !values || !path || !path_len || oracle < 0) return VP_EINVAL;
     VP_ENTER(ctx);
-    if (ctx->pcs) return pcs_fri_open(ctx, oracle, leaf, values, path, path_capacity, path_len);
-    VPCHK(pc_hash_outstanding(ctx, 3u));
-    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
-    const u32 N = 1u << ln, M = 1u << lm;
-    const F *cw; const Dig *tree; u32 Nc, n_leaves;
-    if (oracle == 0) { if (!ctx->pc_private_done) return VP_EINVAL; cw = ctx->pc_cw; tree = ctx->pc_tree; Nc = N; n_leaves = M >> 1; }
-    else if (oracle == 1) { if (!ctx->pc_public_done) return VP_EINVAL; cw = ctx->pc_hcw; tree = ctx->pc_tree_h; Nc = N; n_leaves = M >> 1; }
-    else {
-        const int lvl = oracle - 2;
-        if (lvl >= ctx->fri_step || lvl >= (int) ctx->fri_cw_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-        cw = ctx->pc_fri_all + ctx->fri_cw_off[lvl]; tree = ctx->pc_fri_tree + ctx->fri_tree_off[lvl];
-        Nc = N >> (lvl + 1); n_leaves = 16 * Nc;
-    }
-    if (leaf >= n_leaves) return VP_EINVAL;
-    int depth = 0; while ((1u << depth) < n_leaves) ++depth;
+    PcOpenDesc d;
+    VPCHK(pc_open_desc(ctx, oracle, &d));
+    if (leaf >= d.n_leaves) return VP_EINVAL;
+    if (d.top && !pcs_owns(ctx, leaf)) { ctx->err = "this rank does not own the leaf (owner = (leaf >> 5) mod world)"; return VP_EINVAL; }
+    const int depth = pc_open_depth(d.n_leaves);
     if (path_capacity < 32 * (depth + 1)) return VP_EINVAL;
     if (!ctx->pc_open_buf) VPCHK(dalloc(ctx, &ctx->pc_open_buf, (size_t) 130 + 2 * 40));
     Dig *dpath = reinterpret_cast<Dig *>(ctx->pc_open_buf + 130);
-    const F *mask_cw = nullptr;                           // the mask slice's codeword of this oracle (zeros otherwise)
-    if (ctx->pc_mask_ms) mask_cw = oracle == 0 ? ctx->pc_lm_cw : oracle == 1 ? ctx->pc_hm_cw : (oracle - 2 < (int) ctx->fri_m_off.size() ? ctx->pc_fm + ctx->fri_m_off[oracle - 2] : nullptr);
-    hipLaunchKernelGGL(k_pc_open, dim3(1), dim3(128), 0, ctx->stream, cw, Nc, tree, n_leaves, (u32) leaf, ctx->pc_open_buf, dpath, mask_cw);
+    hipLaunchKernelGGL(k_pc_open, dim3(1), dim3(128), 0, ctx->stream, d, (u32) oracle, (u32) leaf, ctx->pc_open_buf, dpath);
     HIPCHK(hipMemcpyAsync(values, ctx->pc_open_buf, 130 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(path, dpath, 32 * (size_t) (depth + 1), hipMemcpyDeviceToHost, ctx->stream));
     VPCHK(check_stream(ctx));

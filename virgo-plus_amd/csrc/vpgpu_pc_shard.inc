@@ -34,15 +34,15 @@ struct PcShard {
     // own slices, unsharded layout [S][32][N]
     F *coef = nullptr, *lcw = nullptr, *qcw = nullptr, *hcw = nullptr, *tmp = nullptr, *small = nullptr, *pub = nullptr;
     // every slice, own positions: [64][32][N/W]
-    F *l_loc = nullptr, *h_loc = nullptr, *fri_loc = nullptr; std::vector<size_t> fri_off;     // fri_loc: level 0 input, then every locally folded level
+    F *l_loc = nullptr, *h_loc = nullptr, *fri_loc = nullptr;                                   // fri_loc: level 0 input, then every locally folded level
     Dig *tree_l = nullptr, *tree_h = nullptr, *tree_f = nullptr;                                // local leaves + five levels (heap layout of the local leaf order)
-    Dig *top_l = nullptr, *top_h = nullptr, *top_f = nullptr; std::vector<size_t> top_f_off;    // global trees from level 5 up (every rank holds them)
-    F *tail = nullptr; Dig *tail_tree = nullptr; std::vector<size_t> tail_cw_off, tail_tree_off;  // the last log2 W + 1 FRI levels, whole
-    std::vector<size_t> tree_f_off;
+    Dig *top_l = nullptr, *top_h = nullptr, *top_f = nullptr;                                   // global trees from level 5 up (every rank holds them)
+    F *tail = nullptr; Dig *tail_tree = nullptr;                                                // the last log2 W + 1 FRI levels, whole
+    FriLayout fl;                                                                               // where a FRI level sits in fri_loc, tree_f, top_f, tail, tail_tree (vp_pc_set_shard)
     F *send = nullptr; size_t send_cap = 0;
     unsigned char *ag_send = nullptr, *ag_recv = nullptr; size_t ag_cap = 0;
     Dig *d_roots = nullptr;
-    int n_local = 0, n_steps = 0;
+    int n_steps = 0;
     int f_done = 0, f_mode = 0;                             // FRI levels committed (openable); how: 0 none yet, 1 one pass (vp_fri_commit), 2 step by step (vp_fri_step)
     F step_r;                                               // the vp_fri_step in flight: its challenge
     float acc_ms = 0;                                       // the call in flight: device time of its parts before the collectives it stopped at
@@ -397,53 +397,68 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *
     }
 }
 
+// Stage 0 of the sharded FRI phase: the virtual oracle of the own slices (in place over q), packed for the all-to-all that turns it into position ownership
+void pcs_fri_stage0(vp_ctx *ctx) {
+    PcShard &s = *ctx->pcs;
+    const u32 N = (u32) s.fl.N, M = 32 * N, Nl = (u32) s.fl.Nl, S = (u32) s.S;
+    hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, s.hcw, s.small + 1025 + 80, N,
+                       ctx->pc_rt, M >> 1, f_make(N, 0), S, (const F *) (s.q_tensor ? s.q0cw : nullptr),
+                       (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
+    hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.qcw, s.send, N, s.lw, S * 32);
+    s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
+    s.stage = 1;
+}
+// local fold k < n_local: the rank's positions of level k - 1 (k = 0: of the virtual oracle) to its positions of level k; returns them
+F *pcs_local_fold(vp_ctx *ctx, int k, F r) {
+    PcShard &s = *ctx->pcs;
+    const u32 M = 32 * (u32) s.fl.N, Nk = (u32) s.fl.Nl >> k, No = Nk >> 1;
+    F *out = s.fri_loc + s.fl.loc_cw(k);
+    PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
+            hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (s.fri_loc + s.fl.loc_in(k)), out, Nk, k,
+                               ctx->pc_rt, M >> 1, r, host_inv_real(2), s.lw, (u32) s.rank));
+    return out;
+}
+// One replicated tail step: level k - 1 (whole on every rank) folds to level k > n_local - 1, which is hashed; returns the level's tree (the root is node 1)
+int pcs_tail_step(vp_ctx *ctx, int k, F r, Dig **tree_out) {
+    PcShard &s = *ctx->pcs;
+    const int q = s.fl.tail_q(k);
+    const u32 M = 32 * (u32) s.fl.N, Nt = (u32) s.fl.tail_per_coset(q - 1), Nn = Nt >> 1;
+    F *out = s.tail + s.fl.tail_cw(q);
+    Dig *tree = s.tail_tree + s.fl.tail_tree(q);
+    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * Nn)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (s.tail + s.fl.tail_cw(q - 1)), out, Nt, k, ctx->pc_rt, M >> 1,
+                       r, host_inv_real(2), 0, 0u);
+    VPCHK(pc_hash_level(ctx, out, Nn, nullptr, tree));
+    *tree_out = tree;
+    return VP_OK;
+}
+
 int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     PcShard &s = *ctx->pcs;
-    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
-    const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
+    const FriLayout &fl = s.fl;
+    const int ln = fl.ln, n_local = fl.n_local();                        // n_local: folds whose partners are on this rank: N_k -> N_k/2 while N_k >= 2W
     if (!s.public_done || n_steps != ln) { ctx->err = "sharded vp_fri_commit: all n-6 steps in one call, after vp_commit_public"; return VP_EINVAL; }
     if (s.f_mode == 2) { ctx->err = "vp_fri_commit after vp_fri_step"; return VP_EINVAL; }
     VPCHK(pcs_guard(ctx));
     if (s.op != 3) { s.op = 3; s.stage = 0; }
     VPCHK(pcs_resume(ctx));
-    const int n_local = ln - s.lw;                                        // folds whose partners are on this rank: N_k -> N_k/2 while N_k >= 2W
     for (;;) {
         if (s.stage == 0) {
             s.fri_r.assign(reinterpret_cast<const F *>(r), reinterpret_cast<const F *>(r) + n_steps);
             s.f_done = 0;
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-            // virtual oracle of the own slices (in place over q), then to position ownership
-            hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, s.hcw, s.small + 1025 + 80, N,
-                               ctx->pc_rt, M >> 1, f_make(N, 0), S, (const F *) (s.q_tensor ? s.q0cw : nullptr),
-                               (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
-            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.qcw, s.send, N, s.lw, S * 32);
-            s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
-            s.stage = 1;
+            pcs_fri_stage0(ctx);
             const int rc = pcs_collectives(ctx);
             if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else if (s.stage == 1) {
             // local folds; level k's output has Nl >> (k+1) positions per coset here
-            s.fri_off.assign(1, 0); s.tree_f_off.clear();
-            size_t off = (size_t) 64 * 32 * Nl, toff = 0, at = 0;
             FriLeafArgs la{};
             u32 blocks = 0;
-            std::vector<size_t> ag_at;
             for (int k = 0; k < n_local; ++k) {
-                const u32 Nk = Nl >> k, No = Nk >> 1;
-                const F *in = s.fri_loc + s.fri_off[k];
-                F *out = s.fri_loc + off;
-                s.fri_off.push_back(off);
-                PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
-                        hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, s.fri_r[k],
-                                           host_inv_real(2), s.lw, (u32) s.rank));
-                off += (size_t) 64 * 32 * No;
-                if (No >= 2) {                                             // leaves pair (a', a' + No/2): local
-                    const u32 n_leaves = 16 * No;
-                    Dig *tree = s.tree_f + toff;
-                    s.tree_f_off.push_back(toff);
-                    la.cw[la.n] = out; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
-                    toff += 2 * (size_t) n_leaves;
+                F *out = pcs_local_fold(ctx, k, s.fri_r[k]);
+                if (!fl.is_tail(k)) {                                      // leaves pair (a', a' + No/2): local
+                    const u32 No = (u32) fl.loc_per_coset(k), n_leaves = 16 * No;
+                    la.cw[la.n] = out; la.leaves[la.n] = s.tree_f + fl.loc_tree(k) + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
                 }
             }
             if (la.n) {
@@ -452,68 +467,48 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65,
                         pc_launch_leaf_hash_multi(ctx, la));
             }
+            size_t at = 0;
             for (int q = 0; q < la.n; ++q) {
                 const u32 No = la.N[q];
-                Dig *tree = s.tree_f + s.tree_f_off[q];
+                Dig *tree = s.tree_f + fl.loc_tree(q);
                 VPCHK(pcs_local_levels(ctx, tree, 16 * No));
                 HIPCHK(hipMemcpyAsync(s.ag_send + at, tree + (No >> 1), (size_t) (No >> 1) * 32, hipMemcpyDeviceToDevice, ctx->stream));
                 at += (size_t) (No >> 1) * 32;
             }
             // the one position per coset this rank is left with (output of the last local fold)
-            HIPCHK(hipMemcpyAsync(s.ag_send + at, s.fri_loc + s.fri_off[n_local], (size_t) 2048 * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(s.ag_send + at, s.fri_loc + fl.loc_cw(n_local - 1), (size_t) 2048 * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
             at += (size_t) 2048 * sizeof(F);
             s.x[0] = {2, s.ag_send, s.ag_recv, at}; s.nx = 1;
-            s.n_local = n_local; s.n_steps = n_steps;
+            s.n_steps = n_steps;
             s.stage = 2;
             const int rc = pcs_collectives(ctx);
             if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
         } else {
             // top trees of the locally hashed levels
             size_t at = 0, stride = 0;
-            for (int k = 0; k < n_local; ++k) { const u32 No = Nl >> (k + 1); if (No >= 2) stride += (size_t) (No >> 1) * 32; }
+            for (int k = 0; !fl.is_tail(k); ++k) stride += (size_t) (fl.loc_per_coset(k) >> 1) * 32;
             const size_t tail_at = stride;
             stride += (size_t) 2048 * sizeof(F);
-            s.top_f_off.clear();
-            size_t toff = 0;
-            int lvl = 0;
-            for (int k = 0; k < n_local; ++k) {
-                const u32 No = Nl >> (k + 1);
-                if (No < 2) break;
-                Dig *top = s.top_f + toff;
-                s.top_f_off.push_back(toff);
+            for (int k = 0; !fl.is_tail(k); ++k) {
+                const u32 No = (u32) fl.loc_per_coset(k);
+                Dig *top = s.top_f + fl.top(k);
                 VPCHK(pcs_top(ctx, s.ag_recv, stride, at, No, top));
                 HIPCHK(hipMemcpyAsync(s.d_roots + k, top + 1, 32, hipMemcpyDeviceToDevice, ctx->stream));        // heap layout: the root is node 1
                 at += (size_t) (No >> 1) * 32;
-                toff += (size_t) 2 * ((No >> 1) << s.lw);
-                ++lvl;
             }
             // the tail: level n_local-1's output (W positions per coset) and the last lw folds, whole codewords on every rank
-            F *tmpf = s.send;
+            // (gathered rank by rank behind the tail's own levels: the tail buffer has 2048 (2 W + 1) elements to spare there, while the send buffer,
+            // 2048 N / W elements, is shorter than the W x 2048 gathered ones once N < W^2)
+            F *tmpf = s.tail + fl.tail_gather();
             for (int q = 0; q < s.world; ++q)
                 HIPCHK(hipMemcpyAsync(tmpf + (size_t) q * 2048, s.ag_recv + (size_t) q * stride + tail_at, (size_t) 2048 * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
-            s.tail_cw_off.assign(1, 0); s.tail_tree_off.clear();
             hipLaunchKernelGGL(k_pc_interleave_tail, dim3(nblk(2048u << s.lw)), dim3(VP_BLOCK), 0, ctx->stream, tmpf, s.tail, s.lw);
-            size_t coff = (size_t) 2048 << s.lw, ttoff = 0;
-            u32 Nt = 1u << s.lw;                                           // positions per coset of the tail's first level
-            for (int k = n_local - 1; k < n_steps; ++k) {
-                // level k's codeword is s.tail + tail_cw_off.back() with Nt positions per coset: hash it, then fold to level k + 1
-                const u32 n_leaves = Nt >= 2 ? 16 * Nt : 16;
-                Dig *tree = s.tail_tree + ttoff;
-                s.tail_tree_off.push_back(ttoff);
-                const F *cw = s.tail + s.tail_cw_off.back();
-                if (Nt >= 2) pc_launch_leaf_hash(ctx, cw, Nt, tree + n_leaves);
-                else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, cw, 64, tree + n_leaves);
-                VPCHK(pc_merkle(ctx, tree, n_leaves));
+            Dig *tree = s.tail_tree;
+            VPCHK(pc_hash_level(ctx, s.tail, (u32) fl.W, nullptr, tree));
+            for (int k = n_local - 1;; ++k) {
                 HIPCHK(hipMemcpyAsync(s.d_roots + k, tree + 1, 32, hipMemcpyDeviceToDevice, ctx->stream));
-                ttoff += 2 * (size_t) n_leaves;
-                if (k + 1 < n_steps) {
-                    F *out = s.tail + coff;
-                    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * (Nt >> 1))), dim3(VP_BLOCK), 0, ctx->stream, cw, out, Nt, k + 1, ctx->pc_rt, M >> 1,
-                                       s.fri_r[k + 1], host_inv_real(2), 0, 0u);
-                    s.tail_cw_off.push_back(coff);
-                    coff += (size_t) 64 * 32 * (Nt >> 1);
-                    Nt >>= 1;
-                }
+                if (k + 1 == n_steps) break;
+                VPCHK(pcs_tail_step(ctx, k + 1, s.fri_r[k + 1], &tree));
             }
             HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
             HIPCHK(hipMemcpyAsync(roots, s.d_roots, (size_t) 32 * n_steps, hipMemcpyDeviceToHost, ctx->stream));
@@ -536,22 +531,19 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
 // stops at each collective with VP_EXCHANGE and is repeated with the same r after the exchange; a repeat before the exchange changes nothing.
 int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
     PcShard &s = *ctx->pcs;
-    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
-    const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
+    const FriLayout &fl = s.fl;
+    const int ln = fl.ln, n_local = fl.n_local();
     if (!s.public_done) { ctx->err = "vp_fri_step: vp_commit_public first"; return VP_EINVAL; }
     if (s.op != 0 && s.op != 4) { ctx->err = "vp_fri_step: another call of the sharded commitment is unfinished"; return VP_EINVAL; }
     if (s.f_mode == 1) { ctx->err = "vp_fri_step after vp_fri_commit"; return VP_EINVAL; }
     VPCHK(pcs_guard(ctx));
     if (s.op == 4 && s.nx) return VP_EXCHANGE;                            // the collective this step waits for has not been performed
-    const int n_local = ln - s.lw, k = s.f_done;
+    const int k = s.f_done;
     if (s.op != 4) {
         if (k >= ln) { ctx->err = "FRI commit phase already finished"; return VP_EINVAL; }
         memcpy(&s.step_r, r, sizeof(F));
         s.acc_ms = 0; ctx->ev_used = 0;
-        if (k == 0) {
-            s.f_mode = 2; s.n_steps = ln; s.n_local = n_local;
-            s.fri_off.assign(1, 0); s.tree_f_off.clear(); s.top_f_off.clear(); s.tail_cw_off.clear(); s.tail_tree_off.clear();
-        }
+        if (k == 0) { s.f_mode = 2; s.n_steps = ln; }
         s.op = 4; s.stage = k == 0 ? 0 : k < n_local ? 1 : 3;
     }
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
@@ -563,32 +555,17 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); s.acc_ms += ms;
         return VP_OK;
     };
-    const u32 Nk = k < n_local ? Nl >> k : 0, No = Nk >> 1;               // local step: positions per coset on this rank before / after the fold
-    Dig *d_root = nullptr;
+    const u32 No = k < n_local ? (u32) fl.loc_per_coset(k) : 0;           // local step: positions per coset on this rank after the fold
+    Dig *tree = nullptr;                                                   // the level's tree (heap layout: the root is node 1)
     for (;;) {
         if (s.stage == 0) {
-            // virtual oracle of the own slices (in place over q), then to position ownership
-            hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, s.hcw, s.small + 1025 + 80, N,
-                               ctx->pc_rt, M >> 1, f_make(N, 0), S, (const F *) (s.q_tensor ? s.q0cw : nullptr),
-                               (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
-            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.qcw, s.send, N, s.lw, S * 32);
-            s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
-            s.stage = 1;
+            pcs_fri_stage0(ctx);
             const int rc = pcs_collectives(ctx);
             if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
         } else if (s.stage == 1) {
-            const F *in = s.fri_loc + s.fri_off[k];
-            const size_t off = s.fri_off[k] + (size_t) 64 * 32 * Nk;
-            F *out = s.fri_loc + off;
-            PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
-                    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, s.step_r,
-                                       host_inv_real(2), s.lw, (u32) s.rank));
-            if ((int) s.fri_off.size() == k + 1) s.fri_off.push_back(off);
-            if (No >= 2) {                                                // leaves pair (a', a' + No/2): local; the level-5 nodes go to every rank
-                size_t toff = 0;
-                for (int q = 0; q < k; ++q) toff += (size_t) 32 * (Nl >> (q + 1));
-                if ((int) s.tree_f_off.size() == k) s.tree_f_off.push_back(toff);
-                VPCHK(pcs_hash_local(ctx, out, No, s.tree_f + toff, 0));
+            F *out = pcs_local_fold(ctx, k, s.step_r);
+            if (!fl.is_tail(k)) {                                         // leaves pair (a', a' + No/2): local; the level-5 nodes go to every rank
+                VPCHK(pcs_hash_local(ctx, out, No, s.tree_f + fl.loc_tree(k), 0));
                 s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) (No >> 1) * 32}; s.nx = 1;
             } else {                                                       // the one position per coset this rank is left with
                 HIPCHK(hipMemcpyAsync(s.ag_send, out, (size_t) 2048 * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
@@ -598,44 +575,23 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
             const int rc = pcs_collectives(ctx);
             if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
         } else if (s.stage == 2) {
-            if (No >= 2) {
-                size_t toff = 0;
-                for (int q = 0; q < k; ++q) toff += (size_t) 2 * (((Nl >> (q + 1)) >> 1) << s.lw);
-                if ((int) s.top_f_off.size() == k) s.top_f_off.push_back(toff);
-                VPCHK(pcs_top(ctx, s.ag_recv, (size_t) (No >> 1) * 32, 0, No, s.top_f + toff));
-                d_root = s.top_f + toff + 1;                               // heap layout: the root is node 1
+            if (!fl.is_tail(k)) {
+                tree = s.top_f + fl.top(k);
+                VPCHK(pcs_top(ctx, s.ag_recv, (size_t) (No >> 1) * 32, 0, No, tree));
             } else {
                 // level k = n_local - 1 whole on every rank (W positions per coset): the first level of the replicated tail
                 hipLaunchKernelGGL(k_pc_interleave_tail, dim3(nblk(2048u << s.lw)), dim3(VP_BLOCK), 0, ctx->stream, reinterpret_cast<const F *>(s.ag_recv), s.tail, s.lw);
-                s.tail_cw_off.assign(1, 0); s.tail_tree_off.assign(1, 0);
-                const u32 Nt = 1u << s.lw, n_leaves = Nt >= 2 ? 16 * Nt : 16;
-                if (Nt >= 2) pc_launch_leaf_hash(ctx, s.tail, Nt, s.tail_tree + n_leaves);
-                else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, s.tail, 64, s.tail_tree + n_leaves);
-                VPCHK(pc_merkle(ctx, s.tail_tree, n_leaves));
-                d_root = s.tail_tree + 1;
+                tree = s.tail_tree;
+                VPCHK(pc_hash_level(ctx, s.tail, (u32) fl.W, nullptr, tree));
             }
             break;
         } else {
-            // replicated step: level k - 1 (Nt positions per coset, whole on every rank) folds to level k, which is hashed here
-            const int q = k - (n_local - 1);                              // index of level k among the tail levels, >= 1
-            if ((int) s.tail_cw_off.size() != q || (int) s.tail_tree_off.size() != q) { ctx->err = "internal: sharded FRI tail out of step"; return VP_EINVAL; }
-            const u32 Nt = (1u << s.lw) >> (q - 1), Nn = Nt >> 1, leaves_in = 16 * Nt, n_leaves = Nn >= 2 ? 16 * Nn : 16;
-            const F *cw = s.tail + s.tail_cw_off[q - 1];
-            const size_t coff = s.tail_cw_off[q - 1] + (size_t) 64 * 32 * Nt, ttoff = s.tail_tree_off[q - 1] + (size_t) 2 * leaves_in;
-            F *out = s.tail + coff;
-            Dig *tree = s.tail_tree + ttoff;
-            hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * Nn)), dim3(VP_BLOCK), 0, ctx->stream, cw, out, Nt, k, ctx->pc_rt, M >> 1,
-                               s.step_r, host_inv_real(2), 0, 0u);
-            if (Nn >= 2) pc_launch_leaf_hash(ctx, out, Nn, tree + n_leaves);
-            else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, out, 64, tree + n_leaves);
-            VPCHK(pc_merkle(ctx, tree, n_leaves));
-            s.tail_cw_off.push_back(coff); s.tail_tree_off.push_back(ttoff);
-            d_root = tree + 1;
+            VPCHK(pcs_tail_step(ctx, k, s.step_r, &tree));
             break;
         }
     }
-    HIPCHK(hipMemcpyAsync(s.d_roots + k, d_root, 32, hipMemcpyDeviceToDevice, ctx->stream));
-    VPCHK(part_end(d_root));
+    HIPCHK(hipMemcpyAsync(s.d_roots + k, tree + 1, 32, hipMemcpyDeviceToDevice, ctx->stream));
+    VPCHK(part_end(tree + 1));
     if (ctx->profiling) prof_collect(ctx);
     ctx->commit_ms = s.acc_ms;
     s.op = 0; s.stage = 0; s.f_done = k + 1;
@@ -644,90 +600,29 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
 
 int pcs_fri_final(vp_ctx *ctx, vp_F *final_code) {
     PcShard &s = *ctx->pcs;
-    if (s.tail_cw_off.empty() || s.n_steps == 0 || s.f_done != s.n_steps) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
+    if (s.n_steps == 0 || s.f_done != s.n_steps) { ctx->err = "FRI commit phase not finished"; return VP_EINVAL; }
     std::vector<F> cw(64 * 32);
-    HIPCHK(hipMemcpy(cw.data(), s.tail + s.tail_cw_off.back(), cw.size() * sizeof(F), hipMemcpyDeviceToHost));
-    F *o = reinterpret_cast<F *>(final_code);
-    for (u32 i = 0; i < 16; ++i) for (u32 sl = 0; sl < 64; ++sl) for (u32 hi = 0; hi < 2; ++hi) o[(i << 7) | (sl << 1) | hi] = cw[sl * 32 + i + 16 * hi];
+    HIPCHK(hipMemcpy(cw.data(), s.tail + s.fl.tail_cw(s.lw), cw.size() * sizeof(F), hipMemcpyDeviceToHost));
+    pc_final_order(cw.data(), final_code);
     return VP_OK;
 }
 
-// One leaf of a position-sharded oracle, answered by the rank that owns position a = leaf >> 5: the 65 value pairs from the local
-// codeword, the five lowest siblings from the local tree, the siblings above from the replicated top tree.
-__global__ void k_pc_open_sh(const F *__restrict__ cw, u32 Nl, const Dig *__restrict__ tree_loc, const Dig *__restrict__ top, u32 n5, u32 leaf, int lw,
-                             F *__restrict__ vals, Dig *__restrict__ path) {
-    const u32 t = threadIdx.x;
-    const u32 a = leaf >> 5, b = leaf & 31, al = a >> lw, leaf_loc = 32 * al + b, nl = 16 * Nl;
-    if (t < 64) {
-        const F *row = cw + ((size_t) t * 32 + b) * Nl;
-        vals[2 * t] = row[al]; vals[2 * t + 1] = row[al + (Nl >> 1)];
-    } else if (t == 64) { vals[128] = f_zero(); vals[129] = f_zero(); }
-    u32 depth = 5;
-    while ((1u << (depth - 5)) < n5) ++depth;
-    if (t <= depth) {
-        if (t == depth) path[t] = tree_loc[nl + leaf_loc];
-        else if (t < 5) path[t] = tree_loc[((nl + leaf_loc) >> t) ^ 1];
-        else path[t] = top[((n5 + a) >> (t - 5)) ^ 1];
-    }
-}
-
-int pcs_fri_open(vp_ctx *ctx, int oracle, uint64_t leaf, vp_F values[130], uint8_t *path, int path_capacity, int *path_len) {
-    PcShard &s = *ctx->pcs;
-    const int n = ctx->L[0].bl, ln = n - 6;
-    const u32 N = 1u << ln, Nl = N >> s.lw;
-    if (!ctx->pc_open_buf) VPCHK(dalloc(ctx, &ctx->pc_open_buf, (size_t) 130 + 2 * 40));
-    Dig *dpath = reinterpret_cast<Dig *>(ctx->pc_open_buf + 130);
-    u32 n_leaves;
-    if (oracle >= 2 && oracle - 2 >= s.n_local - 1) {                       // tail level: whole codeword on every rank
-        const int q = oracle - 2 - (s.n_local - 1);
-        if (oracle - 2 >= s.f_done || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-        const u32 Nt = (1u << s.lw) >> q;
-        n_leaves = Nt >= 2 ? 16 * Nt : 16;
-        if (leaf >= n_leaves) return VP_EINVAL;
-        hipLaunchKernelGGL(k_pc_open, dim3(1), dim3(128), 0, ctx->stream, s.tail + s.tail_cw_off[q], Nt, s.tail_tree + s.tail_tree_off[q], n_leaves, (u32) leaf,
-                           ctx->pc_open_buf, dpath, (const F *) nullptr);
-    } else {
-        const F *cw; const Dig *tl, *top; u32 Nc;
-        if (oracle == 0) { if (!s.private_done) return VP_EINVAL; cw = s.l_loc; tl = s.tree_l; top = s.top_l; Nc = Nl; }
-        else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; cw = s.h_loc; tl = s.tree_h; top = s.top_h; Nc = Nl; }
-        else {
-            const int lvl = oracle - 2;
-            if (lvl >= s.f_done || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-            cw = s.fri_loc + s.fri_off[lvl + 1]; tl = s.tree_f + s.tree_f_off[lvl]; top = s.top_f + s.top_f_off[lvl]; Nc = Nl >> (lvl + 1);
-        }
-        n_leaves = (16 * Nc) << s.lw;
-        if (leaf >= n_leaves) return VP_EINVAL;
-        if ((int) ((leaf >> 5) & (u64) (s.world - 1)) != s.rank) { ctx->err = "this rank does not own the leaf (owner = (leaf >> 5) mod world)"; return VP_EINVAL; }
-        hipLaunchKernelGGL(k_pc_open_sh, dim3(1), dim3(128), 0, ctx->stream, cw, Nc, tl, top, (Nc >> 1) << s.lw, (u32) leaf, s.lw, ctx->pc_open_buf, dpath);
-    }
-    int depth = 0; while ((1u << depth) < n_leaves) ++depth;
-    if (path_capacity < 32 * (depth + 1)) return VP_EINVAL;
-    HIPCHK(hipMemcpyAsync(values, ctx->pc_open_buf, 130 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(path, dpath, 32 * (size_t) (depth + 1), hipMemcpyDeviceToHost, ctx->stream));
-    VPCHK(check_stream(ctx));
-    *path_len = depth + 1;
-    return VP_OK;
-}
-
-// vp_fri_open_many on a sharded commitment: the descriptor of one oracle (refusals as in pcs_fri_open) and who answers a leaf of a position-sharded one
+// The descriptor of one oracle of a sharded commitment (pc_open_desc).  A position-sharded oracle (l, h, a locally hashed FRI level) is answered by the
+// rank that owns position a = leaf >> 5 (pcs_owns): the 65 value pairs from the local codeword, the five lowest siblings from the local tree, the siblings
+// above from the replicated top tree.  A tail level is whole on every rank.
 int pcs_open_desc(vp_ctx *ctx, int oracle, PcOpenDesc *d) {
     PcShard &s = *ctx->pcs;
-    const int n = ctx->L[0].bl, ln = n - 6;
-    const u32 N = 1u << ln, Nl = N >> s.lw;
-    if (oracle >= 2 && oracle - 2 >= s.n_local - 1) {                       // tail level: whole codeword on every rank
-        const int q = oracle - 2 - (s.n_local - 1);
-        if (oracle - 2 >= s.f_done || q >= (int) s.tail_tree_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-        const u32 Nt = (1u << s.lw) >> q;
-        d->cw = s.tail + s.tail_cw_off[q]; d->tree = s.tail_tree + s.tail_tree_off[q]; d->Nc = Nt; d->n_leaves = Nt >= 2 ? 16 * Nt : 16;
+    const FriLayout &fl = s.fl;
+    const int lvl = oracle - 2;
+    if (lvl >= s.f_done) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
+    if (lvl >= 0 && fl.is_tail(lvl)) {                                     // tail level: whole codeword on every rank
+        const int q = fl.tail_q(lvl);
+        d->cw = s.tail + fl.tail_cw(q); d->tree = s.tail_tree + fl.tail_tree(q); d->Nc = (u32) fl.tail_per_coset(q); d->n_leaves = (u32) fl.tail_leaves(q);
         return VP_OK;
     }
-    if (oracle == 0) { if (!s.private_done) return VP_EINVAL; d->cw = s.l_loc; d->tree = s.tree_l; d->top = s.top_l; d->Nc = Nl; }
-    else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; d->cw = s.h_loc; d->tree = s.tree_h; d->top = s.top_h; d->Nc = Nl; }
-    else {
-        const int lvl = oracle - 2;
-        if (lvl >= s.f_done || lvl + 1 >= (int) s.fri_off.size() || lvl >= (int) s.tree_f_off.size()) { ctx->err = "FRI level not committed yet"; return VP_EINVAL; }
-        d->cw = s.fri_loc + s.fri_off[lvl + 1]; d->tree = s.tree_f + s.tree_f_off[lvl]; d->top = s.top_f + s.top_f_off[lvl]; d->Nc = Nl >> (lvl + 1);
-    }
+    if (oracle == 0) { if (!s.private_done) return VP_EINVAL; d->cw = s.l_loc; d->tree = s.tree_l; d->top = s.top_l; d->Nc = (u32) fl.Nl; }
+    else if (oracle == 1) { if (!s.public_done) return VP_EINVAL; d->cw = s.h_loc; d->tree = s.tree_h; d->top = s.top_h; d->Nc = (u32) fl.Nl; }
+    else { d->cw = s.fri_loc + fl.loc_cw(lvl); d->tree = s.tree_f + fl.loc_tree(lvl); d->top = s.top_f + fl.top(lvl); d->Nc = (u32) fl.loc_per_coset(lvl); }
     d->n_leaves = (16 * d->Nc) << s.lw; d->n5 = (d->Nc >> 1) << s.lw; d->lw = (u32) s.lw;
     return VP_OK;
 }
@@ -758,12 +653,7 @@ int vp_pc_load_input(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs, int bit
     HIPCHK(hipMemsetAsync(ctx->L[0].val, 0, sizeof(F) << bit_length, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->L[0].val, inputs, n_inputs * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
     VPCHK(check_stream(ctx));
-    ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
-    ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
-    ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
-    ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0; ctx->fri_cw_off.clear(); ctx->fri_tree_off.clear();
-    ctx->pc_fri[0] = ctx->pc_fri[1] = nullptr; ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
-    ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->fri_m_off.clear(); ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
+    pc_forget(ctx);
     ctx->evaluated = true;
     if (ctx->ev_pool.empty()) {
         ctx->ev_pool.resize(1024);
@@ -788,7 +678,7 @@ int vp_pc_set_shard(vp_ctx *ctx, int rank, int world) {
     if (world == 1 && !(ctx->cm && ctx->cm->comm && ctx->cm->world == 1)) return VP_OK;
     ctx->pcs = new PcShard();
     ctx->pcs->rank = rank; ctx->pcs->world = world; ctx->pcs->lw = lw; ctx->pcs->S = 64 / world;
-    ctx->pcs->n_local = ln - lw;                // known before the FRI phase: vp_pc_shard_owner tells the replicated levels by it
+    ctx->pcs->fl = FriLayout(ln, lw);
     return VP_OK;
 }
 
@@ -970,7 +860,7 @@ int vp_allreduce_u64(vp_ctx *ctx, void *dev_buf, uint64_t count) {
 int vp_pc_shard_owner(vp_ctx *ctx, int oracle, uint64_t leaf) {
     if (!ctx || !ctx->pcs || ctx->pcs->world <= 1) return 0;
     const PcShard &s = *ctx->pcs;
-    if (oracle >= 2 && oracle - 2 >= s.n_local - 1) return -1;                 // tail level: replicated
+    if (oracle >= 2 && s.fl.is_tail(oracle - 2)) return -1;                    // tail level: replicated
     return (int) ((leaf >> 5) & (uint64_t) (s.world - 1));
 }
 
