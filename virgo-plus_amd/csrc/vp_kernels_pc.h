@@ -498,12 +498,15 @@ k_pc_virtual_oracle(const F *__restrict__ lcw, F *__restrict__ qcw, const F *__r
 // Position-sharded commitment (vpgpu_pc_shard.inc): a rank holds the positions a = a' * 2^lw + rank of every coset; Nk is then the
 // LOCAL per-coset length and the twiddle uses the global position.  lw = rank = 0: the whole codeword.
 // A thread takes VP_FOLD_SPT slices of one position: mu^-1 r / 2 is per position, so a fold costs ONE multiplication per output (and a halving) instead of three.
+// live: slices >= live are zero in `in` and stay the zero bytes they are in `out` (vp_pc_live.h) — neither read nor written; the grid covers the slice groups
+// that hold a live slice (vp_fold_groups).  64: every slice.
 #define VP_FOLD_SPT 4
+__host__ __device__ inline u32 vp_fold_groups(u32 live, u32 spt) { return (live + spt - 1) / spt; }
 __global__ void __launch_bounds__(VP_BLOCK)
-k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2, int lw, u32 rank) {
+k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2, int lw, u32 rank, u32 live) {
     const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     const u32 No = Nk >> 1;                                   // per-coset length of the output (>= 1)
-    if (t >= (size_t) (64 / VP_FOLD_SPT) * 32 * No) return;
+    if (t >= (size_t) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No) return;
     const u32 al = (u32) (t % No), gb = (u32) (t / No), b = gb & 31, ig = gb >> 5;
     const u32 a = (al << lw) + rank;
     const u32 M = 2 * half_m;
@@ -513,7 +516,7 @@ k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F
 #pragma unroll
     for (int j = 0; j < VP_FOLD_SPT; ++j) {
         const size_t sb = (size_t) (ig * VP_FOLD_SPT + j) * 32 + b;
-        if (Nk >= 2) { p[j] = in[sb * Nk + al]; q[j] = in[sb * Nk + al + No]; }
+        if (Nk >= 2 && ig * VP_FOLD_SPT + j < live) { p[j] = in[sb * Nk + al]; q[j] = in[sb * Nk + al + No]; }
         else { p[j] = f_zero(); q[j] = f_zero(); }
     }
     loads_first();
@@ -521,7 +524,7 @@ k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F
 #pragma unroll
     for (int j = 0; j < VP_FOLD_SPT; ++j) {
         const size_t sb = (size_t) (ig * VP_FOLD_SPT + j) * 32 + b;
-        out[sb * No + al] = f_add(f_half(f_add(p[j], q[j])), f_mul(c, f_sub(p[j], q[j])));      // 1/2 ((p + q) + mu^-1 r (p - q))
+        if (ig * VP_FOLD_SPT + j < live) out[sb * No + al] = f_add(f_half(f_add(p[j], q[j])), f_mul(c, f_sub(p[j], q[j])));      // 1/2 ((p + q) + mu^-1 r (p - q))
     }
 }
 // Round 4: the FIRST fold straight from the three committed codewords — the virtual oracle (k_pc_virtual_oracle) is never written.  With
@@ -538,10 +541,10 @@ k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F
 __global__ void __launch_bounds__(VP_BLOCK)
 k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out, u32 N,
                const F *__restrict__ RTn /* w_N^k, k < N */, const F *__restrict__ cb /* [b] = w_M^-b, [32 + b] = w_32^b - 1 */, F r, F half_n /* N / 2 */,
-               const F *__restrict__ q0, const F *__restrict__ qscal) {
+               const F *__restrict__ q0, const F *__restrict__ qscal, u32 live /* slices >= live: neither read nor written, see k_fri_fold */) {
     const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     const u32 No = N >> 1;
-    if (t >= (size_t) (64 / VP_VO_SPT) * 32 * No) return;
+    if (t >= (size_t) vp_fold_groups(live, VP_VO_SPT) * 32 * No) return;
     const u32 al = (u32) (t % No), sb = (u32) (t / No), b = sb & 31, ig = sb >> 5;
     const F wa = RTn[(N - al) & (N - 1)];                                     // w_N^-a = w_M^-(32 a): contiguous along the lanes
     F q0a = f_zero(), q0b = f_zero();
@@ -550,8 +553,10 @@ k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__
 #pragma unroll
     for (int k = 0; k < VP_VO_SPT; ++k) {
         const size_t p0 = ((size_t) (ig * VP_VO_SPT + k) * 32 + b) * N + al, p1 = p0 + No;
-        la[k] = lcw[p0]; lb[k] = lcw[p1]; ha[k] = hcw[p0]; hb[k] = hcw[p1];
-        if (!q0) { qa[k] = qcw[p0]; qb[k] = qcw[p1]; }
+        if (ig * VP_VO_SPT + k < live) {
+            la[k] = lcw[p0]; lb[k] = lcw[p1]; ha[k] = hcw[p0]; hb[k] = hcw[p1];
+            if (!q0) { qa[k] = qcw[p0]; qb[k] = qcw[p1]; }
+        } else la[k] = lb[k] = ha[k] = hb[k] = qa[k] = qb[k] = f_zero();
     }
     loads_first();
     const F inv_x = f_mul(wa, cb[b]);                                         // x^-1, x = w_M^(32 a + b)
@@ -560,6 +565,7 @@ k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__
 #pragma unroll
     for (int k = 0; k < VP_VO_SPT; ++k) {
         const u32 i = ig * VP_VO_SPT + k;
+        if (i >= live) continue;
         if (q0) { const F sc = qscal[i]; qa[k] = f_mul(sc, q0a); qb[k] = f_mul(sc, q0b); }
         const F s0 = S0[i];
         const F Ga = f_sub(f_sub(f_mul(la[k], qa[k]), f_mul(xn_m1, ha[k])), s0), Gb = f_sub(f_sub(f_mul(lb[k], qb[k]), f_mul(xn_m1, hb[k])), s0);
@@ -588,7 +594,7 @@ static_assert(64 % (VP_VO_SPT * VP_VO_GRP) == 0, "the 64 slices are dealt to wor
 template <bool TENSOR, int GRP> __global__ void __launch_bounds__(256)
 k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out1, F *__restrict__ out2,
                 F *__restrict__ out3, u32 N, const F *__restrict__ RTn, const F *__restrict__ cb, F r0, F r1, F r2, F half_n, F inv2,
-                const F *__restrict__ q0, const F *__restrict__ qscal) {
+                const F *__restrict__ q0, const F *__restrict__ qscal, u32 live) {
     __shared__ F x1[VP_VO_SPT][2][64], x2[VP_VO_SPT][64];
     const u32 E = N >> 3, No = N >> 1, N2 = N >> 2;
     const u32 lane = threadIdx.x & 63, v = threadIdx.x >> 6;
@@ -610,15 +616,20 @@ k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *_
     const F c1 = f_mul(inv2, f_mul(m1, r1));
     // fold 2 (Nk = N / 4): level-2 positions al and al + E;  mu^-1 = x^-4 at al.  Wave 0.
     const F c2 = f_mul(inv2, f_mul(f_mul(m1, m1), r2));
+    const u32 ng = min((u32) GRP, vp_fold_groups(live, VP_VO_SPT) - ig0);     // the workgroup's slice groups that hold a live slice (>= 1: the grid ends with them)
 #pragma unroll 1
-    for (u32 g = 0; g < (u32) GRP; ++g) {
+    for (u32 g = 0; g < ng; ++g) {
         const u32 ig = ig0 + g;
+        // slices >= live (vp_pc_live.h) are neither read nor written: the loop ends with the last group that holds a live slice, and in the one partial
+        // group the loads and stores are guarded per slice — by values that are uniform over the workgroup, so every wave still reaches both barriers
         F la[VP_VO_SPT], lb[VP_VO_SPT], ha[VP_VO_SPT], hb[VP_VO_SPT], qa[VP_VO_SPT], qb[VP_VO_SPT];
 #pragma unroll
         for (int k = 0; k < VP_VO_SPT; ++k) {
             const size_t p0 = ((size_t) (ig * VP_VO_SPT + k) * 32 + b) * N + a, p1 = p0 + No;
-            la[k] = lcw[p0]; lb[k] = lcw[p1]; ha[k] = hcw[p0]; hb[k] = hcw[p1];
-            if (!TENSOR) { qa[k] = qcw[p0]; qb[k] = qcw[p1]; }
+            if (ig * VP_VO_SPT + k < live) {
+                la[k] = lcw[p0]; lb[k] = lcw[p1]; ha[k] = hcw[p0]; hb[k] = hcw[p1];
+                if (!TENSOR) { qa[k] = qcw[p0]; qb[k] = qcw[p1]; }
+            } else { la[k] = lb[k] = ha[k] = hb[k] = f_zero(); if (!TENSOR) qa[k] = qb[k] = f_zero(); }
         }
         loads_first();
         F f1[VP_VO_SPT];
@@ -634,7 +645,7 @@ k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *_
                 const F D = f_sub(Ga, Gb), S = f_add(Ga, Gb);
                 f1[k] = f_mul(hx, f_add(D, f_mul(xr, S)));
             }
-            out1[((size_t) i * 32 + b) * No + a] = f1[k];
+            if (i < live) out1[((size_t) i * 32 + b) * No + a] = f1[k];
             if (v >= 2) x1[k][v - 2][lane] = f1[k];
         }
         __syncthreads();
@@ -645,7 +656,7 @@ k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *_
                 const u32 i = ig * VP_VO_SPT + k;
                 const F gg = x1[k][v][lane];
                 f2[k] = f_add(f_half(f_add(f1[k], gg)), f_mul(c1, f_sub(f1[k], gg)));
-                out2[((size_t) i * 32 + b) * N2 + a] = f2[k];
+                if (i < live) out2[((size_t) i * 32 + b) * N2 + a] = f2[k];
                 if (v == 1) x2[k][lane] = f2[k];
             }
         }
@@ -655,7 +666,7 @@ k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *_
             for (int k = 0; k < VP_VO_SPT; ++k) {
                 const u32 i = ig * VP_VO_SPT + k;
                 const F gg = x2[k][lane];
-                out3[((size_t) i * 32 + b) * E + al] = f_add(f_half(f_add(f2[k], gg)), f_mul(c2, f_sub(f2[k], gg)));
+                if (i < live) out3[((size_t) i * 32 + b) * E + al] = f_add(f_half(f_add(f2[k], gg)), f_mul(c2, f_sub(f2[k], gg)));
             }
         }
         // the next group's x1 is written by waves 2, 3 behind the second barrier (waves 0, 1 have read theirs before it), its x2 by wave 1 behind the

@@ -20,6 +20,7 @@
 #include "../../include/vpgpu.h"
 #include "vp_kernels.h"
 #include "vp_fri_layout.h"
+#include "vp_pc_live.h"
 
 using namespace vp;
 
@@ -169,6 +170,7 @@ struct VpOpt {
     int32_t real_pairs;             // public
     int32_t fft_gkr_batched;        // VP_FFT_GKR_BATCHED: the 2 lg inverse-FFT sumchecks of vp_fft_gkr as one batch                                      [1]
     int32_t split_vu;               // VP_SPLIT_VU: index-split proof: V_u of a split phase 2 from per-rank partial inner products ahead of the graph      [1]
+    int32_t pc_live;                // VP_PC_LIVE: the unsharded, unmasked commitment transforms and folds only the slices the input layer fills (0: all 64)  [1]
 };
 
 struct vp_ctx {
@@ -237,6 +239,10 @@ struct vp_ctx {
     // the slice's l / q / h codewords and its FRI levels end to end (M elements each, coset-major), scratch of its small transforms
     u32 pc_mask_ms = 0; F *pc_lm_cw = nullptr, *pc_qm_cw = nullptr, *pc_hm_cw = nullptr, *pc_fm = nullptr, *pc_mtmp = nullptr;
     size_t pc_mtmp_cap = 0, pc_mB = 0;                 // scratch capacity; B = max(ms, N): the scratch is laid out in blocks of B elements (pc_mask_scratch)
+    // Live slices (vp_pc_live.h): the slices >= pc_lv.live of the input layer are zero, and the unsharded, unmasked commitment leaves them out of its transforms,
+    // products and folds.  Hashes and openings read all 64 slices, so the dead slices of pc_cw, pc_hcw and of every level in pc_fri_all must read as zero bytes:
+    // pc_zf_*: the slice from which on that buffer is known to hold zeros (64: nothing known — a fresh allocation); pc_live_zero keeps them at pc_lv.live.
+    PcLive pc_lv; u32 pc_zf_cw = 64, pc_zf_hcw = 64, pc_zf_fri = 64;
 
     // Deferred completion (vp_set_deferred / vp_flush; round 5).  A GPU that goes idle for a fraction of a millisecond — a host synchronisation between two
     // prover calls, the host work between two proofs — runs the NEXT ten milliseconds at a lower clock (tools/leaf_in_step.py: k_leaf_hash alone 10.1 ms
@@ -384,6 +390,7 @@ void pc_forget(vp_ctx *ctx) {
     ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0;
     ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
+    ctx->pc_lv = PcLive(); ctx->pc_zf_cw = ctx->pc_zf_hcw = ctx->pc_zf_fri = 64;
 }
 
 inline u32 nblk(u64 n) { return (u32) ((n + VP_BLOCK - 1) / VP_BLOCK); }
@@ -1028,6 +1035,7 @@ static void opt_defaults(VpOpt *o) {
     o->real_pairs = 1;
     o->fft_gkr_batched = 1;
     o->split_vu = 1;
+    o->pc_live = 1;
 }
 static void opt_to_public(const VpOpt &o, vp_options *p) {
     memset(p, 0, sizeof *p);
@@ -1059,7 +1067,7 @@ static const OptName g_opt_names[] = {
     {"fold_branches", &VpOpt::fold_branches}, {"fuse_combine", &VpOpt::fuse_combine}, {"plan_autotune", &VpOpt::plan_autotune},
     {"pc_tensor_pub", &VpOpt::pc_tensor_pub}, {"persistent_timeout_ms", &VpOpt::persistent_timeout_ms}, {"graph_explicit", &VpOpt::graph_explicit}, {"ntt_r8", &VpOpt::ntt_r8},
     {"interactive_fast_init", &VpOpt::interactive_fast_init}, {"fuse_p2", &VpOpt::fuse_p2}, {"leaf_asm", &VpOpt::leaf_asm},
-    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}};
+    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}, {"pc_live", &VpOpt::pc_live}};
 int vp_tuning_get(const vp_ctx *ctx, const char *name, int32_t *value) {
     if (!ctx || !name || !value) return VP_EINVAL;
     for (const OptName &n : g_opt_names) if (!strcmp(n.name, name)) { *value = ctx->opt.*(n.field); return VP_OK; }
@@ -1101,6 +1109,7 @@ static int resolve_options(VpOpt *o, const vp_options *user, uint32_t *pinned) {
     flag("VP_REAL_PAIRS", o->real_pairs);
     flag("VP_FFT_GKR_BATCHED", o->fft_gkr_batched);
     flag("VP_SPLIT_VU", o->split_vu);
+    flag("VP_PC_LIVE", o->pc_live);
     flag("VP_PC_TENSOR", o->pc_tensor_pub);
     num("VP_PERSIST_TIMEOUT_MS", o->persistent_timeout_ms);
     num("VP_GRAPH_EXPLICIT", o->graph_explicit);

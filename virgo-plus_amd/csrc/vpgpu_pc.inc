@@ -118,6 +118,13 @@ int pc_scratch_reserve(vp_ctx *ctx, size_t total) {
     return VP_OK;
 }
 
+// k_ntt8_colsx's chunk rule (pc_launch_ntt8: cosets are dealt to `chunks` workgroups per (row, tile) until the launch has 8192 of them; every chunk reloads the
+// row's input): 1 = applied to the row count rounded up to a power of two, so the 57 / 29 rows of the live slices (vp_pc_live.h) chunk like 64 / 32; 0 = applied to
+// the rows themselves (twice the chunks at 57 and 29 rows: more input reloads).  1 keeps the chunking every earlier measurement of these encodes was made with;
+// the other form is not measured yet (profiles/live_slices_ab.md, section 3), which is what the switch is here for.
+#ifndef VP_NTT8X_CHUNK_POW2
+#define VP_NTT8X_CHUNK_POW2 1
+#endif
 #ifndef VP_NTT8X
 #define VP_NTT8X 1          // forward encodes of 2^15 .. 2^17 points: pass A with the coset loop inside the workgroup (k_ntt8_colsx); 0: k_ntt8_cols everywhere
 #endif
@@ -177,7 +184,11 @@ int pc_launch_ntt8(vp_ctx *ctx, const F *in, F *out, int ln, int lm, int inverse
         // the encoder's pass A: one workgroup per (row, tile of 2048 / N1 columns, chunk of cosets)
         const u32 tiles = (512u << l1) / NTT8X_TILE;                  // N2 / columns per tile
         u32 chunks = 1;                                               // enough workgroups for ten rounds of the chip's 768 resident ones, as few input loads as that allows
-        while (chunks < cosets && (u64) rows * tiles * chunks < 8192) chunks <<= 1;
+        // (a row count that is no power of two — the live slices, vp_pc_live.h — chunks like the next power of two: 57 of 64 rows keep the 64 rows' input loads;
+        // VP_NTT8X_CHUNK_POW2 = 0 applies the rule to the rows themselves, which doubles the chunks at 57 and 29 rows)
+        u32 rows_r = rows;
+        if (VP_NTT8X_CHUNK_POW2) { rows_r = 1; while (rows_r < rows) rows_r <<= 1; }
+        while (chunks < cosets && (u64) rows_r * tiles * chunks < 8192) chunks <<= 1;
         x.cpw = cosets / chunks;
         const dim3 g(rows, tiles, chunks);
         const int sl_ = prof_begin(ctx, ctx->stream, VP_K_NTT8_COLS, (u32) (g.x * g.y * g.z), (u32) tr, 16ull * N * tr + 16ull * N * rows, tr * (ntt8_cols_mults(ln, 1) + N / 8));
@@ -596,6 +607,40 @@ static void pc_final_order(const F *cw, vp_F *final_code) {
     for (u32 i = 0; i < 16; ++i) for (u32 s = 0; s < 64; ++s) for (u32 hi = 0; hi < 2; ++hi) o[(i << 7) | (s << 1) | hi] = cw[s * 32 + i + 16 * hi];
 }
 
+// Live slices (vp_pc_live.h).  vp_commit_private fixes the count for the commitment it starts — the input layer's zero tail is what vp_evaluate and
+// vp_pc_load_input leave behind L[0].size — and a commitment with a mask slice runs over all 64.
+static inline void pc_live_set(vp_ctx *ctx, bool masked) {
+    ctx->pc_lv = masked ? PcLive() : PcLive(ctx->L[0].bl, (uint64_t) ctx->L[0].size, ctx->opt.pc_live != 0);
+}
+// The dead slices of a buffer of 64 slices x `per` elements must read as zero bytes (leaf hashes, openings and vp_fri_final read all 64).  mark: the slice
+// from which on the buffer is known to be zero (64: a fresh allocation).  A smaller live count zeroes the gap here, in stream order; a larger one needs
+// nothing, the phase that follows writes every live slice before anything reads the buffer.  (Calls that run over all 64 slices compute the same zeros.)
+static int pc_zero_dead(vp_ctx *ctx, F *buf, size_t per, u32 mark, u32 live) {
+    if (buf && live < mark) HIPCHK(hipMemsetAsync(buf + (size_t) live * per, 0, (size_t) (mark - live) * per * sizeof(F), ctx->stream));
+    return VP_OK;
+}
+static int pc_live_zero_cw(vp_ctx *ctx, u32 written) {            // `written`: slices the encode writes (the paired encode may write one dead slice)
+    const u32 M = 1u << (ctx->L[0].bl - 1);
+    VPCHK(pc_zero_dead(ctx, ctx->pc_cw, M, ctx->pc_zf_cw, written));
+    ctx->pc_zf_cw = written;
+    return VP_OK;
+}
+static int pc_live_zero_hcw(vp_ctx *ctx) {
+    const u32 M = 1u << (ctx->L[0].bl - 1);
+    VPCHK(pc_zero_dead(ctx, ctx->pc_hcw, M, ctx->pc_zf_hcw, ctx->pc_lv.live));
+    ctx->pc_zf_hcw = ctx->pc_lv.live;
+    return VP_OK;
+}
+static int pc_live_zero_fri(vp_ctx *ctx) {
+    if (!ctx->pc_fri_all) return VP_OK;                           // not allocated yet: the mark stays at 64 for the allocation to come
+    const int ln = ctx->L[0].bl - 6;
+    const FriLayout fl(ln, 0);
+    if (ctx->pc_lv.live < ctx->pc_zf_fri)
+        for (int k = 0; k < ln; ++k) VPCHK(pc_zero_dead(ctx, ctx->pc_fri_all + fl.cw(k), 32 * fl.per_coset(k), ctx->pc_zf_fri, ctx->pc_lv.live));
+    ctx->pc_zf_fri = ctx->pc_lv.live;
+    return VP_OK;
+}
+
 // buffers of commit_public and of the FRI commit phase (every level's codeword is kept for the openings): allocated with the commitment,
 // not inside the first fold step
 int pc_public_alloc(vp_ctx *ctx) {
@@ -624,7 +669,9 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
                           const vp_F *pub_mask = nullptr, uint64_t n_pub_mask = 0) {
     const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
     const u32 N = 1u << ln, M = 1u << lm;
+    const u32 live = pub_mask ? 64u : ctx->pc_lv.live;    // slices >= live are zero (vp_pc_live.h): l q, S, T, H, all_sum and h are zero with them
     VPCHK(pc_hash_outstanding(ctx, 2u));                  // an h of an earlier call that no vp_fri_commit has hashed: its codeword is replaced below
+    if (!pub_mask) VPCHK(pc_live_zero_hcw(ctx));
     const bool late = ctx->hash_late && !pub_mask;        // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels
     F *P = ctx->pc_tmp, *ST = ctx->pc_tmp + (size_t) 128 * N, *H = ctx->pc_tmp + (size_t) 256 * N;
     F *parts = ctx->pc_small, *d_inner = ctx->pc_small + 1024, *d_all = ctx->pc_small + 1025;
@@ -660,19 +707,20 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
         VPCHK(pc_launch_ntt(ctx, ctx->pc_pub, ctx->pc_coef, ln, lm, 1, 1, 1, N));
         VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_q0, ln, lm, 0, 1, 32, N));
     } else {
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_pub, ctx->pc_coef, ln, lm, 1, 64, 1, N));
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_qcw, ln, lm, 0, 64, 32, N));
+        // (q of a dead slice is only ever multiplied by zero, and q is no oracle)
+        VPCHK(pc_launch_ntt(ctx, ctx->pc_pub, ctx->pc_coef, ln, lm, 1, live, 1, N));
+        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_qcw, ln, lm, 0, live, 32, N));
     }
     const F *q0 = tensor ? ctx->pc_q0 : nullptr, *qs = tensor ? qscal : nullptr;
     // quotient h of l*q by x^N - 1, per slice (poly_commit.h:264-293)
-    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 128 * N), 1, 48ull * 128 * N, (u64) 128 * N,
-            hipLaunchKernelGGL(k_pc_products, dim3(nblk((u64) 128 * N)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw, N, P, 64u, q0, qs));
-    VPCHK(pc_launch_ntt(ctx, P, ST, ln, lm, 1, 128, 1, N));
-    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(128), 0, ctx->stream, d_all, 65u);
-    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 64 * N), 1, 48ull * 64 * N, (u64) 2 * 64 * N,
-            hipLaunchKernelGGL(k_pc_quotient, dim3(nblk((u64) 64 * N)), dim3(VP_BLOCK), 0, ctx->stream, ST, N, ctx->pc_rt, M >> 1,
-                               host_inv_real(2), f_make(N, 0), H, d_all, 64u));
-    VPCHK(pc_launch_ntt(ctx, H, ctx->pc_hcw, ln, lm, 0, 64, 32, N));
+    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 2 * live * N), 1, 48ull * 2 * live * N, (u64) 2 * live * N,
+            hipLaunchKernelGGL(k_pc_products, dim3(nblk((u64) 2 * live * N)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw, N, P, live, q0, qs));
+    VPCHK(pc_launch_ntt(ctx, P, ST, ln, lm, 1, 2 * live, 1, N));
+    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(256), 0, ctx->stream, d_all, 144u);      // all_sum[65] and S_0 at [80..144): the dead slices' stay zero
+    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) live * N), 1, 48ull * live * N, (u64) 2 * live * N,
+            hipLaunchKernelGGL(k_pc_quotient, dim3(nblk((u64) live * N)), dim3(VP_BLOCK), 0, ctx->stream, ST, N, ctx->pc_rt, M >> 1,
+                               host_inv_real(2), f_make(N, 0), H, d_all, live));
+    VPCHK(pc_launch_ntt(ctx, H, ctx->pc_hcw, ln, lm, 0, live, 32, N));
     // second oracle: leaf chains + tree over h (fri.cpp:36-139 with oracle_indicator = 1)
     const u32 n_leaves = M >> 1;
     if (pub_mask) {
@@ -719,6 +767,8 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
     const u32 N = 1u << ln, M = 1u << lm;
     VPCHK(pc_hash_outstanding(ctx, 3u));                  // an earlier commitment under vp_pc_hash_late whose codeword this call replaces
     const bool late = ctx->hash_late && !mask;            // vp_pc_hash_late: the transforms only; vp_fri_commit hashes l with h and its own levels
+    pc_live_set(ctx, mask != nullptr);
+    const PcLive &lv = ctx->pc_lv;
     u32 ms = 0;
     if (mask) { VPCHK(pc_mask_geometry(ctx, n_mask, &ms)); VPCHK(flush_pending(ctx, (size_t) -1)); }
     VPCHK(pc_root_table(ctx, lm));
@@ -736,13 +786,16 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
     if (ctx->opt.real_pairs && ctx->vreal == 1 && ctx->opt.ntt_r8 && ln >= 13 && ln <= 17) {
         // a REAL witness (every circuit value real, vp_evaluate): slices p and p + 32 travel as ONE complex sequence through both transforms — half the
         // transforms of this call; the encoder's last store splits a row's values into the two slices' (k_ntt8_rows, Ntt8Args)
-        VPCHK(pc_launch_ntt8(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, 32, 1, N, 32));
-        VPCHK(pc_launch_ntt8(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, 32, 32, N, 32));
+        // (PcLive: pair_rows = ceil(live / 2) rows, 32 for a full layer; at odd live the last partner is the first dead slice — zeros in, zeros out)
+        VPCHK(pc_live_zero_cw(ctx, lv.pair_end()));
+        VPCHK(pc_launch_ntt8(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, lv.pair_rows, 1, N, lv.pair_rows));
+        VPCHK(pc_launch_ntt8(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, lv.pair_rows, 32, N, lv.pair_rows));
     } else {
-        VPCHK(pc_launch_ntt(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, 64, 1, N));
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, 64, 32, N));
+        VPCHK(pc_live_zero_cw(ctx, lv.live));
+        VPCHK(pc_launch_ntt(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, lv.live, 1, N));
+        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, lv.live, 32, N));
     }
-    // leaf chains + tree (fri.cpp:95-127)
+    // leaf chains + tree (fri.cpp:95-127): all 64 slices
     const u32 n_leaves = M >> 1;
     ctx->pc_mask_ms = 0;
     if (mask) {
@@ -835,6 +888,7 @@ static int pc_warm(vp_ctx *ctx) {
     struct Dry { vp_ctx *c; ~Dry() { c->pc_dry = false; } } dry{ctx};
     ctx->pc_dry = true;
     // the transform shapes of vp_commit_private (both forms), vp_commit_public / _eq (tensor and general), the quotient
+    // (at the full 64 / 32 rows: the scratch then holds every live count, a masked commitment's 64 included)
     if (ctx->opt.real_pairs && ctx->vreal == 1 && ctx->opt.ntt_r8 && ln >= 13 && ln <= 17) {
         VPCHK(pc_launch_ntt8(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, 32, 1, N, 32));
         VPCHK(pc_launch_ntt8(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, 32, 32, N, 32));
@@ -845,6 +899,13 @@ static int pc_warm(vp_ctx *ctx) {
     VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_q0, ln, lm, 0, 1, 32, N));
     VPCHK(pc_launch_ntt(ctx, ctx->pc_tmp, ctx->pc_tmp + (size_t) 128 * N, ln, lm, 1, 128, 1, N));
     ctx->pc_dry = false;
+    {   // the dead slices' zero bytes (vp_pc_live.h), so that the first commitment does not pay for them
+        pc_live_set(ctx, false);
+        const bool pairs = ctx->opt.real_pairs && ctx->vreal == 1 && ctx->opt.ntt_r8 && ln >= 13 && ln <= 17;
+        VPCHK(pc_live_zero_cw(ctx, pairs ? ctx->pc_lv.pair_end() : ctx->pc_lv.live));
+        VPCHK(pc_live_zero_hcw(ctx));
+        VPCHK(pc_live_zero_fri(ctx));
+    }
     VPCHK(pc_fold0_consts(ctx, lm));
     if (pc_leaf_wg(ctx, (u64) M >> 1)) VPCHK(pc_leaf_prepare(ctx));
     VPCHK(pc_many_reserve(ctx, 33u * (2 + ln)));             // the query phase's records (vp_fri_query)
@@ -947,11 +1008,13 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         VPCHK(dalloc(ctx, &ctx->pc_fri_all, (size_t) 64 * M));            // every level's codeword is kept for the openings
         VPCHK(dalloc(ctx, &ctx->pc_fri_tree, (size_t) M));
     }
+    const u32 live = ctx->pc_mask_ms ? 64u : ctx->pc_lv.live;      // slices >= live: a zero oracle and zero levels (vp_pc_live.h), kept as zero bytes
+    if (!ctx->pc_mask_ms) VPCHK(pc_live_zero_fri(ctx));
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (ctx->fri_step < 0) {
         // virtual oracle in place over the q codeword; S_0 per slice sits behind all_sum in pc_small
-        hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) 64 * M)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw,
-                           ctx->pc_hcw, ctx->pc_small + 1025 + 80, N, ctx->pc_rt, M >> 1, f_make(N, 0), 64u,
+        hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) live * M)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw,
+                           ctx->pc_hcw, ctx->pc_small + 1025 + 80, N, ctx->pc_rt, M >> 1, f_make(N, 0), live,
                            (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr));
         ctx->fri_step = 0;
         if (ctx->pc_mask_ms)      // the mask slice's virtual oracle, in place over its q codeword (poly_commit.h:225-245)
@@ -965,8 +1028,8 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
     const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + fl.cw(k - 1);
     F *out = ctx->pc_fri_all + fl.cw(k);
     F rf; memcpy(&rf, r, sizeof(F));
-    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
-                       host_inv_real(2), 0, 0u);
+    hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
+                       host_inv_real(2), 0, 0u, live);
     // leaves of the folded codeword (M_{k+1} / 2 of them) + tree
     Dig *tree = ctx->pc_fri_tree + fl.tree(k);
     F *out_m = nullptr;
@@ -1030,6 +1093,9 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     EvGuard ev_guard{ctx, &ev_a};
     // the virtual oracle (poly_commit.h:294-318) is consumed by the first fold only: fused into it (k_fri_fold0_vo / k_fri_fold0_vo3)
     ctx->fri_step = 0;
+    // slices >= live have a zero oracle and zero levels (vp_pc_live.h): the folds leave them out, the level regions keep their zero bytes for the hashes
+    u32 live = ctx->pc_lv.live;
+    VPCHK(pc_live_zero_fri(ctx));
     // folds of every level, back to back
     const FriLayout fl(ln, 0);
     FriLeafArgs la{}; MerkleArgs ma{};
@@ -1067,16 +1133,16 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 const u32 E = N >> 3;
                 // VP_VO_GRP slice groups per workgroup where that still leaves >= 2048 workgroups (N >= 2^14), one group per workgroup below
                 const bool grouped = (64 / VP_VO_SPT / VP_VO_GRP) * 32 * (E >> 6) >= 2048;
-                const u32 grid3 = (64 / VP_VO_SPT / (grouped ? VP_VO_GRP : 1)) * 32 * (E >> 6);
+                const u32 grid3 = vp_fold_groups(live, VP_VO_SPT * (grouped ? VP_VO_GRP : 1)) * 32 * (E >> 6);      // the workgroups whose slices include a live one
                 const void *fold3 = ctx->pc_q_tensor ? (grouped ? (const void *) k_fri_fold0_vo3<true, VP_VO_GRP> : (const void *) k_fri_fold0_vo3<true, 1>)
                                                      : (grouped ? (const void *) k_fri_fold0_vo3<false, VP_VO_GRP> : (const void *) k_fri_fold0_vo3<false, 1>);
                 const F *a_lcw = ctx->pc_cw, *a_qcw = ctx->pc_qcw, *a_hcw = ctx->pc_hcw, *a_S0 = ctx->pc_small + 1025 + 80, *a_cb = ctx->pc_cbuf;
                 const F *a_q0 = ctx->pc_q_tensor ? ctx->pc_q0 : nullptr, *a_qs = ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr;
                 u32 a_N = N;
                 F a_half = f_mul(f_make(N, 0), host_inv_real(2)), a_inv2 = host_inv_real(2);
-                void *args3[] = {&a_lcw, &a_qcw, &a_hcw, &a_S0, &o1, &o2, &o3, &a_N, &rtn, &a_cb, &rf, &r1, &r2, &a_half, &a_inv2, &a_q0, &a_qs};
-                PC_PROF(VP_K_FRI_FOLD, grid3, 1, (ctx->pc_q_tensor ? 80ull : 112ull) * 64 * 32 * No + 16ull * 64 * 32 * ((No >> 1) + (No >> 2)),
-                        (u64) (ctx->pc_q_tensor ? 9 : 7) * 64 * 32 * No + 3ull * 64 * 32 * ((No >> 1) + (No >> 2)),
+                void *args3[] = {&a_lcw, &a_qcw, &a_hcw, &a_S0, &o1, &o2, &o3, &a_N, &rtn, &a_cb, &rf, &r1, &r2, &a_half, &a_inv2, &a_q0, &a_qs, &live};
+                PC_PROF(VP_K_FRI_FOLD, grid3, 1, (ctx->pc_q_tensor ? 80ull : 112ull) * live * 32 * No + 16ull * live * 32 * ((No >> 1) + (No >> 2)),
+                        (u64) (ctx->pc_q_tensor ? 9 : 7) * live * 32 * No + 3ull * live * 32 * ((No >> 1) + (No >> 2)),
                         (void) hipLaunchKernel(fold3, dim3(grid3), dim3(256), args3, 0, ctx->stream));
             }
         }
@@ -1088,16 +1154,16 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             const F *rtn = nullptr;
             VPCHK(pc_circle_roots(ctx, lm, ln, &rtn));
             VPCHK(pc_fold0_consts(ctx, lm));
-            PC_PROF(VP_K_FRI_FOLD, nblk((u64) (64 / VP_VO_SPT) * 32 * No), 1, (ctx->pc_q_tensor ? 80ull : 112ull) * 64 * 32 * No, (u64) (ctx->pc_q_tensor ? 9 : 7) * 64 * 32 * No,
-                    hipLaunchKernelGGL(k_fri_fold0_vo, dim3(nblk((u64) (64 / VP_VO_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_cw, (const F *) ctx->pc_qcw,
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No), 1, (ctx->pc_q_tensor ? 80ull : 112ull) * live * 32 * No, (u64) (ctx->pc_q_tensor ? 9 : 7) * live * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold0_vo, dim3(nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_cw, (const F *) ctx->pc_qcw,
                                        (const F *) ctx->pc_hcw, (const F *) (ctx->pc_small + 1025 + 80), out, N, rtn, (const F *) ctx->pc_cbuf, rf,
                                        f_mul(f_make(N, 0), host_inv_real(2)),
-                                       (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr)));
+                                       (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr), live));
         }
         else
-        PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
-                hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
-                                   host_inv_real(2), 0, 0u));
+        PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No), 1, 48ull * live * 32 * No, (u64) 3 * live * 32 * No,
+                hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
+                                   host_inv_real(2), 0, 0u, live));
         const u32 n_leaves = 16 * No;
         Dig *tree = ctx->pc_fri_tree + fl.tree(k);
         ma.tree[ne + k] = tree; ma.count[ne + k] = n_leaves;

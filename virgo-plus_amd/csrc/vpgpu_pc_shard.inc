@@ -415,7 +415,7 @@ F *pcs_local_fold(vp_ctx *ctx, int k, F r) {
     F *out = s.fri_loc + s.fl.loc_cw(k);
     PC_PROF(VP_K_FRI_FOLD, nblk((u64) 64 * 32 * No), 1, 48ull * 64 * 32 * No, (u64) 3 * 64 * 32 * No,
             hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (s.fri_loc + s.fl.loc_in(k)), out, Nk, k,
-                               ctx->pc_rt, M >> 1, r, host_inv_real(2), s.lw, (u32) s.rank));
+                               ctx->pc_rt, M >> 1, r, host_inv_real(2), s.lw, (u32) s.rank, 64u));
     return out;
 }
 // One replicated tail step: level k - 1 (whole on every rank) folds to level k > n_local - 1, which is hashed; returns the level's tree (the root is node 1)
@@ -426,7 +426,7 @@ int pcs_tail_step(vp_ctx *ctx, int k, F r, Dig **tree_out) {
     F *out = s.tail + s.fl.tail_cw(q);
     Dig *tree = s.tail_tree + s.fl.tail_tree(q);
     hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) (64 / VP_FOLD_SPT) * 32 * Nn)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (s.tail + s.fl.tail_cw(q - 1)), out, Nt, k, ctx->pc_rt, M >> 1,
-                       r, host_inv_real(2), 0, 0u);
+                       r, host_inv_real(2), 0, 0u, 64u);
     VPCHK(pc_hash_level(ctx, out, Nn, nullptr, tree));
     *tree_out = tree;
     return VP_OK;
