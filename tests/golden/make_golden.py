@@ -11,6 +11,7 @@ and a gzip copy of the reference's own circuit data file data/SHA256_64.pws.
 
     python tests/golden/make_golden.py            # x1, randomize(8,12), x16
     python tests/golden/make_golden.py --with-x64 # also the 64-block case (~1 min)
+    python tests/golden/make_golden.py --only custom_c   # one custom case and its golden.json entry, every other fixture left as it is
     python tests/golden/make_golden.py --with-big # also BASELINE configs[2] / [4]: SHA-256 x1024 with the commitment (round 3: 131 s circuit
                                                   # build + 809 s verify(), peak RSS 63 GB — needs the whole 62 GiB container, run nothing
                                                   # beside it) and randomize(16, 20) with the commitment (~2 min, 4 GB)
@@ -39,7 +40,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # > 512 gates: the commitment needs bit length >= 7 (vpd_verifier.cpp:115), and the reference's own FFT only works for
 # transforms of >= 8 points (RS_polynomial.cpp:104-133: for order 4 the `dep == 1` loop runs zero times and stale scratch is
 # read), i.e. slices of >= 8 elements = input bit length >= 9.  Below that its Merkle roots are not a function of the input.
-CUSTOM = {"custom_a": (101, [600, 180, 150, 300, 64, 9]), "custom_b": (102, [1500, 2100, 900, 4100, 700])}
+# custom_c: custom_circuits.make_skewed — heavy rows, long subsets and every gate type at the places the fused inits and the chunk kernels branch on
+# (tests/test_skewed_circuits_host.py); its sizes are make_skewed's own.
+CUSTOM = {"custom_a": (101, [600, 180, 150, 300, 64, 9]), "custom_b": (102, [1500, 2100, 900, 4100, 700]), "custom_c": (103, None)}
 
 SURVEY_SHA256 = {
     "sha256_x1": "7d56df550455f8e32dcda3ea158e2606b23f4e8bac761ca6a081b8caeee65047",
@@ -88,12 +91,43 @@ def run_case(name, args):
     }
 
 
+def custom_case(cname):
+    """One entry of CUSTOM through `ref_run --custom`: the circuit goes to the reference as a flat record file, removed afterwards."""
+    import struct
+    import custom_circuits as cc
+    seed, sizes = CUSTOM[cname]
+    szs, ty, l, u, v, c, asr = cc.make(seed, sizes) if sizes is not None else cc.make_skewed(seed)
+    path = os.path.join(HERE, "_%s.circ" % cname)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<i", len(szs)))
+        f.write(szs.tobytes())
+        for g in range(len(ty)):
+            f.write(struct.pack("<iiQQQQB", int(ty[g]), int(l[g]), int(u[g]), int(v[g]), int(c[g][0]), int(c[g][1]), int(asr[g])))
+    try:
+        m = run_case(cname, ["--custom", path])
+    finally:
+        os.remove(path)
+    m["custom"] = {"seed": seed, "sizes": [int(x) for x in szs]}
+    if sizes is None:
+        m["custom"]["generator"] = "make_skewed"
+    return m
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--with-x64", action="store_true")
     ap.add_argument("--with-big", action="store_true")
+    ap.add_argument("--only", choices=sorted(CUSTOM), help="record this custom case alone; no other fixture is rewritten")
     a = ap.parse_args()
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, stdout=subprocess.DEVNULL)
+    if a.only:
+        meta_path = os.path.join(HERE, "golden.json")
+        meta = json.load(open(meta_path))
+        meta[a.only] = custom_case(a.only)
+        meta[a.only]["args"] = [os.path.basename(x) if x.startswith(HERE) else x for x in meta[a.only]["args"]]
+        json.dump(meta, open(meta_path, "w"), indent=1, sort_keys=True)
+        print(json.dumps({a.only: (meta[a.only]["sha256"], meta[a.only]["mult_counter"], meta[a.only]["add_counter"])}, indent=1))
+        return 0
     pws_gz = os.path.join(HERE, "SHA256_64.pws.gz")
     with open(PWS, "rb") as f, gzip.GzipFile(pws_gz, "wb", mtime=0) as g:
         shutil.copyfileobj(f, g)
@@ -111,19 +145,8 @@ def main():
         os.remove(chk)
         meta["randomize_8_12"] = run_case("randomize_8_12", ["--randomize", "8", "12"])
         meta["sha256_x16"] = run_case("sha256_x16", ["--pws", tmp_pws, "--blocks", "16"])
-        import struct
-        import custom_circuits as cc
-        for cname, (seed, sizes) in CUSTOM.items():
-            szs, ty, l, u, v, c, asr = cc.make(seed, sizes)
-            path = os.path.join(HERE, "_%s.circ" % cname)
-            with open(path, "wb") as f:
-                f.write(struct.pack("<i", len(szs)))
-                f.write(szs.tobytes())
-                for g in range(len(ty)):
-                    f.write(struct.pack("<iiQQQQB", int(ty[g]), int(l[g]), int(u[g]), int(v[g]), int(c[g][0]), int(c[g][1]), int(asr[g])))
-            meta[cname] = run_case(cname, ["--custom", path])
-            meta[cname]["custom"] = {"seed": seed, "sizes": sizes}
-            os.remove(path)
+        for cname in CUSTOM:
+            meta[cname] = custom_case(cname)
         if a.with_x64:
             meta["sha256_x64"] = run_case("sha256_x64", ["--pws", tmp_pws, "--blocks", "64"])
         if a.with_big:

@@ -110,6 +110,28 @@ def _both_modes(vp, c, gold):
     return res, res2
 
 
+def _kind(vp, name):
+    """vp_kernel_name(VP_K_<name>), the enum read from include/vpgpu.h."""
+    import re
+    text = open(os.path.join(ROOT, "include", "vpgpu.h")).read()
+    body = re.search(r"enum\s*\{\s*(VP_K_BETA\s*=\s*0.*?)\}", text, re.S).group(1)
+    ids = [x.split("=")[0].strip() for x in body.split(",")]
+    return vp.lib_gpu().vp_kernel_name(ids.index("VP_K_" + name)).decode()
+
+
+def _engagement(vp, s):
+    """One profiled prove_gkr: (transcript, launches per kernel name, summed jobs of the generating fold launches)."""
+    s.set_profiling(1)
+    tr, _ = s.prove_gkr()
+    st = s.launch_stats()
+    s.set_profiling(0)
+    launches = {}
+    for e in st:
+        launches[e["kernel"]] = launches.get(e["kernel"], 0) + 1
+    gen = _kind(vp, "SFGEN")
+    return tr, launches, sum(e["jobs"] for e in st if e["kernel"] == gen)
+
+
 @pytest.mark.parametrize("name,blocks", [("sha256_x1", 1), ("sha256_x16", 16)])
 def test_sha256_transcript_matches_reference(vp, golden, gold_gkr, pws_path, name, blocks):
     c = vp.Circuit.from_pws(pws_path, blocks, seed=1)
@@ -190,13 +212,19 @@ def test_chain_sharded_proof_assembles_to_reference(vp, golden, gold_gkr, pws_pa
 
 def test_chain_sharded_proof_randomize_and_fused_init(vp, golden, gold_gkr, monkeypatch):
     """Sharding with a phase 2 that takes V_u from its own inner-product pass (phase 1 of the layer on another rank), on the
-    synthetic circuit, with the init fused into the first fold launch forced on."""
+    synthetic circuit, with the init fused into the first fold launch forced on: the tables of randomize(8, 12) have 2^12 entries, so the
+    fold kernel is lowered to them as well (VP_SF_BIG_LOG=12, the low end of the measured range) — with VP_FUSE_MIN_LOG alone they stay
+    below it and nothing fuses.  The unsharded plan of the context is shown to run generating fold jobs."""
     monkeypatch.setenv("VP_FUSE_MIN_LOG", "10")
+    monkeypatch.setenv("VP_SF_BIG_LOG", "12")
     c = vp.Circuit.randomize(8, 12, seed=1)
     s = vp.Session(c)
     s.draw_tape()
     for world in (2, 5, 8):
         assert vp.sum_transcripts(_sharded_parts(vp, s, world)) == gold_gkr("randomize_8_12")
+    tr, launches, jobs = _engagement(vp, s)
+    assert tr == gold_gkr("randomize_8_12")
+    assert jobs > 0 and launches.get(_kind(vp, "SFGEN"), 0) > 0, "no init was generated inside a fold launch"
     s.close(); c.close()
 
 

@@ -278,13 +278,14 @@ def test_oracle_commitment_array_vs_reference_x1(ob, golden, pws_path):
     c.close()
 
 
-@pytest.mark.parametrize("name", ["custom_a", "custom_b"])
+@pytest.mark.parametrize("name", ["custom_a", "custom_b", "custom_c"])
 def test_oracle_on_all_gate_types_and_asserts_vs_reference(ob, golden, name):
     """Circuits using every gate type + assert gates, proved by the REAL reference (ref_run --custom): the oracle must
-    reproduce transcript, field-op counters, commitment and FRI data."""
+    reproduce transcript, field-op counters, commitment and FRI data.  custom_c is the skewed circuit of custom_circuits.make_skewed
+    (heavy rows of up to 33000 gates, subsets of bit length 14, two assert gates per layer)."""
     import custom_circuits as cc
     g = golden[name]
-    c = ob.Circuit.custom(*cc.make(g["custom"]["seed"], g["custom"]["sizes"]))
+    c = ob.Circuit.custom(*cc.from_golden(g["custom"]))
     assert c.hash() == g["circuit_hash"]
     tr, st = c.prove_gkr()
     from conftest import GOLDEN
