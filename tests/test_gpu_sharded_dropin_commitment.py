@@ -342,10 +342,13 @@ def test_sharded_eq_point(vp, case, name, world, tensor):
     for c in rk.ctx:
         assert rk.L.vp_set_profiling(c, 1) == 0
     assert rk.commit_public_eq(d["point"]) == d["gold"][-TAIL:]
+    # the pointwise launches of a rank, in order, as (bytes, work): the inner product against the half tables over its used share of V_0, its range of the
+    # table (without the one-slice encoding only), the products and the quotient of its S slices: the rows the unsharded path records for these launches
+    N, S, size = 1 << (n - 6), 64 // world, d["inputs"].shape[0]
     for q in range(world):
-        pw = [(k, b) for k, b, _ in rk.launch_stats(q) if k == "k_pc_pointwise"]
-        assert pw and all(b <= (16 << n) // world for _, b in pw), pw   # the rank's share of V_0 (and of the table, without the one-slice encoding)
-        assert len(pw) == (1 if tensor else 2)
+        used = min(max(size - q * S * N, 0), S * N)
+        want = [(16 * used, used)] + ([] if tensor else [(16 * S * N, S * N)]) + [(96 * S * N, 2 * S * N), (48 * S * N, 2 * S * N)]
+        assert [(b, w) for k, b, w in rk.launch_stats(q) if k == "k_pc_pointwise"] == want, "rank %d" % q
     # the FRI phase goes on from it like from vp_commit_public
     r, roots_gold, _ = d["fri"]
     assert rk.step(r[0])[0] == roots_gold[0]

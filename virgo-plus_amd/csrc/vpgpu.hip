@@ -21,6 +21,7 @@
 #include "vp_kernels.h"
 #include "vp_fri_layout.h"
 #include "vp_pc_live.h"
+#include "vp_pc_corners.h"
 
 using namespace vp;
 

@@ -1,6 +1,11 @@
 // Part of vpgpu.hip (included at its end): host side of the Virgo polynomial commitment entry points.
 // =====================================================================================================
 // Virgo polynomial commitment — commit side
+//
+// The arithmetic between a public vector on the device and the encoded quotient h exists once, pc_quotient_slices, and runs over a PcSlices view: the
+// 64 slices of a context here, a rank's 64 / W in vpgpu_pc_shard.inc.  What differs between the two stays with the callers: the form of the inner product,
+// masks, hashing (at once or late), the pack and the collectives.  The virtual oracle and the first FRI fold read l, q, h, S_0 and the tensor pair through
+// the same view; the eq corners of vp_commit_public_eq come from vp_pc_corners.h on both sides.
 // =====================================================================================================
 namespace {
 
@@ -663,64 +668,103 @@ int pc_public_alloc(vp_ctx *ctx) {
     return VP_OK;
 }
 
-// vp_commit_public / vp_commit_public_eq once the public vector sits in ctx->pc_pub and ev0 is recorded.  corner[i] = pub[i N] (host copies);
-// tensor_state: 0 = check the tensor shape on the device, 1 = a tensor by construction (an eq table)
-int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int tensor_state, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32],
-                          const vp_F *pub_mask = nullptr, uint64_t n_pub_mask = 0) {
-    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
-    const u32 N = 1u << ln, M = 1u << lm;
-    const u32 live = pub_mask ? 64u : ctx->pc_lv.live;    // slices >= live are zero (vp_pc_live.h): l q, S, T, H, all_sum and h are zero with them
-    VPCHK(pc_hash_outstanding(ctx, 2u));                  // an h of an earlier call that no vp_fri_commit has hashed: its codeword is replaced below
-    if (!pub_mask) VPCHK(pc_live_zero_hcw(ctx));
-    const bool late = ctx->hash_late && !pub_mask;        // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels
-    F *P = ctx->pc_tmp, *ST = ctx->pc_tmp + (size_t) 128 * N, *H = ctx->pc_tmp + (size_t) 256 * N;
-    F *parts = ctx->pc_small, *d_inner = ctx->pc_small + 1024, *d_all = ctx->pc_small + 1025;
-    // input_0 = <circuitValue[0], pub>
-    const u32 used = (u32) ctx->L[0].size, g = std::min<u32>(1024, nblk(used));
-    PC_PROF(VP_K_PC_POINTWISE, g, 1, 32ull * used, used, hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val, ctx->pc_pub, used, parts));
-    hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, parts, g, d_inner);
-    // q_eval: the public vector encoded like the private one (poly_commit.h:163-176).  The protocol's public vector is the eq table of the
-    // opening point (src/verifier.cpp:368-369): a tensor, slice i = eq(r_hi, i) * eq(r_lo, .).  Whenever the vector handed in has that shape
-    // (checked exactly on the device: pub[iN + k] pub[0] == pub[iN] pub[k], pub[0] != 0) only slice 0 is encoded and q_i = qscal[i] q_0 is
-    // formed where it is consumed — the same field elements, 32 instead of 2048 forward transforms.  Any other vector: all 64 slices.
-    F *qscal = ctx->pc_small + 1184;
-    bool tensor = false;
-    if (ctx->opt.pc_tensor_pub && (corner[0].re | corner[0].im) != 0 && corner[0].re < P61 && corner[0].im < P61) {
-        if (tensor_state == 1) tensor = true;
+// The slices a context encodes, as the quotient pipeline and the first FRI fold see them: all 64 in the buffers of the context (pc_slices), or a rank's
+// 64 / W in the buffers of its PcShard (vpgpu_pc_shard.inc).  A view, not an owner.  Layout of `small`: [0, 1024) partial sums | [1024] inner product |
+// [1025, 1090) all_sum | [1105, 1169) S_0 per slice | [1184, 1248) the 64 scalars of a tensor public vector; of `tmp`: products | S, T | H, 2 cap N each.
+struct PcSlices {
+    u32 first = 0, cap = 64, rows = 64, N = 0;            // global index of the first slice; slices the buffers hold; slices transformed (live ones); slice length
+    F *lcw = nullptr, *pub = nullptr, *slice0 = nullptr;  // l codeword; the public vector's slices [first, first + cap); where its slice 0 sits (pub itself, or N in front of it)
+    F *coef = nullptr, *qcw = nullptr, *hcw = nullptr, *tmp = nullptr, *small = nullptr, *q0 = nullptr;
+    int *flag = nullptr;
+    bool tensor = false;                                  // the public vector in flight is encoded as slice 0 alone (q0) and the scalars
+    F *P() const { return tmp; }
+    F *ST() const { return tmp + (size_t) 2 * cap * N; }
+    F *H() const { return tmp + (size_t) 4 * cap * N; }
+    F *d_inner() const { return small + 1024; }
+    F *d_all() const { return small + 1025; }
+    F *S0() const { return small + 1025 + 80; }
+    F *qscal() const { return small + 1184; }
+    u32 rows_checked() const { return cap + (u32) ((pub - slice0) / N); }      // slices from slice0 to the end of pub: what the tensor check reads
+    const F *q0_arg() const { return tensor ? q0 : nullptr; }
+    const F *qs_arg() const { return tensor ? qscal() + first : nullptr; }
+};
+PcSlices pc_slices(vp_ctx *ctx, u32 rows) {
+    PcSlices v;
+    v.rows = rows; v.N = 1u << (ctx->L[0].bl - 6);
+    v.lcw = ctx->pc_cw; v.pub = v.slice0 = ctx->pc_pub; v.coef = ctx->pc_coef; v.qcw = ctx->pc_qcw; v.hcw = ctx->pc_hcw; v.tmp = ctx->pc_tmp;
+    v.small = ctx->pc_small; v.q0 = ctx->pc_q0; v.flag = ctx->pc_flag; v.tensor = ctx->pc_q_tensor;
+    return v;
+}
+
+// Can the one-slice encoding apply at all: the option, and a slice-0 corner that has an inverse
+bool pc_tensor_candidate(const vp_ctx *ctx, const F corner[64]) {
+    return ctx->opt.pc_tensor_pub && (corner[0].re | corner[0].im) != 0 && corner[0].re < P61 && corner[0].im < P61;
+}
+
+// The quotient pipeline over the slices of a view, once their part of the public vector (and slice 0) sits on the device: q encoded like l, h = the quotient
+// of l q by x^N - 1 per slice encoded in turn (poly_commit.h:163-176, 264-293), all_sum and S_0 beside them.  corner[i] = pub[i N] (host copies);
+// tensor_state: 0 = check the tensor shape on the device, 1 = a tensor by construction (an eq table).
+// The protocol's public vector is the eq table of the opening point (src/verifier.cpp:368-369): a tensor, slice i = eq(r_hi, i) * eq(r_lo, .).  Whenever
+// the slices in view have that shape against slice 0 (checked exactly on the device: pub[iN + k] pub[0] == pub[iN] pub[k], pub[0] != 0) only slice 0 is
+// encoded and q_i = qscal[i] q_0 is formed where it is consumed: the same field elements, 32 forward transforms instead of 32 rows.  Any other vector:
+// every slice.  Ranks of a sharded commitment need not agree: either way a rank's slices come out as the same field elements.
+int pc_quotient_slices(vp_ctx *ctx, PcSlices &v, const F corner[64], int tensor_state) {
+    const int ln = ctx->L[0].bl - 6, lm = ln + 5;
+    const u32 N = v.N, M = 32 * N, rows = v.rows;
+    v.tensor = false;
+    if (pc_tensor_candidate(ctx, corner)) {
+        if (tensor_state == 1) v.tensor = true;
         else {
-            HIPCHK(hipMemsetAsync(ctx->pc_flag, 0, sizeof(int), ctx->stream));
-            PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 64 * N), 1, 16ull * 64 * N, (u64) 2 * 64 * N,
-                    hipLaunchKernelGGL(k_pc_rank1_check, dim3(nblk((u64) 64 * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_pub, N, 64u, ctx->pc_flag));
+            const u32 chk = v.rows_checked();
+            HIPCHK(hipMemsetAsync(v.flag, 0, sizeof(int), ctx->stream));
+            PC_PROF(VP_K_PC_POINTWISE, nblk((u64) chk * N), 1, 16ull * chk * N, (u64) 2 * chk * N,
+                    hipLaunchKernelGGL(k_pc_rank1_check, dim3(nblk((u64) chk * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) v.slice0, N, chk, v.flag));
             int bad = 1;
-            HIPCHK(hipMemcpyAsync(&bad, ctx->pc_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(&bad, v.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            tensor = bad == 0;
+            v.tensor = bad == 0;
         }
     }
-    ctx->pc_q_tensor = tensor;
-    if (tensor) {
+    if (v.tensor) {
         F *sc = nullptr;                                                  // pinned until the stream has taken it: no wait here
         VPCHK(ring_alloc(ctx, 64 * sizeof(F), (void **) &sc));
         const F inv0 = host_pow(corner[0], (unsigned __int128) P61 * P61 - 2);
         for (int i = 0; i < 64; ++i) sc[i] = f_mul(corner[i], inv0);
-        HIPCHK(hipMemcpyAsync(qscal, sc, 64 * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_pub, ctx->pc_coef, ln, lm, 1, 1, 1, N));
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_q0, ln, lm, 0, 1, 32, N));
+        HIPCHK(hipMemcpyAsync(v.qscal(), sc, 64 * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+        VPCHK(pc_launch_ntt(ctx, v.slice0, v.coef, ln, lm, 1, 1, 1, N));
+        VPCHK(pc_launch_ntt(ctx, v.coef, v.q0, ln, lm, 0, 1, 32, N));
     } else {
         // (q of a dead slice is only ever multiplied by zero, and q is no oracle)
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_pub, ctx->pc_coef, ln, lm, 1, live, 1, N));
-        VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_qcw, ln, lm, 0, live, 32, N));
+        VPCHK(pc_launch_ntt(ctx, v.pub, v.coef, ln, lm, 1, rows, 1, N));
+        VPCHK(pc_launch_ntt(ctx, v.coef, v.qcw, ln, lm, 0, rows, 32, N));
     }
-    const F *q0 = tensor ? ctx->pc_q0 : nullptr, *qs = tensor ? qscal : nullptr;
-    // quotient h of l*q by x^N - 1, per slice (poly_commit.h:264-293)
-    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 2 * live * N), 1, 48ull * 2 * live * N, (u64) 2 * live * N,
-            hipLaunchKernelGGL(k_pc_products, dim3(nblk((u64) 2 * live * N)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw, N, P, live, q0, qs));
-    VPCHK(pc_launch_ntt(ctx, P, ST, ln, lm, 1, 2 * live, 1, N));
-    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(256), 0, ctx->stream, d_all, 144u);      // all_sum[65] and S_0 at [80..144): the dead slices' stay zero
-    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) live * N), 1, 48ull * live * N, (u64) 2 * live * N,
-            hipLaunchKernelGGL(k_pc_quotient, dim3(nblk((u64) live * N)), dim3(VP_BLOCK), 0, ctx->stream, ST, N, ctx->pc_rt, M >> 1,
-                               host_inv_real(2), f_make(N, 0), H, d_all, live));
-    VPCHK(pc_launch_ntt(ctx, H, ctx->pc_hcw, ln, lm, 0, live, 32, N));
+    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) 2 * rows * N), 1, 48ull * 2 * rows * N, (u64) 2 * rows * N,
+            hipLaunchKernelGGL(k_pc_products, dim3(nblk((u64) 2 * rows * N)), dim3(VP_BLOCK), 0, ctx->stream, v.lcw, v.qcw, N, v.P(), rows, v.q0_arg(), v.qs_arg()));
+    VPCHK(pc_launch_ntt(ctx, v.P(), v.ST(), ln, lm, 1, 2 * rows, 1, N));
+    hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(256), 0, ctx->stream, v.d_all(), 144u);      // all_sum[65] and S_0 at [80..144): the dead slices' stay zero
+    PC_PROF(VP_K_PC_POINTWISE, nblk((u64) rows * N), 1, 48ull * rows * N, (u64) 2 * rows * N,
+            hipLaunchKernelGGL(k_pc_quotient, dim3(nblk((u64) rows * N)), dim3(VP_BLOCK), 0, ctx->stream, v.ST(), N, ctx->pc_rt, M >> 1,
+                               host_inv_real(2), f_make(N, 0), v.H(), v.d_all(), rows));
+    return pc_launch_ntt(ctx, v.H(), v.hcw, ln, lm, 0, rows, 32, N);
+}
+
+// vp_commit_public / vp_commit_public_eq once the public vector sits in ctx->pc_pub and ev0 is recorded (corner, tensor_state: pc_quotient_slices)
+int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int tensor_state, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32],
+                          const vp_F *pub_mask = nullptr, uint64_t n_pub_mask = 0) {
+    const int n = ctx->L[0].bl, lm = n - 1;
+    const u32 N = 1u << (n - 6), M = 1u << lm;
+    VPCHK(pc_hash_outstanding(ctx, 2u));                  // an h of an earlier call that no vp_fri_commit has hashed: its codeword is replaced below
+    if (!pub_mask) VPCHK(pc_live_zero_hcw(ctx));
+    const bool late = ctx->hash_late && !pub_mask;        // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels
+    // slices >= live are zero (vp_pc_live.h): l q, S, T, H, all_sum and h are zero with them
+    PcSlices v = pc_slices(ctx, pub_mask ? 64u : ctx->pc_lv.live);
+    F *d_inner = v.d_inner(), *d_all = v.d_all();
+    // input_0 = <circuitValue[0], pub>
+    const u32 used = (u32) ctx->L[0].size, g = std::min<u32>(1024, nblk(used));
+    PC_PROF(VP_K_PC_POINTWISE, g, 1, 32ull * used, used, hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val, ctx->pc_pub, used, v.small));
+    hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, v.small, g, d_inner);
+    VPCHK(pc_quotient_slices(ctx, v, corner, tensor_state));
+    ctx->pc_q_tensor = v.tensor;
     // second oracle: leaf chains + tree over h (fri.cpp:36-139 with oracle_indicator = 1)
     const u32 n_leaves = M >> 1;
     if (pub_mask) {
@@ -962,7 +1006,6 @@ int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner
     for (int i = 0; i < n; ++i) if (point[i].real >= P61 || point[i].img >= P61) { ctx->err = "vp_commit_public_eq: non-canonical coordinate"; return VP_EINVAL; }
     // a sharded commitment: every rank is handed the point and builds what it needs of the table itself (pcs_commit_public)
     if (ctx->pcs) { VPCHK(flush_pending(ctx, (size_t) -1)); return pcs_commit_public(ctx, nullptr, 0, point, inner, all_sum, root_h); }
-    const u32 N = 1u << (n - 6);
     VPCHK(pc_public_alloc(ctx));
     // the public vector never crosses PCIe: eq(point, .) is built where it is consumed (two half tables by one workgroup, then one
     // product per entry — initBetaTable, src/utils.cpp:29-45)
@@ -980,19 +1023,10 @@ int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner
     PC_PROF(VP_K_PC_POINTWISE, grid_for(1ull << n), 1, 16ull << n, 1ull << n,
             hipLaunchKernelGGL(k_beta_expand, dim3(grid_for(1ull << n)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, n >> 1,
                                (u32) (1u << n), ctx->pc_pub));
-    // corner[i] = pub[i N] = eq(point, i N): the host forms these 64 values itself (the same field elements as the table's: eq is a product of
-    // n factors, r_k for a set bit k of the index and 1 - r_k otherwise, src/utils.cpp:8-45) instead of reading them back — no wait for the device
+    // corner[i] = pub[i N] = eq(point, i N): the host forms these 64 values itself (vp_pc_corners.h: the same field elements as the table's) instead of
+    // reading them back — no wait for the device
     F corner[64];
-    {
-        F low = f_one();
-        for (int k = 0; k < n - 6; ++k) low = f_mul(low, f_sub(f_one(), hr[k]));
-        for (int i = 0; i < 64; ++i) {
-            F v = low;
-            for (int k = 0; k < 6; ++k) v = f_mul(v, ((i >> k) & 1) ? hr[n - 6 + k] : f_sub(f_one(), hr[n - 6 + k]));
-            corner[i] = v;
-        }
-    }
-    (void) N;
+    pc_eq_corners(hr, n, corner);
     return pc_commit_public_body(ctx, ev_a, corner, 1, inner, all_sum, root_h);
 }
 
@@ -1013,9 +1047,9 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (ctx->fri_step < 0) {
         // virtual oracle in place over the q codeword; S_0 per slice sits behind all_sum in pc_small
-        hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) live * M)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_cw, ctx->pc_qcw,
-                           ctx->pc_hcw, ctx->pc_small + 1025 + 80, N, ctx->pc_rt, M >> 1, f_make(N, 0), live,
-                           (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr));
+        const PcSlices v = pc_slices(ctx, live);
+        hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) live * M)), dim3(VP_BLOCK), 0, ctx->stream, v.lcw, v.qcw, v.hcw, v.S0(), N, ctx->pc_rt, M >> 1,
+                           f_make(N, 0), live, v.q0_arg(), v.qs_arg());
         ctx->fri_step = 0;
         if (ctx->pc_mask_ms)      // the mask slice's virtual oracle, in place over its q codeword (poly_commit.h:225-245)
             hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
@@ -1098,6 +1132,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     VPCHK(pc_live_zero_fri(ctx));
     // folds of every level, back to back
     const FriLayout fl(ln, 0);
+    const PcSlices v = pc_slices(ctx, live);             // the first fold reads l, q, h, S_0 and the tensor pair through it
     FriLeafArgs la{}; MerkleArgs ma{};
     u32 blocks = 0;
     // vp_pc_hash_late: the oracles whose commit stopped behind its transforms go IN FRONT of the levels in the same lists — an l or h codeword is an entry
@@ -1134,15 +1169,14 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 // VP_VO_GRP slice groups per workgroup where that still leaves >= 2048 workgroups (N >= 2^14), one group per workgroup below
                 const bool grouped = (64 / VP_VO_SPT / VP_VO_GRP) * 32 * (E >> 6) >= 2048;
                 const u32 grid3 = vp_fold_groups(live, VP_VO_SPT * (grouped ? VP_VO_GRP : 1)) * 32 * (E >> 6);      // the workgroups whose slices include a live one
-                const void *fold3 = ctx->pc_q_tensor ? (grouped ? (const void *) k_fri_fold0_vo3<true, VP_VO_GRP> : (const void *) k_fri_fold0_vo3<true, 1>)
+                const void *fold3 = v.tensor ? (grouped ? (const void *) k_fri_fold0_vo3<true, VP_VO_GRP> : (const void *) k_fri_fold0_vo3<true, 1>)
                                                      : (grouped ? (const void *) k_fri_fold0_vo3<false, VP_VO_GRP> : (const void *) k_fri_fold0_vo3<false, 1>);
-                const F *a_lcw = ctx->pc_cw, *a_qcw = ctx->pc_qcw, *a_hcw = ctx->pc_hcw, *a_S0 = ctx->pc_small + 1025 + 80, *a_cb = ctx->pc_cbuf;
-                const F *a_q0 = ctx->pc_q_tensor ? ctx->pc_q0 : nullptr, *a_qs = ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr;
+                const F *a_lcw = v.lcw, *a_qcw = v.qcw, *a_hcw = v.hcw, *a_S0 = v.S0(), *a_cb = ctx->pc_cbuf, *a_q0 = v.q0_arg(), *a_qs = v.qs_arg();
                 u32 a_N = N;
                 F a_half = f_mul(f_make(N, 0), host_inv_real(2)), a_inv2 = host_inv_real(2);
                 void *args3[] = {&a_lcw, &a_qcw, &a_hcw, &a_S0, &o1, &o2, &o3, &a_N, &rtn, &a_cb, &rf, &r1, &r2, &a_half, &a_inv2, &a_q0, &a_qs, &live};
-                PC_PROF(VP_K_FRI_FOLD, grid3, 1, (ctx->pc_q_tensor ? 80ull : 112ull) * live * 32 * No + 16ull * live * 32 * ((No >> 1) + (No >> 2)),
-                        (u64) (ctx->pc_q_tensor ? 9 : 7) * live * 32 * No + 3ull * live * 32 * ((No >> 1) + (No >> 2)),
+                PC_PROF(VP_K_FRI_FOLD, grid3, 1, (v.tensor ? 80ull : 112ull) * live * 32 * No + 16ull * live * 32 * ((No >> 1) + (No >> 2)),
+                        (u64) (v.tensor ? 9 : 7) * live * 32 * No + 3ull * live * 32 * ((No >> 1) + (No >> 2)),
                         (void) hipLaunchKernel(fold3, dim3(grid3), dim3(256), args3, 0, ctx->stream));
             }
         }
@@ -1154,11 +1188,10 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             const F *rtn = nullptr;
             VPCHK(pc_circle_roots(ctx, lm, ln, &rtn));
             VPCHK(pc_fold0_consts(ctx, lm));
-            PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No), 1, (ctx->pc_q_tensor ? 80ull : 112ull) * live * 32 * No, (u64) (ctx->pc_q_tensor ? 9 : 7) * live * 32 * No,
-                    hipLaunchKernelGGL(k_fri_fold0_vo, dim3(nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_cw, (const F *) ctx->pc_qcw,
-                                       (const F *) ctx->pc_hcw, (const F *) (ctx->pc_small + 1025 + 80), out, N, rtn, (const F *) ctx->pc_cbuf, rf,
-                                       f_mul(f_make(N, 0), host_inv_real(2)),
-                                       (const F *) (ctx->pc_q_tensor ? ctx->pc_q0 : nullptr), (const F *) (ctx->pc_q_tensor ? ctx->pc_small + 1184 : nullptr), live));
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No), 1, (v.tensor ? 80ull : 112ull) * live * 32 * No, (u64) (v.tensor ? 9 : 7) * live * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold0_vo, dim3(nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) v.lcw, (const F *) v.qcw,
+                                       (const F *) v.hcw, (const F *) v.S0(), out, N, rtn, (const F *) ctx->pc_cbuf, rf,
+                                       f_mul(f_make(N, 0), host_inv_real(2)), v.q0_arg(), v.qs_arg(), live));
         }
         else
         PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No), 1, 48ull * live * 32 * No, (u64) 3 * live * 32 * No,

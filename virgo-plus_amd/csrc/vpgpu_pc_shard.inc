@@ -4,7 +4,10 @@
 //
 // The 64 data slices of the commitment are independent transforms (lib/virgo/src/poly_commit.h:89-107); a leaf of the
 // Merkle tree chains the values of ALL 64 slices at one position pair (lib/virgo/src/fri.cpp:81-124).  With W ranks:
-//   * rank r transforms slices [r*64/W, (r+1)*64/W): iNTT + rate-1/32 encoding, everything of vpgpu_pc.inc on 64/W rows;
+//   * rank r transforms slices [r*64/W, (r+1)*64/W): iNTT + rate-1/32 encoding, everything of vpgpu_pc.inc on 64/W rows — the same code: PcShard
+//     holds a PcSlices view of its own buffers (first = r*64/W, cap = rows = 64/W, the context's layout of `small` and `tmp`) and vp_commit_public(_eq)
+//     runs pc_quotient_slices over it; this file adds what a shard needs around that: its share of the inner product, slice 0 for the tensor
+//     check, the pack, the collectives and the trees;
 //   * ONE all-to-all per committed oracle (l, h, and the virtual oracle the FRI folds start from) turns slice ownership
 //     into POSITION ownership: rank r' receives, for every slice and coset, the positions a = a'*W + r'.  Ownership by the
 //     low bits of a (not a contiguous range) is what keeps every later step local: a leaf pairs (a, a + N/2), a FRI fold
@@ -25,14 +28,16 @@
 // scope stops their same-named globals, e.g. rocm_smi's tables, from being constructed and destroyed twice).  Without a communicator a sharded call stops at each collective and returns
 // VP_EXCHANGE; vp_shard_exchange_local performs the pending collectives among W contexts of ONE process (device-to-device copies)
 // — how the parity tests run W ranks on the single GPU of the test box.
+// Every sharded call is a state machine over stages: a stage ends in pcs_stage_end (collectives done, or pending with the clock paused), a call in pcs_finish.
 // =====================================================================================================
 #include <dlfcn.h>
 
 struct PcShard {
     int rank = 0, world = 1, lw = 0, S = 64;
     int op = 0, stage = 0;                                  // call in flight: 1 commit_private, 2 commit_public, 3 fri_commit
-    // own slices, unsharded layout [S][32][N]
-    F *coef = nullptr, *lcw = nullptr, *qcw = nullptr, *hcw = nullptr, *tmp = nullptr, *small = nullptr, *pub = nullptr;
+    // own slices, unsharded layout [S][32][N]: the buffers pc_quotient_slices and the virtual oracle work in (allocated by pcs_alloc, laid out like the
+    // context's own; v.slice0 holds slice 0 of the public vector for the tensor check and the one-slice encoding, v.pub sits N behind it)
+    PcSlices v;
     // every slice, own positions: [64][32][N/W]
     F *l_loc = nullptr, *h_loc = nullptr, *fri_loc = nullptr;                                   // fri_loc: level 0 input, then every locally folded level
     Dig *tree_l = nullptr, *tree_h = nullptr, *tree_f = nullptr;                                // local leaves + five levels (heap layout of the local leaf order)
@@ -49,9 +54,6 @@ struct PcShard {
     F *eq = nullptr; F pt[32];                              // vp_commit_public_eq: point | two eq half tables on the device; the point of the call in flight
     std::vector<F> fri_r;
     bool private_done = false, public_done = false;
-    // tensor public vector (round 4; vpgpu_pc.inc: pc_commit_public_body): slice 0 | this rank's slices on the device for the exact check, the ONE
-    // encoded slice, the scalars of all 64 slices
-    F *pub0 = nullptr, *q0cw = nullptr, *qscal = nullptr; int *flag = nullptr; bool q_tensor = false;
     struct X { int kind; const void *send; void *recv; size_t bytes; } x[2];               // kind 1: all-to-all (bytes per peer), 2: all-gather (bytes per rank)
     int nx = 0;
 };
@@ -151,6 +153,24 @@ int pcs_resume(vp_ctx *ctx) {
     else HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     return VP_OK;
 }
+int pcs_collectives(vp_ctx *ctx);
+// A stage ends: its collectives are performed (VP_OK: the next stage follows) or left pending with the clock paused (VP_EXCHANGE: the caller exchanges)
+int pcs_stage_end(vp_ctx *ctx) {
+    const int rc = pcs_collectives(ctx);
+    if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx));
+    return rc;
+}
+// A call ends: the clock stops, the results start their way to the host, the stream drains; device time = the parts before the collectives + this one
+struct PcsOut { void *dst; const void *src; size_t bytes; };
+int pcs_finish(vp_ctx *ctx, std::initializer_list<PcsOut> outs) {
+    HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+    for (const PcsOut &o : outs) HIPCHK(hipMemcpyAsync(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VPCHK(check_stream(ctx));
+    if (ctx->profiling) prof_collect(ctx);
+    float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = ctx->pcs->acc_ms + ms;
+    ctx->pcs->op = 0; ctx->pcs->stage = 0;
+    return VP_OK;
+}
 
 // five tree levels above the local leaves (local leaf order 32a' + b: the 32 cosets of a position are one subtree)
 int pcs_local_levels(vp_ctx *ctx, Dig *tree, u32 n_leaves) {
@@ -187,14 +207,16 @@ int pcs_collectives(vp_ctx *ctx) {
 
 int pcs_alloc(vp_ctx *ctx, int ln, int lm) {
     PcShard &s = *ctx->pcs;
-    if (s.coef) return VP_OK;
+    PcSlices &v = s.v;
+    if (v.coef) return VP_OK;
     const size_t N = (size_t) 1 << ln, Nl = N >> s.lw, S = s.S;
-    VPCHK(dalloc(ctx, &s.coef, S * N));
-    VPCHK(dalloc(ctx, &s.lcw, S * 32 * N)); VPCHK(dalloc(ctx, &s.qcw, S * 32 * N)); VPCHK(dalloc(ctx, &s.hcw, S * 32 * N));
-    VPCHK(dalloc(ctx, &s.tmp, 3 * 2 * S * N)); VPCHK(dalloc(ctx, &s.small, (size_t) 1024 + 160));
-    VPCHK(dalloc(ctx, &s.pub0, (S + 1) * N));                 // [slice 0][own slices]: s.pub points behind slice 0
-    s.pub = s.pub0 + N;
-    VPCHK(dalloc(ctx, &s.q0cw, 32 * N)); VPCHK(dalloc(ctx, &s.qscal, (size_t) 64)); VPCHK(dalloc(ctx, &s.flag, (size_t) 1));
+    v.first = (u32) (s.rank * s.S); v.cap = v.rows = (u32) S; v.N = (u32) N;
+    VPCHK(dalloc(ctx, &v.coef, S * N));
+    VPCHK(dalloc(ctx, &v.lcw, S * 32 * N)); VPCHK(dalloc(ctx, &v.qcw, S * 32 * N)); VPCHK(dalloc(ctx, &v.hcw, S * 32 * N));
+    VPCHK(dalloc(ctx, &v.tmp, 3 * 2 * S * N)); VPCHK(dalloc(ctx, &v.small, (size_t) 1024 + 160 + 64));       // (as pc_public_alloc)
+    VPCHK(dalloc(ctx, &v.slice0, (S + 1) * N));               // [slice 0][own slices]
+    v.pub = v.slice0 + N;
+    VPCHK(dalloc(ctx, &v.q0, 32 * N)); VPCHK(dalloc(ctx, &v.flag, (size_t) 1));
     VPCHK(dalloc(ctx, &s.eq, (size_t) 32 + 2 * ((size_t) 1 << ((ln + 6 + 1) / 2))));       // point | two eq half tables (as pc_public_alloc)
     VPCHK(dalloc(ctx, &s.send, S * 32 * N)); s.send_cap = S * 32 * N;
     VPCHK(dalloc(ctx, &s.l_loc, 64 * 32 * Nl)); VPCHK(dalloc(ctx, &s.h_loc, 64 * 32 * Nl)); VPCHK(dalloc(ctx, &s.fri_loc, 2 * 64 * 32 * Nl));
@@ -244,27 +266,21 @@ int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]) {
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
             const F *in = ctx->L[0].val + (size_t) s.rank * s.S * N;
-            VPCHK(pc_launch_ntt(ctx, in, s.coef, ln, lm, 1, s.S, 1, N));
-            VPCHK(pc_launch_ntt(ctx, s.coef, s.lcw, ln, lm, 0, s.S, 32, N));
-            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) s.S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.send, N, s.lw, (u32) s.S * 32);
+            VPCHK(pc_launch_ntt(ctx, in, s.v.coef, ln, lm, 1, s.S, 1, N));
+            VPCHK(pc_launch_ntt(ctx, s.v.coef, s.v.lcw, ln, lm, 0, s.S, 32, N));
+            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) s.S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.v.lcw, s.send, N, s.lw, (u32) s.S * 32);
             s.x[0] = {1, s.send, s.l_loc, (size_t) s.S * 32 * Nl * sizeof(F)}; s.nx = 1;
             s.stage = 1;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else if (s.stage == 1) {
             VPCHK(pcs_hash_local(ctx, s.l_loc, Nl, s.tree_l, 0));
             s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) (Nl >> 1) * 32}; s.nx = 1;
             s.stage = 2;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else {
             VPCHK(pcs_top(ctx, s.ag_recv, (size_t) (Nl >> 1) * 32, 0, Nl, s.top_l));
-            HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-            HIPCHK(hipMemcpyAsync(root, s.top_l + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
-            VPCHK(check_stream(ctx));
-            if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
-            s.op = 0; s.stage = 0; s.private_done = true;
+            VPCHK(pcs_finish(ctx, {{root, s.top_l + 1, 32}}));
+            s.private_done = true;
             return VP_OK;
         }
     }
@@ -276,8 +292,8 @@ int pcs_commit_private(vp_ctx *ctx, uint8_t root[32]) {
 // <V_0, eq(point, .)>, which k_pc_dot_eq takes from the half tables entry by entry.  The outputs are the field elements vp_commit_public gives for the table.
 int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
     PcShard &s = *ctx->pcs;
-    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
-    const u32 N = 1u << ln, M = 1u << lm, Nl = N >> s.lw, S = (u32) s.S;
+    const int n = ctx->L[0].bl;
+    const u32 N = 1u << (n - 6), Nl = N >> s.lw, S = (u32) s.S;
     if (!s.private_done || (pub && n_pub != (1ull << n))) return VP_EINVAL;
     VPCHK(pcs_guard(ctx));
     if (s.op != 2) { s.op = 2; s.stage = 0; }
@@ -288,7 +304,9 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *
             s.f_done = 0; s.f_mode = 0; s.n_steps = 0;                   // the FRI phase of an earlier public vector is gone
             const int h1 = n >> 1;
             F *dr = s.eq, *dbf = s.eq + 32, *dbs = dbf + ((size_t) 1 << ((n + 1) / 2));
-            if (pub) HIPCHK(hipMemcpyAsync(s.pub, reinterpret_cast<const F *>(pub) + (size_t) s.rank * S * N, (size_t) S * N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+            PcSlices &v = s.v;
+            const F *hp = reinterpret_cast<const F *>(pub);
+            if (pub) HIPCHK(hipMemcpyAsync(v.pub, hp + (size_t) v.first * N, (size_t) S * N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
             else {
                 for (int i = 0; i < n; ++i) s.pt[i] = f_make(point[i].real, point[i].img);
                 s.pt[n] = f_one();
@@ -296,102 +314,51 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *
             }
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-            F *P = s.tmp, *ST = s.tmp + (size_t) 2 * S * N, *H = s.tmp + (size_t) 4 * S * N;
-            F *parts = s.small, *d_inner = s.small + 1024, *d_all = s.small + 1025;
             // partial inner product over this rank's slices (slice i = input wires [i N, (i+1) N))
-            const u64 lo = (u64) s.rank * S * N, used = ctx->L[0].size > lo ? std::min<u64>(ctx->L[0].size - lo, (u64) S * N) : 0;
+            const u64 lo = (u64) v.first * N, used = ctx->L[0].size > lo ? std::min<u64>(ctx->L[0].size - lo, (u64) S * N) : 0;
             const u32 g = std::max<u32>(1, std::min<u32>(1024, nblk(used)));
-            if (pub) hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, s.pub, (u32) used, parts);
+            if (pub) PC_PROF(VP_K_PC_POINTWISE, g, 1, 32ull * used, used, hipLaunchKernelGGL(k_pc_dot, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, v.pub, (u32) used, v.small));
             else {
                 hipLaunchKernelGGL(k_beta_half, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dr, n, (const F *) (dr + n), dbf, dbs);
                 PC_PROF(VP_K_PC_POINTWISE, g, 1, 16ull * used, used,
-                        hipLaunchKernelGGL(k_pc_dot_eq, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, (const F *) dbf, (const F *) dbs, h1, lo, (u32) used, parts));
+                        hipLaunchKernelGGL(k_pc_dot_eq, dim3(g), dim3(VP_BLOCK), 0, ctx->stream, ctx->L[0].val + lo, (const F *) dbf, (const F *) dbs, h1, lo, (u32) used, v.small));
             }
-            hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, parts, g, d_inner);
-            // The protocol's public vector is a tensor (eq table of the opening point, src/verifier.cpp:368-369): slice i = c_i x slice 0.  Checked
-            // exactly on the device for THIS rank's slices against slice 0 (pub[i N + k] pub[0] == pub[i N] pub[k]); when it holds, only slice 0 is
-            // encoded (on every rank: 32 transforms instead of 32 S) and q_i = c_i q_0 is formed where it is consumed.  The ranks need not agree:
-            // either way a rank's slices come out as the same field elements.
-            const F *hp = reinterpret_cast<const F *>(pub);
-            F corner[64];                                                // corner[i] = pub[i N]; of an eq table: the host's own product (vp_commit_public_eq)
+            hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, v.small, g, v.d_inner());
+            // What pc_quotient_slices needs on the device besides the rank's slices: slice 0, if the one-slice encoding can apply (checked there for THIS
+            // rank's slices against it).  Of an eq table, a tensor by construction: slice 0 expanded from the half tables and nothing else, or, with
+            // the encoding switched off, every slice of this rank as a vector handed in would be.
+            F corner[64];                                                // corner[i] = pub[i N]; of an eq table: the host's own product
             if (pub) for (int i = 0; i < 64; ++i) corner[i] = hp[(size_t) i * N];
-            else {
-                F low = f_one();
-                for (int k = 0; k < ln; ++k) low = f_mul(low, f_sub(f_one(), s.pt[k]));
-                for (int i = 0; i < 64; ++i) {
-                    F v = low;
-                    for (int k = 0; k < 6; ++k) v = f_mul(v, ((i >> k) & 1) ? s.pt[ln + k] : f_sub(f_one(), s.pt[ln + k]));
-                    corner[i] = v;
-                }
-            }
-            s.q_tensor = false;
-            if (ctx->opt.pc_tensor_pub && (corner[0].re | corner[0].im) != 0 && corner[0].re < P61 && corner[0].im < P61) {
-                if (pub) {
-                    HIPCHK(hipMemcpyAsync(s.pub0, hp, (size_t) N * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
-                    HIPCHK(hipMemsetAsync(s.flag, 0, sizeof(int), ctx->stream));
-                    hipLaunchKernelGGL(k_pc_rank1_check, dim3(nblk((u64) (S + 1) * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) s.pub0, N, S + 1, s.flag);
-                    int bad = 1;
-                    HIPCHK(hipMemcpyAsync(&bad, s.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-                    HIPCHK(hipStreamSynchronize(ctx->stream));
-                    s.q_tensor = bad == 0;
-                } else {
-                    hipLaunchKernelGGL(k_beta_expand, dim3(grid_for(N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, N, s.pub0);
-                    s.q_tensor = true;
-                }
-            }
-            if (!pub && !s.q_tensor)                                     // every slice of this rank, as a vector handed in would be
-                PC_PROF(VP_K_PC_POINTWISE, grid_for((u64) S * N), 1, 16ull * S * N, (u64) S * N,
-                        hipLaunchKernelGGL(k_pc_eq_range, dim3(grid_for((u64) S * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, lo, S * N, s.pub));
-            if (s.q_tensor) {
-                F sc[64];
-                const F inv0 = host_pow(corner[0], (unsigned __int128) P61 * P61 - 2);
-                for (int i = 0; i < 64; ++i) sc[i] = f_mul(corner[i], inv0);
-                HIPCHK(hipMemcpyAsync(s.qscal, sc, sizeof sc, hipMemcpyHostToDevice, ctx->stream));
-                HIPCHK(hipStreamSynchronize(ctx->stream));                        // sc lives on this frame
-                VPCHK(pc_launch_ntt(ctx, s.pub0, s.coef, ln, lm, 1, 1, 1, N));
-                VPCHK(pc_launch_ntt(ctx, s.coef, s.q0cw, ln, lm, 0, 1, 32, N));
-            } else {
-                VPCHK(pc_launch_ntt(ctx, s.pub, s.coef, ln, lm, 1, S, 1, N));
-                VPCHK(pc_launch_ntt(ctx, s.coef, s.qcw, ln, lm, 0, S, 32, N));
-            }
-            hipLaunchKernelGGL(k_pc_products, dim3(nblk((u64) 2 * S * N)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, N, P, S,
-                               (const F *) (s.q_tensor ? s.q0cw : nullptr), (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
-            VPCHK(pc_launch_ntt(ctx, P, ST, ln, lm, 1, 2 * S, 1, N));
-            hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(256), 0, ctx->stream, d_all, 160u);
-            hipLaunchKernelGGL(k_pc_quotient, dim3(nblk((u64) S * N)), dim3(VP_BLOCK), 0, ctx->stream, ST, N, ctx->pc_rt, M >> 1,
-                               host_inv_real(2), f_make(N, 0), H, d_all, S);
-            VPCHK(pc_launch_ntt(ctx, H, s.hcw, ln, lm, 0, S, 32, N));
-            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.hcw, s.send, N, s.lw, S * 32);
+            else pc_eq_corners(s.pt, n, corner);
+            const bool cand = pc_tensor_candidate(ctx, corner);
+            if (pub) { if (cand) HIPCHK(hipMemcpyAsync(v.slice0, hp, (size_t) N * sizeof(F), hipMemcpyHostToDevice, ctx->stream)); }
+            else if (cand) hipLaunchKernelGGL(k_beta_expand, dim3(grid_for(N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, N, v.slice0);
+            else PC_PROF(VP_K_PC_POINTWISE, grid_for((u64) S * N), 1, 16ull * S * N, (u64) S * N,
+                         hipLaunchKernelGGL(k_pc_eq_range, dim3(grid_for((u64) S * N)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) dbf, (const F *) dbs, h1, lo, S * N, v.pub));
+            VPCHK(pc_quotient_slices(ctx, v, corner, pub ? 0 : 1));
+            hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, v.hcw, s.send, N, s.lw, S * 32);
             s.x[0] = {1, s.send, s.h_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
             s.stage = 1;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else if (s.stage == 1) {
             VPCHK(pcs_hash_local(ctx, s.h_loc, Nl, s.tree_h, 0));
             // this rank's all_sum entries and its share of the inner product ride on the same all-gather
-            HIPCHK(hipMemcpyAsync(s.ag_send + sums_at, s.small + 1025, (size_t) S * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
-            HIPCHK(hipMemcpyAsync(s.ag_send + sums_at + (size_t) S * sizeof(F), s.small + 1024, sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(s.ag_send + sums_at, s.v.d_all(), (size_t) S * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
+            HIPCHK(hipMemcpyAsync(s.ag_send + sums_at + (size_t) S * sizeof(F), s.v.d_inner(), sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
             s.x[0] = {2, s.ag_send, s.ag_recv, sums_at + (size_t) (S + 1) * sizeof(F)}; s.nx = 1;
             s.stage = 2;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else {
             const size_t stride = sums_at + (size_t) (S + 1) * sizeof(F);
             VPCHK(pcs_top(ctx, s.ag_recv, stride, 0, Nl, s.top_h));
-            F *g_all = s.tmp, *g_inner = s.tmp + 80;                       // tmp is free again
+            F *g_all = s.v.tmp, *g_inner = s.v.tmp + 80;                   // tmp is free again
             hipLaunchKernelGGL(k_zero_f, dim3(1), dim3(128), 0, ctx->stream, g_all, 66u);
             for (int r = 0; r < s.world; ++r)
                 HIPCHK(hipMemcpyAsync(g_all + (size_t) r * S, s.ag_recv + (size_t) r * stride + sums_at, (size_t) S * sizeof(F), hipMemcpyDeviceToDevice, ctx->stream));
             hipLaunchKernelGGL(k_pc_sum_gathered, dim3(1), dim3(64), 0, ctx->stream, reinterpret_cast<const F *>(s.ag_recv + sums_at + (size_t) S * sizeof(F)),
                                (u32) (stride / sizeof(F)), (u32) s.world, g_inner);
-            HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-            HIPCHK(hipMemcpyAsync(root_h, s.top_h + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipMemcpyAsync(inner, g_inner, sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-            HIPCHK(hipMemcpyAsync(all_sum, g_all, 65 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-            VPCHK(check_stream(ctx));
-            if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
-            s.op = 0; s.stage = 0; s.public_done = true;
+            VPCHK(pcs_finish(ctx, {{root_h, s.top_h + 1, 32}, {inner, g_inner, sizeof(F)}, {all_sum, g_all, 65 * sizeof(F)}}));
+            s.public_done = true;
             return VP_OK;
         }
     }
@@ -401,10 +368,10 @@ int pcs_commit_public(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const vp_F *
 void pcs_fri_stage0(vp_ctx *ctx) {
     PcShard &s = *ctx->pcs;
     const u32 N = (u32) s.fl.N, M = 32 * N, Nl = (u32) s.fl.Nl, S = (u32) s.S;
-    hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, s.lcw, s.qcw, s.hcw, s.small + 1025 + 80, N,
-                       ctx->pc_rt, M >> 1, f_make(N, 0), S, (const F *) (s.q_tensor ? s.q0cw : nullptr),
-                       (const F *) (s.q_tensor ? s.qscal + (size_t) s.rank * S : nullptr));
-    hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, s.qcw, s.send, N, s.lw, S * 32);
+    const PcSlices &v = s.v;
+    hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) S * M)), dim3(VP_BLOCK), 0, ctx->stream, v.lcw, v.qcw, v.hcw, v.S0(), N,
+                       ctx->pc_rt, M >> 1, f_make(N, 0), S, v.q0_arg(), v.qs_arg());
+    hipLaunchKernelGGL(k_pc_pack, dim3(nblk((u64) S * 32 * N)), dim3(VP_BLOCK), 0, ctx->stream, v.qcw, s.send, N, s.lw, S * 32);
     s.x[0] = {1, s.send, s.fri_loc, (size_t) S * 32 * Nl * sizeof(F)}; s.nx = 1;
     s.stage = 1;
 }
@@ -448,8 +415,7 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             ctx->ev_used = 0;
             HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
             pcs_fri_stage0(ctx);
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else if (s.stage == 1) {
             // local folds; level k's output has Nl >> (k+1) positions per coset here
             FriLeafArgs la{};
@@ -481,8 +447,7 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
             s.x[0] = {2, s.ag_send, s.ag_recv, at}; s.nx = 1;
             s.n_steps = n_steps;
             s.stage = 2;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(pcs_pause(ctx)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else {
             // top trees of the locally hashed levels
             size_t at = 0, stride = 0;
@@ -510,12 +475,8 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
                 if (k + 1 == n_steps) break;
                 VPCHK(pcs_tail_step(ctx, k + 1, s.fri_r[k + 1], &tree));
             }
-            HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-            HIPCHK(hipMemcpyAsync(roots, s.d_roots, (size_t) 32 * n_steps, hipMemcpyDeviceToHost, ctx->stream));
-            VPCHK(check_stream(ctx));
-            if (ctx->profiling) prof_collect(ctx);
-            float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); ctx->commit_ms = s.acc_ms + ms;
-            s.op = 0; s.stage = 0; s.f_done = n_steps; s.f_mode = 1;
+            VPCHK(pcs_finish(ctx, {{roots, s.d_roots, (size_t) 32 * n_steps}}));
+            s.f_done = n_steps; s.f_mode = 1;
             return VP_OK;
         }
     }
@@ -547,21 +508,12 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         s.op = 4; s.stage = k == 0 ? 0 : k < n_local ? 1 : 3;
     }
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    // a part of the step ends: at a collective the caller has to perform, or with the level's root
-    auto part_end = [&](const Dig *d_root) -> int {
-        HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
-        if (d_root) HIPCHK(hipMemcpyAsync(root, d_root, 32, hipMemcpyDeviceToHost, ctx->stream));
-        VPCHK(check_stream(ctx));
-        float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1); s.acc_ms += ms;
-        return VP_OK;
-    };
     const u32 No = k < n_local ? (u32) fl.loc_per_coset(k) : 0;           // local step: positions per coset on this rank after the fold
     Dig *tree = nullptr;                                                   // the level's tree (heap layout: the root is node 1)
     for (;;) {
         if (s.stage == 0) {
             pcs_fri_stage0(ctx);
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else if (s.stage == 1) {
             F *out = pcs_local_fold(ctx, k, s.step_r);
             if (!fl.is_tail(k)) {                                         // leaves pair (a', a' + No/2): local; the level-5 nodes go to every rank
@@ -572,8 +524,7 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
                 s.x[0] = {2, s.ag_send, s.ag_recv, (size_t) 2048 * sizeof(F)}; s.nx = 1;
             }
             s.stage = 2;
-            const int rc = pcs_collectives(ctx);
-            if (rc != VP_OK) { if (rc == VP_EXCHANGE) VPCHK(part_end(nullptr)); return rc; }
+            VPCHK(pcs_stage_end(ctx));
         } else if (s.stage == 2) {
             if (!fl.is_tail(k)) {
                 tree = s.top_f + fl.top(k);
@@ -591,10 +542,8 @@ int pcs_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         }
     }
     HIPCHK(hipMemcpyAsync(s.d_roots + k, tree + 1, 32, hipMemcpyDeviceToDevice, ctx->stream));
-    VPCHK(part_end(tree + 1));
-    if (ctx->profiling) prof_collect(ctx);
-    ctx->commit_ms = s.acc_ms;
-    s.op = 0; s.stage = 0; s.f_done = k + 1;
+    VPCHK(pcs_finish(ctx, {{root, tree + 1, 32}}));
+    s.f_done = k + 1;
     return VP_OK;
 }
 
