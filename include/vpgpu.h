@@ -465,7 +465,10 @@ int vp_allreduce_u64(vp_ctx *, void *device_buffer, uint64_t count);
  * assert_random), r_u (bit_length(layer-1) entries), r_v (n_v = maxDadBitLength(layer) entries, 0 when the layer has no
  * phase 2).  out[0..5) = coeff_l[Copy], coeff_l[Not], coeff_l[Addc], coeff_l[Mulc], bias — WITHOUT the factor beta_v[0]
  * that predicatePhase2 applies (verifier.cpp:95-96); out[5 + t*layer + l] = coeff_r[type t][l], t in the order Add, Sub,
- * AntiSub, Mul, Naab, AntiNaab, Xor, l < layer.  n_out must be 5 + 7*layer.                                            */
+ * AntiSub, Mul, Naab, AntiNaab, Xor, l < layer.  n_out must be 5 + 7*layer.  A bucket without gates is exactly zero.
+ * n_v must be max(0, maxDadBitLength(layer)) — the bit length the layer's subset slots are numbered in; any other value is VP_EINVAL before
+ * anything is launched (a shorter beta_v table would be indexed past its end).  Every challenge must be canonical (both limbs < 2^61 - 1),
+ * as for vp_round: VP_EINVAL otherwise, here and in vp_liu_gr / vp_layer_mle, and the context is left as it was.                        */
 int vp_predicates(vp_ctx *, int layer, const vp_F *r_g, const vp_F *assert_random, const vp_F *r_u, const vp_F *r_v, int n_v,
                   vp_F *out, uint64_t n_out);
 
@@ -473,7 +476,8 @@ int vp_predicates(vp_ctx *, int layer, const vp_F *r_g, const vp_F *assert_rando
  * sum_u mult_Liu[u] * eq(r_liu, u), with mult_Liu the table prover::sumcheckInitLiu builds from (r_u, r_v[], s) — same
  * arguments as vp_liu_init — and r_liu the bit_length(layer-1) challenges of that Liu sumcheck.  vp_layer_mle: the
  * multilinear extension of a layer's values at r (layer 0: the input check of verifier.cpp:363-389 when the polynomial
- * commitment is off).  Both leave no sumcheck in progress.                                                          */
+ * commitment is off).  Both leave no sumcheck in progress.  vp_liu_gr checks all its arguments (layer, r_u, r_liu, s, the r_v[k] of
+ * every later layer with a non-empty subset, canonical limbs) BEFORE it builds the table: a refused call changes nothing on the context. */
 int vp_liu_gr(vp_ctx *, int layer, const vp_F *r_u, const vp_F *const *r_v, const vp_F *s, const vp_F *r_liu, vp_F *out);
 int vp_layer_mle(vp_ctx *, int layer, const vp_F *r, int n, vp_F *out);
 
@@ -506,7 +510,8 @@ int vp_get_resident_resumes(const vp_ctx *, uint64_t *n);
 /* 0: no per-kernel events (default); 1: the next vp_prove_gkr replays its launch plan on ONE stream and brackets EVERY
  * launch with hipEvents (in the default run the launches of independent sumchecks overlap on several streams, so
  * per-kernel times would be meaningless there); vp_commit_private / vp_commit_public / vp_fri_commit bracket their
- * launches as well.  The table of the last profiled call is read with vp_get_launch_stats.                          */
+ * launches as well, and so do vp_layer_mle / vp_liu_gr (k_beta_half_direct, k_dot_multi, k_dotfin_multi: three entries) and vp_predicates
+ * (its half-table launch; the bucket kernels have no VP_K_* kind).  The table of the last profiled call is read with vp_get_launch_stats. */
 int vp_set_profiling(vp_ctx *, int level);
 
 /* One kernel launch of the last profiled call: which kernel, how much it covered, its ALGORITHMIC bytes (SURVEY.md §8d:

@@ -668,22 +668,86 @@ struct Sha3Stream {
     }
 };
 
-struct Verifier {
-    Prover *p;
+// The verifier's O(|C|) loops on explicit points (verifier.cpp:50-113 the wiring predicates, :311-323 the Liu `gr`, :363-389 the input check with the
+// commitment off).  Verifier below runs them on its own challenges; orc_predicates / orc_liu_gr / orc_layer_mle export the same loops by value.
+struct VerifierSums {
     const Circuit &C;
-    vector<F> beta_g, beta_u, beta_v, r_u, r_liu, sig;
-    vector<vector<F>> r_v;
+    vector<F> beta_g, beta_u, beta_v;
     F coeff_l[12];
     vector<F> coeff_r[12];
-    F bias, final_claim_u;
+    F bias;
+
+    explicit VerifierSums(const Circuit &c) : C(c) { for (auto &v : coeff_r) v.resize(C.size); }
+
+    void predicatePhase1(int layer_id, const F *r_g, const F &assert_random, const F *r_u) {      // verifier.cpp:50-90
+        const Layer &cur = C.circuit[layer_id];
+        init_beta_table(beta_g, cur.bitLength, r_g, F_ONE);
+        for (u64 g = 0; g < cur.size; ++g) if (cur.gates[g].is_assert) beta_g[g] *= assert_random;     // verifier.cpp:53-54
+        init_beta_table(beta_u, C.circuit[layer_id - 1].bitLength, r_u, F_ONE);
+        coeff_l[Copy] = coeff_l[Not] = coeff_l[Addc] = coeff_l[Mulc] = F_ZERO;
+        bias = F_ZERO;
+        for (u64 g = 0; g < cur.size; ++g) {
+            const Gate &gt = cur.gates[g];
+            switch (gt.ty) {
+                case Addc: bias += beta_g[g] * beta_u[gt.u] * gt.c;   // falls through
+                case Not: case Copy: coeff_l[gt.ty] += beta_g[g] * beta_u[gt.u]; break;
+                case Mulc: coeff_l[gt.ty] += beta_g[g] * beta_u[gt.u] * gt.c; break;
+                default: break;
+            }
+        }
+        for (int t : {Add, Sub, AntiSub, Mul, Naab, AntiNaab, Xor}) std::fill(coeff_r[t].begin(), coeff_r[t].end(), F_ZERO);
+    }
+    void predicatePhase2(int layer_id, const F *r_v) {                // verifier.cpp:58-61,92-113
+        const Layer &cur = C.circuit[layer_id];
+        init_beta_table(beta_v, cur.maxDadBitLength, r_v, F_ONE);
+        coeff_l[Copy] *= beta_v[0]; coeff_l[Not] *= beta_v[0]; coeff_l[Addc] *= beta_v[0]; coeff_l[Mulc] *= beta_v[0];
+        bias *= beta_v[0];
+        for (u64 g = 0; g < cur.size; ++g) {
+            const Gate &gt = cur.gates[g];
+            switch (gt.ty) {
+                case Add: case Sub: case AntiSub: case Mul: case Naab: case AntiNaab: case Xor:
+                    coeff_r[gt.ty][gt.l] += beta_g[g] * beta_u[gt.u] * beta_v[gt.lv];
+                default: break;
+            }
+        }
+    }
+    // r_v[j], j = layer_id .. C.size - 1: the phase-2 challenges of layer j (its first dadBitLength[j][layer_id - 1] entries are used); sig[0] goes with r_u,
+    // sig[j - layer_id + 1] with layer j
+    F liuGr(int layer_id, const F *r_u, const F *const *r_v, const F *sig, const F *r_liu) {           // verifier.cpp:311-323
+        const int pre_layer_id = layer_id - 1;
+        const Layer &pre = C.circuit[pre_layer_id];
+        F gr = F_ZERO;
+        init_beta_table(beta_u, pre.bitLength, r_liu, F_ONE);
+        init_beta_table(beta_g, pre.bitLength, r_u, sig[0]);
+        for (u64 g = 0; g < pre.size; ++g) gr = gr + beta_g[g] * beta_u[g];
+        for (int j = layer_id; j < C.size; ++j) {
+            init_beta_table(beta_g, C.circuit[j].dadBitLength[pre_layer_id], r_v[j], sig[j - pre_layer_id]);
+            for (u64 g = 0; g < C.circuit[j].dadSize[pre_layer_id]; ++g)
+                gr = gr + beta_g[g] * beta_u[C.circuit[j].dadId[pre_layer_id][g]];
+        }
+        return gr;
+    }
+    static F layerMle(const vector<F> &values, u64 size, int n, const F *r) {
+        vector<F> beta;
+        init_beta_table(beta, n, r, F_ONE);
+        F acc = F_ZERO;
+        for (u64 g = 0; g < size; ++g) acc = acc + beta[g] * values[g];
+        return acc;
+    }
+};
+
+struct Verifier : VerifierSums {
+    Prover *p;
+    vector<F> r_u, r_liu, sig;
+    vector<vector<F>> r_v;
+    F final_claim_u;
     vector<vector<F>> final_claims_v;
     vector<unsigned char> *out;
     Timer vt;
 
-    Verifier(Prover *pr, const Circuit &c, vector<unsigned char> *o) : p(pr), C(c), out(o) {   // verifier.cpp:12-48
+    Verifier(Prover *pr, const Circuit &c, vector<unsigned char> *o) : VerifierSums(c), p(pr), out(o) {   // verifier.cpp:12-48
         final_claims_v.resize(C.size);
         for (int i = 1; i < C.size; ++i) final_claims_v[i].resize(i);
-        for (auto &v : coeff_r) v.resize(C.size);
         r_v.resize(C.size + 2);
         p->init();
         int max_bl = 0, max_dad_bl = 0;
@@ -748,38 +812,8 @@ struct Verifier {
     void putQ(const Quad &q) { putF(q.a); putF(q.b); putF(q.c); }
 
     F assert_random;
-    void predicatePhase1(int layer_id) {                             // verifier.cpp:50-90
-        const Layer &cur = C.circuit[layer_id];
-        init_beta_table(beta_g, cur.bitLength, r_liu.data(), F_ONE);
-        for (u64 g = 0; g < cur.size; ++g) if (cur.gates[g].is_assert) beta_g[g] *= assert_random;     // verifier.cpp:53-54
-        init_beta_table(beta_u, C.circuit[layer_id - 1].bitLength, r_u.data(), F_ONE);
-        coeff_l[Copy] = coeff_l[Not] = coeff_l[Addc] = coeff_l[Mulc] = F_ZERO;
-        bias = F_ZERO;
-        for (u64 g = 0; g < cur.size; ++g) {
-            const Gate &gt = cur.gates[g];
-            switch (gt.ty) {
-                case Addc: bias += beta_g[g] * beta_u[gt.u] * gt.c;   // falls through
-                case Not: case Copy: coeff_l[gt.ty] += beta_g[g] * beta_u[gt.u]; break;
-                case Mulc: coeff_l[gt.ty] += beta_g[g] * beta_u[gt.u] * gt.c; break;
-                default: break;
-            }
-        }
-        for (int t : {Add, Sub, AntiSub, Mul, Naab, AntiNaab, Xor}) std::fill(coeff_r[t].begin(), coeff_r[t].end(), F_ZERO);
-    }
-    void predicatePhase2(int layer_id) {                             // verifier.cpp:58-61,92-113
-        const Layer &cur = C.circuit[layer_id];
-        init_beta_table(beta_v, cur.maxDadBitLength, r_v[layer_id].data(), F_ONE);
-        coeff_l[Copy] *= beta_v[0]; coeff_l[Not] *= beta_v[0]; coeff_l[Addc] *= beta_v[0]; coeff_l[Mulc] *= beta_v[0];
-        bias *= beta_v[0];
-        for (u64 g = 0; g < cur.size; ++g) {
-            const Gate &gt = cur.gates[g];
-            switch (gt.ty) {
-                case Add: case Sub: case AntiSub: case Mul: case Naab: case AntiNaab: case Xor:
-                    coeff_r[gt.ty][gt.l] += beta_g[g] * beta_u[gt.u] * beta_v[gt.lv];
-                default: break;
-            }
-        }
-    }
+    void predicatePhase1(int layer_id) { VerifierSums::predicatePhase1(layer_id, r_liu.data(), assert_random, r_u.data()); }
+    void predicatePhase2(int layer_id) { VerifierSums::predicatePhase2(layer_id, r_v[layer_id].data()); }
     F getFinalValue(int layer_id, const F &cu, const F *cv) {        // verifier.cpp:115-132
         F res = coeff_l[Not] * (F_ONE - cu) + coeff_l[Copy] * cu + coeff_l[Addc] * cu + bias + coeff_l[Mulc] * cu;
         for (int j = 0; j < layer_id; ++j) {
@@ -864,18 +898,13 @@ struct Verifier {
             previousSum = poly.eval(previousRandom);
             vt.stop();
         }
-        F gr = F_ZERO, vr;
+        F vr;
         p->sumcheckLiuFinalize(previousRandom, vr);
         putF(vr);
         vt.start();
-        init_beta_table(beta_u, pre.bitLength, r_liu.data(), F_ONE);
-        init_beta_table(beta_g, pre.bitLength, r_u.data(), sig[0]);
-        for (u64 g = 0; g < pre.size; ++g) gr = gr + beta_g[g] * beta_u[g];
-        for (int j = layer_id; j < C.size; ++j) {
-            init_beta_table(beta_g, C.circuit[j].dadBitLength[pre_layer_id], r_v[j].data(), sig[j - pre_layer_id]);
-            for (u64 g = 0; g < C.circuit[j].dadSize[pre_layer_id]; ++g)
-                gr = gr + beta_g[g] * beta_u[C.circuit[j].dadId[pre_layer_id][g]];
-        }
+        vector<const F *> rv(C.size, nullptr);
+        for (int j = layer_id; j < C.size; ++j) rv[j] = r_v[j].data();
+        const F gr = liuGr(layer_id, r_u.data(), rv.data(), sig.data(), r_liu.data());
         bool ok = (vr * gr == previousSum);
         if (!ok) fprintf(stderr, "oracle: Liu fail, semi final, circuit %d\n", layer_id);
         previousSum = vr;
@@ -903,12 +932,9 @@ struct Verifier {
         }
         // verifyPoly (verifier.cpp:363-389) would now check previousSum against the committed input.
         // With PC off we check it directly against the input layer's MLE at r_liu.
-        {
-            vector<F> beta;
-            init_beta_table(beta, C.circuit[0].bitLength, r_liu.data(), F_ONE);
-            F acc = F_ZERO;
-            for (u64 g = 0; g < C.circuit[0].size; ++g) acc = acc + beta[g] * p->circuitValue[0][g];
-            if (acc != previousSum) { fprintf(stderr, "oracle: final input check fail\n"); return false; }
+        if (layerMle(p->circuitValue[0], C.circuit[0].size, C.circuit[0].bitLength, r_liu.data()) != previousSum) {
+            fprintf(stderr, "oracle: final input check fail\n");
+            return false;
         }
         return true;
     }
@@ -1054,6 +1080,15 @@ void orc_circuit_export_layer(orc_circuit *oc, int layer, int32_t *ty, int32_t *
     }
 }
 
+int orc_circuit_subsets(orc_circuit *oc, int layer, int64_t *dad_size, int32_t *dad_bitlen, int32_t *max_dad_bitlen) {
+    subset_init(oc->c);
+    if (layer < 0 || layer >= oc->c.size) return -1;
+    const Layer &L = oc->c.circuit[layer];
+    for (int j = 0; j < layer; ++j) { dad_size[j] = (int64_t) L.dadSize[j]; dad_bitlen[j] = L.dadBitLength[j]; }
+    *max_dad_bitlen = L.maxDadBitLength;
+    return 0;
+}
+
 void orc_circuit_inputs(const orc_circuit *oc, orc_F *out) {
     const Layer &L = oc->c.circuit[0];
     for (u64 g = 0; g < L.size; ++g) { out[g].real = F((long long) L.gates[g].u).re; out[g].img = 0; }
@@ -1106,6 +1141,52 @@ int64_t orc_prove_fs(orc_circuit *oc, uint8_t *proof, int64_t capacity, orc_stat
 
 static inline F toF(const orc_F *x) { return F(x->real, x->img); }
 static inline void fromF(const F &x, orc_F *o) { o->real = x.re; o->img = x.im; }
+
+static vector<F> toFs(const orc_F *x, int n) { vector<F> v(n > 0 ? n : 0); for (int i = 0; i < n; ++i) v[i] = toF(&x[i]); return v; }
+
+int orc_predicates(orc_circuit *oc, int layer, const orc_F *r_g, const orc_F *assert_random, const orc_F *r_u, const orc_F *r_v, int n_v, orc_F *out) {
+    subset_init(oc->c);
+    const Circuit &C = oc->c;
+    if (layer < 1 || layer >= C.size || n_v != std::max(0, C.circuit[layer].maxDadBitLength)) return -1;
+    VerifierSums s(C);
+    const vector<F> rg = toFs(r_g, C.circuit[layer].bitLength), ru = toFs(r_u, C.circuit[layer - 1].bitLength), rv = toFs(r_v, n_v);
+    s.predicatePhase1(layer, rg.data(), toF(assert_random), ru.data());
+    const F head[5] = {s.coeff_l[Copy], s.coeff_l[Not], s.coeff_l[Addc], s.coeff_l[Mulc], s.bias};     // before predicatePhase2 scales them by beta_v[0]
+    if (C.circuit[layer].maxDadBitLength != -1) s.predicatePhase2(layer, rv.data());
+    for (int k = 0; k < 5; ++k) fromF(head[k], &out[k]);
+    const int order[7] = {Add, Sub, AntiSub, Mul, Naab, AntiNaab, Xor};
+    for (int t = 0; t < 7; ++t)
+        for (int l = 0; l < layer; ++l) fromF(s.coeff_r[order[t]][l], &out[5 + t * layer + l]);
+    return 0;
+}
+
+int orc_liu_gr(orc_circuit *oc, int layer, const orc_F *r_u, const orc_F *const *r_v, const orc_F *sig, const orc_F *r_liu, orc_F *out) {
+    subset_init(oc->c);
+    const Circuit &C = oc->c;
+    if (layer < 1 || layer >= C.size) return -1;
+    const int n = C.circuit[layer - 1].bitLength;
+    const vector<F> ru = toFs(r_u, n), rl = toFs(r_liu, n), sg = toFs(sig, C.size - layer + 1);
+    vector<vector<F>> rv(C.size);
+    vector<const F *> rvp(C.size, nullptr);
+    for (int j = layer; j < C.size; ++j) {
+        const int bl = C.circuit[j].dadSize[layer - 1] ? C.circuit[j].dadBitLength[layer - 1] : 0;
+        if (bl && (!r_v || !r_v[j])) return -1;
+        rv[j] = toFs(bl ? r_v[j] : nullptr, bl);
+        rvp[j] = rv[j].data();
+    }
+    VerifierSums s(C);
+    fromF(s.liuGr(layer, ru.data(), rvp.data(), sg.data(), rl.data()), out);
+    return 0;
+}
+
+int orc_layer_mle(orc_circuit *oc, int layer, const orc_F *r, int n, orc_F *out) {
+    const Circuit &C = oc->c;
+    if (layer < 0 || layer >= C.size || n != C.circuit[layer].bitLength) return -1;
+    Prover p(C);
+    const vector<F> rr = toFs(r, n);
+    fromF(VerifierSums::layerMle(p.circuitValue[layer], C.circuit[layer].size, n, rr.data()), out);
+    return 0;
+}
 
 void orc_f_add(const orc_F *a, const orc_F *b, orc_F *out) { fromF(toF(a) + toF(b), out); }
 void orc_f_sub(const orc_F *a, const orc_F *b, orc_F *out) { fromF(toF(a) - toF(b), out); }

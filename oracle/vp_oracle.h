@@ -61,8 +61,26 @@ void orc_circuit_hash(orc_circuit *, uint64_t out[2]);
 /* Flat export of one layer's gate table (after subsetInit): arrays of length layer size.              */
 void orc_circuit_export_layer(orc_circuit *, int layer, int32_t *ty, int32_t *l, uint64_t *u, uint64_t *v,
                               uint64_t *lv);
+/* The subsets of one layer (after subsetInit): dad_size[j] and dad_bitlen[j] for j < layer (an empty subset has size 0 and bit
+ * length 0, see subset_init), and the layer's maxDadBitLength (-1: no binary gate, no phase 2).  Returns 0, -1 for a bad layer. */
+int orc_circuit_subsets(orc_circuit *, int layer, int64_t *dad_size, int32_t *dad_bitlen, int32_t *max_dad_bitlen);
 /* Input-layer witness (layer 0 values as drawn), length = layer 0 size.                               */
 void orc_circuit_inputs(const orc_circuit *, orc_F *out);
+
+/* ---- the verifier's O(|C|) loops by value ---------------------------------------------------------- */
+/* The loops orc_prove_gkr's verifier runs on its own challenges (src/verifier.cpp:50-113, 311-323, 363-389), on the caller's points: the
+ * same code, not a copy.  All return 0, or -1 for an argument that does not fit the circuit.
+ * orc_predicates: out[0..5) = coeff_l[Copy], [Not], [Addc], [Mulc], bias after predicatePhase1 (before predicatePhase2 scales them by
+ *   beta_v[0]); out[5 + t * layer + l] = coeff_r[t][l], t in the order Add, Sub, AntiSub, Mul, Naab, AntiNaab, Xor.  r_g: bit_length(layer)
+ *   entries, r_u: bit_length(layer - 1), r_v: n_v = max(0, maxDadBitLength(layer)) entries.
+ * orc_liu_gr: the `gr` of verifyLiu(layer).  r_v[j] for j = layer .. n_layers - 1 are the phase-2 challenges of layer j (its first
+ *   dadBitLength[j][layer - 1] entries are read; may be NULL where that is 0); sig has n_layers - layer + 1 entries; r_u and r_liu have
+ *   bit_length(layer - 1).
+ * orc_layer_mle: the multilinear extension of the layer's values (prover::evaluate) at r, n = bit_length(layer).                       */
+int orc_predicates(orc_circuit *, int layer, const orc_F *r_g, const orc_F *assert_random, const orc_F *r_u, const orc_F *r_v, int n_v,
+                   orc_F *out);
+int orc_liu_gr(orc_circuit *, int layer, const orc_F *r_u, const orc_F *const *r_v, const orc_F *sig, const orc_F *r_liu, orc_F *out);
+int orc_layer_mle(orc_circuit *, int layer, const orc_F *r, int n, orc_F *out);
 
 /* ---- whole GKR proof ----------------------------------------------------------------------------- */
 /* F::init() (srand(3396)), subsetInit, prover(evaluate), verifier::verify with the polynomial

@@ -161,8 +161,165 @@ def make_skewed(seed, layer_sizes=None, only_type=None, real_consts=False):
     return (np.array(sizes, np.uint64), np.concatenate(ty), np.concatenate(l), np.concatenate(u), np.concatenate(v), np.concatenate(c), np.concatenate(a))
 
 
+# ---- bucketed circuits: the size of every (type, operand layer) bucket of the verifier's wiring predicates fixed by construction -------------------------
+def make_bucketed(seed, n_inputs, layer_buckets, v_wires=None, asserts=None):
+    """The same seven arrays as make().  layer_buckets[i - 1] = {(type, operand layer; -1 for a unary type): number of gates} for gate layer i: the layer is
+    exactly these gates, shuffled, so a bucket's members are scattered over it; u is uniform over layer i - 1.
+    v_wires[(i, l)] = the number of distinct wires of layer l that layer i's binary gates read (default: as many as there are gates and wires), so the subset's
+    size, and with it dadBitLength[i][l], is fixed too (tests/test_verifier_sums_host.py asserts all of it from the arrays).
+    asserts[i] = the buckets of layer i that get ONE assert gate each: binary, unary (Copy) or unary with a constant (Mulc).  They are legal by construction:
+    one input is 0, one Copy gate per layer (taken from its Copy bucket) carries that 0 upwards as far as the assert gates need it, and an assert gate reads
+    nothing else (x op 0-wire pairs: 0 + 0, 0 * 0, 0 xor 0, ...; Copy(0); c * 0)."""
+    rng = np.random.default_rng(seed)
+    v_wires, asserts = v_wires or {}, asserts or {}
+    sizes = [n_inputs]
+    inp = rng.integers(0, P, n_inputs).astype(np.uint64)
+    zero = [int(rng.integers(0, n_inputs))]
+    inp[zero[0]] = 0
+    ty = [np.full(n_inputs, INPUT, np.int32)]; l = [np.full(n_inputs, -1, np.int32)]; u = [inp]; v = [np.zeros(n_inputs, np.uint64)]
+    c = [np.zeros((n_inputs, 2), np.uint64)]; a = [np.zeros(n_inputs, np.uint8)]
+    chain_to = max(asserts, default=0) - 1
+    for i, buckets in enumerate(layer_buckets, start=1):
+        m = sizes[i - 1]
+        for (t, lay) in buckets:
+            assert (lay == -1) == (t in UNARY) and lay < i and t in ALL_TYPES
+        keys = [k for k, cnt in buckets.items() if cnt]
+        tt = np.concatenate([np.full(buckets[k], k[0], np.int32) for k in keys])
+        ll = np.concatenate([np.full(buckets[k], k[1], np.int32) for k in keys])
+        start = dict(zip(keys, np.concatenate([[0], np.cumsum([buckets[k] for k in keys])])[:-1]))
+        n = len(tt)
+        uu = rng.integers(0, m, n).astype(np.int64)
+        vv = np.zeros(n, np.int64); aa = np.zeros(n, np.uint8)
+        taken = {k: 0 for k in keys}
+
+        def pin(key):
+            g = int(start[key]) + taken[key]
+            taken[key] += 1
+            assert taken[key] <= buckets[key], "bucket %r of layer %d is too small for its pinned gates" % (key, i)
+            uu[g] = zero[i - 1]
+            return g
+        carrier = pin((COPY, -1)) if i <= chain_to else None
+        forced = {}
+        for key in asserts.get(i, ()):
+            g = pin(key)
+            aa[g] = 1
+            if key[1] >= 0:
+                forced.setdefault(key[1], []).append(g)
+        for lay in range(i):
+            idx = np.flatnonzero(ll == lay)
+            if not len(idx):
+                continue
+            k = min(v_wires.get((i, lay), sizes[lay]), sizes[lay], len(idx))
+            f = np.array(forced.get(lay, []), np.int64)
+            if len(f):
+                others = np.setdiff1d(np.arange(sizes[lay]), [zero[lay]])
+                wires = np.concatenate([[zero[lay]], rng.choice(others, k - 1, replace=False)])
+                vv[f] = zero[lay]
+                rest = rng.permutation(np.setdiff1d(idx, f))
+                vv[rest[:k - 1]] = wires[1:]
+                vv[rest[k - 1:]] = wires[rng.integers(0, k, max(len(rest) - (k - 1), 0))]
+            else:
+                wires = rng.choice(sizes[lay], k, replace=False)
+                rest = rng.permutation(idx)
+                vv[rest[:k]] = wires
+                vv[rest[k:]] = wires[rng.integers(0, k, len(rest) - k)]
+        cc = np.zeros((n, 2), np.uint64)
+        isc = np.isin(tt, (MULC, ADDC))
+        cc[isc] = rng.integers(0, P, (int(isc.sum()), 2))
+        perm = rng.permutation(n)
+        if carrier is not None:
+            zero.append(int(np.flatnonzero(perm == carrier)[0]))
+        else:
+            zero.append(None)
+        ty.append(tt[perm]); l.append(ll[perm]); u.append(uu[perm].astype(np.uint64)); v.append(vv[perm].astype(np.uint64)); c.append(cc[perm]); a.append(aa[perm])
+        sizes.append(n)
+    return (np.array(sizes, np.uint64), np.concatenate(ty), np.concatenate(l), np.concatenate(u), np.concatenate(v), np.concatenate(c), np.concatenate(a))
+
+
+# The ladder circuit: gate layer 4 has four layers below it and carries every bucket size at which the device sums change shape (a wave strides a piece of
+# <= 512 gates by 64 lanes; a bucket's pieces are added with a 64-lane stride, so HUGE = 65 pieces takes a second trip).  Naab and AntiNaab are empty for
+# operand layer 3 and filled for layer 2; Sub is empty for layer 2; five types are empty for layer 1, whose subset (3 wires, bit length 2) is far shorter than
+# the longest (600 wires of layer 0, bit length 10 = maxDadBitLength).  n_g = 16, n_u = 9, n_v = 10.  Addc feeds two sums (coeff_l[Addc] and bias): 513 gates
+# here, 65 in layer 1.  Layer 1 (113 gates, bit length 7) holds an assert gate of each flag class, layer 4 too (inside HUGE, the 513-gate Xor bucket, Copy and
+# Mulc).  Layer 5 is a small top layer.
+LADDER_LAYER = 4
+LADDER_INPUTS = 600
+LADDER_BUCKETS = [
+    {**{(t, 0): 5 for t in BINARY}, (COPY, -1): 4, (NOT, -1): 3, (MULC, -1): 6, (ADDC, -1): 65},
+    {**{(t, 1): 20 for t in BINARY}, **{(t, 0): 17 for t in BINARY}, (COPY, -1): 11, (NOT, -1): 10, (MULC, -1): 10, (ADDC, -1): 10},
+    {**{(t, 2): 40 for t in BINARY}, **{(t, 0): 20 for t in BINARY}, (MUL, 1): 30, (COPY, -1): 10, (NOT, -1): 10, (MULC, -1): 10, (ADDC, -1): 20},
+    {(ADD, 3): HUGE, (MUL, 3): 1025, (SUB, 3): 1024, (XOR, 3): 513, (NAAB, 3): 0, (ANTINAAB, 3): 0, (ANTISUB, 3): 1,
+     (NAAB, 2): 512, (ANTINAAB, 2): 511, (ANTISUB, 2): 65, (MUL, 2): 64, (ADD, 2): 63, (SUB, 2): 0, (XOR, 2): 1,
+     (MUL, 1): 3, (XOR, 1): 2, (ADD, 1): 0, (SUB, 1): 0, (ANTISUB, 1): 0, (NAAB, 1): 0, (ANTINAAB, 1): 0,
+     (MUL, 0): 513, (NAAB, 0): 1, (ANTINAAB, 0): 64, (SUB, 0): 511, (ADD, 0): 0, (XOR, 0): 65, (ANTISUB, 0): 512,
+     (COPY, -1): 63, (NOT, -1): 1, (ADDC, -1): 513, (MULC, -1): 1024},
+    {(ADD, 4): 6, (MUL, 4): 5, (XOR, 3): 2, (SUB, 0): 3, (NAAB, 2): 1, (COPY, -1): 1, (ADDC, -1): 1, (MULC, -1): 1},
+]
+LADDER_V_WIRES = {(4, 1): 3, (4, 0): 600, (4, 3): 400, (4, 2): 100}
+LADDER_ASSERTS = {1: [(ADD, 0), (COPY, -1), (MULC, -1)], 4: [(ADD, 3), (XOR, 3), (COPY, -1), (MULC, -1)]}
+
+
+def make_ladder(seed):
+    return make_bucketed(seed, LADDER_INPUTS, LADDER_BUCKETS, LADDER_V_WIRES, LADDER_ASSERTS)
+
+
+# A layer of unary gates only (layer 2) in the middle of a circuit: maxDadBitLength -1, no phase 2, vp_predicates with n_v = 0.  Layers 3 and 4 read it and the
+# layers below it; layer 2's subset of layers 0 and 1 is empty, which the Liu sums of layers 1 and 2 meet.
+UNARY_MID_LAYER = 2
+UNARY_MID_INPUTS = 600      # > 512 inputs: the real reference's commitment needs them (tests/golden/make_golden.py)
+UNARY_MID_BUCKETS = [
+    {**{(t, 0): 4 for t in BINARY}, (COPY, -1): 2},
+    {(COPY, -1): 7, (NOT, -1): 6, (ADDC, -1): 7, (MULC, -1): 5},
+    {**{(t, 2): 3 for t in BINARY}, (ADD, 1): 4, (MUL, 0): 5, (XOR, 1): 2, (NOT, -1): 2},
+    {(MUL, 3): 4, (ADD, 2): 3, (SUB, 1): 2, (XOR, 0): 3, (ANTINAAB, 2): 2, (ADDC, -1): 1},
+]
+UNARY_MID_ASSERTS = {2: [(COPY, -1), (MULC, -1)]}
+
+
+def make_unary_mid(seed):
+    return make_bucketed(seed, UNARY_MID_INPUTS, UNARY_MID_BUCKETS, None, UNARY_MID_ASSERTS)
+
+
+# Zero-variable layers: layer 1 is one gate (n_g = 0, n_u = 3), layer 2 is one gate above a layer of one wire (n_g = n_u = 0; its one-wire subset has bit length 0).
+ZERO_VAR_INPUTS = 8
+ZERO_VAR_BUCKETS = [{(MUL, 0): 1}, {(XOR, 0): 1}]
+
+
+def make_zero_var(seed):
+    return make_bucketed(seed, ZERO_VAR_INPUTS, ZERO_VAR_BUCKETS)
+
+
+# Layers for the inner products <eq(r, .), values>: bit lengths 17, 17, 16, 15, 7, 2, 1, 0.  n >= 16 takes the whole-runs branch of the dot kernel (half table of
+# 2^(n >> 1) >= 256 entries) and the sizes 2^16 + 3 and 2^16 - 5 leave the last run partial; both have more than 128 x 256 entries, so the 128 workgroups loop.
+# Mostly Mulc / Addc with complex constants, so every layer above the inputs holds complex values.
+DOT_INPUTS = (1 << 16) + 3
+DOT_SIZES = [(1 << 16) + 3, (1 << 16) - 5, (1 << 15) - 7, 100, 3, 2, 1]
+
+
+def _dot_buckets():
+    out = []
+    for i, n in enumerate(DOT_SIZES, start=1):
+        nb = n // 8 if n >= 8 else (1 if n > 1 else 0)
+        b = {(MULC, -1): (n - nb + 1) // 2, (ADDC, -1): (n - nb) // 2}
+        if nb:
+            b[(MUL, i - 1)] = nb - nb // 2
+            if nb // 2:
+                b[(ADD, 0)] = nb // 2
+        out.append(b)
+    return out
+
+
+DOT_BUCKETS = _dot_buckets()
+
+
+def make_dot_layers(seed):
+    return make_bucketed(seed, DOT_INPUTS, DOT_BUCKETS)
+
+
 def from_golden(entry):
     """The circuit of a custom case of tests/golden/golden.json (its "custom" entry: generator, seed, sizes)."""
     if entry.get("generator") == "make_skewed":
         return make_skewed(entry["seed"], entry["sizes"])
+    if entry.get("generator") == "make_unary_mid":
+        return make_unary_mid(entry["seed"])
     return make(entry["seed"], entry["sizes"])

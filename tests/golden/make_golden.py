@@ -42,7 +42,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # read), i.e. slices of >= 8 elements = input bit length >= 9.  Below that its Merkle roots are not a function of the input.
 # custom_c: custom_circuits.make_skewed — heavy rows, long subsets and every gate type at the places the fused inits and the chunk kernels branch on
 # (tests/test_skewed_circuits_host.py); its sizes are make_skewed's own.
-CUSTOM = {"custom_a": (101, [600, 180, 150, 300, 64, 9]), "custom_b": (102, [1500, 2100, 900, 4100, 700]), "custom_c": (103, None)}
+# custom_d: custom_circuits.make_unary_mid — a layer of unary gates only in the middle (maxDadBitLength -1: no phase 2), assert flags on unary gates
+CUSTOM = {"custom_a": (101, [600, 180, 150, 300, 64, 9]), "custom_b": (102, [1500, 2100, 900, 4100, 700]), "custom_c": (103, None),
+          "custom_d": (104, "make_unary_mid")}
 
 SURVEY_SHA256 = {
     "sha256_x1": "7d56df550455f8e32dcda3ea158e2606b23f4e8bac761ca6a081b8caeee65047",
@@ -96,7 +98,10 @@ def custom_case(cname):
     import struct
     import custom_circuits as cc
     seed, sizes = CUSTOM[cname]
-    szs, ty, l, u, v, c, asr = cc.make(seed, sizes) if sizes is not None else cc.make_skewed(seed)
+    if isinstance(sizes, str):
+        szs, ty, l, u, v, c, asr = getattr(cc, sizes)(seed)
+    else:
+        szs, ty, l, u, v, c, asr = cc.make(seed, sizes) if sizes is not None else cc.make_skewed(seed)
     path = os.path.join(HERE, "_%s.circ" % cname)
     with open(path, "wb") as f:
         f.write(struct.pack("<i", len(szs)))
@@ -110,6 +115,8 @@ def custom_case(cname):
     m["custom"] = {"seed": seed, "sizes": [int(x) for x in szs]}
     if sizes is None:
         m["custom"]["generator"] = "make_skewed"
+    elif isinstance(sizes, str):
+        m["custom"]["generator"] = sizes
     return m
 
 

@@ -55,6 +55,11 @@ def lib():
         L.orc_f_random_seq.argtypes = [ctypes.c_uint, ctypes.c_int, vp]
         L.orc_beta_table.argtypes = [vp, ctypes.c_int, vp, vp]
         L.orc_update_each.argtypes = [vp, vp, vp, u64, u64, vp, vp]
+        L.orc_circuit_export_layer.argtypes = [vp, ctypes.c_int] + [vp] * 5
+        L.orc_circuit_subsets.argtypes = [vp, ctypes.c_int, vp, vp, vp]
+        L.orc_predicates.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp]
+        L.orc_liu_gr.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, vp]
+        L.orc_layer_mle.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
         _lib = L
     return _lib
 
@@ -114,6 +119,59 @@ class Circuit:
         if n < 0:
             raise RuntimeError("oracle FS prove failed")
         return buf.raw[:n], st.as_dict()
+
+    def layer_bitlen(self, i):
+        return lib().orc_circuit_layer_bitlen(self.h, i)
+
+    def export_layer(self, layer):
+        """The layer's gate table after subsetInit: dict of numpy arrays ty, l, u, v, lv (lv: the gate's slot in the subset of layer l)."""
+        import numpy as np
+        n = self.layer_size(layer)
+        a = {"ty": np.zeros(n, np.int32), "l": np.zeros(n, np.int32), "u": np.zeros(n, np.uint64), "v": np.zeros(n, np.uint64), "lv": np.zeros(n, np.uint64)}
+        lib().orc_circuit_export_layer(self.h, layer, *[a[k].ctypes.data for k in ("ty", "l", "u", "v", "lv")])
+        return a
+
+    def subsets(self, layer):
+        """(dadSize[j] for j < layer, dadBitLength[j] for j < layer, maxDadBitLength) of the layer."""
+        import numpy as np
+        ds, db, mx = np.zeros(max(layer, 1), np.int64), np.zeros(max(layer, 1), np.int32), ctypes.c_int32(0)
+        if lib().orc_circuit_subsets(self.h, layer, ds.ctypes.data, db.ctypes.data, ctypes.byref(mx)):
+            raise RuntimeError("orc_circuit_subsets: bad layer")
+        return [int(x) for x in ds[:layer]], [int(x) for x in db[:layer]], mx.value
+
+    # ---- the verifier's loops by value: points are lists of (re, im) pairs of Python ints, results likewise -------------------------------
+    @staticmethod
+    def _pts(p):
+        import numpy as np
+        return np.ascontiguousarray(np.array([[int(a), int(b)] for a, b in p], dtype=np.uint64).reshape(-1, 2))
+
+    def predicates(self, layer, r_g, assert_random, r_u, r_v):
+        import numpy as np
+        g, a, u, v = self._pts(r_g), self._pts([assert_random]), self._pts(r_u), self._pts(r_v)
+        out = np.zeros((5 + 7 * layer, 2), np.uint64)
+        if lib().orc_predicates(self.h, layer, g.ctypes.data, a.ctypes.data, u.ctypes.data, v.ctypes.data, len(r_v), out.ctypes.data):
+            raise RuntimeError("orc_predicates: arguments do not fit the circuit")
+        return [(int(x), int(y)) for x, y in out]
+
+    def liu_gr(self, layer, r_u, r_v, sig, r_liu):
+        """r_v: dict or list indexed by layer j >= layer (missing / empty where the subset is empty)."""
+        import numpy as np
+        n = self.layers
+        keep = [self._pts(r_v[j]) if (j >= layer and len(r_v[j])) else None for j in range(n)]
+        ptrs = (ctypes.c_void_p * n)(*[k.ctypes.data if k is not None else None for k in keep])
+        u, s, rl = self._pts(r_u), self._pts(sig), self._pts(r_liu)
+        out = np.zeros((1, 2), np.uint64)
+        if lib().orc_liu_gr(self.h, layer, u.ctypes.data, ctypes.cast(ptrs, ctypes.c_void_p), s.ctypes.data, rl.ctypes.data, out.ctypes.data):
+            raise RuntimeError("orc_liu_gr: arguments do not fit the circuit")
+        return (int(out[0, 0]), int(out[0, 1]))
+
+    def layer_mle(self, layer, r):
+        import numpy as np
+        rr = self._pts(r)
+        out = np.zeros((1, 2), np.uint64)
+        if lib().orc_layer_mle(self.h, layer, rr.ctypes.data, len(r), out.ctypes.data):
+            raise RuntimeError("orc_layer_mle: arguments do not fit the circuit")
+        return (int(out[0, 0]), int(out[0, 1]))
 
     def close(self):
         if self.h:

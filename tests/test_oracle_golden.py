@@ -278,11 +278,12 @@ def test_oracle_commitment_array_vs_reference_x1(ob, golden, pws_path):
     c.close()
 
 
-@pytest.mark.parametrize("name", ["custom_a", "custom_b", "custom_c"])
+@pytest.mark.parametrize("name", ["custom_a", "custom_b", "custom_c", "custom_d"])
 def test_oracle_on_all_gate_types_and_asserts_vs_reference(ob, golden, name):
     """Circuits using every gate type + assert gates, proved by the REAL reference (ref_run --custom): the oracle must
     reproduce transcript, field-op counters, commitment and FRI data.  custom_c is the skewed circuit of custom_circuits.make_skewed
-    (heavy rows of up to 33000 gates, subsets of bit length 14, two assert gates per layer)."""
+    (heavy rows of up to 33000 gates, subsets of bit length 14, two assert gates per layer); custom_d is custom_circuits.make_unary_mid
+    (a layer of unary gates only, so no phase 2 there, and assert flags on a Copy and a Mulc gate)."""
     import custom_circuits as cc
     g = golden[name]
     c = ob.Circuit.custom(*cc.from_golden(g["custom"]))

@@ -1544,12 +1544,26 @@ static int round1_prefetch(vp_ctx *ctx) {
     return VP_OK;
 }
 
+// the verifier-side entry points take canonical challenges only, as vp_round does: checked on the host, before anything is queued
+static bool pred_canonical(const vp_F *x, int n) {
+    for (int i = 0; i < n; ++i) {
+        F v; memcpy(&v, &x[i], sizeof(F));
+        if (v.re >= P61 || v.im >= P61) return false;
+    }
+    return true;
+}
+
 int vp_predicates(vp_ctx *ctx, int layer, const vp_F *r_g, const vp_F *assert_random, const vp_F *r_u, const vp_F *r_v, int n_v,
                   vp_F *out, uint64_t n_out) {
     if (!ctx || layer < 1 || layer >= ctx->n_layers || !assert_random || !out) return VP_EINVAL;
     LayerDev &D = ctx->L[layer], &pre = ctx->L[layer - 1];
     if ((D.bl > 0 && !r_g) || (pre.bl > 0 && !r_u)) return VP_EINVAL;       // zero-variable layers have no challenges
     if (n_v < 0 || n_v > 31 || (n_v > 0 && !r_v) || n_out != D.p_buckets) { ctx->err = "vp_predicates: bad sizes"; return VP_EINVAL; }
+    // the beta_v half tables are built for n_v bits and indexed with the gates' subset slots: any other n_v than the layer's own would read entries this call never wrote
+    if (n_v != std::max(0, D.max_dad_bl)) { ctx->err = "vp_predicates: n_v is not the layer's maxDadBitLength (0 for a layer without binary gates)"; return VP_EINVAL; }
+    if (!pred_canonical(r_g, D.bl) || !pred_canonical(r_u, pre.bl) || !pred_canonical(r_v, n_v) || !pred_canonical(assert_random, 1)) {
+        ctx->err = "vp_predicates: a challenge is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL;
+    }
     VP_ENTER(ctx);
     // scratch: challenges, three pairs of half tables, piece sums, bucket sums (sized for the largest layer, once)
     if (!ctx->pred_r) {
@@ -1581,14 +1595,19 @@ int vp_predicates(vp_ctx *ctx, int layer, const vp_F *r_g, const vp_F *assert_ra
     }
     HIPCHK(hipMemcpyAsync(ctx->pred_jobs, jb, sizeof(jb), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));          // h and jb are stack/heap temporaries
+    ctx->ev_used = 0;                                    // profiled: the table lists the half-table launch (the bucket kernels have no VP_K_* kind)
+    const int sl_b = prof_begin(ctx, ctx->stream, VP_K_BETA, 3 * bpj, 3, 0, 0);
     hipLaunchKernelGGL(k_beta_half_direct, dim3(3 * bpj), dim3(VP_BLOCK), 0, ctx->stream, ctx->pred_jobs, bpj);
+    prof_end(ctx, ctx->stream, sl_b);
     PredArgs a{};
     a.idx = D.p_idx; a.flag = D.p_flag; a.chunk_beg = D.p_cbeg; a.chunk_end = D.p_cend; a.n_chunks = D.p_chunks;
     a.hg = hh[0]; a.hu = hh[1]; a.hv = hh[2]; a.gu = D.gu; a.glv = D.glv; a.gc = D.gc; a.assert_r = ctx->pred_r + 97; a.part = ctx->pred_part;
     if (D.p_chunks) hipLaunchKernelGGL(k_pred_chunks, dim3((D.p_chunks + 3) / 4), dim3(VP_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_pred_combine, dim3((D.p_buckets + 3) / 4), dim3(VP_BLOCK), 0, ctx->stream, D.p_bptr, D.p_buckets, ctx->pred_part, ctx->pred_out);
     HIPCHK(hipMemcpyAsync(out, ctx->pred_out, (size_t) D.p_buckets * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-    return check_stream(ctx);
+    const int rc = check_stream(ctx);
+    if (rc == VP_OK && ctx->profiling) prof_collect(ctx);
+    return rc;
 }
 
 // <eq(r, .), table> for a device table of `size` entries: the verifier-side building block of vp_liu_gr / vp_layer_mle
@@ -1620,21 +1639,45 @@ static int pred_inner_product(vp_ctx *ctx, const vp_F *r, int n, const F *table,
     HIPCHK(hipMemcpyAsync(ctx->pred_dot, &d, sizeof(d), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));          // h, jb, d are temporaries
     const u32 bpj = nblk(((u64) 1 << (n >> 1)) + ((u64) 1 << (n - (n >> 1))));
+    // profiled (vp_set_profiling): the launch table of the call is these three launches — bytes = the table read once, work = its entries
+    ctx->ev_used = 0;
+    int sl = prof_begin(ctx, ctx->stream, VP_K_BETA, bpj, 1, 0, 0);
     hipLaunchKernelGGL(k_beta_half_direct, dim3(bpj), dim3(VP_BLOCK), 0, ctx->stream, ctx->pred_jobs, bpj);
+    prof_end(ctx, ctx->stream, sl);
+    sl = prof_begin(ctx, ctx->stream, VP_K_DOT, d.nblk, 1, (u64) size * sizeof(F), size);
     hipLaunchKernelGGL(k_dot_multi, dim3(d.nblk), dim3(VP_BLOCK), 0, ctx->stream, ctx->pred_dot, ctx->pred_map);
+    prof_end(ctx, ctx->stream, sl);
+    sl = prof_begin(ctx, ctx->stream, VP_K_DOTFIN, 1, 1, (u64) d.nblk * sizeof(F), d.nblk);
     hipLaunchKernelGGL(k_dotfin_multi, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, ctx->pred_dot);
+    prof_end(ctx, ctx->stream, sl);
     HIPCHK(hipMemcpyAsync(out, ctx->pred_out, sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
-    return check_stream(ctx);
+    const int rc = check_stream(ctx);
+    if (rc == VP_OK && ctx->profiling) prof_collect(ctx);
+    return rc;
 }
 
 int vp_layer_mle(vp_ctx *ctx, int layer, const vp_F *r, int n, vp_F *out) {
     if (!ctx || !ctx->evaluated || layer < 0 || layer >= ctx->n_layers || !out || n != ctx->L[layer].bl || (n && !r)) return VP_EINVAL;
+    if (!pred_canonical(r, n)) { ctx->err = "vp_layer_mle: r is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     return pred_inner_product(ctx, r, n, ctx->L[layer].val, (u32) ctx->L[layer].size, out);
 }
 
 int vp_liu_gr(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, const vp_F *s, const vp_F *r_liu, vp_F *out) {
-    if (!ctx || !out) return VP_EINVAL;
+    // every argument is checked before vp_liu_init touches the context: a refused call leaves a sumcheck in progress as it was
+    if (!ctx) return VP_EINVAL;
+    if (!out || !ctx->evaluated || layer < 1 || layer >= ctx->n_layers || !s) { ctx->err = "vp_liu_gr: no witness, layer out of range, or s / out missing"; return VP_EINVAL; }
+    {
+        const LayerDev &pre = ctx->L[layer - 1];
+        if (pre.bl && (!r_u || !r_liu)) { ctx->err = "vp_liu_gr: r_u / r_liu missing"; return VP_EINVAL; }
+        bool canon = pred_canonical(r_u, pre.bl) && pred_canonical(r_liu, pre.bl) && pred_canonical(s, ctx->n_layers - layer + 1);
+        for (int k = layer; k < ctx->n_layers; ++k)
+            if (ctx->L[k].dad_size[layer - 1] && ctx->L[k].dad_bl[layer - 1]) {
+                if (!r_v || !r_v[k]) { ctx->err = "vp_liu_gr: r_v of a layer with a subset is missing"; return VP_EINVAL; }
+                canon = canon && pred_canonical(r_v[k], ctx->L[k].dad_bl[layer - 1]);
+            }
+        if (!canon) { ctx->err = "vp_liu_gr: a challenge is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
+    }
     VP_ENTER(ctx);
     const int keep = ctx->opt.prefetch_round1;
     ctx->opt.prefetch_round1 = 0;                                    // only the table is wanted here: no round is coming
@@ -1646,7 +1689,6 @@ int vp_liu_gr(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, c
     if (rc != VP_OK) return rc;
     ctx->sc.phase = 0; ctx->sc_open = false;                         // not a sumcheck in progress
     LayerDev &pre = ctx->L[layer - 1];
-    if (pre.bl && !r_liu) return VP_EINVAL;
     return pred_inner_product(ctx, r_liu, pre.bl, ctx->tab[0][1], (u32) pre.size, out);
 }
 
