@@ -1593,7 +1593,15 @@ struct FftGkr {
     double p_sec = 0, v_sec = 0;
     u64 rounds = 0, pairs = 0;
 
-    static void draws(vector<F> &v, int n) { for (int i = 0; i < n; ++i) v[i] = frandom(); }
+    // the one source of every draw: the glibc stream (orc_fft_gkr), or the next element of a caller's tape (orc_fft_gkr_tape)
+    const u64 *tape = nullptr;
+    int64_t n_tape = 0, t_pos = 0;
+    F draw() {
+        if (!tape) return frandom();
+        const int64_t i = t_pos++;
+        return i < n_tape ? F(tape[2 * i], tape[2 * i + 1]) : F_ZERO;               // an overrun shows in t_pos != n_tape
+    }
+    void draws(vector<F> &v, int n) { for (int i = 0; i < n; ++i) v[i] = draw(); }
     // alpha * eq(r0[0..n), g) + beta * eq(r1[0..n), g), bit b of g set <-> r[b] (the beta_g half tables, :193-216)
     vector<F> g_table(int n) const {
         vector<F> t0, t1;
@@ -1667,7 +1675,7 @@ struct FftGkr {
         for (u64 i = 0; i < N; ++i) S[i] = B[lg][i] * inv_n;
         xs.resize(64); Pm.resize(64 * N); O.assign(64, F_ZERO);
         for (int i = 0; i < 64; ++i) {
-            xs[i] = frandom();
+            xs[i] = draw();
             F x = F_ONE;
             for (u64 j = 0; j < N; ++j) { Pm[j + ((u64) i << lg)] = S[j] * x; x = x * xs[i]; }
         }
@@ -1790,7 +1798,7 @@ struct FftGkr {
             }
             tv.stop(); v_sec += tv.total;
             for (int i = 0; i < lg; ++i) { r0[i] = ru[i]; r1[i] = rv[i]; }
-            alpha = frandom(); beta = frandom();
+            alpha = draw(); beta = draw();
             claim = alpha * vu + beta * vv;
         }
     }
@@ -1798,15 +1806,27 @@ struct FftGkr {
 
 }  // namespace
 
+static int64_t fft_gkr_out(const FftGkr &f, uint8_t *msgs, int64_t capacity, int *verified) {
+    if (verified) *verified = f.ok ? 1 : 0;
+    const int64_t n = (int64_t) f.msgs.size() * 16;
+    if (n > capacity) return -1;
+    for (size_t i = 0; i < f.msgs.size(); ++i) { u64 w[2] = {f.msgs[i].re, f.msgs[i].im}; memcpy(msgs + 16 * i, w, 16); }
+    return n;
+}
 extern "C" int64_t orc_fft_gkr(int lg, long seed, uint8_t *msgs, int64_t capacity, double *prove_sec, int *verified) {
     if (lg < 1 || lg > 24) return -2;
     if (seed >= 0) srand((unsigned) seed);
     FftGkr f; f.lg = lg;
     f.run();
     if (prove_sec) *prove_sec = f.p_sec;
-    if (verified) *verified = f.ok ? 1 : 0;
-    const int64_t n = (int64_t) f.msgs.size() * 16;
-    if (n > capacity) return -1;
-    for (size_t i = 0; i < f.msgs.size(); ++i) { u64 w[2] = {f.msgs[i].re, f.msgs[i].im}; memcpy(msgs + 16 * i, w, 16); }
-    return n;
+    return fft_gkr_out(f, msgs, capacity, verified);
+}
+extern "C" int64_t orc_fft_gkr_tape(int lg, const uint64_t *tape, int64_t n_tape, uint8_t *msgs, int64_t capacity, int *verified) {
+    if (lg < 1 || lg > 24) return -2;
+    if (!tape || n_tape != orc_fft_gkr_draws(lg)) return -3;
+    for (int64_t i = 0; i < 2 * n_tape; ++i) if (tape[i] >= P) return -4;
+    FftGkr f; f.lg = lg; f.tape = reinterpret_cast<const u64 *>(tape); f.n_tape = n_tape;
+    f.run();
+    if (f.t_pos != n_tape) return -5;
+    return fft_gkr_out(f, msgs, capacity, verified);
 }

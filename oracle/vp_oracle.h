@@ -118,6 +118,12 @@ int orc_fft_gkr_draws(int lg);
  * byte count (16 * (64 + 3 * (2 lg^2 + 2 lg + 6) + 2 + 2 lg)), -1 if capacity is too small.  *verified = every check of the
  * reference's embedded verifier held.                                                                 */
 int64_t orc_fft_gkr(int lg, long seed, uint8_t *msgs, int64_t capacity, double *prove_sec, int *verified);
+/* The same prover and verifier with every draw taken from the caller's tape instead of the glibc stream: n_tape elements of (re, im) limbs in
+ * draw order,  r[lg] | x[64] | r_0[lg+10] | r_1[lg+10] | r_u[lg+6], r_v[lg+6] (addition layer) | r_u[lg], r_v[lg] (multiplication layer) |
+ * per inverse-FFT depth r_u[lg], r_v[lg], alpha, beta  — the layout of vp_fft_gkr's tape (include/vpgpu.h).  Fed orc_f_random_seq(seed) it
+ * returns the bytes of orc_fft_gkr(lg, seed).  Returns the byte count, -1 capacity too small, -2 lg out of range, -3 n_tape is not
+ * orc_fft_gkr_draws(lg), -4 a limb >= p, -5 the run did not consume exactly n_tape elements.             */
+int64_t orc_fft_gkr_tape(int lg, const uint64_t *tape, int64_t n_tape, uint8_t *msgs, int64_t capacity, int *verified);
 /* initBetaTable(beta, n, r, init): out has 2^n entries.                                               */
 void orc_beta_table(const orc_F *r, int n, const orc_F *init, orc_F *out);
 /* One call of prover::sumcheckUpdateEach on value tables (the .a parts implied zero / carried in

@@ -53,6 +53,11 @@ def lib():
         L.orc_f_inv.argtypes = [vp, vp]
         L.orc_f_root_of_unity.argtypes = [ctypes.c_int, vp]
         L.orc_f_random_seq.argtypes = [ctypes.c_uint, ctypes.c_int, vp]
+        L.orc_fft_gkr_draws.argtypes = [ctypes.c_int]
+        L.orc_fft_gkr.restype = ctypes.c_int64
+        L.orc_fft_gkr.argtypes = [ctypes.c_int, ctypes.c_long, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+        L.orc_fft_gkr_tape.restype = ctypes.c_int64
+        L.orc_fft_gkr_tape.argtypes = [ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]
         L.orc_beta_table.argtypes = [vp, ctypes.c_int, vp, vp]
         L.orc_update_each.argtypes = [vp, vp, vp, u64, u64, vp, vp]
         L.orc_circuit_export_layer.argtypes = [vp, ctypes.c_int] + [vp] * 5
@@ -62,6 +67,53 @@ def lib():
         L.orc_layer_mle.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, vp]
         _lib = L
     return _lib
+
+
+def fft_gkr_msgs(lg):
+    """Message elements of fft_gkr(lg): the 64 outputs, then per sumcheck three per round and the claimed value."""
+    return 64 + 3 * (2 * lg * lg + 2 * lg + 6) + 2 + 2 * lg
+
+
+def random_seq(seed, n):
+    """orc_f_random_seq: srand(seed), then n draws of F::random(), as an (n, 2) uint64 array."""
+    import numpy as np
+    out = np.zeros((n, 2), np.uint64)
+    lib().orc_f_random_seq(seed, n, out.ctypes.data)
+    return out
+
+
+def root_of_unity(log_order):
+    out = (ctypes.c_uint64 * 2)()
+    lib().orc_f_root_of_unity(log_order, out)
+    return (int(out[0]), int(out[1]))
+
+
+def fft_gkr_seeded(lg, seed):
+    """orc_fft_gkr: (message bytes, verified)."""
+    buf = ctypes.create_string_buffer(16 * fft_gkr_msgs(lg))
+    ok = ctypes.c_int(0)
+    n = lib().orc_fft_gkr(lg, seed, buf, len(buf), None, ctypes.byref(ok))
+    if n != len(buf):
+        raise RuntimeError("orc_fft_gkr: %d" % n)
+    return buf.raw, ok.value
+
+
+def fft_gkr_tape_rc(lg, tape, n_tape=None, capacity=None):
+    """orc_fft_gkr_tape as it is: (return code, message buffer, verified).  tape: (n, 2) uint64 array in draw order."""
+    import numpy as np
+    t = np.ascontiguousarray(tape, np.uint64)
+    buf = ctypes.create_string_buffer(16 * fft_gkr_msgs(lg))
+    ok = ctypes.c_int(0)
+    rc = lib().orc_fft_gkr_tape(lg, t.ctypes.data, t.shape[0] if n_tape is None else n_tape, buf, len(buf) if capacity is None else capacity, ctypes.byref(ok))
+    return rc, buf.raw, ok.value
+
+
+def fft_gkr_tape(lg, tape):
+    """The oracle's fft_gkr on the caller's tape: (message bytes, verified)."""
+    rc, raw, ok = fft_gkr_tape_rc(lg, tape)
+    if rc != len(raw):
+        raise RuntimeError("orc_fft_gkr_tape: %d" % rc)
+    return raw, ok
 
 
 class Circuit:

@@ -68,6 +68,23 @@ int main(int argc, char **argv) {
         orc_sha3_256_64(z, d);
         if (d[0] != 0x07 || d[1] != 0x0f) return fail("sha3");
     }
+    {   // fft_gkr at a small lg: the seeded entry, the tape entry on the same draws (same bytes), an edge-limb tape, and the tape entry's refusals
+        const int lg = 3, nt = orc_fft_gkr_draws(lg);
+        const uint64_t P = 2305843009213693951ull, edge[5] = {0, 1, 2, P - 2, P - 1};
+        const int64_t want = 16 * (64 + 3 * (2 * lg * lg + 2 * lg + 6) + 2 + 2 * lg);
+        std::vector<uint8_t> a(want), b(want);
+        int ok = 0;
+        if (orc_fft_gkr(lg, 3396, a.data(), want, nullptr, &ok) != want || !ok) return fail("fft_gkr seeded");
+        std::vector<orc_F> tape(nt);
+        orc_f_random_seq(3396, nt, tape.data());
+        if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want, &ok) != want || !ok || memcmp(a.data(), b.data(), (size_t) want)) return fail("fft_gkr tape");
+        for (int i = 0; i < nt; ++i) tape[i] = {edge[(7 * i + 3) % 5], edge[(3 * i + 1) % 5]};
+        if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want, &ok) != want || !ok) return fail("fft_gkr edge tape");
+        if (orc_fft_gkr_tape(lg, &tape[0].real, nt - 1, b.data(), want, &ok) != -3) return fail("fft_gkr tape length");
+        if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want - 1, &ok) != -1) return fail("fft_gkr capacity");
+        tape[nt - 1].img = P;
+        if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want, &ok) != -4) return fail("fft_gkr non-canonical limb");
+    }
     puts("oracle_asan ok");
     return 0;
 }

@@ -378,6 +378,33 @@ def test_oracle_fft_gkr_vs_reference_record(ob, lg):
     assert rec == open(os.path.join(GOLDEN, "fftgkr_lg%d.bin" % lg), "rb").read()
 
 
+@pytest.mark.parametrize("lg", [7, 13])
+def test_oracle_fft_gkr_on_a_tape_vs_reference_record(ob, lg):
+    """orc_fft_gkr_tape (the same prover with its draws taken from the caller's tape) fed the reference's own draw sequence: the real reference's record.
+    (lg 17 and the entry's other properties: tests/test_fft_gkr_host.py.)"""
+    from conftest import GOLDEN
+    rec, ok = ob.fft_gkr_tape(lg, ob.random_seq(3396, ob.lib().orc_fft_gkr_draws(lg)))
+    assert ok == 1 and rec == open(os.path.join(GOLDEN, "fftgkr_lg%d.bin" % lg), "rb").read()
+
+
+def test_oracle_fft_gkr_on_the_protocols_own_draws(ob, golden):
+    """... and fed the draws the stream holds where the reference's complete run calls fft_gkr (after commit_public): its record from inside that run."""
+    from conftest import GOLDEN
+    c = ob.Circuit.randomize(8, 12, seed=1)
+    L = ob.lib()
+    L.orc_prove_full.restype = ctypes.c_int64
+    L.orc_prove_full.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    buf = ctypes.create_string_buffer(1 << 20)
+    n = L.orc_prove_full(c.h, buf, len(buf), None)
+    assert buf.raw[:n] == open(os.path.join(GOLDEN, golden["randomize_8_12"]["transcript"]), "rb").read()
+    L.orc_f_random_next.argtypes = [ctypes.c_int, ctypes.c_void_p]
+    tape = np.zeros((L.orc_fft_gkr_draws(6), 2), dtype=np.uint64)
+    L.orc_f_random_next(tape.shape[0], tape.ctypes.data)
+    rec, ok = ob.fft_gkr_tape(6, tape)
+    assert ok == 1 and rec == open(os.path.join(GOLDEN, "fftgkr_randomize_8_12.bin"), "rb").read()
+    c.close()
+
+
 @pytest.mark.parametrize("name,lg", [("sha256_x1", 7), ("randomize_8_12", 6)])
 def test_oracle_fft_gkr_inside_the_protocol(ob, golden, pws_path, name, lg):
     """The same record taken INSIDE the reference's complete run (verify_poly_commitment, vpd_verifier.cpp:92): the oracle proves up to
