@@ -292,7 +292,7 @@ int vp_commit_public(vp_ctx *, const vp_F *pub, uint64_t n_pub, vp_F *inner_prod
  * slice encoding (pc_tensor_pub) applies without its check.  On a sharded commitment (vp_pc_set_shard) every rank passes the point and builds
  * only what it needs: slice 0 and the 64 slice scalars for the one-slice encoding, and its share of the inner product straight from the two
  * half tables (no part of the table is stored; with pc_tensor_pub = 0 the rank's own slices are expanded instead).  Collectives and VP_EXCHANGE
- * as for vp_commit_public; outputs equal it byte for byte on every rank.  A masked commitment is refused.                                */
+ * as for vp_commit_public; outputs equal it byte for byte on every rank.  A masked commitment is refused (vp_commit_public_eq_masked).     */
 int vp_commit_public_eq(vp_ctx *, const vp_F *point, int n_point, vp_F *inner_product_sum, vp_F all_sum[65], uint8_t root_h[32]);
 /* fri::commit_phase_step(r) (lib/virgo/src/fri.cpp:289-424), called n-6 times by poly_commit_prover::commit_phase
  * (vpd_verifier.cpp:44-74): fold the current codewords of all slices by r, hash the new leaves, build the Merkle
@@ -308,7 +308,11 @@ int vp_fri_step(vp_ctx *, const vp_F *r, uint8_t root[32]);
  * reference verifier's challenges do not depend on the transcript, fieldElement.cpp:119-124): r[0..n_steps) in, the
  * n_steps Merkle roots out (32 bytes each, in step order).  Folds run back to back; the leaves of all levels are hashed
  * by one launch and the trees are built level by level across all of them.  Must start from a fresh vp_commit_public
- * (not after vp_fri_step); afterwards vp_fri_final / vp_fri_open behave as after n_steps vp_fri_step calls.          */
+ * (not after vp_fri_step); afterwards vp_fri_final / vp_fri_open behave as after n_steps vp_fri_step calls.  A commitment
+ * with a mask slice (vp_commit_private_masked) takes the same pass: the fused first folds run over its 64 slices, the
+ * 65th follows in arrays of its own (its virtual oracle, one fold per level), its pairs close the chains of the one
+ * leaf launch, and the roots come back in one copy; vp_fri_final_mask and a vp_fri_step after a partial phase
+ * (n_steps < n - 6) continue from there.                                                                             */
 int vp_fri_commit(vp_ctx *, const vp_F *r, int n_steps, uint8_t *roots);
 /* fri::commit_phase_final() (fri.cpp:426-431): the last codeword, 2048 elements in the reference's interleaved
  * layout [i << 7 | slice << 1 | hi], i < 16.                                                            */
@@ -371,11 +375,18 @@ int vp_fft_gkr_cancel(vp_ctx *);
  * Limits: ms >= 8 (below that the reference's own transforms read stale scratch, RS_polynomial.cpp:104-133: VP_EINVAL), gap >= 2 (the reference asserts it,
  * poly_commit.h:195: VP_EINVAL) and ms <= 2^16 (the quotient's 2 ms-point transform is at most 2^17 points: VP_ELIMIT); not on a sharded commitment;
  * vp_commit_public_eq refuses a masked commitment.  vp_commit_private (or a new witness) returns the context to the zero mask.
+ * vp_commit_public_eq_masked is vp_commit_public_masked for the public vector the protocol passes, pub = eq(point, .): the device builds the table
+ * (vp_commit_public_eq), nothing of it crosses PCIe; vp_commit_public_masked's checks and limits, every refusal before the first launch; the mask is copied during the
+ * call, which may complete deferred (vp_set_deferred) like vp_commit_public_eq.  Leaf chains of a masked oracle: the generated fixed-register chain with the mask
+ * pair as its last block (vp_keccak_asm.h, vp_leaf_chain_mask_asm) under the workgroup rules of the unmasked launches, the compiler's form below 2^17 leaves, with
+ * leaf_asm = 0 and in the checked build.  Not built: masks on a sharded commitment, live slices under a mask (a masked commitment transforms all 64 slices), a
+ * host verifier for masked commitments (the reference's own verifier decides them, oracle/integration/masked_main.cpp).
  * What the reference's VERIFIER makes of it (vpd_verifier.cpp:76-328 with the public mask, oracle/integration/masked_main.cpp): a commitment whose ms is at most a
  * slice's message length 2^(n-6) is accepted; a longer mask is committed exactly as the reference's prover commits it and rejected exactly as the reference's verifier
  * rejects that prover's (its last check, :318-324: n - 6 folds do not reduce the mask slice to a constant).                                                        */
 int vp_commit_private_masked(vp_ctx *, const vp_F *mask, uint64_t n_mask, uint8_t root[32]);
 int vp_commit_public_masked(vp_ctx *, const vp_F *pub, uint64_t n_pub, const vp_F *pub_mask, uint64_t n_pub_mask, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]);
+int vp_commit_public_eq_masked(vp_ctx *, const vp_F *point, int n_point, const vp_F *pub_mask, uint64_t n_pub_mask, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]);
 /* fri::cpd.rs_codeword_msk[last] (vpd_verifier.cpp:321-325): the mask slice's last codeword, 32 values, out[2 i + hi] = value at position i + 16 hi (zeros
  * for the zero mask).  After the last FRI step.                                                                                                              */
 int vp_fri_final_mask(vp_ctx *, vp_F out[32]);
@@ -403,10 +414,13 @@ int vp_pending(vp_ctx *, int *n);
  * (input_0 and all_sum are delivered as always).  The one-pass vp_fri_commit then puts every such oracle in front of its own levels: one launch hashes all
  * leaves (an l or h codeword is a list entry like a level's, same digests), the trees are built together, and the roots are written, each where its call
  * asked for it, when vp_fri_commit completes (at once, or in vp_flush under vp_set_deferred).  The root buffers must stay valid until then.
- * No call sequence sees a missing tree: vp_fri_open / _open_many / _query(_bytes), vp_fri_step (and the masked vp_fri_commit), another vp_commit_private or
- * vp_commit_public(_eq), the masked commits, vp_evaluate, vp_circuit_upload, vp_pc_load_input, vp_pc_set_shard, vp_destroy, and vp_flush once the mode is
- * off, first hash what is outstanding with the single-oracle launches of the synchronous calls, wait, and write the same root bytes.  Masked and sharded
- * commitments ignore the mode.  vp_pc_hash_late(ctx, 0) itself leaves what is unhashed unhashed; vp_pending's counts are those of the mode off. */
+ * No call sequence sees a missing tree: vp_fri_open / _open_many / _query(_bytes), vp_fri_step, another vp_commit_private or
+ * vp_commit_public(_eq) (masked or not), vp_evaluate, vp_circuit_upload, vp_pc_load_input, vp_pc_set_shard, vp_destroy, and vp_flush once the mode is
+ * off, first hash what is outstanding with the single-oracle launches of the synchronous calls (the masked one for a masked commitment), wait, and write
+ * the same root bytes.  Sharded commitments ignore the mode; masked commitments ignore on = 1 and hash at once, as they always have — with
+ * on = VP_HASH_LATE_MASKED (2) vp_commit_private_masked, vp_commit_public_masked and vp_commit_public_eq_masked stop behind their transforms as well, and
+ * vp_fri_commit puts l and h in front of its levels with the mask slices' codewords as their mask entries (vph_prove_protocol_masked runs its pass this way).  vp_pc_hash_late(ctx, 0) itself leaves what is unhashed unhashed; vp_pending's counts are those of the mode off. */
+enum { VP_HASH_LATE_MASKED = 2 };
 int vp_pc_hash_late(vp_ctx *, int on);
 /* device time in ms of the last finished vp_commit_private | vp_prove_gkr | vp_commit_public(_eq) | vp_fri_commit | vp_fri_final of the context */
 int vp_phase_ms(vp_ctx *, double out[5]);

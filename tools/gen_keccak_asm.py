@@ -264,6 +264,74 @@ def stats(code):
     return n
 
 
+MACRO = "vp_kround"
+
+
+def compact_rounds(L, iota_regs):
+    """The asm lines of a chain with its identical rounds written ONCE: the list is cut behind every second s_barrier (a piece = chi + iota of one round, the
+    column sums and rotations of the next, up to the barrier behind its rho); pieces that differ only in iota's round constant become invocations of one assembler
+    macro (.macro vp_kround lo, hi ... .endm; a half that is zero has no instruction: .if).  The assembler expands them to the very lines of L — expand_rounds() does
+    the same here and the generator refuses to write anything else.  -> (macro body, lines with invocations)"""
+    import re
+    iota = [re.compile(r"v_xor_b32 %s, 0x([0-9a-f]+), %s$" % (r, r)) for r in iota_regs]
+    pieces, cur, nb = [], [], 0
+    for t in L:
+        cur.append(t)
+        if t == "s_barrier":
+            nb += 1
+            if nb % 2 == 0:
+                pieces.append(cur)
+                cur = []
+    pieces.append(cur)
+
+    def strip(piece):                       # -> (lines without iota's, where they stood, the two constants) or None where the piece has none
+        at, k, rest = None, [0, 0], []
+        for t in piece:
+            m = [rx.match(t) for rx in iota]
+            h = 0 if m[0] else 1 if m[1] else -1
+            if h >= 0 and (at is None or len(rest) == at) and not k[h] and not (h == 0 and k[1]):
+                at = len(rest) if at is None else at
+                k[h] = int(m[h].group(1), 16)
+            else:
+                rest.append(t)
+        return (tuple(rest), at, tuple(k)) if at is not None and "1:" not in piece and not any("%[" in t or t.endswith(":") or "f" == t[-1:] for t in piece) else None
+    keyed = [strip(pc) for pc in pieces]
+    count = {}
+    for kd in keyed:
+        if kd:
+            count[kd[:2]] = count.get(kd[:2], 0) + 1
+    best = max(count, key=lambda q: count[q] * len(q[0]))
+    body = list(best[0][:best[1]])
+    for h, name in enumerate(("lo", "hi")):
+        body += [".if \\%s" % name, "v_xor_b32 %s, \\%s, %s" % (iota_regs[h], name, iota_regs[h]), ".endif"]
+    body += list(best[0][best[1]:])
+    lines = []
+    for pc, kd in zip(pieces, keyed):
+        if kd and kd[:2] == best and count[best] > 1:
+            lines.append("%s 0x%x, 0x%x" % (MACRO, kd[2][0], kd[2][1]))
+        else:
+            lines += pc
+    return body, lines
+
+
+def expand_rounds(body, lines, iota_regs):
+    out = []
+    for t in lines:
+        if not t.startswith(MACRO + " "):
+            out.append(t)
+            continue
+        lo, hi = [int(x, 16) for x in t[len(MACRO) + 1:].split(", ")]
+        val, skip = {"lo": lo, "hi": hi}, False
+        for b in body:
+            if b.startswith(".if "):
+                skip = not val[b[5:]]
+            elif b == ".endif":
+                skip = False
+            elif not skip:
+                out.append(b.replace("\\lo", "0x%x" % lo).replace("\\hi", "0x%x" % hi))
+    return out
+
+
 def emit_header(out, rot1, barriers, msg_after=True, addr="mad", bar_mode="after", bar_every=1):
     code, regs = build_body(rot1, barriers, msg_after_barrier=msg_after, bar_mode=bar_mode, bar_every=bar_every)
     n = stats(code)
@@ -332,6 +400,29 @@ def emit_header(out, rot1, barriers, msg_after=True, addr="mad", bar_mode="after
         out.write('        "%s\\n\\t"\n' % t)
     out.write('        :\n')
     out.write('        : [addr0] "v"(addr0), [addr1] "v"(addr1), [stride] "v"(stride), [count] "s"(count), [out] "v"(out), [active] "v"(active)\n')
+    out.write('        : "memory", "vcc", "scc", "s44", "s45", "s46", "s47", %s);\n' % ", ".join('"v%d"' % r for r in regs["used"]))
+    out.write("}\n")
+    out.write("// The same chain with CONTENT in the mask slice (poly_commit.h:74-86, fri.cpp:107-122): the last block's message is the pair at mask0 / mask1 (this thread's\n")
+    out.write("// two elements of the mask slice's codeword) instead of zeros.  `count` >= 1; everything else as above.  The same instructions as above but for the block\n")
+    out.write("// that closes the chain, written shorter: the rounds of Keccak-f that differ only in their round constant are invocations of one assembler macro (defined in\n")
+    out.write("// front, purged behind: the text is assembled once per kernel it is inlined into); compact_rounds() of the generator, which checks the expansion line by line.\n")
+    out.write("__device__ __forceinline__ void vp_leaf_chain_mask_asm(const void *addr0, const void *addr1, unsigned stride, unsigned count, const void *mask0, const void *mask1,\n")
+    out.write("                                                       void *out, unsigned active) {\n")
+    out.write("    asm volatile(\n")
+    # the masked chain: the plain one with the zero fill of the message registers (label 2:) replaced.  s44 == 2: the block that follows is the mask slice's — its
+    # pair on its way; s44 == 1: this IS that block, nothing follows (a load issued here would land in the registers the digest is gathered in below)
+    z = L.index("2:") + 1
+    assert L[z:z + 8] == ["v_mov_b32 %s, 0" % r for r in M] and L[z + 8] == "3:"
+    full = L[:z] + ["s_cmp_lg_u32 s44, 2", "s_cbranch_scc1 3f", "global_load_dwordx4 v[%d:%d], %%[mask0], off" % (mlo, mlo + 3),
+                    "global_load_dwordx4 v[%d:%d], %%[mask1], off" % (mlo + 4, mhi)] + L[z + 8:]
+    iota_regs = regs["A"][0][0]
+    body, short = compact_rounds(full, iota_regs)
+    if expand_rounds(body, short, iota_regs) != full:
+        raise RuntimeError("compact_rounds: the macro form does not expand to the chain")
+    for t in [".macro %s lo, hi" % MACRO] + body + [".endm"] + short + [".purgem %s" % MACRO]:
+        out.write('        "%s\\n\\t"\n' % t.replace("\\", "\\\\"))
+    out.write('        :\n')
+    out.write('        : [addr0] "v"(addr0), [addr1] "v"(addr1), [stride] "v"(stride), [count] "s"(count), [mask0] "v"(mask0), [mask1] "v"(mask1), [out] "v"(out), [active] "v"(active)\n')
     out.write('        : "memory", "vcc", "scc", "s44", "s45", "s46", "s47", %s);\n' % ", ".join('"v%d"' % r for r in regs["used"]))
     out.write("}\n")
     sys.stderr.write("per block: %s; fixed registers %d\n" % (n, len(regs["used"])))

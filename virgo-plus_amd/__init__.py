@@ -154,6 +154,9 @@ def lib_gpu():
         L.vp_commit_private.argtypes = [vp, vp]
         L.vp_commit_public.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, vp]
         L.vp_commit_public_eq.argtypes = [vp, vp, ctypes.c_int, vp, vp, vp]
+        L.vp_commit_public_eq_masked.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_uint64, vp, vp, vp]
+        L.vp_commit_public_masked.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp]
+        L.vp_fri_final_mask.argtypes = [vp, vp]
         L.vp_fri_commit.argtypes = [vp, vp, ctypes.c_int, vp]
         L.vp_fri_step.argtypes = [vp, vp, vp]
         L.vp_commit_private_masked.argtypes = [vp, vp, ctypes.c_uint64, vp]
@@ -213,6 +216,7 @@ def lib_host():
         L.vph_session_create_sharded.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_commit_private_masked.argtypes = [vp, vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
         L.vph_commit_public_eq.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
+        L.vph_commit_public_eq_masked.argtypes = [vp, vp, ctypes.c_int, vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
         L.vph_fri_open_many.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_fri_query.argtypes = [vp, ctypes.c_int, vp, vp, u64, ctypes.POINTER(u64), ctypes.c_char_p, ctypes.c_int]
         L.vph_session_rank_ctx.restype = vp
@@ -244,6 +248,7 @@ def lib_host():
         L.vph_draw_protocol_tape.argtypes = [vp]
         L.vph_prove_protocol.argtypes = [vp, vp, u64, ctypes.POINTER(u64), vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_protocol_ex.argtypes = [vp, vp, u64, ctypes.POINTER(u64), vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_prove_protocol_masked.argtypes = [vp, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, u64, vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_last_point.argtypes = [vp, vp, ctypes.c_int]
         L.vph_last_fft_gkr.restype = ctypes.c_int64
         L.vph_last_fft_gkr.argtypes = [vp, vp, u64]
@@ -972,11 +977,20 @@ class Session:
             raise RuntimeError("prove_full failed: " + err.value.decode())
         return buf.raw[: n.value], rc == 0
 
-    def commit_public_eq(self, point):
-        """prover::commit_public on pub = eq(point, .) built on the device (vp_commit_public_eq): (root_h, input_0 bytes, all_sum bytes, device ms)."""
+    def commit_public_eq(self, point, pub_mask=None):
+        """prover::commit_public on pub = eq(point, .) built on the device (vp_commit_public_eq): (root_h, input_0 bytes, all_sum bytes, device ms).
+        pub_mask: (k, 2) uint64, the public mask vector behind commit_private(mask) (vp_commit_public_eq_masked); behind a zero private mask it changes nothing."""
         import numpy as np
         point = np.ascontiguousarray(point, dtype=np.uint64)
         out = ctypes.create_string_buffer(32 + 16 + 65 * 16)
+        if pub_mask is not None:
+            pub_mask = np.ascontiguousarray(pub_mask, dtype=np.uint64).reshape(-1, 2)
+            ms = ctypes.c_double(0)
+            err = ctypes.create_string_buffer(512)
+            if lib_host().vph_commit_public_eq_masked(self.h, point.ctypes.data, point.shape[0], pub_mask.ctypes.data, pub_mask.shape[0], ctypes.cast(out, ctypes.c_void_p),
+                                                      ctypes.byref(ms), err, len(err)):
+                raise RuntimeError("vp_commit_public_eq_masked failed: " + err.value.decode())
+            return out.raw[:32], out.raw[32:48], out.raw[48:], ms.value
         if self._shard_pc:                                  # every rank is handed the point
             ms = ctypes.c_double(0)
             err = ctypes.create_string_buffer(512)
@@ -1001,20 +1015,36 @@ class Session:
         if lib_host().vph_draw_protocol_tape(self.h):
             raise RuntimeError("draw_protocol_tape: the commitment needs an input layer of at least 2^7 wires")
 
-    def prove_protocol(self, deferred=False, queue_next=False, hash_per_call=False):
+    def prove_protocol(self, deferred=False, queue_next=False, hash_per_call=False, mask=None, pub_mask=None):
         """The prover side of the complete protocol in one pass (no verifier work): commit_private -> batched GKR -> commit_public on
         eq(r_liu, .) -> fft_gkr -> FRI commit phase.  Returns (transcript in the golden layout, FRI roots bytes, final codeword (2048, 2),
         seconds dict {total, commit_private, gkr, commit_public, fft_gkr, fri_commit}).
         deferred: the calls are queued back to back and collected at the end (vp_set_deferred: no idle device between them); the per-call seconds are then
         device times.  queue_next: the pass also queues the next pass's commit_private behind its own folds (vphost.h, VPH_PASS_QUEUE_NEXT): for a
         session that proves back to back; this pass's commitment cannot be opened afterwards.  hash_per_call: every commit hashes its own oracle (three
-        leaf-hash launches) instead of the one launch behind the FRI folds (vphost.h, VPH_PASS_HASH_PER_CALL): same bytes, the A/B partner."""
+        leaf-hash launches) instead of the one launch behind the FRI folds (vphost.h, VPH_PASS_HASH_PER_CALL): same bytes, the A/B partner.
+        mask / pub_mask: (k, 2) uint64 mask vectors of a hiding commitment (vph_prove_protocol_masked: the 65th slice of every oracle carries them); with a
+        mask given the result has a fifth element, the mask slice's final codeword (32, 2) — zeros for an all-zero mask, which is the pass without one.
+        queue_next is refused together with a non-zero mask."""
         import numpy as np
         if not hasattr(self, "_pp"):
             cap = self._cap + 32 + 32 + 16 + 65 * 16
             self._pp = (ctypes.create_string_buffer(cap), cap, ctypes.create_string_buffer(32 * 32), np.zeros((2048, 2), dtype=np.uint64),
                         (ctypes.c_double * 6)(), ctypes.c_uint64(0), ctypes.create_string_buffer(512))
         buf, cap, roots, fin, sec, n, err = self._pp
+        flags = (1 if deferred or queue_next else 0) | (2 if queue_next else 0) | (4 if hash_per_call else 0)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(-1, 2)
+            pm = np.ascontiguousarray(pub_mask if pub_mask is not None else np.zeros((0, 2)), dtype=np.uint64).reshape(-1, 2)
+            fm = np.zeros((32, 2), dtype=np.uint64)
+            rc = lib_host().vph_prove_protocol_masked(self.h, mask.ctypes.data, mask.shape[0], pm.ctypes.data if pm.shape[0] else None, pm.shape[0],
+                                                      ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n), ctypes.cast(roots, ctypes.c_void_p), len(roots),
+                                                      fin.ctypes.data, fm.ctypes.data, sec, flags, err, len(err))
+            if rc:
+                raise RuntimeError("prove_protocol failed: " + err.value.decode())
+            st = self.circuit.layer_bitlen(0) - 6
+            return (buf.raw[: n.value], roots.raw[:32 * st], fin.copy(),
+                    {"total": sec[0], "commit_private": sec[1], "gkr": sec[2], "commit_public": sec[3], "fft_gkr": sec[4], "fri_commit": sec[5]}, fm)
         rc = lib_host().vph_prove_protocol_ex(self.h, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n), ctypes.cast(roots, ctypes.c_void_p), len(roots),
                                               fin.ctypes.data, sec, (1 if deferred or queue_next else 0) | (2 if queue_next else 0) | (4 if hash_per_call else 0), err, len(err))
         if rc:

@@ -872,6 +872,62 @@ k_leaf_hash_cm(const F *__restrict__ cw, u32 N, int n_slices, const F *__restric
     const F x = mask[(size_t) b * N + a], y = mask[(size_t) b * N + a + halfN];
     leaves[32 * a + b] = hhash64(x.re, x.im, y.re, y.im, h);
 }
+// Several oracles with their mask slices in one launch (the masked vp_fri_commit: l, h and every level): FriLeafArgs and one mask codeword per entry, coset-major
+// like its oracle's (m[b N + a], m[b N + a + N / 2]; the last level: m[t], m[t + 16]).  The compiler's form, blocks dealt per entry (blk_start).
+struct FriLeafMaskArgs { FriLeafArgs a; const F *mask[VP_FRI_MAX]; };
+__global__ void __launch_bounds__(VP_BLOCK) k_leaf_hash_multi_cm(FriLeafMaskArgs ma) {
+    const FriLeafArgs &a = ma.a;
+    int j = 0;
+    while (j + 1 < a.n && blockIdx.x >= a.blk_start[j + 1]) ++j;
+    const u32 t = (blockIdx.x - a.blk_start[j]) * blockDim.x + threadIdx.x;
+    const u32 N = a.N[j], halfN = N >> 1;
+    const F *cw = a.cw[j], *mask = ma.mask[j];
+    Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
+    if (N == 1) {
+        if (t >= 16) return;
+        for (int s = 0; s < 64; ++s) { const F x = cw[(size_t) s * 32 + t], y = cw[(size_t) s * 32 + t + 16]; h = hhash64(x.re, x.im, y.re, y.im, h); }
+        const F x = mask[t], y = mask[t + 16];
+        a.leaves[j][t] = hhash64(x.re, x.im, y.re, y.im, h);
+        return;
+    }
+    if (t >= 32 * halfN) return;
+    const u32 p = t % halfN, b = t / halfN;
+    for (int s = 0; s < 64; ++s) {
+        const F *row = cw + ((size_t) s * 32 + b) * N;
+        const F x = row[p], y = row[p + halfN];
+        h = hhash64(x.re, x.im, y.re, y.im, h);
+    }
+    const F x = mask[(size_t) b * N + p], y = mask[(size_t) b * N + p + halfN];
+    a.leaves[j][32 * p + b] = hhash64(x.re, x.im, y.re, y.im, h);
+}
+// The generated chain with the mask pair as its last block (vp_leaf_chain_mask_asm): k_leaf_hash / k_leaf_hash_multi's workgroup rules — one workgroup per CU, waves
+// in phase, a thread past the end runs the last leaf's chain and stores nothing.
+__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS)
+k_leaf_hash_m(const F *__restrict__ cw, u32 N, int n_slices, const F *__restrict__ mask, Dig *__restrict__ leaves) {
+    VP_LEAF_STAMP_BEGIN
+    const u32 halfN = N >> 1, total = 32 * halfN;
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 tc = t < total ? t : total - 1;
+    const u32 a = tc % halfN, b = tc / halfN;
+    const F *x = cw + (size_t) b * N + a, *m = mask + (size_t) b * N + a;
+    vp_leaf_chain_mask_asm(x, x + halfN, 32u * N * 16u, (unsigned) n_slices, m, m + halfN, leaves + (32 * a + b), t < total ? 1u : 0u);
+    VP_LEAF_STAMP_END(0u)
+}
+__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS) k_leaf_hash_multi_m(FriLeafMaskArgs ma) {
+    VP_LEAF_STAMP_BEGIN
+    const FriLeafArgs &a = ma.a;
+    const u32 total = a.leaf_start[a.n];
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x, gc = g < total ? g : total - 1;
+    int j = 0;
+    while (j + 1 < a.n && gc >= a.leaf_start[j + 1]) ++j;
+    const u32 t = gc - a.leaf_start[j], N = a.N[j];
+    const bool last = N == 1;
+    const u32 halfN = last ? 16u : N >> 1;
+    const u32 p = last ? t : t % halfN, b = last ? 0u : t / halfN;
+    const F *x = a.cw[j] + (size_t) b * N + p, *m = ma.mask[j] + (size_t) b * N + p;
+    vp_leaf_chain_mask_asm(x, x + halfN, 32u * N * 16u, 64u, m, m + halfN, a.leaves[j] + (last ? t : 32 * p + b), g < total ? 1u : 0u);
+    VP_LEAF_STAMP_END(1u)
+}
 __global__ void __launch_bounds__(VP_BLOCK) k_fill_f(F *__restrict__ p, u32 n, F v) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;

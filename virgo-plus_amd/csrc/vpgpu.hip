@@ -2089,7 +2089,7 @@ int vp_flush(vp_ctx *ctx, int count) {
 int vp_pc_hash_late(vp_ctx *ctx, int on) {
     if (!ctx) return VP_EINVAL;
     VP_ENTER_Q(ctx);
-    ctx->hash_late = on ? 1 : 0;                              // (what is unhashed stays so: vp_fri_commit, vp_flush with the mode off, or whatever needs a tree hashes it)
+    ctx->hash_late = on >= VP_HASH_LATE_MASKED ? 2 : on ? 1 : 0;      // (what is unhashed stays so: vp_fri_commit, vp_flush with the mode off, or whatever needs a tree hashes it)
     return VP_OK;
 }
 int vp_phase_ms(vp_ctx *ctx, double out[5]) {

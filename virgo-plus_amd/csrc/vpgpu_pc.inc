@@ -354,6 +354,8 @@ static inline int pc_leaf_prepare(vp_ctx *ctx) {                        // once 
     if (ctx->leaf_attr_done) return ctx->leaf_attr_done > 0 ? VP_OK : VP_EHIP;     // asks for more dynamic LDS than the default limit
     hipError_t err = hipFuncSetAttribute((const void *) k_leaf_hash, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_m, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_multi_m, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     ctx->leaf_attr_done = err == hipSuccess ? 1 : -1;
     if (err != hipSuccess) { ctx->err = "hipFuncSetAttribute (leaf hash)"; return VP_EHIP; }
     return VP_OK;
@@ -380,6 +382,30 @@ static inline u32 pc_launch_leaf_hash_multi(vp_ctx *ctx, FriLeafArgs &la) {     
     else hipLaunchKernelGGL(k_leaf_hash_multi_c, dim3(blocks), dim3(VP_BLOCK), 0, ctx->stream, la);
     return blocks;
 }
+// The same two with CONTENT in the mask slice (vp_commit_private_masked ...): `mask` is the slice's codeword of that oracle, coset-major like it.  The generated
+// chain with the mask pair as its last block under pc_leaf_wg's rules, k_leaf_hash_cm / k_leaf_hash_multi_cm (the compiler's form) everywhere else.
+static inline void pc_launch_leaf_hash_masked(vp_ctx *ctx, const F *cw, u32 N, const F *mask, Dig *leaves) {      // N = 1: the last FRI level
+    const u32 n_leaves = N >= 2 ? 16 * N : 16u, wg = N >= 2 ? pc_leaf_wg(ctx, n_leaves) : 0u;
+    if (wg && pc_leaf_prepare(ctx) == VP_OK) hipLaunchKernelGGL(k_leaf_hash_m, dim3(pc_leaf_blocks(wg, n_leaves)), dim3(wg), pc_leaf_lds(wg), ctx->stream, cw, N, 64, mask, leaves);
+    else hipLaunchKernelGGL(k_leaf_hash_cm, dim3(nblk(n_leaves)), dim3(VP_BLOCK), 0, ctx->stream, cw, N, 64, mask, leaves);
+}
+static inline u32 pc_launch_leaf_hash_multi_masked(vp_ctx *ctx, FriLeafMaskArgs &lm) {       // a.cw / a.leaves / a.N / a.n and mask filled in
+    FriLeafArgs &la = lm.a;
+    u64 all = 0;
+    for (int q = 0; q < la.n; ++q) all += la.N[q] >= 2 ? 16ull * la.N[q] : 16ull;
+    u32 wg = pc_leaf_wg(ctx, all);
+    if (wg && pc_leaf_prepare(ctx) != VP_OK) wg = 0;
+    u32 blocks = 0, leaves = 0;
+    for (int q = 0; q < la.n; ++q) {
+        const u32 nl = la.N[q] >= 2 ? 16 * la.N[q] : 16u;
+        la.blk_start[q] = blocks; la.leaf_start[q] = leaves;
+        blocks += nblk(nl); leaves += nl;
+    }
+    la.blk_start[la.n] = blocks; la.leaf_start[la.n] = leaves;
+    if (wg) { blocks = pc_leaf_blocks(wg, leaves); hipLaunchKernelGGL(k_leaf_hash_multi_m, dim3(blocks), dim3(wg), pc_leaf_lds(wg), ctx->stream, lm); }
+    else hipLaunchKernelGGL(k_leaf_hash_multi_cm, dim3(blocks), dim3(VP_BLOCK), 0, ctx->stream, lm);
+    return blocks;
+}
 
 int pc_merkle(vp_ctx *ctx, Dig *tree, u32 n_leaves) {    // leaves already at tree[n_leaves .. 2 n_leaves)
     u32 c = n_leaves >> 1;
@@ -403,7 +429,9 @@ int pc_hash_outstanding(vp_ctx *ctx, unsigned which) {
         if (!(which >> o & 1)) continue;
         const F *cw = o ? ctx->pc_hcw : ctx->pc_cw;
         Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
-        PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65, pc_launch_leaf_hash(ctx, cw, N, tree + n_leaves));
+        const F *mcw = ctx->pc_mask_ms ? (o ? ctx->pc_hm_cw : ctx->pc_lm_cw) : nullptr;      // a masked commitment: the mask slice's codeword of this oracle closes its chains
+        PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
+                if (mcw) pc_launch_leaf_hash_masked(ctx, cw, N, mcw, tree + n_leaves); else pc_launch_leaf_hash(ctx, cw, N, tree + n_leaves));
         VPCHK(pc_merkle(ctx, tree, n_leaves));
         HIPCHK(hipMemcpyAsync(got[o], tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -585,17 +613,13 @@ static int pc_mask_encode(vp_ctx *ctx, F *coef, u32 ms, F *dst) {
 static int pc_mask_lde(vp_ctx *ctx, const vp_F *mask, uint64_t n_mask, u32 ms, F *dst) {
     const int lm = ctx->L[0].bl - 1;
     for (uint64_t i = 0; i < n_mask; ++i) if (mask[i].real >= P61 || mask[i].img >= P61) { ctx->err = "non-canonical mask element"; return VP_EINVAL; }
-    std::vector<F> h(ms, f_zero());
-    for (uint64_t i = 0; i < n_mask; ++i) h[i] = f_make(mask[i].real, mask[i].img);
+    F *h = nullptr;                                     // pinned until the stream has taken it (ms <= 2^16: 1 MB): no wait here
+    VPCHK(ring_alloc(ctx, (size_t) ms * sizeof(F), (void **) &h));
+    for (uint64_t i = 0; i < ms; ++i) h[i] = i < n_mask ? f_make(mask[i].real, mask[i].img) : f_zero();
     F *t = ctx->pc_mtmp;
-    HIPCHK(hipMemcpyAsync(t, h.data(), (size_t) ms * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));          // (h goes out of scope)
+    HIPCHK(hipMemcpyAsync(t, h, (size_t) ms * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
     VPCHK(pc_launch_ntt(ctx, t, t + ctx->pc_mB, ilog2(ms), lm, 1, 1, 1, ms));
     return pc_mask_encode(ctx, t + ctx->pc_mB, ms, dst);
-}
-static inline void pc_launch_leaf_hash_masked(vp_ctx *ctx, const F *cw, u32 N, const F *mask, Dig *leaves) {      // N = 1: the last FRI level
-    const u32 n_leaves = N >= 2 ? 16 * N : 16u;
-    hipLaunchKernelGGL(k_leaf_hash_cm, dim3(nblk(n_leaves)), dim3(VP_BLOCK), 0, ctx->stream, cw, N, 64, mask, leaves);
 }
 
 // One whole FRI level, unprofiled: its leaf chains (Nc == 1: the 16 leaves of the last level; mask: the mask slice's pair closes every chain) and the tree
@@ -754,8 +778,8 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
     const int n = ctx->L[0].bl, lm = n - 1;
     const u32 N = 1u << (n - 6), M = 1u << lm;
     VPCHK(pc_hash_outstanding(ctx, 2u));                  // an h of an earlier call that no vp_fri_commit has hashed: its codeword is replaced below
-    if (!pub_mask) VPCHK(pc_live_zero_hcw(ctx));
-    const bool late = ctx->hash_late && !pub_mask;        // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels
+    VPCHK(pc_live_zero_hcw(ctx));                         // (a masked commitment runs over all 64: nothing to zero, and the mark says so afterwards)
+    const bool late = ctx->hash_late && (!pub_mask || ctx->hash_late >= 2);      // vp_pc_hash_late: the transforms only; vp_fri_commit hashes h with its own levels (a masked commit: VP_HASH_LATE_MASKED)
     // slices >= live are zero (vp_pc_live.h): l q, S, T, H, all_sum and h are zero with them
     PcSlices v = pc_slices(ctx, pub_mask ? 64u : ctx->pc_lv.live);
     F *d_inner = v.d_inner(), *d_all = v.d_all();
@@ -778,7 +802,8 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
         VPCHK(pc_launch_ntt(ctx, t + 2 * B, t + 4 * B, ilog2(2 * ms), lm, 1, 1, 1, 2 * ms));
         hipLaunchKernelGGL(k_mask_hcoef, dim3(nblk((u64) B)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (t + 4 * B), ms, (u32) B, f_make(ms, 0), t, S0m, d_all + 64);
         VPCHK(pc_mask_encode(ctx, t, ms, ctx->pc_hm_cw));
-        pc_launch_leaf_hash_masked(ctx, ctx->pc_hcw, N, ctx->pc_hm_cw, ctx->pc_tree_h + n_leaves);
+        if (!late) PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
+                           pc_launch_leaf_hash_masked(ctx, ctx->pc_hcw, N, ctx->pc_hm_cw, ctx->pc_tree_h + n_leaves));
     } else if (!late)
     PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
             pc_launch_leaf_hash(ctx, ctx->pc_hcw, N, ctx->pc_tree_h + n_leaves));
@@ -810,7 +835,7 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
                                    "which overflows at 2^26 wires"; return VP_ELIMIT; }
     const u32 N = 1u << ln, M = 1u << lm;
     VPCHK(pc_hash_outstanding(ctx, 3u));                  // an earlier commitment under vp_pc_hash_late whose codeword this call replaces
-    const bool late = ctx->hash_late && !mask;            // vp_pc_hash_late: the transforms only; vp_fri_commit hashes l with h and its own levels
+    const bool late = ctx->hash_late && (!mask || ctx->hash_late >= 2);      // vp_pc_hash_late: the transforms only; vp_fri_commit hashes l with h and its own levels (a masked commit: VP_HASH_LATE_MASKED)
     pc_live_set(ctx, mask != nullptr);
     const PcLive &lv = ctx->pc_lv;
     u32 ms = 0;
@@ -845,16 +870,16 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
     if (mask) {
         // the 65th slice: the padded mask's low-degree extension (poly_commit.h:74-86); its pairs close the leaf chains (fri.cpp:107-122)
         VPCHK(pc_mask_lde(ctx, mask, n_mask, ms, ctx->pc_lm_cw));
-        pc_launch_leaf_hash_masked(ctx, ctx->pc_cw, N, ctx->pc_lm_cw, ctx->pc_tree + n_leaves);
         ctx->pc_mask_ms = ms;
-    } else if (late) {
+    }
+    if (late) {
         ctx->pc_unhashed |= 1u; ctx->late_root[0] = root;
         ctx->pc_private_done = true; ++ctx->private_epoch;
         ctx->pc_public_done = false;
         return defer_end(ctx, ev_a, VP_PH_PRIVATE, [ctx](float ms) { ctx->commit_ms = ms; return VP_OK; });
     } else
     PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-            pc_launch_leaf_hash(ctx, ctx->pc_cw, N, ctx->pc_tree + n_leaves));
+            if (mask) pc_launch_leaf_hash_masked(ctx, ctx->pc_cw, N, ctx->pc_lm_cw, ctx->pc_tree + n_leaves); else pc_launch_leaf_hash(ctx, ctx->pc_cw, N, ctx->pc_tree + n_leaves));
     VPCHK(pc_merkle(ctx, ctx->pc_tree, n_leaves));
     void *st = nullptr;
     VPCHK(ring_alloc(ctx, 32, &st));
@@ -996,16 +1021,10 @@ int vp_commit_public_masked(vp_ctx *ctx, const vp_F *pub, uint64_t n_pub, const 
     return pc_commit_public_host(ctx, pub, n_pub, inner, all_sum, root_h, pub_mask, n_pub_mask);
 }
 
-int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
-    if (!ctx || !ctx->evaluated || !point || !inner || !all_sum || !root_h) return VP_EINVAL;
-    VP_ENTER_Q(ctx);
-    if (ctx->pc_mask_ms) { ctx->err = "vp_commit_public_eq: the private commitment carries a mask (vp_commit_public_masked)"; return VP_EINVAL; }
-    if (!(ctx->pcs ? pcs_private_done(ctx) : ctx->pc_private_done)) return VP_EINVAL;
+// vp_commit_public_eq / vp_commit_public_eq_masked behind their checks (unsharded; the point canonical, n coordinates): eq(point, .) built on the device, the 64
+// corners on the host, then the quotient pipeline (with the public mask, if there is one)
+static int pc_commit_public_eq_body(vp_ctx *ctx, const vp_F *point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32], const vp_F *pub_mask, uint64_t n_pub_mask) {
     const int n = ctx->L[0].bl;
-    if (n_point != n) return VP_EINVAL;
-    for (int i = 0; i < n; ++i) if (point[i].real >= P61 || point[i].img >= P61) { ctx->err = "vp_commit_public_eq: non-canonical coordinate"; return VP_EINVAL; }
-    // a sharded commitment: every rank is handed the point and builds what it needs of the table itself (pcs_commit_public)
-    if (ctx->pcs) { VPCHK(flush_pending(ctx, (size_t) -1)); return pcs_commit_public(ctx, nullptr, 0, point, inner, all_sum, root_h); }
     VPCHK(pc_public_alloc(ctx));
     // the public vector never crosses PCIe: eq(point, .) is built where it is consumed (two half tables by one workgroup, then one
     // product per entry — initBetaTable, src/utils.cpp:29-45)
@@ -1027,7 +1046,33 @@ int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner
     // reading them back — no wait for the device
     F corner[64];
     pc_eq_corners(hr, n, corner);
-    return pc_commit_public_body(ctx, ev_a, corner, 1, inner, all_sum, root_h);
+    return pc_commit_public_body(ctx, ev_a, corner, 1, inner, all_sum, root_h, pub_mask, n_pub_mask);
+}
+int vp_commit_public_eq(vp_ctx *ctx, const vp_F *point, int n_point, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
+    if (!ctx || !ctx->evaluated || !point || !inner || !all_sum || !root_h) return VP_EINVAL;
+    VP_ENTER_Q(ctx);
+    if (ctx->pc_mask_ms) { ctx->err = "vp_commit_public_eq: the private commitment carries a mask (vp_commit_public_eq_masked, vp_commit_public_masked)"; return VP_EINVAL; }
+    if (!(ctx->pcs ? pcs_private_done(ctx) : ctx->pc_private_done)) return VP_EINVAL;
+    const int n = ctx->L[0].bl;
+    if (n_point != n) return VP_EINVAL;
+    for (int i = 0; i < n; ++i) if (point[i].real >= P61 || point[i].img >= P61) { ctx->err = "vp_commit_public_eq: non-canonical coordinate"; return VP_EINVAL; }
+    // a sharded commitment: every rank is handed the point and builds what it needs of the table itself (pcs_commit_public)
+    if (ctx->pcs) { VPCHK(flush_pending(ctx, (size_t) -1)); return pcs_commit_public(ctx, nullptr, 0, point, inner, all_sum, root_h); }
+    return pc_commit_public_eq_body(ctx, point, inner, all_sum, root_h, nullptr, 0);
+}
+// vp_commit_public_masked on pub = eq(point, .) built on the device: vp_commit_public_eq's table and corners, vp_commit_public_masked's checks and limits.  Every
+// refusal comes before the first launch; the mask is copied during the call, so the call may be deferred like its unmasked twin.
+int vp_commit_public_eq_masked(vp_ctx *ctx, const vp_F *point, int n_point, const vp_F *pub_mask, uint64_t n_pub_mask, vp_F *inner, vp_F all_sum[65], uint8_t root_h[32]) {
+    if (!ctx || !ctx->evaluated || !point || !pub_mask || !inner || !all_sum || !root_h) return VP_EINVAL;
+    VP_ENTER_Q(ctx);
+    if (ctx->pcs) { ctx->err = "masked commitment: not on a sharded commitment"; return VP_EINVAL; }
+    if (!ctx->pc_mask_ms || !ctx->pc_private_done) { ctx->err = "vp_commit_public_eq_masked: vp_commit_private_masked first"; return VP_EINVAL; }
+    if (n_pub_mask < 1 || n_pub_mask > ctx->pc_mask_ms) { ctx->err = "public mask longer than the private commitment's padded mask"; return VP_EINVAL; }
+    const int n = ctx->L[0].bl;
+    if (n_point != n) return VP_EINVAL;
+    for (int i = 0; i < n; ++i) if (point[i].real >= P61 || point[i].img >= P61) { ctx->err = "vp_commit_public_eq_masked: non-canonical coordinate"; return VP_EINVAL; }
+    for (uint64_t i = 0; i < n_pub_mask; ++i) if (pub_mask[i].real >= P61 || pub_mask[i].img >= P61) { ctx->err = "non-canonical mask element"; return VP_EINVAL; }
+    return pc_commit_public_eq_body(ctx, point, inner, all_sum, root_h, pub_mask, n_pub_mask);
 }
 
 int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
@@ -1043,7 +1088,7 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         VPCHK(dalloc(ctx, &ctx->pc_fri_tree, (size_t) M));
     }
     const u32 live = ctx->pc_mask_ms ? 64u : ctx->pc_lv.live;      // slices >= live: a zero oracle and zero levels (vp_pc_live.h), kept as zero bytes
-    if (!ctx->pc_mask_ms) VPCHK(pc_live_zero_fri(ctx));
+    VPCHK(pc_live_zero_fri(ctx));                                   // (all 64 live under a mask: nothing to zero, and the mark says so afterwards)
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (ctx->fri_step < 0) {
         // virtual oracle in place over the q codeword; S_0 per slice sits behind all_sum in pc_small
@@ -1106,14 +1151,9 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     const u32 N = 1u << ln, M = 1u << lm;
     if (ctx->fri_step >= 0 && ctx->fri_step != 0) { ctx->err = "vp_fri_commit after vp_fri_step"; return VP_EINVAL; }
     if (n_steps > ln || n_steps > VP_FRI_MAX) { ctx->err = "too many FRI steps"; return VP_EINVAL; }
-    if (ctx->pc_mask_ms) {             // a commitment with a mask slice: the per-step path carries the 65th slice (the fused first folds and the all-level leaf launch do not)
-        VPCHK(flush_pending(ctx, (size_t) -1));
-        VPCHK(pc_hash_outstanding(ctx, 3u));
-        double ms_sum = 0;
-        for (int k = 0; k < n_steps; ++k) { VPCHK(vp_fri_step(ctx, r + k, roots + 32 * (size_t) k)); ms_sum += ctx->commit_ms; }
-        ctx->commit_ms = ms_sum;
-        return VP_OK;
-    }
+    // A commitment with a mask slice takes the same pass: its 64 slices through the folds below (all live), the 65th in arrays of its own behind them
+    // (k_mask_vo, k_fri_fold_one), and its pairs close the chains of the one leaf launch (FriLeafMaskArgs)
+    const bool masked = ctx->pc_mask_ms != 0;
     if (!ctx->pc_fri_all) {
         VPCHK(dalloc(ctx, &ctx->pc_fri_all, (size_t) 64 * M));
         VPCHK(dalloc(ctx, &ctx->pc_fri_tree, (size_t) M));
@@ -1133,7 +1173,8 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     // folds of every level, back to back
     const FriLayout fl(ln, 0);
     const PcSlices v = pc_slices(ctx, live);             // the first fold reads l, q, h, S_0 and the tensor pair through it
-    FriLeafArgs la{}; MerkleArgs ma{};
+    FriLeafMaskArgs lmk{}; MerkleArgs ma{};
+    FriLeafArgs &la = lmk.a;
     u32 blocks = 0;
     // vp_pc_hash_late: the oracles whose commit stopped behind its transforms go IN FRONT of the levels in the same lists — an l or h codeword is an entry
     // with N values per coset and 16 N leaves like a level's.  VP_FRI_MAX covers n_steps + 2 (n <= 25: 21 entries) and the u32 leaf offsets 3 x 2^23 leaves.
@@ -1146,6 +1187,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
         const u32 n_leaves = M >> 1;
         ma.tree[ne] = tree; ma.count[ne] = n_leaves;
+        lmk.mask[la.n] = masked ? (o ? ctx->pc_hm_cw : ctx->pc_lm_cw) : nullptr;
         la.cw[la.n] = o ? ctx->pc_hcw : ctx->pc_cw; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = N; blocks += nblk(n_leaves); ++la.n;
         late_root[ne] = ctx->late_root[o];
         ++ne;
@@ -1202,12 +1244,29 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         ma.tree[ne + k] = tree; ma.count[ne + k] = n_leaves;
         {   // every level, the single-value last one included, goes into the one leaf-hash launch (the chain of 65 Keccak-f is
             // a fixed ~1 ms latency however few leaves there are)
+            lmk.mask[la.n] = masked ? ctx->pc_fm + fl.mask(k) : nullptr;
             la.cw[la.n] = out; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
+        }
+    }
+    if (masked) {
+        // the mask slice behind them: its virtual oracle in place over its q codeword (poly_commit.h:225-245), then one fold per level (fri.cpp:366-374) — what
+        // vp_fri_step queues for it, without the waits in between
+        PC_PROF(VP_K_FRI_FOLD, nblk(M), 1, 64ull * M, 4ull * M,
+                hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
+                                   (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw));
+        for (int k = 0; k < n_steps; ++k) {
+            const u32 Nk = N >> k, No = Nk >> 1;
+            const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
+            F rf; memcpy(&rf, r + k, sizeof(F));
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) 32 * No), 1, 48ull * 32 * No, (u64) 3 * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, ctx->pc_fm + fl.mask(k), Nk, k, ctx->pc_rt, M >> 1, rf,
+                                       host_inv_real(2)));
         }
     }
     u64 all_leaves = 0;
     for (int k = 0; k < nt; ++k) all_leaves += ma.count[k];
-    if (la.n) PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65, pc_launch_leaf_hash_multi(ctx, la));
+    if (la.n) PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65,
+                      if (masked) pc_launch_leaf_hash_multi_masked(ctx, lmk); else pc_launch_leaf_hash_multi(ctx, la));
     if (merged) { ctx->pc_unhashed = 0; ctx->late_root[0] = ctx->late_root[1] = nullptr; }      // queued: whatever follows in stream order finds the trees
     // Merkle trees of all levels (and of the merged oracles), one launch per height while some tree still has more than 512 nodes at it
     for (;;) {

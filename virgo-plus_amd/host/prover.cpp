@@ -474,6 +474,15 @@ prover::hhash_digest prover::commit_public_eq(const std::vector<F> &point, F &in
     check(vp_commit_public_eq(ctx, cF(point.data()), (int) point.size(), mF(&inner_product_sum), mF(all_sum.data()), d.b), "vp_commit_public_eq");
     return d;
 }
+prover::hhash_digest prover::commit_public_eq(const std::vector<F> &point, const std::vector<F> &mask, F &inner_product_sum, std::vector<F> &all_sum) {
+    if (!masked) return commit_public_eq(point, inner_product_sum, all_sum);      // behind a zero private mask the public mask's slice is multiplied by zero everywhere
+    hhash_digest d;
+    all_sum.resize(65);
+    std::vector<F> one_zero(1, F_ZERO);
+    const std::vector<F> &m = mask.empty() ? one_zero : mask;
+    check(vp_commit_public_eq_masked(ctx, cF(point.data()), (int) point.size(), cF(m.data()), m.size(), mF(&inner_product_sum), mF(all_sum.data()), d.b), "vp_commit_public_eq_masked");
+    return d;
+}
 std::vector<F> prover::predicates(int layer, const std::vector<F> &r_g, const F &assert_random, const std::vector<F> &r_u,
                                   const std::vector<F> &r_v, int n_v) {
     std::vector<F> out(5 + 7 * (size_t) layer);

@@ -76,6 +76,10 @@ public:
     // extension: the protocol's own public vector, pub = eq(point, .) (src/verifier.cpp:368-369), built on the device from the point
     // (vp_commit_public_eq) — same outputs as commit_public on that table, nothing of it crosses PCIe
     hhash_digest commit_public_eq(const std::vector<F> &point, F &inner_product_sum, std::vector<F> &all_sum);
+    // the same behind commit_private(mask) with the public mask vector (vp_commit_public_eq_masked); behind a zero private mask it is the call above
+    hhash_digest commit_public_eq(const std::vector<F> &point, const std::vector<F> &mask, F &inner_product_sum, std::vector<F> &all_sum);
+    void setMasked(bool m) { masked = m; }               // vph_prove_protocol_masked commits through the C ABI itself (its roots are written late)
+    bool isMasked() const { return masked; }
     // poly_commit_prover::commit_phase pieces (vpd_verifier.cpp:44-74 -> fri::commit_phase_step / commit_phase_final)
     // verifier-side wiring predicates of one layer on the device (vp_predicates): 5 + 7*layer sums, see include/vpgpu.h
     std::vector<F> predicates(int layer, const std::vector<F> &r_g, const F &assert_random, const std::vector<F> &r_u,

@@ -316,6 +316,24 @@ int vph_commit_public_eq(vph_session *s, const uint64_t *point_pairs, int n_poin
     }
 }
 
+int vph_commit_public_eq_masked(vph_session *s, const uint64_t *point_pairs, int n_point, const uint64_t *mask_pairs, uint64_t n_mask, uint8_t *out, double *ms, char *err, int errlen) {
+    try {
+        std::vector<F> point((size_t) std::max(0, n_point)), mask(mask_pairs ? n_mask : 0), all_sum;
+        for (int i = 0; i < n_point; ++i) { point[i].real = point_pairs[2 * i]; point[i].img = point_pairs[2 * i + 1]; }
+        for (u64 i = 0; i < mask.size(); ++i) { mask[i].real = mask_pairs[2 * i]; mask[i].img = mask_pairs[2 * i + 1]; }
+        F inner;
+        prover::hhash_digest d = s->p->commit_public_eq(point, mask, inner, all_sum);
+        memcpy(out, d.b, 32);
+        memcpy(out + 32, &inner, 16);
+        memcpy(out + 48, all_sum.data(), 65 * 16);
+        if (ms) *ms = s->p->commitDeviceMs();
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
 int vph_fri_open_many(vph_session *s, int n, const int32_t *oracle, const uint64_t *leaf, uint64_t *values_pairs, uint8_t *paths, int path_stride,
                       int32_t *path_len, char *err, int errlen) {
     try {
@@ -542,11 +560,17 @@ int vph_draw_protocol_tape(vph_session *s) {
 // sec[6] = whole pass (host wall clock) | commit_private | GKR | commit_public | fft_gkr (host time of its begin + end) | FRI commit phase + final;
 // synchronous: host wall clock of each call, deferred: device time of each call (vp_phase_ms).  The fft_gkr messages stay with the session
 // (vph_last_fft_gkr), the FRI data too (vph_last_fri).  0 = done, < 0 = error.
-int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
-                          uint64_t *final_pairs, double sec[6], int flags, char *err, int errlen) {
+// pri_mask / pub_mask: the mask vectors of a hiding commitment (vph_prove_protocol_masked; null or all zero: the reference's own pass, one zero element)
+static int prove_protocol_pass(vph_session *s, const uint64_t *pri_mask, uint64_t n_pri, const uint64_t *pub_mask, uint64_t n_pub, uint8_t *transcript, uint64_t capacity,
+                               uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *final_mask_pairs, double sec[6], int flags,
+                               char *err, int errlen) {
     if (s->p->commitmentSharded()) { set_err(err, errlen, "vph_prove_protocol: not on a session with a sharded commitment (vph_prove_and_verify_full runs it)"); return -1; }
     vp_ctx *ctx = s->p->context();
     const bool defer = (flags & VPH_PASS_DEFERRED) != 0, queue_next = defer && (flags & VPH_PASS_QUEUE_NEXT) != 0;
+    bool with_mask = false;
+    for (uint64_t i = 0; pri_mask && i < 2 * n_pri; ++i) with_mask = with_mask || pri_mask[i] != 0;
+    // the queued head of the next pass is a vp_commit_private of the same witness: it would have to carry this pass's mask, which the caller owns
+    if (with_mask && (flags & VPH_PASS_QUEUE_NEXT)) { set_err(err, errlen, "vph_prove_protocol_masked: VPH_PASS_QUEUE_NEXT is not available with a mask (the queued head is an unmasked commit_private)"); return -1; }
     // a run of fft_gkr that is begun and not collected when this function leaves, for whatever reason, is dropped (it would make every later pass of the
     // session fail with "not collected")
     struct FftGuard { prover *p; bool armed; ~FftGuard() { if (armed) p->fftGkrCancel(); } } fft_guard{s->p.get(), false};
@@ -570,18 +594,24 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         chk(vp_set_deferred(ctx, defer ? 1 : 0), "vp_set_deferred");
         // the pass hashes once: commit_private and commit_public_eq stop behind their transforms, vp_fri_commit hashes l, h and its levels in one launch and
         // writes pp_root_l / pp_root_h with its own roots (VPH_PASS_HASH_PER_CALL / VPH_HASH_PER_CALL: every call hashes its own oracle, as before)
-        chk(vp_pc_hash_late(ctx, hash_once ? 1 : 0), "vp_pc_hash_late");
+        chk(vp_pc_hash_late(ctx, hash_once ? (with_mask ? VP_HASH_LATE_MASKED : 1) : 0), "vp_pc_hash_late");
         // ---- head: fft_gkr (depends on the verifier's draws only: queued on its own stream, its small launches run in the gaps of everything below;
         // VPH_FFT_GKR_SYNC=1: in the reference's place, between commit_public and the FRI folds) and commit_private (src/verifier.cpp:137) —
         // unless the previous pass queued them for this one and that commitment still stands
         uint64_t epoch = 0; int valid = 0;
         chk(vp_commit_private_state(ctx, &epoch, &valid), "vp_commit_private_state");
-        const bool have_head = s->head_queued && valid && epoch == s->head_epoch;
+        const bool have_head = !with_mask && s->head_queued && valid && epoch == s->head_epoch;     // (a masked pass commits anew: the queued head carries no mask)
         s->head_queued = false;
         auto t = clk::now();
         double s_fft = 0, s_priv = 0, s_gkr = 0, s_pub = 0, s_fri = 0;
-        if (!have_head) {
+        if (with_mask) {
+            // the 65th slice with content (the call reads the mask and completes at once, whatever the mode; under hash_once its leaf chains wait for vp_fri_commit)
+            chk(vp_commit_private_masked(ctx, reinterpret_cast<const vp_F *>(pri_mask), n_pri, s->pp_root_l), "vp_commit_private_masked");
+            s->p->setMasked(true);
+            s_priv = since(t);
+        } else if (!have_head) {
             chk(vp_commit_private(ctx, s->pp_root_l), "vp_commit_private");
+            s->p->setMasked(false);
             s_priv = since(t);
         }
         // ---- GKR (src/verifier.cpp:144-169)
@@ -599,6 +629,12 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         s->last_point.assign(s->tape.end() - max_bl, s->tape.end() - max_bl + n);
         // ---- commit_public on eq(r_liu, .) (:368-379)
         t = clk::now();
+        if (with_mask) {
+            static const uint64_t one_zero[2] = {0, 0};
+            const bool have_pub = pub_mask && n_pub;
+            chk(vp_commit_public_eq_masked(ctx, reinterpret_cast<const vp_F *>(s->last_point.data()), n, reinterpret_cast<const vp_F *>(have_pub ? pub_mask : one_zero), have_pub ? n_pub : 1,
+                                           reinterpret_cast<vp_F *>(&s->pp_inner), reinterpret_cast<vp_F *>(s->pp_all.data()), s->pp_root_h), "vp_commit_public_eq_masked");
+        } else
         chk(vp_commit_public_eq(ctx, reinterpret_cast<const vp_F *>(s->last_point.data()), n, reinterpret_cast<vp_F *>(&s->pp_inner),
                                 reinterpret_cast<vp_F *>(s->pp_all.data()), s->pp_root_h), "vp_commit_public_eq");
         s_pub = since(t);
@@ -625,6 +661,10 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
             s_priv = ms[0] * 1e-3; s_gkr = ms[1] * 1e-3; s_pub = ms[2] * 1e-3; s_fri = (ms[3] + ms[4]) * 1e-3;
         }
         chk(vp_set_deferred(ctx, 0), "vp_set_deferred");      // the mode belongs to this pass: whatever the session calls next waits for its results as usual
+        if (final_mask_pairs) {                               // the mask slice's last codeword: zeros without a mask (and a queued head has replaced the commitment by now)
+            if (with_mask) chk(vp_fri_final_mask(ctx, reinterpret_cast<vp_F *>(final_mask_pairs)), "vp_fri_final_mask");
+            else memset(final_mask_pairs, 0, 32 * sizeof(F));
+        }
         // fft_gkr is collected last: its launches had the whole pass to run beside the main stream's
         if (!fft_sync) { t = clk::now(); fft_guard.armed = false; s->fft_gkr_msgs = s->p->fftGkrEnd(ln); s_fft += since(t); }
         const uint64_t total = 32 + s->pp_written + 32 + 16 + 65 * 16;
@@ -652,6 +692,15 @@ int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity
         set_err(err, errlen, e.what());
         return -2;
     }
+}
+int vph_prove_protocol_ex(vph_session *s, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
+                          uint64_t *final_pairs, double sec[6], int flags, char *err, int errlen) {
+    return prove_protocol_pass(s, nullptr, 0, nullptr, 0, transcript, capacity, n_written, fri_roots, roots_cap, final_pairs, nullptr, sec, flags, err, errlen);
+}
+int vph_prove_protocol_masked(vph_session *s, const uint64_t *pri_mask_pairs, uint64_t n_pri, const uint64_t *pub_mask_pairs, uint64_t n_pub, uint8_t *transcript, uint64_t capacity,
+                              uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *final_mask_pairs, double sec[6], int flags,
+                              char *err, int errlen) {
+    return prove_protocol_pass(s, pri_mask_pairs, n_pri, pub_mask_pairs, n_pub, transcript, capacity, n_written, fri_roots, roots_cap, final_pairs, final_mask_pairs, sec, flags, err, errlen);
 }
 int vph_prove_protocol(vph_session *s, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
                        uint64_t *final_pairs, double sec[6], char *err, int errlen) {

@@ -141,6 +141,10 @@ int vph_fri_commit_batched(vph_session *, const uint64_t *r_pairs, int n_steps, 
  * vp_fri_query with their layouts (path_stride in bytes, a multiple of 32).                                                                      */
 int vph_commit_private_masked(vph_session *, const uint64_t *mask_pairs, uint64_t n_mask, uint8_t root[32], double *ms, char *err, int errlen);
 int vph_commit_public_eq(vph_session *, const uint64_t *point_pairs, int n_point, uint8_t out[32 + 16 + 65 * 16], double *ms, char *err, int errlen);
+/* prover::commit_public_eq(point, mask, ...): behind vph_commit_private_masked with a non-zero mask, vp_commit_public_eq_masked (mask_pairs null or n_mask = 0: one
+ * zero element); behind a zero private mask it is vph_commit_public_eq, whatever the public mask.  Same layout of `out`.                                          */
+int vph_commit_public_eq_masked(vph_session *, const uint64_t *point_pairs, int n_point, const uint64_t *mask_pairs, uint64_t n_mask, uint8_t out[32 + 16 + 65 * 16],
+                                double *ms, char *err, int errlen);
 int vph_fri_open_many(vph_session *, int n, const int32_t *oracle, const uint64_t *leaf, uint64_t *values_pairs, uint8_t *paths, int path_stride,
                       int32_t *path_len, char *err, int errlen);
 int vph_fri_query(vph_session *, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written, char *err, int errlen);
@@ -172,6 +176,16 @@ int vph_prove_protocol(vph_session *, uint8_t *transcript, uint64_t capacity, ui
 enum { VPH_PASS_DEFERRED = 1, VPH_PASS_QUEUE_NEXT = 2, VPH_PASS_HASH_PER_CALL = 4 };
 int vph_prove_protocol_ex(vph_session *, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap,
                           uint64_t *final_pairs, double sec[6], int flags, char *err, int errlen);
+/* The same pass with the mask vectors of a hiding commitment (include/vpgpu.h, "the mask slice with CONTENT"): vp_commit_private_masked(pri_mask) ->
+ * batched GKR -> vp_commit_public_eq_masked(r_liu, pub_mask; null or n_pub = 0: one zero element) -> fft_gkr -> the one-pass FRI commit phase, whose single leaf
+ * launch closes every chain with the mask slice's pair.  Outputs and sec[] as vph_prove_protocol_ex; final_mask_pairs (may be null): the mask slice's last
+ * codeword, 32 elements (vp_fri_final_mask).  flags as above, with two differences: the masked commit_private reads the caller's mask and completes at once in
+ * every mode (under hash-once its leaf chains still wait for the FRI call), and VPH_PASS_QUEUE_NEXT is refused (-1, message) — the queued head is an unmasked
+ * commit_private of the same witness, and a head queued by an earlier pass is not used.  A null or all-zero private mask is vph_prove_protocol_ex, byte for byte
+ * (final_mask_pairs: zeros), QUEUE_NEXT included.                                                                                                               */
+int vph_prove_protocol_masked(vph_session *, const uint64_t *pri_mask_pairs, uint64_t n_pri, const uint64_t *pub_mask_pairs, uint64_t n_pub, uint8_t *transcript,
+                              uint64_t capacity, uint64_t *n_written, uint8_t *fri_roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *final_mask_pairs /* 32 */,
+                              double sec[6], int flags, char *err, int errlen);
 /* No GPU needed: F::init(), draw the tape for `circuit`, replay the host verifier over `transcript`
  * (GKR slice).  0 = accepted, 1 = rejected.                                                            */
 int vph_verify_transcript(vph_circuit *, const uint8_t *transcript, uint64_t n, int skip_predicates);
