@@ -12,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import test_gpu_masked_fast_path as masked
 import test_gpu_parity as parity
 from conftest import GOLDEN, ROOT
 
@@ -267,6 +268,58 @@ def test_masked_commitment_ignores_the_mode(abi):
     assert got == want
     abi.mode(0)
     abi.private()                                               # the next test starts from an unmasked commitment
+
+
+# ---- 2b. the unmasked chain at each workgroup form ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [18, 19, 20])
+def test_asm_chain_at_each_workgroup_form(vp, n):
+    """The generated chain that ends in the all-zero block (vp_leaf_chain_asm), every form it is launched in — the unmasked twin of
+    test_gpu_masked_fast_path.py::test_asm_mask_chain_at_each_workgroup_form, on arbitrary uniform inputs:
+         per call — one oracle per launch: the compiler's form at n = 18, 2^17 leaves at n = 19 (512 threads + LDS blocker), 2^18 at n = 20 (1024 threads);
+         vp_pc_hash_late(1) — the merged launch: 3 x 2^16 - 16 leaves at n = 18 (512 threads), 3 x 2^17 - 16 at n = 19 and 3 x 2^18 - 16 at n = 20 (1024
+         threads; no multiple of 1024: the last workgroup's clamped tail runs and stores nothing).
+    Reference: the same input on a context created with VP_LEAF_ASM=0 — every root, the FRI roots, the final codeword and 16 openings per oracle.
+    Independently, for the 42 leaves the masked test picks (the ends of l and h, the ends of coset blocks, the first two levels, leaves 0 and 15 of the
+    single-value last level), hashlib.sha3_256 over the 64 opened pairs and the zero pair equals the path's leaf entry."""
+    st = n - 6
+    vals, point, r = masked._uniform(1 << n, 800 + n), masked._uniform(n, 900 + n), masked._uniform(st, 1000 + n)
+    req = masked._requests(n, st, 16)
+
+    def run(c, late):
+        assert c.L.vp_pc_hash_late(c.ctx, 1 if late else 0) == 0
+        c.commit_private()
+        c.commit_public_eq(point)
+        roots = c.fri_commit(r)
+        assert c.L.vp_pc_hash_late(c.ctx, 0) == 0
+        fin = np.zeros((2048, 2), np.uint64)
+        assert c.L.vp_fri_final(c.ctx, fin.ctypes.data) == 0, c.err()
+        return c.state(), roots, fin.tobytes()
+
+    ref = masked.Ctx(vp, vals, n, env={"VP_LEAF_ASM": "0"})
+    try:
+        want = run(ref, False)
+        wv, wp, wl = ref.open_many(req)
+    finally:
+        ref.close()
+    c = masked.Ctx(vp, vals, n)
+    try:
+        for late in (False, True):
+            assert run(c, late) == want, ("late" if late else "per call")
+            v, p, pl = c.open_many(req)
+            assert np.array_equal(v, wv) and np.array_equal(p, wp) and np.array_equal(pl, wl), late
+            pick = {(o, lf) for o in (0, 1) for lf in masked._leaves_of(1 << (n - 2), 16)}
+            pick |= {(o, lf) for o in (2, 3) for lf in masked._leaves_of(16 * ((1 << (n - 6)) >> (o - 1)), 4)}
+            pick |= {(2 + st - 1, 0), (2 + st - 1, 15)}
+            checked = 0
+            for i, (o, lf) in enumerate(req):
+                if (o, lf) in pick:
+                    pairs = np.zeros((130, 2), np.uint64)
+                    pairs[:128] = v[i][:128]                                    # the 64 slices' pairs; the 65th block is the zero pair
+                    assert p[i, 32 * (pl[i] - 1):32 * pl[i]].tobytes() == masked._sha3_leaf(pairs), (late, o, lf)
+                    checked += 1
+            assert checked == len(pick) == 42
+    finally:
+        c.close()
 
 
 # ---- 3. passes that queue the next pass's head ------------------------------------------------------------------------------------------------

@@ -103,9 +103,13 @@ def test_new_symbols_are_declared_with_their_signatures_and_exported(vp):
 
 
 def test_masked_kernels_are_in_the_code_object_and_options_abi_is_unchanged(vp):
+    """The leaf-hash family of the code object: the generated chain without and with the mask pair (the two instantiations of k_leaf_hash<MASK>, by their
+    mangled template arguments) and the compiler's form — and none of the single-purpose copies they replaced."""
     data = open(vp.LIB_GPU, "rb").read()
-    for k in (b"k_leaf_hash_m", b"k_leaf_hash_multi_m", b"k_leaf_hash_multi_cm", b"k_leaf_hash_cm"):
+    for k in (b"11k_leaf_hashILb0EE", b"11k_leaf_hashILb1EE", b"13k_leaf_hash_cE"):
         assert k in data, k
+    for k in (b"k_leaf_hash_multi", b"k_leaf_hash_m", b"k_leaf_hash_cm", b"k_leaf_hash_final", b"k_merkle_level_multi", b"k_merkle_top_multi"):
+        assert k not in data, k
     o = vp.Options()
     assert ctypes.sizeof(vp.Options) == 4 * (2 + 12 + 4) == o.struct_size
     hdr = open(os.path.join(ROOT, "include", "vpgpu.h")).read()

@@ -4,7 +4,8 @@
 Needs the diagnostic build of the library (stamps in the leaf-hash kernels only, written to a buffer of their own):
     hipcc ... -DVP_LEAF_STAMPS -o tools/_build/stamps/libvpgpu.so virgo-plus_amd/csrc/vpgpu.hip
     VP_LIBGPU=tools/_build/stamps/libvpgpu.so python tools/leaf_in_step.py [BLOCKS]
-Every workgroup of k_leaf_hash / k_leaf_hash_multi stamps {s_memtime, s_memrealtime} before and after its 65-step chains.  Per launch this prints the
+Every workgroup of k_leaf_hash<> stamps {s_memtime, s_memrealtime} before and after its 65-step chains, tagged by whether its launch hashes one oracle
+(reported as k_leaf_hash) or a list of several (reported as k_leaf_hash_multi, the merged launch).  Per launch this prints the
 launch's duration by the 100 MHz real-time counter (first workgroup in -> last workgroup out), the median duration of one workgroup in shader
 cycles (work: it does not depend on the clock) and the median effective shader clock d(memtime) / d(memrealtime) x 100 MHz of its workgroups —
 (a) inside the protocol step (commit_private -> GKR -> commit_public -> fft_gkr -> FRI; one launch for l, h and the FRI levels), after >= 2 s of

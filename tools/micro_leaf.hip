@@ -1,4 +1,4 @@
-// The product's two leaf-hash kernels (k_leaf_hash: generated fixed-register chains in phase; k_leaf_hash_c: the compiler's Keccak-f) on a synthetic
+// The product's two leaf-hash kernels (k_leaf_hash<false>: generated fixed-register chains in phase; k_leaf_hash_c: the compiler's Keccak-f) on a synthetic
 // codeword of the x1024 geometry (64 slices x 32 cosets x 2^17 values: 2^21 leaves), alternating.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -o tools/_build/micro_leaf tools/micro_leaf.hip
 #include <hip/hip_runtime.h>
@@ -23,11 +23,14 @@ int main(int argc, char **argv) {
     hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, cw, n_el); CK(hipDeviceSynchronize());
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     float best[2] = {1e9f, 1e9f};
+    FriLeafArgs la{};                                  // one oracle: a list of one (the maps as pc_hash_leaves fills them)
+    la.cw[0] = cw; la.N[0] = N; la.n = 1; la.blk_start[1] = (n_leaves + 255) / 256; la.leaf_start[1] = n_leaves;
     for (int rep = 0; rep < 6; ++rep) {
         for (int v = 0; v < 2; ++v) {
             CK(hipEventRecord(e0));
-            if (v == 0) hipLaunchKernelGGL(k_leaf_hash_c, dim3((n_leaves + 255) / 256), dim3(256), 0, 0, cw, N, 64, o1);
-            else hipLaunchKernelGGL(k_leaf_hash, dim3((n_leaves + 1023) / 1024), dim3(1024), 0, 0, cw, N, 64, o2);
+            la.leaves[0] = v ? o2 : o1;
+            if (v == 0) hipLaunchKernelGGL(k_leaf_hash_c, dim3((n_leaves + 255) / 256), dim3(256), 0, 0, la);
+            else hipLaunchKernelGGL(k_leaf_hash<false>, dim3((n_leaves + 1023) / 1024), dim3(1024), 0, 0, la);
             CK(hipEventRecord(e1)); CK(hipDeviceSynchronize());
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             if (rep) best[v] = ms < best[v] ? ms : best[v];

@@ -7,12 +7,14 @@ import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
 ming = float(sys.argv[2]) if len(sys.argv) > 2 else 5.0
 rows = [(n.split("(")[0].replace("vp::", "").replace("void ", ""), s, e) for n, s, e in db.execute("select name, start, end from kernels order by start")]
-# a step starts at the inverse transform of commit_private: k_ntt8_cols<true> whose predecessor chain contains k_leaf_hash_multi (end of the previous step's FRI)
+# a step starts at the inverse transform of commit_private: the first k_ntt8_cols<true> behind a fold of the previous step's FRI phase (k_fri_fold0_vo3,
+# k_fri_fold0_vo, k_fri_fold).  The folds mark the FRI phase whether the pass hashes once or every commit hashes its own oracle; the leaf-hash launch does
+# not (k_leaf_hash<> is the kernel of the single-oracle launches too, and commit_public has inverse transforms of its own).
 starts = []
-seen_multi = True
+seen_fri = True
 for i, (n, s, e) in enumerate(rows):
-    if "k_leaf_hash_multi" in n: seen_multi = True
-    if n.startswith("k_ntt8_cols<true>") and seen_multi: starts.append(i); seen_multi = False
+    if n.startswith("k_fri_fold"): seen_fri = True
+    if n.startswith("k_ntt8_cols<true>") and seen_fri: starts.append(i); seen_fri = False
 if len(starts) < 3: sys.exit("need three steps in the trace (found %d starts)" % len(starts))
 for w in (3, 2):
     lo, hi = starts[-w], starts[-w + 1]

@@ -263,65 +263,79 @@ __device__ __forceinline__ Dig hhash64(u64 m0, u64 m1, u64 m2, u64 m3, const Dig
 }
 
 // Leaf hashes of fri::request_init_commit (fri.cpp:95-124): leaf j chains the 64 slices' pairs
-// (cw[s][j], cw[s][j + half]) and then the mask slice's pair (all zero here, src/prover.cpp:526).
+// (cw[s][j], cw[s][j + half]) and then the mask slice's pair (all zero in the protocol's own calls, src/prover.cpp:526).
 // The codeword is coset-major: cw[(s*32 + b)*N + a] = value at position 32a + b; position j + half is (a + N/2, b).
 // Thread t -> (b, a) with a fastest (coalesced loads); the digest goes to the natural leaf index 32a + b.
-__global__ void __launch_bounds__(VP_BLOCK)
-k_leaf_hash_c(const F *__restrict__ cw, u32 N, int n_slices, Dig *__restrict__ leaves) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 halfN = N >> 1;
-    if (t >= 32 * halfN) return;
-    const u32 a = t % halfN, b = t / halfN;
-    Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-    for (int s = 0; s < n_slices; ++s) {
-        const F *row = cw + ((size_t) s * 32 + b) * N;
-        F x = f_zero(), y = f_zero();
-        if (VP_CHK(a + halfN < N && b < 32, 7, a, b, N)) { x = row[a]; y = row[a + halfN]; }
-        h = hhash64(x.re, x.im, y.re, y.im, h);
-    }
-    h = hhash64(0, 0, 0, 0, h);                       // mask slice (zero polynomial)
-    leaves[32 * a + b] = h;
-}
-
-// One Merkle level (merkle_tree.cpp:40-50): parent[i] = H(child[2i] || child[2i+1]); heap layout, root at index 1.
-// Batched commit phase (vp_fri_commit): with every challenge known up front the folds of all levels run back to back, and
-// ONE launch hashes the leaves of all levels — the 65 chained Keccak-f of a leaf are a fixed latency (~0.8 ms for a lone
-// wave) that the per-step path pays once per level.
+// The last FRI level (N == 1) keeps ONE value per coset (32 per slice); its 16 leaves pair coset t with coset t + 16.
+//
+// Every leaf-hash kernel takes a LIST of oracles (FriLeafArgs), and a single oracle is a list of one.  With every challenge known up front
+// (vp_fri_commit) the folds of all levels run back to back and ONE launch hashes the leaves of l, h and all levels — the 65 chained Keccak-f of
+// a leaf are a fixed latency (~0.8 ms for a lone wave) that a launch per level pays once per level.  mask[q] is the mask slice's codeword of
+// entry q, coset-major like its oracle's (m[b N + a], m[b N + a + N / 2]; the last level: m[t], m[t + 16]) — the 65th slice of a commitment
+// with CONTENT in its mask (vp_commit_private_masked ...); null means the zero block.  The caller fills cw / leaves / N / mask / n, pc_hash_leaves
+// (vpgpu_pc.inc) the two maps.
 #define VP_FRI_MAX 32
-struct FriLeafArgs { const F *cw[VP_FRI_MAX]; Dig *leaves[VP_FRI_MAX]; u32 N[VP_FRI_MAX]; u32 blk_start[VP_FRI_MAX + 1]; u32 leaf_start[VP_FRI_MAX + 1]; int n; };     // blk_start: k_leaf_hash_multi_c, leaf_start: k_leaf_hash_multi
-__global__ void __launch_bounds__(VP_BLOCK) k_leaf_hash_multi_c(FriLeafArgs a) {
+struct FriLeafArgs {
+    const F *cw[VP_FRI_MAX]; Dig *leaves[VP_FRI_MAX]; u32 N[VP_FRI_MAX];
+    u32 blk_start[VP_FRI_MAX + 1];                    // k_leaf_hash_c: the first workgroup of entry q
+    u32 leaf_start[VP_FRI_MAX + 1];                   // k_leaf_hash<>: the first leaf of entry q, the entries laid end to end
+    int n;
+    const F *mask[VP_FRI_MAX];                        // the last member: only the code that closes a chain with a mask pair reads it
+};
+// The compiler's form of the chains: the cross-check (leaf_asm = 0), launches below 2^17 leaves and the checked build.  Workgroups are dealt per entry.
+__global__ void __launch_bounds__(VP_BLOCK) k_leaf_hash_c(FriLeafArgs a) {
     int j = 0;
     while (j + 1 < a.n && blockIdx.x >= a.blk_start[j + 1]) ++j;
     const u32 t = (blockIdx.x - a.blk_start[j]) * blockDim.x + threadIdx.x;
-    const u32 N = a.N[j], halfN = N >> 1;
-    const F *cw = a.cw[j];
+    const u32 N = a.N[j];
+    const bool last = N == 1;
+    const u32 halfN = last ? 16u : N >> 1;            // distance between the two values of a pair
+    if (t >= (last ? 16u : 32 * halfN)) return;
+    const u32 p = last ? t : t % halfN, b = last ? 0u : t / halfN;
+    const size_t at = (size_t) b * N + p;
+    const bool inside = VP_CHK(p + halfN < (last ? 32u : N) && b < 32, 7, p, b, N);
     Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-    if (N == 1) {                                     // last level: one value per coset, leaf j pairs cosets j and j + 16
-        if (t >= 16) return;
-        for (int s = 0; s < 64; ++s) {
-            const F x = cw[(size_t) s * 32 + t], y = cw[(size_t) s * 32 + t + 16];
-            h = hhash64(x.re, x.im, y.re, y.im, h);
-        }
-        h = hhash64(0, 0, 0, 0, h);
-        a.leaves[j][t] = h;
-        return;
-    }
-    if (t >= 32 * halfN) return;
-    const u32 p = t % halfN, b = t / halfN;
     for (int s = 0; s < 64; ++s) {
-        const F *row = cw + ((size_t) s * 32 + b) * N;
-        const F x = row[p], y = row[p + halfN];
+        const F *row = a.cw[j] + (size_t) s * 32 * N;
+        F x = f_zero(), y = f_zero();
+        if (inside) { x = row[at]; y = row[at + halfN]; }
         h = hhash64(x.re, x.im, y.re, y.im, h);
     }
-    h = hhash64(0, 0, 0, 0, h);
-    a.leaves[j][32 * p + b] = h;
+    F x = f_zero(), y = f_zero();                     // the mask slice's pair (the zero polynomial without one)
+    if (const F *m = a.mask[j]; m && inside) { x = m[at]; y = m[at + halfN]; }
+    a.leaves[j][last ? t : 32 * p + b] = hhash64(x.re, x.im, y.re, y.im, h);
 }
+
+// Merkle trees (merkle_tree.cpp:40-50): parent[i] = H(child[2i] || child[2i+1]); heap layout, root at index 1.  Both kernels take a list of trees like the
+// leaf hashes (a single tree is a list of one).  k_merkle_level writes ONE level of every tree: count[q] nodes, workgroups dealt per tree (blk_start).
+// k_merkle_top finishes every tree in one workgroup each: count[q] <= 1024 nodes are there, the levels above them down to the root follow, and the root
+// also goes to roots[q] unless roots is null.
 struct MerkleArgs { Dig *tree[VP_FRI_MAX]; u32 count[VP_FRI_MAX]; u32 blk_start[VP_FRI_MAX + 1]; int n; };
+__global__ void __launch_bounds__(VP_BLOCK) k_merkle_level(MerkleArgs a) {
+    int j = 0;
+    while (j + 1 < a.n && blockIdx.x >= a.blk_start[j + 1]) ++j;
+    const u32 i = (blockIdx.x - a.blk_start[j]) * blockDim.x + threadIdx.x, c = a.count[j];
+    if (i >= c) return;
+    Dig *tree = a.tree[j];
+    const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
+    tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
+}
+__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top(MerkleArgs a, Dig *roots) {
+    Dig *tree = a.tree[blockIdx.x];
+    for (u32 c = a.count[blockIdx.x] >> 1; c >= 1; c >>= 1) {
+        for (u32 i = threadIdx.x; i < c; i += blockDim.x) {
+            const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
+            tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
+        }
+        __syncthreads();
+    }
+    if (roots && threadIdx.x == 0) roots[blockIdx.x] = tree[1];
+}
+
 // Round 4: the same leaf chains by the generated fixed-register block (vp_keccak_asm.h, tools/gen_keccak_asm.py): workgroups of 1024 threads, one per
 // CU, whose sixteen waves rotate (v_alignbit_b32, half rate) and do logic (v_bitop3_b32 / v_xor_b32, full rate) IN PHASE — a SIMD with waves in
 // both kinds of code at once issues everything at the rotation's rate.  x1024: 14.3 -> 11.6 ms per 2^21-leaf tree, digests unchanged.  A thread past
-// the end runs the chain of the last leaf (it must keep step with its workgroup) and stores nothing.  k_leaf_hash_c / k_leaf_hash_multi_c above are
-// the compiler's form of the same chains: the cross-check (leaf_asm = 0) and the checked build.
+// the end runs the chain of the last leaf (it must keep step with its workgroup) and stores nothing.
 #ifdef VP_LEAF_STAMPS
 // Diagnostic build only (tools/leaf_in_step.py; MI355X_MICROARCH.md, DVFS item 6): every workgroup of the leaf-hash kernels leaves
 // {s_memtime, s_memrealtime} from before and after its chains in a buffer of its own that nothing else reads; the effective shader clock of the
@@ -336,20 +350,10 @@ __device__ unsigned int g_leaf_stamp_n;
 #define VP_LEAF_STAMP_BEGIN
 #define VP_LEAF_STAMP_END(tag)
 #endif
-__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS)
-k_leaf_hash(const F *__restrict__ cw, u32 N, int n_slices, Dig *__restrict__ leaves) {
-    VP_LEAF_STAMP_BEGIN
-    const u32 halfN = N >> 1, total = 32 * halfN;
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 tc = t < total ? t : total - 1;
-    const u32 a = tc % halfN, b = tc / halfN;
-    const F *x = cw + (size_t) b * N + a;
-    vp_leaf_chain_asm(x, x + halfN, 32u * N * 16u, (unsigned) n_slices, leaves + (32 * a + b), t < total ? 1u : 0u);
-    VP_LEAF_STAMP_END(0u)
-}
-// All levels of the FRI commit phase in one launch: thread g takes leaf g of the levels laid end to end (leaf_start), so that the launch is exactly
-// ceil(leaves / workgroup) workgroups — a level of 16 leaves does not cost a workgroup (and with it a CU for the whole chain) of its own.
-__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS) k_leaf_hash_multi(FriLeafArgs a) {
+// Thread g takes leaf g of the entries laid end to end (leaf_start), so that the launch is exactly ceil(leaves / workgroup) workgroups — a level of 16
+// leaves does not cost a workgroup (and with it a CU for the whole chain) of its own.  MASK: every entry has a mask codeword, and the chain ends in its pair
+// (vp_leaf_chain_mask_asm) where the other one ends in the all-zero block (vp_leaf_chain_asm).
+template <bool MASK> __global__ void __launch_bounds__(VP_LEAF_ASM_THREADS) k_leaf_hash(FriLeafArgs a) {
     VP_LEAF_STAMP_BEGIN
     const u32 total = a.leaf_start[a.n];
     const u32 g = blockIdx.x * blockDim.x + threadIdx.x, gc = g < total ? g : total - 1;
@@ -362,44 +366,12 @@ __global__ void __launch_bounds__(VP_LEAF_ASM_THREADS) k_leaf_hash_multi(FriLeaf
     const u32 halfN = last ? 16u : N >> 1;
     const u32 p = last ? t : t % halfN, b = last ? 0u : t / halfN;
     const F *x = cw + (size_t) b * N + p;
-    vp_leaf_chain_asm(x, x + halfN, 32u * N * 16u, 64u, a.leaves[j] + (last ? t : 32 * p + b), g < total ? 1u : 0u);
-    VP_LEAF_STAMP_END(1u)
-}
-__global__ void __launch_bounds__(VP_BLOCK) k_merkle_level_multi(MerkleArgs a) {
-    int j = 0;
-    while (j + 1 < a.n && blockIdx.x >= a.blk_start[j + 1]) ++j;
-    const u32 i = (blockIdx.x - a.blk_start[j]) * blockDim.x + threadIdx.x, c = a.count[j];
-    if (i >= c) return;
-    Dig *tree = a.tree[j];
-    const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
-    tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
-}
-__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top_multi(MerkleArgs a, Dig *roots) {     // one workgroup per tree
-    Dig *tree = a.tree[blockIdx.x];
-    for (u32 c = a.count[blockIdx.x] >> 1; c >= 1; c >>= 1) {
-        for (u32 i = threadIdx.x; i < c; i += blockDim.x) {
-            const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
-            tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) roots[blockIdx.x] = tree[1];
-}
-__global__ void __launch_bounds__(VP_BLOCK) k_merkle_level(Dig *tree, u32 level_start, u32 count) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const Dig l = tree[2 * (level_start + i)], r = tree[2 * (level_start + i) + 1];
-    tree[level_start + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
-}
-// The top of the tree (<= 1024 leaves at `level_start`) in one workgroup.
-__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top(Dig *tree, u32 count) {
-    for (u32 c = count >> 1; c >= 1; c >>= 1) {
-        for (u32 i = threadIdx.x; i < c; i += blockDim.x) {
-            const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
-            tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
-        }
-        __syncthreads();
-    }
+    if constexpr (MASK) {
+        const F *m = a.mask[j] + (size_t) b * N + p;
+        vp_leaf_chain_mask_asm(x, x + halfN, 32u * N * 16u, 64u, m, m + halfN, a.leaves[j] + (last ? t : 32 * p + b), g < total ? 1u : 0u);
+    } else
+        vp_leaf_chain_asm(x, x + halfN, 32u * N * 16u, 64u, a.leaves[j] + (last ? t : 32 * p + b), g < total ? 1u : 0u);
+    VP_LEAF_STAMP_END(a.n > 1 ? 1u : 0u)              // single oracle / merged launch (tools/leaf_in_step.py)
 }
 
 __global__ void k_test_sha3(const u64 *__restrict__ in, u64 *__restrict__ out, u32 n) {
@@ -673,19 +645,6 @@ k_fri_fold0_vo3(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *_
         // next first barrier (which wave 0 reaches after the reads above): no barrier of its own at the end of the loop
     }
 }
-// The last fold leaves ONE value per coset (32 per slice); its 16 leaves pair coset b with coset b + 16.
-__global__ void k_leaf_hash_final(const F *__restrict__ cw, int n_slices, Dig *__restrict__ leaves) {
-    const u32 j = threadIdx.x;
-    if (j >= 16) return;
-    Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-    for (int s = 0; s < n_slices; ++s) {
-        const F x = cw[(size_t) s * 32 + j], y = cw[(size_t) s * 32 + j + 16];
-        h = hhash64(x.re, x.im, y.re, y.im, h);
-    }
-    h = hhash64(0, 0, 0, 0, h);
-    leaves[j] = h;
-}
-
 }  // namespace vp
 
 // ---- transforms longer than the LDS (2^13 < N <= 2^17): N = N1 * N2 with N1 = 2^l1 <= 16, N2 = 2^13 --------
@@ -845,89 +804,9 @@ k_pc_open_many(const PcOpenDesc *__restrict__ tab, u32 n_oracles, const uint2 *_
 }
 
 // ---- the mask slice WITH CONTENT (round 6; lib/virgo/src/poly_commit.h:42,55-86,138-161,187-191, fri.cpp:96-124,366-386,403-411) --------------------------------
-// The protocol's own calls pass one zero (src/prover.cpp:526, src/verifier.cpp:375-377) and take the kernels above; a caller that hands vp_commit_private_masked /
+// The protocol's own calls pass one zero (src/prover.cpp:526, src/verifier.cpp:375-377) and leave FriLeafArgs::mask null; a caller that hands vp_commit_private_masked /
 // vp_commit_public_masked a non-zero mask gets a 65th slice through every piece of the commitment.  The slice lives in arrays of its own (coset-major like the
-// others: m[b * Nk + a] = value at position 32 a + b), so nothing of the 64-slice path changes shape.
-// Leaf chains with the mask slice's pair as the last block (the compiler's form: the generated chains end in the all-zero block).
-__global__ void __launch_bounds__(VP_BLOCK)
-k_leaf_hash_cm(const F *__restrict__ cw, u32 N, int n_slices, const F *__restrict__ mask, Dig *__restrict__ leaves) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (N == 1) {                                     // last FRI level: one value per coset, leaf j pairs cosets j and j + 16
-        if (t >= 16) return;
-        Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-        for (int s = 0; s < n_slices; ++s) { const F x = cw[(size_t) s * 32 + t], y = cw[(size_t) s * 32 + t + 16]; h = hhash64(x.re, x.im, y.re, y.im, h); }
-        const F x = mask[t], y = mask[t + 16];
-        leaves[t] = hhash64(x.re, x.im, y.re, y.im, h);
-        return;
-    }
-    const u32 halfN = N >> 1;
-    if (t >= 32 * halfN) return;
-    const u32 a = t % halfN, b = t / halfN;
-    Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-    for (int s = 0; s < n_slices; ++s) {
-        const F *row = cw + ((size_t) s * 32 + b) * N;
-        const F x = row[a], y = row[a + halfN];
-        h = hhash64(x.re, x.im, y.re, y.im, h);
-    }
-    const F x = mask[(size_t) b * N + a], y = mask[(size_t) b * N + a + halfN];
-    leaves[32 * a + b] = hhash64(x.re, x.im, y.re, y.im, h);
-}
-// Several oracles with their mask slices in one launch (the masked vp_fri_commit: l, h and every level): FriLeafArgs and one mask codeword per entry, coset-major
-// like its oracle's (m[b N + a], m[b N + a + N / 2]; the last level: m[t], m[t + 16]).  The compiler's form, blocks dealt per entry (blk_start).
-struct FriLeafMaskArgs { FriLeafArgs a; const F *mask[VP_FRI_MAX]; };
-__global__ void __launch_bounds__(VP_BLOCK) k_leaf_hash_multi_cm(FriLeafMaskArgs ma) {
-    const FriLeafArgs &a = ma.a;
-    int j = 0;
-    while (j + 1 < a.n && blockIdx.x >= a.blk_start[j + 1]) ++j;
-    const u32 t = (blockIdx.x - a.blk_start[j]) * blockDim.x + threadIdx.x;
-    const u32 N = a.N[j], halfN = N >> 1;
-    const F *cw = a.cw[j], *mask = ma.mask[j];
-    Dig h; h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0;
-    if (N == 1) {
-        if (t >= 16) return;
-        for (int s = 0; s < 64; ++s) { const F x = cw[(size_t) s * 32 + t], y = cw[(size_t) s * 32 + t + 16]; h = hhash64(x.re, x.im, y.re, y.im, h); }
-        const F x = mask[t], y = mask[t + 16];
-        a.leaves[j][t] = hhash64(x.re, x.im, y.re, y.im, h);
-        return;
-    }
-    if (t >= 32 * halfN) return;
-    const u32 p = t % halfN, b = t / halfN;
-    for (int s = 0; s < 64; ++s) {
-        const F *row = cw + ((size_t) s * 32 + b) * N;
-        const F x = row[p], y = row[p + halfN];
-        h = hhash64(x.re, x.im, y.re, y.im, h);
-    }
-    const F x = mask[(size_t) b * N + p], y = mask[(size_t) b * N + p + halfN];
-    a.leaves[j][32 * p + b] = hhash64(x.re, x.im, y.re, y.im, h);
-}
-// The generated chain with the mask pair as its last block (vp_leaf_chain_mask_asm): k_leaf_hash / k_leaf_hash_multi's workgroup rules — one workgroup per CU, waves
-// in phase, a thread past the end runs the last leaf's chain and stores nothing.
-__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS)
-k_leaf_hash_m(const F *__restrict__ cw, u32 N, int n_slices, const F *__restrict__ mask, Dig *__restrict__ leaves) {
-    VP_LEAF_STAMP_BEGIN
-    const u32 halfN = N >> 1, total = 32 * halfN;
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 tc = t < total ? t : total - 1;
-    const u32 a = tc % halfN, b = tc / halfN;
-    const F *x = cw + (size_t) b * N + a, *m = mask + (size_t) b * N + a;
-    vp_leaf_chain_mask_asm(x, x + halfN, 32u * N * 16u, (unsigned) n_slices, m, m + halfN, leaves + (32 * a + b), t < total ? 1u : 0u);
-    VP_LEAF_STAMP_END(0u)
-}
-__global__ void __launch_bounds__(VP_LEAF_ASM_THREADS) k_leaf_hash_multi_m(FriLeafMaskArgs ma) {
-    VP_LEAF_STAMP_BEGIN
-    const FriLeafArgs &a = ma.a;
-    const u32 total = a.leaf_start[a.n];
-    const u32 g = blockIdx.x * blockDim.x + threadIdx.x, gc = g < total ? g : total - 1;
-    int j = 0;
-    while (j + 1 < a.n && gc >= a.leaf_start[j + 1]) ++j;
-    const u32 t = gc - a.leaf_start[j], N = a.N[j];
-    const bool last = N == 1;
-    const u32 halfN = last ? 16u : N >> 1;
-    const u32 p = last ? t : t % halfN, b = last ? 0u : t / halfN;
-    const F *x = a.cw[j] + (size_t) b * N + p, *m = ma.mask[j] + (size_t) b * N + p;
-    vp_leaf_chain_mask_asm(x, x + halfN, 32u * N * 16u, 64u, m, m + halfN, a.leaves[j] + (last ? t : 32 * p + b), g < total ? 1u : 0u);
-    VP_LEAF_STAMP_END(1u)
-}
+// others: m[b * Nk + a] = value at position 32 a + b), so nothing of the 64-slice path changes shape; its pairs close the leaf chains through FriLeafArgs::mask.
 __global__ void __launch_bounds__(VP_BLOCK) k_fill_f(F *__restrict__ p, u32 n, F v) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;

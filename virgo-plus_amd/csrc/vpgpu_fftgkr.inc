@@ -351,13 +351,12 @@ static void warm_kernel_functions() {
     static const void *const fns[] = {
         // commitment
         (const void *) k_ntt8_colsx<6>, (const void *) k_ntt8_colsx<7>, (const void *) k_ntt8_colsx<8>, (const void *) k_ntt8_cols<true>, (const void *) k_ntt8_cols<false>,
-        (const void *) k_ntt8_rows<true>, (const void *) k_ntt8_rows<false>, (const void *) k_ntt_lds, (const void *) k_leaf_hash, (const void *) k_leaf_hash_multi,
-        (const void *) k_leaf_hash_c, (const void *) k_leaf_hash_multi_c, (const void *) k_leaf_hash_final, (const void *) k_merkle_level, (const void *) k_merkle_top,
-        (const void *) k_merkle_level_multi, (const void *) k_merkle_top_multi, (const void *) k_pc_products, (const void *) k_pc_quotient, (const void *) k_pc_rank1_check,
+        (const void *) k_ntt8_rows<true>, (const void *) k_ntt8_rows<false>, (const void *) k_ntt_lds, (const void *) k_leaf_hash<false>, (const void *) k_leaf_hash<true>,
+        (const void *) k_leaf_hash_c, (const void *) k_merkle_level, (const void *) k_merkle_top, (const void *) k_pc_products, (const void *) k_pc_quotient, (const void *) k_pc_rank1_check,
         (const void *) k_pc_dot, (const void *) k_pc_sum_parts, (const void *) k_pc_open, (const void *) k_beta_half, (const void *) k_beta_expand, (const void *) k_zero_f,
         (const void *) k_fri_fold, (const void *) k_fri_fold0_vo, (const void *) k_fri_fold0_vo3<true, VP_VO_GRP>, (const void *) k_fri_fold0_vo3<false, VP_VO_GRP>, (const void *) k_fri_fold0_vo3<true, 1>, (const void *) k_fri_fold0_vo3<false, 1>,
-        // the commitment with a mask slice
-        (const void *) k_leaf_hash_m, (const void *) k_leaf_hash_multi_m, (const void *) k_leaf_hash_cm, (const void *) k_leaf_hash_multi_cm, (const void *) k_mask_vo, (const void *) k_fri_fold_one,
+        // the commitment with a mask slice (its leaf chains: k_leaf_hash<true> above)
+        (const void *) k_mask_vo, (const void *) k_fri_fold_one,
         // fft_gkr
         (const void *) k_fg_pows, (const void *) k_fg_expand, (const void *) k_fg_butterfly, (const void *) k_fg_xsq, (const void *) k_fg_xtab, (const void *) k_fg_polyeval,
         (const void *) k_fg_rowsum, (const void *) k_fg_gtab, (const void *) k_fg_add_init, (const void *) k_fg_mul_init, (const void *) k_fg_gtab_multi, (const void *) k_fg_dot_multi,

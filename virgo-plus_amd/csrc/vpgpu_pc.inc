@@ -19,13 +19,15 @@ constexpr int PC_MAX_LN = 13;            // largest in-LDS transform (2^13 x 16 
 #endif
 constexpr int PC_SPLIT_LN = VP_NTT_SPLIT_LOG;
 
-// profiled calls (vp_set_profiling): every launch of the commitment is bracketed with events on the library stream
-#define PC_PROF(kind, grid, jobs, bytes, work, launch)                                                   \
+// profiled calls (vp_set_profiling): every launch of the commitment is bracketed with events on the library stream (PC_PROF_IF: where the caller says so —
+// the per-step FRI path leaves some launches out of the table)
+#define PC_PROF_IF(on, kind, grid, jobs, bytes, work, ...)                                               \
     do {                                                                                                  \
-        const int sl_ = prof_begin(ctx, ctx->stream, (kind), (u32) (grid), (u32) (jobs), (u64) (bytes), (u64) (work)); \
-        launch;                                                                                           \
+        const int sl_ = (on) ? prof_begin(ctx, ctx->stream, (kind), (u32) (grid), (u32) (jobs), (u64) (bytes), (u64) (work)) : -1; \
+        __VA_ARGS__;                                      /* the launch */                                \
         prof_end(ctx, ctx->stream, sl_);                                                                  \
     } while (0)
+#define PC_PROF(kind, grid, jobs, bytes, work, ...) PC_PROF_IF(true, kind, grid, jobs, bytes, work, __VA_ARGS__)
 
 F host_pow(F x, unsigned __int128 e) { F r = f_one(); while (e) { if (e & 1) r = f_mul(r, x); x = f_mul(x, x); e >>= 1; } return r; }
 F host_root_of_unity(int log_order) {    // fieldElement::getRootOfUnity (fieldElement.cpp:237-249)
@@ -352,66 +354,77 @@ static inline u32 pc_leaf_wg(const vp_ctx *ctx, u64 n_leaves) {        // thread
 static inline size_t pc_leaf_lds(u32 wg) { return wg == 1024 ? 0 : 96 * 1024; }
 static inline int pc_leaf_prepare(vp_ctx *ctx) {                        // once per context (the attribute belongs to the device the context sits on): the 512-thread form
     if (ctx->leaf_attr_done) return ctx->leaf_attr_done > 0 ? VP_OK : VP_EHIP;     // asks for more dynamic LDS than the default limit
-    hipError_t err = hipFuncSetAttribute((const void *) k_leaf_hash, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_m, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash_multi_m, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    hipError_t err = hipFuncSetAttribute((const void *) k_leaf_hash<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    if (err == hipSuccess) err = hipFuncSetAttribute((const void *) k_leaf_hash<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     ctx->leaf_attr_done = err == hipSuccess ? 1 : -1;
     if (err != hipSuccess) { ctx->err = "hipFuncSetAttribute (leaf hash)"; return VP_EHIP; }
     return VP_OK;
 }
-static inline u32 pc_leaf_blocks(u32 wg, u64 n_leaves) { const u32 th = wg ? wg : VP_BLOCK; return (u32) ((n_leaves + th - 1) / th); }
-static inline void pc_launch_leaf_hash(vp_ctx *ctx, const F *cw, u32 N, Dig *leaves) {      // N >= 2: 16 N leaves
-    const u32 n_leaves = 16 * N, wg = pc_leaf_wg(ctx, n_leaves);
-    if (wg && pc_leaf_prepare(ctx) == VP_OK) hipLaunchKernelGGL(k_leaf_hash, dim3(pc_leaf_blocks(wg, n_leaves)), dim3(wg), pc_leaf_lds(wg), ctx->stream, cw, N, 64, leaves);
-    else hipLaunchKernelGGL(k_leaf_hash_c, dim3(nblk(n_leaves)), dim3(VP_BLOCK), 0, ctx->stream, cw, N, 64, leaves);
-}
-static inline u32 pc_launch_leaf_hash_multi(vp_ctx *ctx, FriLeafArgs &la) {                  // cw / leaves / N / n filled in: block map by workgroup size here
-    u64 all = 0;
-    for (int q = 0; q < la.n; ++q) all += la.N[q] >= 2 ? 16ull * la.N[q] : 16ull;
-    u32 wg = pc_leaf_wg(ctx, all);
-    if (wg && pc_leaf_prepare(ctx) != VP_OK) wg = 0;
+// THE leaf-hash launch: la.cw / leaves / N / mask / n filled in (N[q] values per coset: 16 N[q] leaves, 16 at the last FRI level's N[q] = 1; one oracle is a
+// list of one).  The workgroup form goes by the launch's leaves together (pc_leaf_wg), the mask chain runs iff the entries carry mask codewords (all or none),
+// and the launch-table row, when asked for, counts workgroups of the compiler's form whichever kernel runs: what every call site has always recorded.
+static int pc_hash_leaves(vp_ctx *ctx, FriLeafArgs &la, bool profiled) {
+    if (la.n < 1) return VP_OK;
     u32 blocks = 0, leaves = 0;
+    int n_masked = 0;
     for (int q = 0; q < la.n; ++q) {
         const u32 nl = la.N[q] >= 2 ? 16 * la.N[q] : 16u;
         la.blk_start[q] = blocks; la.leaf_start[q] = leaves;
         blocks += nblk(nl); leaves += nl;
+        if (la.mask[q]) ++n_masked;
     }
     la.blk_start[la.n] = blocks; la.leaf_start[la.n] = leaves;
-    if (wg) { blocks = pc_leaf_blocks(wg, leaves); hipLaunchKernelGGL(k_leaf_hash_multi, dim3(blocks), dim3(wg), pc_leaf_lds(wg), ctx->stream, la); }
-    else hipLaunchKernelGGL(k_leaf_hash_multi_c, dim3(blocks), dim3(VP_BLOCK), 0, ctx->stream, la);
-    return blocks;
-}
-// The same two with CONTENT in the mask slice (vp_commit_private_masked ...): `mask` is the slice's codeword of that oracle, coset-major like it.  The generated
-// chain with the mask pair as its last block under pc_leaf_wg's rules, k_leaf_hash_cm / k_leaf_hash_multi_cm (the compiler's form) everywhere else.
-static inline void pc_launch_leaf_hash_masked(vp_ctx *ctx, const F *cw, u32 N, const F *mask, Dig *leaves) {      // N = 1: the last FRI level
-    const u32 n_leaves = N >= 2 ? 16 * N : 16u, wg = N >= 2 ? pc_leaf_wg(ctx, n_leaves) : 0u;
-    if (wg && pc_leaf_prepare(ctx) == VP_OK) hipLaunchKernelGGL(k_leaf_hash_m, dim3(pc_leaf_blocks(wg, n_leaves)), dim3(wg), pc_leaf_lds(wg), ctx->stream, cw, N, 64, mask, leaves);
-    else hipLaunchKernelGGL(k_leaf_hash_cm, dim3(nblk(n_leaves)), dim3(VP_BLOCK), 0, ctx->stream, cw, N, 64, mask, leaves);
-}
-static inline u32 pc_launch_leaf_hash_multi_masked(vp_ctx *ctx, FriLeafMaskArgs &lm) {       // a.cw / a.leaves / a.N / a.n and mask filled in
-    FriLeafArgs &la = lm.a;
-    u64 all = 0;
-    for (int q = 0; q < la.n; ++q) all += la.N[q] >= 2 ? 16ull * la.N[q] : 16ull;
-    u32 wg = pc_leaf_wg(ctx, all);
+    if (n_masked && n_masked != la.n) { ctx->err = "internal: leaf-hash entries with and without a mask slice in one launch"; return VP_EINVAL; }
+    u32 wg = pc_leaf_wg(ctx, leaves);
     if (wg && pc_leaf_prepare(ctx) != VP_OK) wg = 0;
-    u32 blocks = 0, leaves = 0;
-    for (int q = 0; q < la.n; ++q) {
-        const u32 nl = la.N[q] >= 2 ? 16 * la.N[q] : 16u;
-        la.blk_start[q] = blocks; la.leaf_start[q] = leaves;
-        blocks += nblk(nl); leaves += nl;
-    }
-    la.blk_start[la.n] = blocks; la.leaf_start[la.n] = leaves;
-    if (wg) { blocks = pc_leaf_blocks(wg, leaves); hipLaunchKernelGGL(k_leaf_hash_multi_m, dim3(blocks), dim3(wg), pc_leaf_lds(wg), ctx->stream, lm); }
-    else hipLaunchKernelGGL(k_leaf_hash_multi_cm, dim3(blocks), dim3(VP_BLOCK), 0, ctx->stream, lm);
-    return blocks;
+    const void *kernel = !wg ? (const void *) k_leaf_hash_c : n_masked ? (const void *) k_leaf_hash<true> : (const void *) k_leaf_hash<false>;
+    void *args[] = {&la};
+    PC_PROF_IF(profiled, VP_K_LEAF_HASH, blocks, la.n, (u64) leaves * (64 * 32 + 32), (u64) leaves * 65,
+               (void) hipLaunchKernel(kernel, dim3(wg ? (leaves + wg - 1) / wg : blocks), dim3(wg ? wg : VP_BLOCK), args, wg ? pc_leaf_lds(wg) : 0, ctx->stream));
+    return VP_OK;
 }
 
-int pc_merkle(vp_ctx *ctx, Dig *tree, u32 n_leaves) {    // leaves already at tree[n_leaves .. 2 n_leaves)
-    u32 c = n_leaves >> 1;
-    for (; c > 512; c >>= 1)
-        PC_PROF(VP_K_MERKLE, nblk(c), 1, 96ull * c, c, hipLaunchKernelGGL(k_merkle_level, dim3(nblk(c)), dim3(VP_BLOCK), 0, ctx->stream, tree, c, c));
-    if (c >= 1) PC_PROF(VP_K_MERKLE, 1, 1, 96ull * 2 * c, 2 * c - 1, hipLaunchKernelGGL(k_merkle_top, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, tree, 2 * c));
+// Merkle trees over leaves already in place: ma.tree / count / n filled in, count[q] leaves at tree[q][count .. 2 count) (at least 2).  One k_merkle_level
+// launch per height while any tree has more than 512 nodes there, then one k_merkle_top launch for all trees; root q also lands in d_roots[q] unless d_roots
+// is null.  levels >= 0: exactly that many level launches whatever the width, and no top (the local part of a sharded tree).  ma.count is used up.
+static int pc_merkle_trees(vp_ctx *ctx, MerkleArgs &ma, Dig *d_roots, int levels = -1) {
+    for (int h = 0; levels < 0 || h < levels; ++h) {
+        MerkleArgs lv{}; u32 b = 0; u64 hs = 0;
+        for (int q = 0; q < ma.n; ++q) {
+            const u32 c = ma.count[q] >> 1;
+            if (levels < 0 && c <= 512) continue;
+            lv.tree[lv.n] = ma.tree[q]; lv.count[lv.n] = c; lv.blk_start[lv.n] = b; b += nblk(c); hs += c; ++lv.n;
+            ma.count[q] = c;
+        }
+        if (!lv.n) break;
+        lv.blk_start[lv.n] = b;
+        PC_PROF(VP_K_MERKLE, b, lv.n, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_level, dim3(b), dim3(VP_BLOCK), 0, ctx->stream, lv));
+    }
+    if (levels >= 0) return VP_OK;
+    u64 hs = 0;
+    for (int q = 0; q < ma.n; ++q) hs += ma.count[q] - 1;
+    // (the row's bytes: 96 per hash where the roots are collected, 96 per node of the widest level where they are not — the two forms this launch had)
+    PC_PROF(VP_K_MERKLE, ma.n, ma.n, 96ull * (d_roots ? hs : hs + ma.n), hs, hipLaunchKernelGGL(k_merkle_top, dim3(ma.n), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots));
+    return VP_OK;
+}
+int pc_merkle(vp_ctx *ctx, Dig *tree, u32 n_leaves) {    // one tree, leaves already at tree[n_leaves .. 2 n_leaves); the root stays at tree[1]
+    MerkleArgs ma{};
+    ma.tree[0] = tree; ma.count[0] = n_leaves; ma.n = 1;
+    return pc_merkle_trees(ctx, ma, nullptr);
+}
+
+// Oracle o (0 = l, 1 = h) hashed now, by a launch of its own: leaf chains (closed by the oracle's mask codeword under a masked commitment), tree, and the
+// root on its way to `root` (host memory that outlives the stream's work).  The synchronous commits and whatever vp_pc_hash_late left unhashed come here.
+static int pc_hash_oracle(vp_ctx *ctx, int o, void *root) {
+    const int n = ctx->L[0].bl;
+    const u32 n_leaves = 1u << (n - 2);
+    Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
+    FriLeafArgs la{};
+    la.cw[0] = o ? ctx->pc_hcw : ctx->pc_cw; la.leaves[0] = tree + n_leaves; la.N[0] = 1u << (n - 6); la.n = 1;
+    if (ctx->pc_mask_ms) la.mask[0] = o ? ctx->pc_hm_cw : ctx->pc_lm_cw;
+    VPCHK(pc_hash_leaves(ctx, la, true));
+    VPCHK(pc_merkle(ctx, tree, n_leaves));
+    HIPCHK(hipMemcpyAsync(root, tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
     return VP_OK;
 }
 
@@ -422,19 +435,8 @@ int pc_hash_outstanding(vp_ctx *ctx, unsigned which) {
     which &= ctx->pc_unhashed;
     if (!which) return VP_OK;
     if (ctx->L.empty() || !ctx->pc_cw || !ctx->pc_tree) { ctx->pc_unhashed = 0; ctx->err = "internal: unhashed oracle without its codeword"; return VP_EINVAL; }
-    const int n = ctx->L[0].bl;
-    const u32 N = 1u << (n - 6), n_leaves = 1u << (n - 2);
     uint8_t got[2][32];
-    for (int o = 0; o < 2; ++o) {
-        if (!(which >> o & 1)) continue;
-        const F *cw = o ? ctx->pc_hcw : ctx->pc_cw;
-        Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
-        const F *mcw = ctx->pc_mask_ms ? (o ? ctx->pc_hm_cw : ctx->pc_lm_cw) : nullptr;      // a masked commitment: the mask slice's codeword of this oracle closes its chains
-        PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-                if (mcw) pc_launch_leaf_hash_masked(ctx, cw, N, mcw, tree + n_leaves); else pc_launch_leaf_hash(ctx, cw, N, tree + n_leaves));
-        VPCHK(pc_merkle(ctx, tree, n_leaves));
-        HIPCHK(hipMemcpyAsync(got[o], tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
+    for (int o = 0; o < 2; ++o) if (which >> o & 1) VPCHK(pc_hash_oracle(ctx, o, got[o]));
     ctx->pc_unhashed &= ~which;
     VPCHK(check_stream(ctx));
     for (int o = 0; o < 2; ++o) if ((which >> o & 1) && ctx->late_root[o]) { memcpy(ctx->late_root[o], got[o], 32); ctx->late_root[o] = nullptr; }
@@ -622,13 +624,34 @@ static int pc_mask_lde(vp_ctx *ctx, const vp_F *mask, uint64_t n_mask, u32 ms, F
     return pc_mask_encode(ctx, t + ctx->pc_mB, ms, dst);
 }
 
-// One whole FRI level, unprofiled: its leaf chains (Nc == 1: the 16 leaves of the last level; mask: the mask slice's pair closes every chain) and the tree
+// One whole FRI level by launches of its own (vp_fri_step, the tail of a sharded commitment): its leaf chains, which stay out of the launch table
+// (Nc == 1: the 16 leaves of the last level; mask: the mask slice's pair closes every chain), and the tree
 static int pc_hash_level(vp_ctx *ctx, const F *cw, u32 Nc, const F *mask, Dig *tree) {
     const u32 n_leaves = 16 * Nc;
-    if (mask) pc_launch_leaf_hash_masked(ctx, cw, Nc, mask, tree + n_leaves);
-    else if (Nc >= 2) pc_launch_leaf_hash(ctx, cw, Nc, tree + n_leaves);
-    else hipLaunchKernelGGL(k_leaf_hash_final, dim3(1), dim3(64), 0, ctx->stream, cw, 64, tree + n_leaves);
+    FriLeafArgs la{};
+    la.cw[0] = cw; la.leaves[0] = tree + n_leaves; la.N[0] = Nc; la.mask[0] = mask; la.n = 1;
+    VPCHK(pc_hash_leaves(ctx, la, false));
     return pc_merkle(ctx, tree, n_leaves);
+}
+// The mask slice (the 65th) in the FRI commit phase, in arrays of its own behind the 64: its virtual oracle in place over its q codeword
+// (poly_commit.h:225-245), then one fold per level like the others (fri.cpp:366-374); pc_mask_fold returns level k's codeword, whose pairs close the
+// level's leaf chains (fri.cpp:403-411)
+static void pc_mask_vo(vp_ctx *ctx, bool profiled) {
+    const int n = ctx->L[0].bl;
+    const u32 N = 1u << (n - 6), M = 1u << (n - 1);
+    PC_PROF_IF(profiled, VP_K_FRI_FOLD, nblk(M), 1, 64ull * M, 4ull * M,
+               hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
+                                  (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw));
+}
+static const F *pc_mask_fold(vp_ctx *ctx, int k, F r, bool profiled) {
+    const int n = ctx->L[0].bl;
+    const FriLayout fl(n - 6, 0);
+    const u32 M = 1u << (n - 1), Nk = (1u << (n - 6)) >> k, No = Nk >> 1;
+    const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
+    F *out_m = ctx->pc_fm + fl.mask(k);
+    PC_PROF_IF(profiled, VP_K_FRI_FOLD, nblk((u64) 32 * No), 1, 48ull * 32 * No, (u64) 3 * 32 * No,
+               hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, r, host_inv_real(2)));
+    return out_m;
 }
 // the last level's codeword ([slice][32], one value per coset) in the reference's order: out[(i << 7) | (slice << 1) | hi] = value at position i + 16 hi
 static void pc_final_order(const F *cw, vp_F *final_code) {
@@ -789,8 +812,6 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
     hipLaunchKernelGGL(k_pc_sum_parts, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, v.small, g, d_inner);
     VPCHK(pc_quotient_slices(ctx, v, corner, tensor_state));
     ctx->pc_q_tensor = v.tensor;
-    // second oracle: leaf chains + tree over h (fri.cpp:36-139 with oracle_indicator = 1)
-    const u32 n_leaves = M >> 1;
     if (pub_mask) {
         // the mask slice (poly_commit.h:150-161,187-247): q = the public mask's low-degree extension; l q at 2 ms points -> its 2 ms coefficients -> h = the upper
         // half, all_sum[64] = (lq_coef[0] + h_coef[0]) ms; h's low-degree extension closes the leaf chains of this oracle
@@ -802,15 +823,11 @@ int pc_commit_public_body(vp_ctx *ctx, hipEvent_t &ev_a, const F corner[64], int
         VPCHK(pc_launch_ntt(ctx, t + 2 * B, t + 4 * B, ilog2(2 * ms), lm, 1, 1, 1, 2 * ms));
         hipLaunchKernelGGL(k_mask_hcoef, dim3(nblk((u64) B)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) (t + 4 * B), ms, (u32) B, f_make(ms, 0), t, S0m, d_all + 64);
         VPCHK(pc_mask_encode(ctx, t, ms, ctx->pc_hm_cw));
-        if (!late) PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-                           pc_launch_leaf_hash_masked(ctx, ctx->pc_hcw, N, ctx->pc_hm_cw, ctx->pc_tree_h + n_leaves));
-    } else if (!late)
-    PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-            pc_launch_leaf_hash(ctx, ctx->pc_hcw, N, ctx->pc_tree_h + n_leaves));
-    if (!late) VPCHK(pc_merkle(ctx, ctx->pc_tree_h, n_leaves));
+    }
     unsigned char *st = nullptr;                          // root_h | inner | all_sum[65]
     VPCHK(ring_alloc(ctx, 32 + 66 * sizeof(F), (void **) &st));
-    if (!late) HIPCHK(hipMemcpyAsync(st, ctx->pc_tree_h + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    // second oracle: leaf chains + tree over h (fri.cpp:36-139 with oracle_indicator = 1)
+    if (!late) VPCHK(pc_hash_oracle(ctx, 1, st));
     HIPCHK(hipMemcpyAsync(st + 32, d_inner, 66 * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));        // d_all = d_inner + 1
     ctx->pc_public_done = true; ctx->fri_step = -1;
     if (late) { ctx->pc_unhashed |= 2u; ctx->late_root[1] = root_h; }
@@ -864,8 +881,6 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
         VPCHK(pc_launch_ntt(ctx, ctx->L[0].val, ctx->pc_coef, ln, lm, 1, lv.live, 1, N));
         VPCHK(pc_launch_ntt(ctx, ctx->pc_coef, ctx->pc_cw, ln, lm, 0, lv.live, 32, N));
     }
-    // leaf chains + tree (fri.cpp:95-127): all 64 slices
-    const u32 n_leaves = M >> 1;
     ctx->pc_mask_ms = 0;
     if (mask) {
         // the 65th slice: the padded mask's low-degree extension (poly_commit.h:74-86); its pairs close the leaf chains (fri.cpp:107-122)
@@ -877,13 +892,11 @@ static int pc_commit_private_body(vp_ctx *ctx, uint8_t root[32], const vp_F *mas
         ctx->pc_private_done = true; ++ctx->private_epoch;
         ctx->pc_public_done = false;
         return defer_end(ctx, ev_a, VP_PH_PRIVATE, [ctx](float ms) { ctx->commit_ms = ms; return VP_OK; });
-    } else
-    PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-            if (mask) pc_launch_leaf_hash_masked(ctx, ctx->pc_cw, N, ctx->pc_lm_cw, ctx->pc_tree + n_leaves); else pc_launch_leaf_hash(ctx, ctx->pc_cw, N, ctx->pc_tree + n_leaves));
-    VPCHK(pc_merkle(ctx, ctx->pc_tree, n_leaves));
+    }
+    // leaf chains + tree (fri.cpp:95-127): all 64 slices
     void *st = nullptr;
     VPCHK(ring_alloc(ctx, 32, &st));
-    HIPCHK(hipMemcpyAsync(st, ctx->pc_tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    VPCHK(pc_hash_oracle(ctx, 0, st));
     ctx->pc_private_done = true; ++ctx->private_epoch;
     ctx->pc_public_done = false;                          // a commit_public / FRI state of an earlier proof does not belong to this codeword
     return defer_end(ctx, ev_a, VP_PH_PRIVATE, [ctx, root, st](float ms) { memcpy(root, st, 32); ctx->commit_ms = ms; return VP_OK; });
@@ -1096,9 +1109,7 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
         hipLaunchKernelGGL(k_pc_virtual_oracle, dim3(nblk((u64) live * M)), dim3(VP_BLOCK), 0, ctx->stream, v.lcw, v.qcw, v.hcw, v.S0(), N, ctx->pc_rt, M >> 1,
                            f_make(N, 0), live, v.q0_arg(), v.qs_arg());
         ctx->fri_step = 0;
-        if (ctx->pc_mask_ms)      // the mask slice's virtual oracle, in place over its q codeword (poly_commit.h:225-245)
-            hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
-                               (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw);
+        if (ctx->pc_mask_ms) pc_mask_vo(ctx, false);
     }
     const int k = ctx->fri_step;
     if (k >= ln) { ctx->err = "FRI commit phase already finished"; return VP_EINVAL; }
@@ -1111,13 +1122,8 @@ int vp_fri_step(vp_ctx *ctx, const vp_F *r, uint8_t root[32]) {
                        host_inv_real(2), 0, 0u, live);
     // leaves of the folded codeword (M_{k+1} / 2 of them) + tree
     Dig *tree = ctx->pc_fri_tree + fl.tree(k);
-    F *out_m = nullptr;
-    if (ctx->pc_mask_ms) {
-        // the mask slice folds like the others (fri.cpp:366-374) and its pair closes every leaf chain of the level (:403-411)
-        const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
-        out_m = ctx->pc_fm + fl.mask(k);
-        hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, rf, host_inv_real(2));
-    }
+    // the mask slice folds like the others (fri.cpp:366-374) and its pair closes every leaf chain of the level (:403-411)
+    const F *out_m = ctx->pc_mask_ms ? pc_mask_fold(ctx, k, rf, false) : nullptr;
     VPCHK(pc_hash_level(ctx, out, No, out_m, tree));
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     HIPCHK(hipMemcpyAsync(root, tree + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
@@ -1152,7 +1158,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     if (ctx->fri_step >= 0 && ctx->fri_step != 0) { ctx->err = "vp_fri_commit after vp_fri_step"; return VP_EINVAL; }
     if (n_steps > ln || n_steps > VP_FRI_MAX) { ctx->err = "too many FRI steps"; return VP_EINVAL; }
     // A commitment with a mask slice takes the same pass: its 64 slices through the folds below (all live), the 65th in arrays of its own behind them
-    // (k_mask_vo, k_fri_fold_one), and its pairs close the chains of the one leaf launch (FriLeafMaskArgs)
+    // (pc_mask_vo, pc_mask_fold), and its pairs close the chains of the one leaf launch (FriLeafArgs::mask)
     const bool masked = ctx->pc_mask_ms != 0;
     if (!ctx->pc_fri_all) {
         VPCHK(dalloc(ctx, &ctx->pc_fri_all, (size_t) 64 * M));
@@ -1173,9 +1179,7 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
     // folds of every level, back to back
     const FriLayout fl(ln, 0);
     const PcSlices v = pc_slices(ctx, live);             // the first fold reads l, q, h, S_0 and the tensor pair through it
-    FriLeafMaskArgs lmk{}; MerkleArgs ma{};
-    FriLeafArgs &la = lmk.a;
-    u32 blocks = 0;
+    FriLeafArgs la{}; MerkleArgs ma{};
     // vp_pc_hash_late: the oracles whose commit stopped behind its transforms go IN FRONT of the levels in the same lists — an l or h codeword is an entry
     // with N values per coset and 16 N leaves like a level's.  VP_FRI_MAX covers n_steps + 2 (n <= 25: 21 entries) and the u32 leaf offsets 3 x 2^23 leaves.
     if (n_steps + 2 > VP_FRI_MAX) VPCHK(pc_hash_outstanding(ctx, 3u));
@@ -1187,8 +1191,8 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         Dig *tree = o ? ctx->pc_tree_h : ctx->pc_tree;
         const u32 n_leaves = M >> 1;
         ma.tree[ne] = tree; ma.count[ne] = n_leaves;
-        lmk.mask[la.n] = masked ? (o ? ctx->pc_hm_cw : ctx->pc_lm_cw) : nullptr;
-        la.cw[la.n] = o ? ctx->pc_hcw : ctx->pc_cw; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = N; blocks += nblk(n_leaves); ++la.n;
+        la.cw[ne] = o ? ctx->pc_hcw : ctx->pc_cw; la.leaves[ne] = tree + n_leaves; la.N[ne] = N;
+        if (masked) la.mask[ne] = o ? ctx->pc_hm_cw : ctx->pc_lm_cw;
         late_root[ne] = ctx->late_root[o];
         ++ne;
     }
@@ -1239,56 +1243,24 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No), 1, 48ull * live * 32 * No, (u64) 3 * live * 32 * No,
                 hipLaunchKernelGGL(k_fri_fold, dim3(nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rf,
                                    host_inv_real(2), 0, 0u, live));
+        // every level, the single-value last one included, goes into the one leaf-hash launch (the chain of 65 Keccak-f is a fixed ~1 ms latency
+        // however few leaves there are)
         const u32 n_leaves = 16 * No;
         Dig *tree = ctx->pc_fri_tree + fl.tree(k);
         ma.tree[ne + k] = tree; ma.count[ne + k] = n_leaves;
-        {   // every level, the single-value last one included, goes into the one leaf-hash launch (the chain of 65 Keccak-f is
-            // a fixed ~1 ms latency however few leaves there are)
-            lmk.mask[la.n] = masked ? ctx->pc_fm + fl.mask(k) : nullptr;
-            la.cw[la.n] = out; la.leaves[la.n] = tree + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
-        }
+        la.cw[ne + k] = out; la.leaves[ne + k] = tree + n_leaves; la.N[ne + k] = No;
     }
-    if (masked) {
-        // the mask slice behind them: its virtual oracle in place over its q codeword (poly_commit.h:225-245), then one fold per level (fri.cpp:366-374) — what
-        // vp_fri_step queues for it, without the waits in between
-        PC_PROF(VP_K_FRI_FOLD, nblk(M), 1, 64ull * M, 4ull * M,
-                hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
-                                   (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw));
+    if (masked) {      // the mask slice behind them: what vp_fri_step queues for it, without the waits in between
+        pc_mask_vo(ctx, true);
         for (int k = 0; k < n_steps; ++k) {
-            const u32 Nk = N >> k, No = Nk >> 1;
-            const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
             F rf; memcpy(&rf, r + k, sizeof(F));
-            PC_PROF(VP_K_FRI_FOLD, nblk((u64) 32 * No), 1, 48ull * 32 * No, (u64) 3 * 32 * No,
-                    hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, ctx->pc_fm + fl.mask(k), Nk, k, ctx->pc_rt, M >> 1, rf,
-                                       host_inv_real(2)));
+            la.mask[ne + k] = pc_mask_fold(ctx, k, rf, true);
         }
     }
-    u64 all_leaves = 0;
-    for (int k = 0; k < nt; ++k) all_leaves += ma.count[k];
-    if (la.n) PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65,
-                      if (masked) pc_launch_leaf_hash_multi_masked(ctx, lmk); else pc_launch_leaf_hash_multi(ctx, la));
+    la.n = ma.n = nt;
+    VPCHK(pc_hash_leaves(ctx, la, true));
     if (merged) { ctx->pc_unhashed = 0; ctx->late_root[0] = ctx->late_root[1] = nullptr; }      // queued: whatever follows in stream order finds the trees
-    // Merkle trees of all levels (and of the merged oracles), one launch per height while some tree still has more than 512 nodes at it
-    for (;;) {
-        MerkleArgs lv{}; u32 b = 0;
-        for (int k = 0; k < nt; ++k) {
-            const u32 c = ma.count[k] >> 1;
-            if (c <= 512) continue;
-            lv.tree[lv.n] = ma.tree[k]; lv.count[lv.n] = c; lv.blk_start[lv.n] = b; b += nblk(c); ++lv.n;
-            ma.count[k] = c;
-        }
-        if (!lv.n) break;
-        lv.blk_start[lv.n] = b;
-        u64 hs = 0;
-        for (int q = 0; q < lv.n; ++q) hs += lv.count[q];
-        PC_PROF(VP_K_MERKLE, b, lv.n, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_level_multi, dim3(b), dim3(VP_BLOCK), 0, ctx->stream, lv));
-    }
-    ma.n = nt;
-    {
-        u64 hs = 0;
-        for (int k = 0; k < nt; ++k) hs += ma.count[k] ? ma.count[k] - 1 : 0;
-        PC_PROF(VP_K_MERKLE, nt, nt, 96ull * hs, hs, hipLaunchKernelGGL(k_merkle_top_multi, dim3(nt), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots));
-    }
+    VPCHK(pc_merkle_trees(ctx, ma, d_roots));
     unsigned char *st = nullptr;                          // the merged oracles' roots | the levels' roots: one pinned copy
     VPCHK(ring_alloc(ctx, (size_t) 32 * nt, (void **) &st));
     HIPCHK(hipMemcpyAsync(st, d_roots, (size_t) 32 * nt, hipMemcpyDeviceToHost, ctx->stream));
@@ -1463,8 +1435,9 @@ int vp_debug_leaf_only(vp_ctx *ctx, int reps) {
     if (!ctx || !ctx->pc_private_done || ctx->pcs) return VP_EINVAL;
     VP_ENTER(ctx);
     const int n = ctx->L[0].bl;
-    const u32 N = 1u << (n - 6), M = 1u << (n - 1);
-    for (int i = 0; i < reps; ++i) pc_launch_leaf_hash(ctx, ctx->pc_cw, N, ctx->pc_tree + (M >> 1));
+    FriLeafArgs la{};
+    la.cw[0] = ctx->pc_cw; la.leaves[0] = ctx->pc_tree + (1u << (n - 2)); la.N[0] = 1u << (n - 6); la.n = 1;
+    for (int i = 0; i < reps; ++i) VPCHK(pc_hash_leaves(ctx, la, false));
     return check_stream(ctx);
 }
 #endif

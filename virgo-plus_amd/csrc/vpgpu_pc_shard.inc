@@ -174,10 +174,9 @@ int pcs_finish(vp_ctx *ctx, std::initializer_list<PcsOut> outs) {
 
 // five tree levels above the local leaves (local leaf order 32a' + b: the 32 cosets of a position are one subtree)
 int pcs_local_levels(vp_ctx *ctx, Dig *tree, u32 n_leaves) {
-    u32 c = n_leaves >> 1;
-    for (int lvl = 0; lvl < 5; ++lvl, c >>= 1)
-        PC_PROF(VP_K_MERKLE, nblk(c), 1, 96ull * c, c, hipLaunchKernelGGL(k_merkle_level, dim3(nblk(c)), dim3(VP_BLOCK), 0, ctx->stream, tree, c, c));
-    return VP_OK;
+    MerkleArgs ma{};
+    ma.tree[0] = tree; ma.count[0] = n_leaves; ma.n = 1;
+    return pc_merkle_trees(ctx, ma, nullptr, 5);
 }
 
 // the collectives a stage ends with: over RCCL when a communicator is attached, otherwise left pending for vp_shard_exchange_local
@@ -233,8 +232,9 @@ int pcs_alloc(vp_ctx *ctx, int ln, int lm) {
 int pcs_hash_local(vp_ctx *ctx, const F *cw_loc, u32 Nl, Dig *tree, size_t at) {
     PcShard &s = *ctx->pcs;
     const u32 n_leaves = 16 * Nl;                                              // Nl >= 2
-    PC_PROF(VP_K_LEAF_HASH, nblk(n_leaves), 1, (u64) n_leaves * (64 * 32 + 32), (u64) n_leaves * 65,
-            pc_launch_leaf_hash(ctx, cw_loc, Nl, tree + n_leaves));
+    FriLeafArgs la{};
+    la.cw[0] = cw_loc; la.leaves[0] = tree + n_leaves; la.N[0] = Nl; la.n = 1;
+    VPCHK(pc_hash_leaves(ctx, la, true));
     VPCHK(pcs_local_levels(ctx, tree, n_leaves));
     HIPCHK(hipMemcpyAsync(s.ag_send + at, tree + (Nl >> 1), (size_t) (Nl >> 1) * 32, hipMemcpyDeviceToDevice, ctx->stream));        // level with Nl/2 nodes
     return VP_OK;
@@ -419,20 +419,14 @@ int pcs_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         } else if (s.stage == 1) {
             // local folds; level k's output has Nl >> (k+1) positions per coset here
             FriLeafArgs la{};
-            u32 blocks = 0;
             for (int k = 0; k < n_local; ++k) {
                 F *out = pcs_local_fold(ctx, k, s.fri_r[k]);
                 if (!fl.is_tail(k)) {                                      // leaves pair (a', a' + No/2): local
-                    const u32 No = (u32) fl.loc_per_coset(k), n_leaves = 16 * No;
-                    la.cw[la.n] = out; la.leaves[la.n] = s.tree_f + fl.loc_tree(k) + n_leaves; la.N[la.n] = No; blocks += nblk(n_leaves); ++la.n;
+                    const u32 No = (u32) fl.loc_per_coset(k);
+                    la.cw[la.n] = out; la.leaves[la.n] = s.tree_f + fl.loc_tree(k) + 16 * No; la.N[la.n] = No; ++la.n;
                 }
             }
-            if (la.n) {
-                u64 all_leaves = 0;
-                for (int q = 0; q < la.n; ++q) all_leaves += 16ull * la.N[q];
-                PC_PROF(VP_K_LEAF_HASH, blocks, la.n, all_leaves * (64 * 32 + 32), all_leaves * 65,
-                        pc_launch_leaf_hash_multi(ctx, la));
-            }
+            VPCHK(pc_hash_leaves(ctx, la, true));
             size_t at = 0;
             for (int q = 0; q < la.n; ++q) {
                 const u32 No = la.N[q];
