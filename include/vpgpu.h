@@ -13,6 +13,10 @@
  *     (the reference calls exit(EXIT_FAILURE) on a violated assert gate, src/prover.cpp:18-21,211).
  *   - A field element F of F_p^2, p = 2^61-1, is two little-endian uint64 {real, img}, canonical
  *     (each < p), exactly the in-memory layout of virgo::fieldElement (lib/virgo/src/fieldElement.hpp:96-97).
+ *   - Challenges: every challenge argument and every tape element must be canonical.  A limb >= 2^61 - 1 in one of them is refused with
+ *     VP_EINVAL and a vp_last_error text, on the host, before anything is queued: the context, and a sumcheck in progress on it, stay as
+ *     they were.  This holds for vp_prove_gkr, vp_shard_vu_partials, vp_vres, vp_phase1_init, vp_phase2_init, vp_liu_init, vp_round,
+ *     vp_finalize, vp_fft_gkr(_begin), vp_predicates, vp_liu_gr and vp_layer_mle (the kernels' lazy forms take canonical factors only).
  *   - All buffers passed in are caller-owned host memory and may be freed after the call returns.
  *   - One context = one GPU = one proof at a time (the reference prover is not re-entrant either).
  *     Call order is the reference's state machine (SURVEY.md §8b "Threading").

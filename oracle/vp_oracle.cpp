@@ -797,7 +797,15 @@ struct Verifier : VerifierSums {
         fs_absorb(st.w[0], st.w[1], st.w[2], st.w[3]);
         fs_absorb((u64) C.size, 0, 0, 0x53);
     }
+    // the one source of every draw: the glibc stream (orc_prove_gkr), the next element of a caller's tape (orc_prove_gkr_tape), or the
+    // SHA3 chain (orc_prove_fs)
+    const u64 *tape = nullptr;
+    int64_t n_tape = 0, t_pos = 0;
     F draw() {
+        if (tape) {
+            const int64_t i = t_pos++;
+            return i < n_tape ? F(tape[2 * i], tape[2 * i + 1]) : F_ZERO;           // an overrun shows in t_pos != n_tape
+        }
         if (!fs) return frandom();
         fs_absorb(fs_ctr++, 0, 0, 0x43);
         u64 a = fs_state.w[0] & P, b = fs_state.w[1] & P;
@@ -1094,13 +1102,27 @@ void orc_circuit_inputs(const orc_circuit *oc, orc_F *out) {
     for (u64 g = 0; g < L.size; ++g) { out[g].real = F((long long) L.gates[g].u).re; out[g].img = 0; }
 }
 
-int64_t orc_prove_gkr(orc_circuit *oc, uint8_t *transcript, int64_t capacity, orc_stats *st) {
-    srand(3396);                                                     // F::init(), fieldElement.cpp:106-111
+// Draws of Verifier::verify_gkr in the interactive mode: r_0[bl(out)], then for i = n-1 .. 1: r_u[max_bl], assert_random,
+// r_v[i][maxDadBl(i)] if the layer has a binary gate, sig[n_layers], r_liu[max_bl] — the tape layout of include/vpgpu.h.
+int64_t orc_gkr_draws(orc_circuit *oc) {
+    subset_init(oc->c);
+    const Circuit &C = oc->c;
+    int max_bl = 0;
+    for (auto &l : C.circuit) max_bl = std::max(max_bl, l.bitLength);
+    int64_t n = C.circuit[C.size - 1].bitLength;
+    for (int i = C.size - 1; i; --i) n += 2 * max_bl + 1 + C.size + std::max(0, C.circuit[i].maxDadBitLength);
+    return n;
+}
+
+// orc_prove_gkr and orc_prove_gkr_tape: one prover, one verifier; `tape` == nullptr draws from the glibc stream after F::init().
+static int64_t prove_gkr_from(orc_circuit *oc, const u64 *tape, int64_t n_tape, uint8_t *transcript, int64_t capacity, orc_stats *st) {
+    if (!tape) srand(3396);                                          // F::init(), fieldElement.cpp:106-111
     g_cnt = Counter();
     subset_init(oc->c);
     Prover p(oc->c);
     vector<unsigned char> out;
     Verifier v(&p, oc->c, &out);
+    v.tape = tape; v.n_tape = n_tape;
     bool ok = v.verify_gkr();
     if (st) {
         st->prove_sec = p.prove_timer.total;
@@ -1113,9 +1135,20 @@ int64_t orc_prove_gkr(orc_circuit *oc, uint8_t *transcript, int64_t capacity, or
         st->proof_kb = (double) p.proof_size / 1024.0;
         st->verified = ok ? 1 : 0;
     }
+    if (tape && v.t_pos != n_tape) return -5;
     if ((int64_t) out.size() > capacity) return -1;
     memcpy(transcript, out.data(), out.size());
     return (int64_t) out.size();
+}
+
+int64_t orc_prove_gkr(orc_circuit *oc, uint8_t *transcript, int64_t capacity, orc_stats *st) {
+    return prove_gkr_from(oc, nullptr, 0, transcript, capacity, st);
+}
+
+int64_t orc_prove_gkr_tape(orc_circuit *oc, const uint64_t *tape, int64_t n_tape, uint8_t *transcript, int64_t capacity, orc_stats *st) {
+    if (!tape || n_tape != orc_gkr_draws(oc)) return -3;
+    for (int64_t i = 0; i < 2 * n_tape; ++i) if (tape[i] >= P) return -4;
+    return prove_gkr_from(oc, reinterpret_cast<const u64 *>(tape), n_tape, transcript, capacity, st);
 }
 
 // Fiat-Shamir mode: same prover, challenges from the SHA3 chain over the statement and the messages (Verifier::fs_*).  The proof is the

@@ -88,6 +88,16 @@ int orc_layer_mle(orc_circuit *, int layer, const orc_F *r, int n, orc_F *out);
  * and without the trailing PC fields) into `transcript`; returns its length in bytes, or <0 on error
  * (-1: capacity too small).                                                                           */
 int64_t orc_prove_gkr(orc_circuit *, uint8_t *transcript, int64_t capacity, orc_stats *stats);
+/* Number of draws orc_prove_gkr's verifier makes, and their order: r_0[bl(n-1)], then for i = n-1 .. 1: r_u[max_bl], assert_random,
+ * r_v[i][maxDadBitLength(i)] if the layer has a binary gate, sig[n_layers], r_liu[max_bl] — the tape layout of vp_prove_gkr (include/vpgpu.h).
+ * Of r_u and r_liu only the first bl(i-1) entries are read, of sig the first n_layers - i + 1.                                            */
+int64_t orc_gkr_draws(orc_circuit *);
+/* The same prover and verifier with every draw taken from the caller's tape (n_tape elements of (re, im) limbs in draw order) instead of
+ * the glibc stream.  Fed orc_f_random_seq(3396, n) it returns the bytes of orc_prove_gkr.  A failed verifier check ends the run early
+ * (stats->verified = 0) as in orc_prove_gkr; the verifier is complete, so on a valid tape that means a defect of the oracle.  Returns
+ * the byte count, -1 capacity too small, -3 n_tape is not orc_gkr_draws(circuit), -4 a limb >= p, -5 the run did not consume exactly
+ * n_tape elements.                                                                                                                      */
+int64_t orc_prove_gkr_tape(orc_circuit *, const uint64_t *tape, int64_t n_tape, uint8_t *transcript, int64_t capacity, orc_stats *stats);
 
 /* The same proof in Fiat-Shamir mode (not a reference mode — the reference draws glibc random()): every challenge
  * is derived by a SHA3-256 chain from the statement (serialised circuit, subset tables, input values) and all prover messages before

@@ -45,6 +45,10 @@ def lib():
         L.orc_circuit_inputs.argtypes = [vp, vp]
         L.orc_prove_gkr.restype = ctypes.c_int64
         L.orc_prove_gkr.argtypes = [vp, vp, ctypes.c_int64, ctypes.POINTER(Stats)]
+        L.orc_gkr_draws.restype = ctypes.c_int64
+        L.orc_gkr_draws.argtypes = [vp]
+        L.orc_prove_gkr_tape.restype = ctypes.c_int64
+        L.orc_prove_gkr_tape.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.POINTER(Stats)]
         L.orc_prove_fs.restype = ctypes.c_int64
         L.orc_prove_fs.argtypes = [vp, vp, ctypes.c_int64, ctypes.POINTER(Stats)]
         for f in ("orc_f_add", "orc_f_sub", "orc_f_mul"):
@@ -162,6 +166,27 @@ class Circuit:
         if n < 0:
             raise RuntimeError("oracle prove failed")
         return buf.raw[:n], st.as_dict()
+
+    def gkr_draws(self):
+        """Number of challenges orc_prove_gkr's verifier draws: the tape length of vp_prove_gkr."""
+        return lib().orc_gkr_draws(self.h)
+
+    def prove_gkr_tape_rc(self, tape, n_tape=None, capacity=1 << 20):
+        """orc_prove_gkr_tape as it is: (return code, buffer, stats dict).  tape: (n, 2) uint64 array in draw order."""
+        import numpy as np
+        t = np.ascontiguousarray(tape, np.uint64)
+        buf = ctypes.create_string_buffer(max(capacity, 1))
+        st = Stats()
+        rc = lib().orc_prove_gkr_tape(self.h, t.ctypes.data, t.shape[0] if n_tape is None else n_tape, ctypes.cast(buf, ctypes.c_void_p),
+                                      capacity, ctypes.byref(st))
+        return rc, buf.raw, st.as_dict()
+
+    def prove_gkr_tape(self, tape, capacity=1 << 20):
+        """The oracle's GKR proof on the caller's tape: (transcript bytes, stats dict)."""
+        rc, raw, st = self.prove_gkr_tape_rc(tape, capacity=capacity)
+        if rc < 0:
+            raise RuntimeError("orc_prove_gkr_tape: %d" % rc)
+        return raw[:rc], st
 
     def prove_fs(self, capacity=1 << 20):
         """The same proof in Fiat-Shamir mode (orc_prove_fs): (proof bytes, stats dict)."""

@@ -50,6 +50,9 @@ int main(int argc, char **argv) {
         const size_t a = 32, b = t.size() - 32 - 16 - 65 * 16;
         if (vph_verify_transcript(c, t.data() + a, b - a, 0) != 0) return fail("golden randomize(8,12) rejected");
         if (vph_verify_fs(c, t.data() + a, b - a) == 0) return fail("interactive transcript accepted as an FS proof");
+        const uint64_t one_elem[2] = {1, 0};                    // a caller's tape of the wrong length, and none at all: refused before the replay
+        if (vph_verify_transcript_tape(c, one_elem, 1, t.data() + a, b - a, 0) != -1) return fail("a one-element tape was taken");
+        if (vph_verify_transcript_tape(c, nullptr, 0, t.data() + a, b - a, 0) != -1) return fail("a null tape was taken");
         vph_circuit_free(c);
     }
     {

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY.  Sanitizer leg of the CPU build (SURVEY.md §5 "ASan/UBSan CPU targets"): the oracle compiled with
 // -fsanitize=address,undefined (make -C oracle asan -> oracle/_build/oracle_asan) and driven through every code path the parity tests use —
 // loader + replication, randomize, custom circuits with every gate type, GKR proof, Fiat-Shamir proof, the full protocol with the
-// commitment, FRI commit phase, primitives.  Exit code 0 and no sanitizer report = pass (tests/test_sanitizers.py).
+// commitment, FRI commit phase, primitives, fft_gkr and the GKR prover on caller's tapes.  Exit code 0 and no sanitizer report = pass (tests/test_sanitizers.py).
 #include "../../oracle/vp_oracle.h"
 #include <cstdio>
 #include <cstdlib>
@@ -84,6 +84,26 @@ int main(int argc, char **argv) {
         if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want - 1, &ok) != -1) return fail("fft_gkr capacity");
         tape[nt - 1].img = P;
         if (orc_fft_gkr_tape(lg, &tape[0].real, nt, b.data(), want, &ok) != -4) return fail("fft_gkr non-canonical limb");
+    }
+    {   // the GKR prover on a caller's tape: the seeded draws (same bytes as orc_prove_gkr), an edge-limb tape, and the entry's refusals
+        orc_circuit *c = orc_circuit_randomize(4, 6, 3);
+        if (!c) return fail("randomize for the tape entry");
+        const uint64_t P = 2305843009213693951ull, edge[8] = {0, 1, 2, (1ull << 31) - 1, (1ull << 31) + 1, 1ull << 60, P - 2, P - 1};
+        const int64_t nt = orc_gkr_draws(c);
+        const int64_t want = orc_prove_gkr(c, buf.data(), (int64_t) buf.size(), &st);
+        if (nt <= 0 || want <= 0 || !st.verified) return fail("prove_gkr before the tape entry");
+        std::vector<uint8_t> b(want);
+        std::vector<orc_F> tape(nt);
+        orc_f_random_seq(3396, (int) nt, tape.data());
+        if (orc_prove_gkr_tape(c, &tape[0].real, nt, b.data(), want, &st) != want || !st.verified || memcmp(buf.data(), b.data(), (size_t) want)) return fail("prove_gkr_tape seeded");
+        for (int64_t i = 0; i < nt; ++i) tape[i] = {edge[(7 * i + 3) % 8], edge[(3 * i + 1) % 8]};
+        if (orc_prove_gkr_tape(c, &tape[0].real, nt, b.data(), want, &st) != want || !st.verified) return fail("prove_gkr_tape edge tape");
+        if (orc_prove_gkr_tape(c, &tape[0].real, nt - 1, b.data(), want, &st) != -3) return fail("prove_gkr_tape length");
+        if (orc_prove_gkr_tape(c, nullptr, nt, b.data(), want, &st) != -3) return fail("prove_gkr_tape null tape");
+        if (orc_prove_gkr_tape(c, &tape[0].real, nt, b.data(), want - 1, &st) != -1) return fail("prove_gkr_tape capacity");
+        tape[nt - 1].img = P;
+        if (orc_prove_gkr_tape(c, &tape[0].real, nt, b.data(), want, &st) != -4) return fail("prove_gkr_tape non-canonical limb");
+        orc_circuit_free(c);
     }
     puts("oracle_asan ok");
     return 0;

@@ -509,3 +509,64 @@ def test_reference_verifier_on_the_references_own_masked_commitments(name, tmp_p
     assert r.returncode == (0 if want else 1)
     if not want:
         assert "Fri msk rs code check fail" in r.stderr
+
+
+# ---- the GKR prover on a caller's tape (orc_prove_gkr_tape): the entry tests/test_gpu_gkr_tapes.py takes its expected bytes from ---------------------------
+def _gkr_tape_circuits(ob, golden, pws_path):
+    import custom_circuits as cc
+    yield "sha256_x1", ob.Circuit.from_pws(pws_path, 1, seed=1)
+    yield "randomize_8_12", ob.Circuit.randomize(8, 12, seed=1)
+    for name in ("custom_a", "custom_b", "custom_c", "custom_d"):
+        yield name, ob.Circuit.custom(*cc.from_golden(golden[name]["custom"]))
+
+
+def test_oracle_gkr_on_the_seeded_tape_vs_reference_records(ob, golden, gold_gkr, pws_path):
+    """Fed the draws of F::init()'s stream, orc_prove_gkr_tape returns the REAL reference's recorded GKR slice (and with it orc_prove_gkr's bytes), consuming
+    exactly orc_gkr_draws elements — the layout of include/vpgpu.h: r_0, then per layer r_u[max_bl], assert_random, r_v, sig[n_layers], r_liu[max_bl].  Another
+    seed gives other bytes."""
+    for name, c in _gkr_tape_circuits(ob, golden, pws_path):
+        n = c.gkr_draws()
+        bl = [c.layer_bitlen(i) for i in range(c.layers)]
+        assert n == bl[-1] + sum(2 * max(bl) + 1 + c.layers + max(0, c.subsets(i)[2]) for i in range(1, c.layers)), name
+        tr, st = c.prove_gkr_tape(ob.random_seq(3396, n))
+        assert st["verified"] == 1 and tr == gold_gkr(name), name
+        if name in ("randomize_8_12", "custom_d"):
+            assert (tr, 1) == (c.prove_gkr()[0], c.prove_gkr()[1]["verified"])
+            other, st = c.prove_gkr_tape(ob.random_seq(77, n))
+            assert st["verified"] == 1 and other != tr and len(other) == len(tr)
+        c.close()
+
+
+def test_oracle_gkr_tape_refusals_and_dont_care_draws(ob):
+    import custom_circuits as cc
+    P = (1 << 61) - 1
+    c = ob.Circuit.custom(*cc.make(4, [5, 3, 2, 1]))            # bit lengths 3, 2, 1, 0: every r_u and r_liu vector has drawn entries nobody reads
+    n, max_bl, layers = c.gkr_draws(), 3, 4
+    t = ob.random_seq(3396, n)
+    full = len(c.prove_gkr()[0])
+    assert c.prove_gkr_tape_rc(t)[0] == full
+    assert c.prove_gkr_tape_rc(t, n_tape=n - 1)[0] == -3 and c.prove_gkr_tape_rc(np.concatenate([t, t[:1]]))[0] == -3      # a short count, a long count
+    assert ob.lib().orc_prove_gkr_tape(c.h, None, n, None, 0, None) == -3
+    assert c.prove_gkr_tape_rc(t, capacity=full - 1)[0] == -1 and c.prove_gkr_tape_rc(t, capacity=full)[0] == full
+    dont_care = c.layer_bitlen(3) + c.layer_bitlen(2)          # the first entry of r_u past the bit length of layer 2 (1 < max_bl = 3): drawn, never read
+    assert c.layer_bitlen(2) < max_bl
+    for at, limb, v in ((0, 0, P), (n - 1, 1, P), (n // 2, 0, 2 ** 64 - 1), (dont_care, 1, P)):       # a don't-care position is checked too
+        bad = t.copy()
+        bad[at, limb] = v
+        assert c.prove_gkr_tape_rc(bad)[0] == -4
+        bad[at, limb] = P - 1
+        assert c.prove_gkr_tape_rc(bad)[0] == full
+    # draws the prover never reads (r_u / r_liu past bit_length(i - 1), sig past n_layers - i + 1) do not move a byte; a draw it reads does
+    want = c.prove_gkr_tape(t)[0]
+    moved = t.copy()
+    at = c.layer_bitlen(3)
+    for i in range(layers - 1, 0, -1):
+        used = c.layer_bitlen(i - 1)
+        moved[at + used:at + max_bl] = [5, 7]; at += max_bl + 1 + max(0, c.subsets(i)[2])
+        moved[at + layers - i + 1:at + layers] = [P - 1, P - 1]; at += layers
+        moved[at + used:at + max_bl] = [0, 1]; at += max_bl
+    assert at == n and (moved != t).any() and c.prove_gkr_tape(moved)[0] == want
+    moved[n - max_bl + c.layer_bitlen(0) - 1, 0] ^= 1          # the last challenge of the last Liu sumcheck: only the closing claim follows it
+    got = c.prove_gkr_tape(moved)[0]
+    assert got != want and got[:-16] == want[:-16]
+    c.close()

@@ -235,6 +235,8 @@ def lib_host():
         L.vph_prove_interactive.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(VphResult), ctypes.c_char_p,
                                             ctypes.c_int]
         L.vph_draw_tape.argtypes = [vp]
+        L.vph_set_tape.argtypes = [vp, vp, u64]
+        L.vph_verify_transcript_tape.argtypes = [vp, vp, u64, vp, u64, ctypes.c_int]
         L.vph_prove_gkr.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(VphResult), ctypes.c_char_p, ctypes.c_int]
         L.vph_check.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         L.vph_verify_transcript.argtypes = [vp, vp, u64, ctypes.c_int]
@@ -618,6 +620,18 @@ class Circuit:
         return lib_host().vph_verify_transcript(self.h, ctypes.cast(buf, ctypes.c_void_p), len(transcript),
                                                 1 if skip_predicates else 0) == 0
 
+    def verify_transcript_tape(self, tape, transcript, skip_predicates=False):
+        """Host verifier replay (no GPU) of a GKR transcript against the caller's tape, an (n, 2) uint64 array in draw order.  Raises when the tape does
+        not fit the circuit (length, a limb >= p)."""
+        import numpy as np
+        t = np.ascontiguousarray(tape, dtype=np.uint64).reshape(-1, 2)
+        buf = ctypes.create_string_buffer(bytes(transcript), max(len(transcript), 1))
+        rc = lib_host().vph_verify_transcript_tape(self.h, t.ctypes.data, int(t.shape[0]), ctypes.cast(buf, ctypes.c_void_p), len(transcript),
+                                                   1 if skip_predicates else 0)
+        if rc < 0:
+            raise ValueError("verify_transcript_tape: the tape does not fit the circuit")
+        return rc == 0
+
     def verify_full_record(self, record):
         """Verify the record of a complete-protocol run (Session.last_full_record) on the host: no GPU, no session."""
         buf = ctypes.create_string_buffer(bytes(record), max(len(record), 1))
@@ -825,6 +839,14 @@ class Session:
 
     def draw_tape(self):
         lib_host().vph_draw_tape(self.h)
+
+    def set_tape(self, tape):
+        """Attach the caller's tape, an (n, 2) uint64 array in draw order (include/vpgpu.h: vp_prove_gkr), in place of draw_tape()'s.  Raises, and keeps the
+        attached tape, when the length is not the circuit's draw count or a limb is >= p."""
+        import numpy as np
+        t = np.ascontiguousarray(tape, dtype=np.uint64).reshape(-1, 2)
+        if lib_host().vph_set_tape(self.h, t.ctypes.data, int(t.shape[0])):
+            raise ValueError("set_tape: wrong length or a non-canonical limb")
 
     def prove_gkr(self):
         """One batched device pass from the attached tape: returns (transcript bytes, stats)."""

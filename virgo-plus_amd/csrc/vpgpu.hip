@@ -1544,9 +1544,9 @@ static int round1_prefetch(vp_ctx *ctx) {
     return VP_OK;
 }
 
-// the verifier-side entry points take canonical challenges only, as vp_round does: checked on the host, before anything is queued
-static bool pred_canonical(const vp_F *x, int n) {
-    for (int i = 0; i < n; ++i) {
+// every entry point takes canonical challenges only (include/vpgpu.h, "Challenges"): checked on the host, before anything is queued
+static bool pred_canonical(const vp_F *x, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
         F v; memcpy(&v, &x[i], sizeof(F));
         if (v.re >= P61 || v.im >= P61) return false;
     }
@@ -1694,6 +1694,7 @@ int vp_liu_gr(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, c
 
 int vp_vres(vp_ctx *ctx, const vp_F *r_0, int r_0_size, vp_F *out) {
     if (!ctx || !ctx->evaluated || !out || r_0_size != ctx->L[ctx->n_layers - 1].bl || (r_0_size && !r_0)) return VP_EINVAL;
+    if (!pred_canonical(r_0, r_0_size)) { ctx->err = "vp_vres: r_0 is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     ctx->rlog.clear();
     // a new proof starts here: a sumcheck the caller left unfinished is abandoned (vp_set_round_shard accepts the context again)
@@ -1712,6 +1713,9 @@ int vp_vres(vp_ctx *ctx, const vp_F *r_0, int r_0_size, vp_F *out) {
 int vp_phase1_init(vp_ctx *ctx, int layer, const vp_F *r_liu, const vp_F *assert_random) {
     if (!ctx || !ctx->evaluated || layer < 1 || layer >= ctx->n_layers || !assert_random) return VP_EINVAL;
     if (ctx->L[layer].bl && !r_liu) return VP_EINVAL;
+    if (!pred_canonical(r_liu, ctx->L[layer].bl) || !pred_canonical(assert_random, 1)) {
+        ctx->err = "vp_phase1_init: a challenge is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL;
+    }
     VP_ENTER(ctx);
     const u64 off = layer == ctx->n_layers - 1 ? 0 : ctx->rliu_off[layer + 1];
     VPCHK(stage(ctx, off, r_liu, ctx->L[layer].bl));
@@ -1728,6 +1732,7 @@ int vp_phase2_init(vp_ctx *ctx, int layer, const vp_F *r_u) {
     if (!ctx || !ctx->evaluated || layer < 1 || layer >= ctx->n_layers) return VP_EINVAL;
     if (ctx->L[layer - 1].bl && !r_u) return VP_EINVAL;
     if (ctx->sc.layer != layer || ctx->L[layer].max_dad_bl == -1) { ctx->err = "phase2 out of order"; return VP_EINVAL; }
+    if (!pred_canonical(r_u, ctx->L[layer - 1].bl)) { ctx->err = "vp_phase2_init: r_u is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     VPCHK(stage(ctx, ctx->ru_off[layer], r_u, ctx->L[layer - 1].bl));
     ctx->sc_open = false;
@@ -1741,8 +1746,17 @@ int vp_phase2_init(vp_ctx *ctx, int layer, const vp_F *r_u) {
 int vp_liu_init(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, const vp_F *s) {
     if (!ctx || !ctx->evaluated || layer < 1 || layer >= ctx->n_layers || !s) return VP_EINVAL;
     if (ctx->L[layer - 1].bl && !r_u) return VP_EINVAL;
-    VP_ENTER(ctx);
     const int n = ctx->n_layers;
+    {   // all of it before the context is touched: a refused call leaves a sumcheck in progress as it was
+        bool canon = pred_canonical(r_u, ctx->L[layer - 1].bl) && pred_canonical(s, n - layer + 1);
+        for (int k = layer; k < n; ++k)
+            if (ctx->L[k].dad_size[layer - 1] && ctx->L[k].dad_bl[layer - 1]) {
+                if (!r_v || !r_v[k]) return VP_EINVAL;
+                canon = canon && pred_canonical(r_v[k], ctx->L[k].dad_bl[layer - 1]);
+            }
+        if (!canon) { ctx->err = "vp_liu_init: a challenge is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
+    }
+    VP_ENTER(ctx);
     VPCHK(stage(ctx, ctx->ru_off[layer], r_u, ctx->L[layer - 1].bl));
     VPCHK(stage(ctx, ctx->sig_off[layer], s, n - layer + 1));
     for (int k = layer; k < n; ++k)
@@ -1982,6 +1996,7 @@ int vp_shard_chains(vp_ctx *ctx, int32_t *owner, double *cost, int capacity, int
 int vp_prove_gkr(vp_ctx *ctx, const vp_F *tape, uint64_t n_tape, uint8_t *transcript, uint64_t capacity,
                  uint64_t *n_written) {
     if (!ctx || !ctx->evaluated || !tape || !transcript || n_tape != ctx->n_tape) return VP_EINVAL;
+    if (!pred_canonical(tape, n_tape)) { ctx->err = "vp_prove_gkr: a tape element is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     { uint64_t need = 0; (void) vp_gkr_sizes(ctx, nullptr, &need); if (ctx->opt.debug & 1) fprintf(stderr, "[vp] vp_prove_gkr: capacity %llu need %llu\n", (unsigned long long) capacity, (unsigned long long) need); if (capacity < need) return VP_EINVAL; }
     if (!ctx->simple_path) return prove_gkr_fused(ctx, tape, n_tape, transcript, n_written);
 #ifndef VP_TEST_DRIVERS

@@ -1567,6 +1567,7 @@ static int prove_gkr_fused(vp_ctx *ctx, const vp_F *tape, uint64_t n_tape, uint8
 // Index-split proof, caller-side exchange of the split phase-2 chains' V_u (include/vpgpu.h): this rank's partial inner products ...
 int vp_shard_vu_partials(vp_ctx *ctx, const vp_F *tape_, uint64_t n_tape, vp_F *partials, uint64_t capacity, uint64_t *n_out) {
     if (!ctx || !ctx->evaluated || !n_out || (n_tape && !tape_) || n_tape != ctx->n_tape) return VP_EINVAL;
+    if (!pred_canonical(tape_, n_tape)) { ctx->err = "vp_shard_vu_partials: a tape element is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     *n_out = 0;
     ctx->vu_supplied = false;

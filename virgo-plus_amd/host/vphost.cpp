@@ -1,5 +1,6 @@
 #include "vphost.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -200,6 +201,28 @@ int vph_draw_tape(vph_session *s) {
     F::init();
     verifier v(nullptr, s->circ->c);
     s->tape = v.drawTape();
+    return 0;
+}
+
+// a caller's tape: the layout and length of verifier::drawTape(), canonical limbs
+static bool tape_fits(const layeredCircuit &c, const uint64_t *pairs, uint64_t n, std::vector<F> &out) {
+    if (!pairs) return false;
+    int max_bl = 0;
+    for (int i = 0; i < c.size; ++i) max_bl = std::max(max_bl, c.circuit[i].bitLength);
+    uint64_t want = c.circuit[c.size - 1].bitLength;
+    for (int i = c.size - 1; i; --i) want += 2 * (uint64_t) max_bl + 1 + c.size + (c.circuit[i].maxDadBitLength != -1 ? c.circuit[i].maxDadBitLength : 0);
+    if (n != want) return false;
+    const uint64_t p = (1ull << 61) - 1;
+    for (uint64_t i = 0; i < 2 * n; ++i) if (pairs[i] >= p) return false;
+    out.resize(n);
+    for (uint64_t i = 0; i < n; ++i) { out[i].real = pairs[2 * i]; out[i].img = pairs[2 * i + 1]; }
+    return true;
+}
+
+int vph_set_tape(vph_session *s, const uint64_t *tape_pairs, uint64_t n) {
+    std::vector<F> t;
+    if (!s || !tape_fits(s->circ->c, tape_pairs, n, t)) return -1;
+    s->tape.swap(t);
     return 0;
 }
 
@@ -712,6 +735,17 @@ int vph_verify_transcript(vph_circuit *c, const uint8_t *transcript, uint64_t n,
         F::init();
         verifier v(nullptr, c->c);
         const std::vector<F> tape = v.drawTape();
+        v.skip_predicates = skip_predicates != 0;
+        std::vector<uint8_t> tr(transcript, transcript + n);
+        return v.check(tape, tr) ? 0 : 1;
+    } catch (const std::exception &) { return 1; }
+}
+
+int vph_verify_transcript_tape(vph_circuit *c, const uint64_t *tape_pairs, uint64_t n_tape, const uint8_t *transcript, uint64_t n, int skip_predicates) {
+    try {
+        std::vector<F> tape;
+        if (!c || !tape_fits(c->c, tape_pairs, n_tape, tape)) return -1;
+        verifier v(nullptr, c->c);
         v.skip_predicates = skip_predicates != 0;
         std::vector<uint8_t> tr(transcript, transcript + n);
         return v.check(tape, tr) ? 0 : 1;

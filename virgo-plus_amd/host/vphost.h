@@ -74,6 +74,10 @@ int vph_prove_interactive(vph_session *, uint8_t *transcript, uint64_t capacity,
                           vph_result *res, char *err, int errlen);
 /* F::init() + draw the verifier tape once; it stays attached to the session.                           */
 int vph_draw_tape(vph_session *);
+/* Attach the caller's tape in place of vph_draw_tape's: n elements of {real, img} in the draw order of verifier::drawTape() (the layout of
+ * vp_prove_gkr's tape, include/vpgpu.h).  -1, and the attached tape stays as it was, when n is not the circuit's draw count or a limb is >= 2^61 - 1.
+ * vph_prove_gkr, vph_check, vph_shard_vu_partials and the sharded proofs of vph_set_shard then run on it.                                             */
+int vph_set_tape(vph_session *, const uint64_t *tape_pairs, uint64_t n);
 /* One batched GKR proof from the attached tape (a bench "step").                                       */
 int vph_prove_gkr(vph_session *, uint8_t *transcript, uint64_t capacity, uint64_t *n_written, vph_result *res,
                   char *err, int errlen);
@@ -189,6 +193,8 @@ int vph_prove_protocol_masked(vph_session *, const uint64_t *pri_mask_pairs, uin
 /* No GPU needed: F::init(), draw the tape for `circuit`, replay the host verifier over `transcript`
  * (GKR slice).  0 = accepted, 1 = rejected.                                                            */
 int vph_verify_transcript(vph_circuit *, const uint8_t *transcript, uint64_t n, int skip_predicates);
+/* The same replay against the caller's tape (vph_set_tape's conditions: -1 if it does not fit the circuit).  No GPU, no generator.   */
+int vph_verify_transcript_tape(vph_circuit *, const uint64_t *tape_pairs, uint64_t n_tape, const uint8_t *transcript, uint64_t n, int skip_predicates);
 /* Fiat-Shamir mode: a non-interactive GKR proof.  Every verifier challenge is derived with SHA3-256 from the
  * circuit's structural hash and all prover messages before it (one challenge per sumcheck round, after that round's
  * polynomial); the prover runs through its interactive entry points.  The proof has the transcript layout of vph_prove_gkr.
