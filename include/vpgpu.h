@@ -347,6 +347,31 @@ int vp_fri_open_many(vp_ctx *, int n, const int32_t *oracle, const uint64_t *lea
  * (one k_pc_open_many launch) and leaves every other byte of `out` untouched, as vp_fri_open_many does: the ranks' buffers merge into one.    */
 int vp_fri_query_bytes(vp_ctx *, int n_queries, uint64_t *bytes);
 int vp_fri_query(vp_ctx *, int n_queries, const uint64_t *leaf0, uint8_t *out, uint64_t capacity, uint64_t *n_written);
+/* ---- the commitment VERIFIER's two heavy loops (host/verifier.cpp, verifyPoly) ------------------------------------------------------------------
+ * Both read public data only and, like vp_predicates, return VALUES: every comparison and the verdict stay with the host verifier.  They take n (the bit
+ * length of the input layer) as an argument, work on a context without circuit, witness or commitment, and leave a commitment in progress on the context
+ * untouched (its oracles, codewords and trees are neither read nor written; transform scratch is shared).  N = 2^(n-6), M = 2^(n-1), w = the root of
+ * unity of order M.
+ * vp_pc_public_evals: the values of the 64 slice interpolants q_j of the public vector (degree < N; q_j(w_N^i) = slice j's entry i) at the query points:
+ *     out[(q 2 + 0) 64 + j] = q_j(w^leaf0[q]),   out[(q 2 + 1) 64 + j] = q_j(-w^leaf0[q]),   canonical.
+ * Exactly one of `point` (n canonical coordinates: the public vector is eq(point, .), as in vp_commit_public_eq; built on the device, and q_j = eq(point[n-6 .. n), j)
+ * times the interpolant of eq(point[0 .. n-6), .): one transform) and `pub` (2^n canonical entries, as in vp_commit_public: 64 transforms) is given.
+ * Refusals, all before any launch and with the context unchanged: n < 7 VP_EINVAL, n > 25 VP_ELIMIT; both or neither of point / pub, a limb >= 2^61 - 1 in
+ * either, n_queries outside 1 .. 4096, a leaf0 outside [N/2, M/2): VP_EINVAL.  Launches: the existing eq builders / inverse transforms, then k_pc_poly_eval
+ * ONCE (every workgroup a run of coefficients, loaded once for all its query points; q(x) and q(-x) from the shared even and odd parts) and its closing
+ * launch k_pc_poly_eval_fin.
+ * vp_fri_query_digests: `answer` is a block in vp_fri_query's layout for (n, n_queries) — n_bytes must be that layout's size, VP_EINVAL otherwise (and for n,
+ * n_queries and leaf0 as above).  For every opening, in the layout's order, 64 bytes of `out`: the leaf-chain digest recomputed from its 130 values (65 blocks
+ * from the zero state) | the root reached from that digest through path[0 .. depth).  path[depth], the prover's copy of the leaf digest, is not read.  Bytes
+ * are hashed as given (canonicity of the opened values is the host reader's check).  One launch (k_pc_opening_digests, a lane per opening), one copy of the
+ * answer in (the leaf list, 8 bytes a position, in front of it), one copy out, one synchronise.  Both calls work in one device arena the context keeps and
+ * grows to the largest request: a call allocates only when it needs more than any call before it.
+ * With vp_set_profiling(1) the launch table of either call holds its launches (VP_K_PC_POLY_EVAL: work = the F-multiplications the launch executes, 4 096 per
+ * workgroup and query, = N per row and query for rows of at least 4 096 coefficients; bytes = coefficients read;
+ * VP_K_PC_OPENING_DIGESTS: work = Keccak-f permutations).                                                                                              */
+int vp_pc_public_evals(vp_ctx *, int n, const vp_F *point /* n, or NULL */, const vp_F *pub /* 2^n, or NULL */, int n_queries, const uint64_t *leaf0,
+                       vp_F *out /* n_queries x 2 x 64 */);
+int vp_fri_query_digests(vp_ctx *, int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out /* n_queries x (n - 4) x 64 */);
 /* fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp:833-849), prover side: the self-contained GKR over the inverse-FFT +
  * polynomial-evaluation circuit that verify_poly_commitment runs between commit_public and the FRI commit phase (vpd_verifier.cpp:92,
  * lg = bit_length(layer 0) - 6) and whose prover time the reference adds to "Polynomial commitment: prove time" (:94, src/verifier.cpp:183).
@@ -542,7 +567,8 @@ int vp_set_profiling(vp_ctx *, int level);
  * launch on every table it holds; closing kernels: the remaining ones), `first_round` the earliest of them (1-based).   */
 enum { VP_K_BETA = 0, VP_K_LIGHT, VP_K_CHUNKS, VP_K_COMBINE, VP_K_DOT, VP_K_DOTFIN, VP_K_SFGEN, VP_K_SF, VP_K_SEG, VP_K_EMIT,
        VP_K_FIXUP, VP_K_NTT_SPLIT, VP_K_NTT_LDS, VP_K_NTT_UNSPLIT, VP_K_LEAF_HASH, VP_K_MERKLE, VP_K_PC_POINTWISE, VP_K_FRI_FOLD,
-       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_NTT_LONG_SPLIT, VP_K_NTT_LONG_MERGE, VP_K_PC_OPEN_MANY, VP_K_COUNT };
+       VP_K_ROUND, VP_K_NTT8_COLS, VP_K_NTT8_ROWS, VP_K_NTT_LONG_SPLIT, VP_K_NTT_LONG_MERGE, VP_K_PC_POLY_EVAL, VP_K_PC_POLY_EVAL_FIN, VP_K_PC_OPENING_DIGESTS,
+       VP_K_PC_OPEN_MANY, VP_K_COUNT };
 /* VP_K_NTT_UNSPLIT is no longer emitted (the long transforms store in natural order themselves); it keeps its value so the others do not move. */
 typedef struct {
     int32_t kind;             /* VP_K_*                                                          */

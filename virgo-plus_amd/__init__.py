@@ -26,7 +26,7 @@ LIB_GPU_TESTDRV = os.path.join(ROOT, "tools", "_build", "testdrv", "libvpgpu.so"
 LIB_HOST = os.path.join(HOST, "libvphost.so")
 CLI = os.path.join(HOST, "virgo_plus_run")
 
-GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vpgpu_pc.inc", "vpgpu_pc_shard.inc", "vpgpu_fftgkr.inc", "vpgpu_upload.inc", "vp_kernels_fftgkr.h", "vp_kernels.h", "vp_kernels_round.h", "vp_kernels_persist.h", "vp_kernels_batch.h",
+GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vpgpu_pc.inc", "vpgpu_pc_shard.inc", "vpgpu_pcverify.inc", "vp_kernels_pcverify.h", "vpgpu_fftgkr.inc", "vpgpu_upload.inc", "vp_kernels_fftgkr.h", "vp_kernels.h", "vp_kernels_round.h", "vp_kernels_persist.h", "vp_kernels_batch.h",
                                               "vp_kernels_plan.h", "vp_kernels_pc.h", "vp_kernels_ntt8.h", "vp_kernels_ntt_long.h", "vp_keccak_asm.h", "vp_check.h", "vp_field.h", "vp_fri_layout.h", "vp_pc_live.h", "vp_pc_corners.h")] + [
     os.path.join(ROOT, "include", "vpgpu.h")]
 HOST_SRC = [os.path.join(HOST, f) for f in ("circuit.cpp", "prover.cpp", "verifier.cpp", "vphost.cpp")]
@@ -167,6 +167,8 @@ def lib_gpu():
         L.vp_fri_open_many.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, vp]
         L.vp_fri_query_bytes.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
         L.vp_fri_query.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+        L.vp_pc_public_evals.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]
+        L.vp_fri_query_digests.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint64, vp]
         L.vp_commit_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.vp_comm_unique_id.argtypes = [vp]
         L.vp_comm_init.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
@@ -246,6 +248,16 @@ def lib_host():
         L.vph_prove_and_verify_full_ex.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_char_p, ctypes.c_int]
         L.vph_last_full_record.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
         L.vph_verify_full_record.argtypes = [vp, vp, u64]
+        L.vph_verifier_launches.argtypes = [vp, ctypes.POINTER(LaunchStat), ctypes.c_int]
+        L.vph_verify_full_record_dev.argtypes = [vp, ctypes.c_int, vp, u64, ctypes.c_char_p, ctypes.c_int]
+        L.vph_last_verify_split.restype = None
+        L.vph_last_verify_split.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        L.vph_pc_public_evals_host.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.vph_pc_opening_digests_host.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, u64, vp]
+        L.vph_pc_query_answer_bytes.restype = u64
+        L.vph_pc_query_answer_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.vph_pc_public_evals.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_fri_query_digests.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, u64, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_last_fri.argtypes = [vp, vp, u64, vp, vp]
         L.vph_draw_protocol_tape.argtypes = [vp]
         L.vph_prove_protocol.argtypes = [vp, vp, u64, ctypes.POINTER(u64), vp, u64, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
@@ -632,10 +644,53 @@ class Circuit:
             raise ValueError("verify_transcript_tape: the tape does not fit the circuit")
         return rc == 0
 
-    def verify_full_record(self, record):
-        """Verify the record of a complete-protocol run (Session.last_full_record) on the host: no GPU, no session."""
+    def verify_full_record(self, record, device=None):
+        """Verify the record of a complete-protocol run (Session.last_full_record) on the host: no GPU, no session.  device=k: the same replay with the
+        verifier's heavy loops (wiring predicates, public polynomial values, opening digests) on GPU k, on a context made for the call; the comparisons
+        and the verdict stay on the host."""
         buf = ctypes.create_string_buffer(bytes(record), max(len(record), 1))
+        if device is not None:
+            err = ctypes.create_string_buffer(512)
+            rc = lib_host().vph_verify_full_record_dev(self.h, int(device), ctypes.cast(buf, ctypes.c_void_p), len(record), err, len(err))
+            if rc < 0:
+                raise RuntimeError("verify_full_record(device=%d) failed: %s" % (device, err.value.decode()))
+            return rc == 0
         return lib_host().vph_verify_full_record(self.h, ctypes.cast(buf, ctypes.c_void_p), len(record)) == 0
+
+    @staticmethod
+    def pc_query_answer_bytes(n, n_queries):
+        """Size of vp_fri_query's answer to n_queries positions at input bit length n."""
+        return int(lib_host().vph_pc_query_answer_bytes(int(n), int(n_queries)))
+
+    @staticmethod
+    def pc_public_evals_host(n, leaf0, point=None, pub=None, tensor=False):
+        """The verifier's public-polynomial loop on the host, by value (no GPU): (n_queries, 2, 64, 2) uint64 — [q, 0, j] = q_j(w^leaf0[q]),
+        [q, 1, j] = q_j(-w^leaf0[q]).  point: (n, 2) uint64, the public vector is eq(point, .); pub: (2^n, 2), a general vector; tensor: the point
+        form through one transform.  Raises ValueError on refused arguments."""
+        import numpy as np
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        pt = None if point is None else np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 2)
+        pb = None if pub is None else np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 2)
+        if (pt is not None and pt.shape[0] != n) or (pb is not None and (n < 0 or n > 30 or pb.shape[0] != 1 << n)):
+            raise ValueError("pc_public_evals_host: a point of n coordinates or a vector of 2^n entries")
+        out = np.zeros((max(len(lf), 1), 2, 64, 2), dtype=np.uint64)
+        rc = lib_host().vph_pc_public_evals_host(int(n), None if pt is None else pt.ctypes.data, None if pb is None else pb.ctypes.data, 1 if tensor else 0,
+                                                 len(lf), lf.ctypes.data, out.ctypes.data)
+        if rc:
+            raise ValueError("pc_public_evals_host: refused")
+        return out[: len(lf)]
+
+    @staticmethod
+    def pc_opening_digests_host(n, leaf0, answer):
+        """The verifier's opening-digest loop on the host, by value (no GPU): answer = bytes in vp_fri_query's layout for (n, len(leaf0)); returns
+        64 bytes per opening, in the layout's order: recomputed leaf-chain digest | root reached through the path.  Raises ValueError when refused."""
+        import numpy as np
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        buf = ctypes.create_string_buffer(bytes(answer), max(len(answer), 1))
+        out = ctypes.create_string_buffer(max(len(lf) * max(n - 4, 0) * 64, 1))
+        if lib_host().vph_pc_opening_digests_host(int(n), len(lf), lf.ctypes.data, ctypes.cast(buf, ctypes.c_void_p), len(answer), ctypes.cast(out, ctypes.c_void_p)):
+            raise ValueError("pc_opening_digests_host: refused")
+        return out.raw[: len(lf) * (n - 4) * 64]
 
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
@@ -1075,16 +1130,18 @@ class Session:
         return (buf.raw[: n.value], roots.raw[:32 * st], fin.copy(),
                 {"total": sec[0], "commit_private": sec[1], "gkr": sec[2], "commit_public": sec[3], "fft_gkr": sec[4], "fri_commit": sec[5]})
 
-    def prove_and_verify_full(self, reps=33, batched_openings=False):
+    def prove_and_verify_full(self, reps=33, batched_openings=False, device_verifier=False):
         """The complete protocol incl. commitment verification: (transcript bytes, accepted, times dict).  batched_openings: the query phase is
-        answered in one device pass (vp_fri_query) instead of one vp_fri_open per opening; same positions, openings and checks."""
+        answered in one device pass (vp_fri_query) instead of one vp_fri_open per opening; same positions, openings and checks.  device_verifier: the
+        verifier's heavy loops — wiring predicates, public polynomial values, opening digests — run on the session's device (VPH_VERIFY_DEVICE_LOOPS;
+        implies the one-pass query phase); every comparison stays on the host, and transcript, record and verdict are the host mode's."""
         cap = self._cap + 32 + 32 + 16 + 65 * 16
         buf = ctypes.create_string_buffer(cap)
         n = ctypes.c_uint64(0)
         t = [ctypes.c_double(0) for _ in range(3)]
         err = ctypes.create_string_buffer(512)
-        if batched_openings:
-            rc = lib_host().vph_prove_and_verify_full_ex(self.h, reps, 1, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
+        if batched_openings or device_verifier:
+            rc = lib_host().vph_prove_and_verify_full_ex(self.h, reps, (1 if batched_openings else 0) | (2 if device_verifier else 0), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
                                                          ctypes.byref(t[0]), ctypes.byref(t[1]), ctypes.byref(t[2]), err, len(err))
         else:
             rc = lib_host().vph_prove_and_verify_full(self.h, reps, ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
@@ -1093,8 +1150,54 @@ class Session:
             raise RuntimeError("prove_and_verify_full failed: " + err.value.decode())
         pt = (ctypes.c_double * 3)()
         lib_host().vph_last_pc_times(self.h, pt)
+        vs = (ctypes.c_double * 4)()
+        lib_host().vph_last_verify_split(self.h, vs)
         return buf.raw[: n.value], rc == 0, {"gkr_prove_sec": t[0].value, "pc_prove_sec": t[1].value, "verify_sec": t[2].value,
-                                            "pc_fft_gkr_sec": pt[1], "pc_query_answer_sec": pt[2]}
+                                            "pc_fft_gkr_sec": pt[1], "pc_query_answer_sec": pt[2],
+                                            "verify_predicates_sec": vs[0], "verify_public_eval_sec": vs[1], "verify_digests_sec": vs[2], "verify_rest_sec": vs[3]}
+
+    def verifier_launch_stats(self):
+        """With set_profiling(1): the launch tables of the verifier-side device calls of the last prove_and_verify_full (vp_predicates, vp_liu_gr,
+        vp_pc_public_evals, vp_fri_query_digests ...), one after the other — [{kernel, workgroups, jobs, bytes, work, us}]."""
+        n = lib_host().vph_verifier_launches(self.h, None, 0)
+        arr = (LaunchStat * max(n, 1))()
+        n = min(n, lib_host().vph_verifier_launches(self.h, arr, max(n, 1)))
+        return [{"kernel": lib_gpu().vp_kernel_name(e.kind).decode(), "workgroups": e.workgroups, "jobs": e.jobs, "bytes": e.bytes, "work": e.work, "us": e.us}
+                for e in arr[:max(n, 0)]]
+
+    def pc_public_evals(self, leaf0, point=None, pub=None, n=None):
+        """vp_pc_public_evals on the session's device: the public polynomials' values at the query points, (n_queries, 2, 64, 2) uint64 as
+        Circuit.pc_public_evals_host.  point: (n, 2) uint64 (the vector is eq(point, .)) or pub: (2^n, 2); n defaults to the point's / the vector's size.
+        Raises RuntimeError with the library's status and message on a refusal."""
+        import numpy as np
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        pt = None if point is None else np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 2)
+        pb = None if pub is None else np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 2)
+        if n is None:
+            n = pt.shape[0] if pt is not None else int(pb.shape[0]).bit_length() - 1
+        out = np.zeros((max(len(lf), 1), 2, 64, 2), dtype=np.uint64)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_pc_public_evals(self.h, int(n), None if pt is None else pt.ctypes.data, None if pb is None else pb.ctypes.data, len(lf),
+                                            lf.ctypes.data, out.ctypes.data, err, len(err))
+        if rc:
+            raise RuntimeError("vp_pc_public_evals failed: %d %s" % (rc, err.value.decode()))
+        return out[: len(lf)]
+
+    def fri_query_digests(self, leaf0, answer, n=None):
+        """vp_fri_query_digests on the session's device: 64 bytes per opening of `answer` (vp_fri_query's layout for (n, len(leaf0)); n defaults to the
+        circuit's input bit length) — recomputed leaf-chain digest | root reached through the path.  Raises RuntimeError on a refusal."""
+        import numpy as np
+        if n is None:
+            n = self.circuit.layer_bitlen(0)
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        buf = ctypes.create_string_buffer(bytes(answer), max(len(answer), 1))
+        out = ctypes.create_string_buffer(max(len(lf) * max(n - 4, 0) * 64, 1))
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_fri_query_digests(self.h, int(n), len(lf), lf.ctypes.data, ctypes.cast(buf, ctypes.c_void_p), len(answer),
+                                              ctypes.cast(out, ctypes.c_void_p), err, len(err))
+        if rc:
+            raise RuntimeError("vp_fri_query_digests failed: %d %s" % (rc, err.value.decode()))
+        return out.raw[: len(lf) * (n - 4) * 64]
 
     def last_full_record(self):
         """Record of the last accepted prove_and_verify_full() (layout: host/vphost.h): everything the prover handed over, for

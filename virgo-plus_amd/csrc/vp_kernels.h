@@ -21,4 +21,5 @@
 #include "vp_kernels_batch.h"
 #include "vp_kernels_plan.h"
 #include "vp_kernels_pc.h"
+#include "vp_kernels_pcverify.h"
 #include "vp_kernels_fftgkr.h"

@@ -231,6 +231,8 @@ struct vp_ctx {
     F *pc_q0 = nullptr, *pc_eq = nullptr, *pc_cbuf = nullptr; int pc_cbuf_lm = -1; int *pc_flag = nullptr; bool pc_q_tensor = false;   // tensor public vector: its one encoded slice (commit_public)
     F *pc_pub = nullptr, *pc_qcw = nullptr, *pc_hcw = nullptr, *pc_tmp = nullptr, *pc_small = nullptr; Dig *pc_tree_h = nullptr; bool pc_private_done = false;
     F *pc_scr = nullptr; size_t pc_scr_cap = 0;
+    std::map<int, F *> pv_rt;                              // vp_pc_public_evals: order-2^lm root tables of its own, for sizes the context's table is not of
+    F *pv_buf = nullptr; size_t pv_cap = 0;                // device arena of vp_pc_public_evals / vp_fri_query_digests (elements of F), grown on demand and kept
     F *pc_fri_all = nullptr, *pc_open_buf = nullptr;     // every FRI level's codeword, end to end (where: FriLayout, vp_fri_layout.h)
     // vp_fri_open_many / vp_fri_query: records on the device, descriptor table + request list on the device, pinned staging of both directions
     PcOpenRec *pc_many_buf = nullptr; unsigned char *pc_many_in = nullptr; u32 pc_many_cap = 0; unsigned char *h_many = nullptr; size_t h_many_cap = 0;
@@ -385,7 +387,7 @@ void free_all(vp_ctx *ctx) {
 }
 // the commitment's device arrays went with free_all: forget them and whatever was committed (a new circuit, or a new input layer of vp_pc_load_input)
 void pc_forget(vp_ctx *ctx) {
-    ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear();
+    ctx->pc_rt = ctx->pc_coef = ctx->pc_cw = nullptr; ctx->pc_tree = nullptr; ctx->pc_lm = -1; ctx->pc_rtc.clear(); ctx->pv_rt.clear(); ctx->pv_buf = nullptr; ctx->pv_cap = 0;
     ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
     ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
     ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0;
@@ -409,6 +411,12 @@ int prof_begin(vp_ctx *ctx, hipStream_t st, int kind, u32 grid, u32 jobs, u64 by
     e.kind = kind; e.grid = grid; e.jobs = jobs; e.bytes = bytes; e.work = work; e.rounds = rounds; e.first_round = first_round;
     hipEventRecord(e.a, st);
     return (int) ctx->ev_used++;
+}
+// event pool for the profiled launches: made with a context's first circuit or input layer, or by the first profiled call that runs without either
+void ensure_event_pool(vp_ctx *ctx) {
+    if (!ctx->ev_pool.empty()) return;
+    ctx->ev_pool.resize(1024);
+    for (auto &e : ctx->ev_pool) { hipEventCreate(&e.a); hipEventCreate(&e.b); e.bytes = 0; e.kind = -1; e.grid = e.jobs = e.rounds = e.first_round = 0; e.work = 0; }
 }
 void prof_end(vp_ctx *ctx, hipStream_t st, int slot) { if (slot >= 0) hipEventRecord(ctx->ev_pool[slot].b, st); }
 // after the stream has been waited for: durations of the bracketed launches -> ctx->lstats
@@ -1457,11 +1465,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_vp_chk_err), z, sizeof z));
     }
 #endif
-    // event pool for the profiled launches
-    if (ctx->ev_pool.empty()) {
-        ctx->ev_pool.resize(1024);
-        for (auto &e : ctx->ev_pool) { hipEventCreate(&e.a); hipEventCreate(&e.b); e.bytes = 0; e.kind = -1; e.grid = e.jobs = e.rounds = e.first_round = 0; e.work = 0; }
-    }
+    ensure_event_pool(ctx);
     return VP_OK;
 }
 
@@ -2136,7 +2140,7 @@ const char *vp_kernel_name(int kind) {
     static const char *names[VP_K_COUNT] = {"k_beta_half_direct", "k_light_multi", "k_chunks_multi", "k_combine_multi", "k_dot_multi", "k_dotfin_multi",
         "k_sumfold3b_gen_multi", "k_sumfold3b_multi", "k_seg_multi", "k_emit_multi", "k_fixup", "k_ntt_split", "k_ntt_lds", "k_ntt_unsplit",
         "k_leaf_hash", "k_merkle", "k_pc_pointwise", "k_fri_fold", "k_round", "k_ntt8_cols", "k_ntt8_rows",
-        "k_ntt_long_split", "k_ntt_long_merge", "k_pc_open_many"};
+        "k_ntt_long_split", "k_ntt_long_merge", "k_pc_poly_eval", "k_pc_poly_eval_fin", "k_pc_opening_digests", "k_pc_open_many"};
     return (kind >= 0 && kind < VP_K_COUNT) ? names[kind] : "?";
 }
 
@@ -2188,4 +2192,5 @@ int vp_test_beta(vp_ctx *ctx, const vp_F *r, int n, const vp_F *init, vp_F *out)
 #include "vpgpu_batched.inc"
 #include "vpgpu_pc.inc"
 #include "vpgpu_pc_shard.inc"
+#include "vpgpu_pcverify.inc"
 #include "vpgpu_fftgkr.inc"

@@ -37,19 +37,23 @@ F host_root_of_unity(int log_order) {    // fieldElement::getRootOfUnity (fieldE
 }
 F host_inv_real(u64 x) { return host_pow(f_make(x, 0), (unsigned __int128) P61 - 2); }   // RS_polynomial.cpp:214
 
-// RT[j] = w^j for j < M/2, M = 2^lm (doubling, one small launch per level; done once per circuit)
-int pc_root_table(vp_ctx *ctx, int lm) {
-    if (ctx->pc_lm == lm && ctx->pc_rt) return VP_OK;
+// RT[j] = w^j for j < M/2, M = 2^lm (doubling, one small launch per level; done once per circuit).  pc_root_fill: into a table of the caller's.
+int pc_root_fill(vp_ctx *ctx, F *rt, int lm) {
     const u32 half = 1u << (lm - 1);
-    VPCHK(dalloc(ctx, &ctx->pc_rt, (size_t) half));
     const F one = f_one();
-    HIPCHK(hipMemcpyAsync(ctx->pc_rt, &one, sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(rt, &one, sizeof(F), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     F step = host_root_of_unity(lm);                    // w^(2^s)
     for (u32 have = 1; have < half; have <<= 1) {
-        hipLaunchKernelGGL(k_root_table_step, dim3(nblk(have)), dim3(VP_BLOCK), 0, ctx->stream, ctx->pc_rt, have, step);
+        hipLaunchKernelGGL(k_root_table_step, dim3(nblk(have)), dim3(VP_BLOCK), 0, ctx->stream, rt, have, step);
         step = f_mul(step, step);
     }
+    return VP_OK;
+}
+int pc_root_table(vp_ctx *ctx, int lm) {
+    if (ctx->pc_lm == lm && ctx->pc_rt) return VP_OK;
+    VPCHK(dalloc(ctx, &ctx->pc_rt, (size_t) 1 << (lm - 1)));
+    VPCHK(pc_root_fill(ctx, ctx->pc_rt, lm));
     ctx->pc_lm = lm;
     return VP_OK;
 }
@@ -921,9 +925,10 @@ int vp_commit_private_masked(vp_ctx *ctx, const vp_F *mask, uint64_t n_mask, uin
 // The caller's public vector (pageable memory: the reference hands a std::vector, src/prover.cpp:542) -> ctx->pc_pub.  With the pinned staging of
 // vp_warm: four host threads copy it into pinned memory in 4 MB pieces while the copy engine takes the pieces that are ready, in order — the upload
 // runs at the bus's speed instead of the pageable path's.  Without it: one hipMemcpyAsync from the caller's memory, as before.
-static int pc_upload_pub(vp_ctx *ctx, const vp_F *pub, size_t bytes) {
+static int pc_upload_pub(vp_ctx *ctx, const vp_F *pub, size_t bytes, F *dst = nullptr) {       // dst: another device array than ctx->pc_pub (vp_pc_public_evals)
+    if (!dst) dst = ctx->pc_pub;
     if (!ctx->h_pub || ctx->h_pub_cap < bytes || bytes < ((size_t) 8 << 20)) {
-        HIPCHK(hipMemcpyAsync(ctx->pc_pub, pub, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(dst, pub, bytes, hipMemcpyHostToDevice, ctx->stream));
         return VP_OK;
     }
     const size_t piece = (size_t) 4 << 20, n_pieces = (bytes + piece - 1) / piece;
@@ -944,7 +949,7 @@ static int pc_upload_pub(vp_ctx *ctx, const vp_F *pub, size_t bytes) {
     for (size_t q = 0; q < n_pieces && rc == VP_OK; ++q) {
         while (!ready[q].load(std::memory_order_acquire)) std::this_thread::yield();
         const size_t off = q * piece, len = std::min(piece, bytes - off);
-        if (hipMemcpyAsync(reinterpret_cast<unsigned char *>(ctx->pc_pub) + off, ctx->h_pub + off, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "hipMemcpyAsync (public vector)"; rc = VP_EHIP; }
+        if (hipMemcpyAsync(reinterpret_cast<unsigned char *>(dst) + off, ctx->h_pub + off, len, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { ctx->err = "hipMemcpyAsync (public vector)"; rc = VP_EHIP; }
     }
     for (auto &t : thr) t.join();
     return rc;

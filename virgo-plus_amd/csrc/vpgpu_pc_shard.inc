@@ -598,10 +598,7 @@ int vp_pc_load_input(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs, int bit
     VPCHK(check_stream(ctx));
     pc_forget(ctx);
     ctx->evaluated = true;
-    if (ctx->ev_pool.empty()) {
-        ctx->ev_pool.resize(1024);
-        for (auto &e : ctx->ev_pool) { hipEventCreate(&e.a); hipEventCreate(&e.b); e.bytes = 0; e.kind = -1; e.grid = e.jobs = e.rounds = e.first_round = 0; e.work = 0; }
-    }
+    ensure_event_pool(ctx);
     return VP_OK;
 }
 

@@ -483,11 +483,19 @@ prover::hhash_digest prover::commit_public_eq(const std::vector<F> &point, const
     check(vp_commit_public_eq_masked(ctx, cF(point.data()), (int) point.size(), cF(m.data()), m.size(), mF(&inner_product_sum), mF(all_sum.data()), d.b), "vp_commit_public_eq_masked");
     return d;
 }
+void prover::logLaunches() {
+    if (!log_launches) return;
+    int n = 0;
+    if (vp_get_launch_stats(ctx, nullptr, 0, &n) != VP_OK || n <= 0) return;
+    std::vector<vp_launch_stat> t((size_t) n);
+    if (vp_get_launch_stats(ctx, t.data(), n, &n) == VP_OK) verifier_launches_.insert(verifier_launches_.end(), t.begin(), t.end());
+}
 std::vector<F> prover::predicates(int layer, const std::vector<F> &r_g, const F &assert_random, const std::vector<F> &r_u,
                                   const std::vector<F> &r_v, int n_v) {
     std::vector<F> out(5 + 7 * (size_t) layer);
     check(vp_predicates(ctx, layer, cF(r_g.data()), cF(&assert_random), cF(r_u.data()), n_v ? cF(r_v.data()) : nullptr, n_v,
                         mF(out.data()), out.size()), "vp_predicates");
+    logLaunches();
     return out;
 }
 F prover::liuGr(int layer, const std::vector<F> &ru, const std::vector<std::vector<F>> &rv_all, const std::vector<F> &sig, const std::vector<F> &rliu) {
@@ -495,11 +503,33 @@ F prover::liuGr(int layer, const std::vector<F> &ru, const std::vector<std::vect
     for (int k = layer; k < C.size; ++k) if (!rv_all[k].empty()) rv[k] = cF(rv_all[k].data());
     F out;
     check(vp_liu_gr(ctx, layer, cF(ru.data()), rv.data(), cF(sig.data()), cF(rliu.data()), mF(&out)), "vp_liu_gr");
+    logLaunches();
     return out;
 }
 F prover::layerMle(int layer, const std::vector<F> &r, int n) {
     F out;
     check(vp_layer_mle(ctx, layer, n ? cF(r.data()) : nullptr, n, mF(&out)), "vp_layer_mle");
+    logLaunches();
+    return out;
+}
+std::vector<F> prover::pcPublicEvals(int n, const std::vector<F> &point, const std::vector<u64> &leaf0) {
+    std::vector<F> out(leaf0.size() * 128);
+    static_assert(sizeof(u64) == sizeof(uint64_t), "leaf indices are passed as they are");
+    check(vp_pc_public_evals(ctx, n, cF(point.data()), nullptr, (int) leaf0.size(), reinterpret_cast<const uint64_t *>(leaf0.data()), mF(out.data())), "vp_pc_public_evals");
+    logLaunches();
+    return out;
+}
+std::vector<F> prover::pcPublicEvalsPub(int n, const std::vector<F> &pub, const std::vector<u64> &leaf0) {
+    if (n < 0 || n > 30 || pub.size() != (1ull << n)) throw std::invalid_argument("pcPublicEvalsPub: a public vector of 2^n entries");
+    std::vector<F> out(leaf0.size() * 128);
+    check(vp_pc_public_evals(ctx, n, nullptr, cF(pub.data()), (int) leaf0.size(), reinterpret_cast<const uint64_t *>(leaf0.data()), mF(out.data())), "vp_pc_public_evals");
+    logLaunches();
+    return out;
+}
+std::vector<uint8_t> prover::pcOpeningDigests(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes) {
+    std::vector<uint8_t> out(leaf0.size() * (size_t) std::max(0, n - 4) * 64);
+    check(vp_fri_query_digests(ctx, n, (int) leaf0.size(), reinterpret_cast<const uint64_t *>(leaf0.data()), answer, n_bytes, out.data()), "vp_fri_query_digests");
+    logLaunches();
     return out;
 }
 prover::hhash_digest prover::friStep(const F &r) {

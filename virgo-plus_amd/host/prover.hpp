@@ -87,6 +87,16 @@ public:
     // the verifier's other O(|C|) loops on the device: gr of verifyLiu (vp_liu_gr) and a layer's MLE at r (vp_layer_mle)
     F liuGr(int layer, const std::vector<F> &r_u, const std::vector<std::vector<F>> &r_v, const std::vector<F> &sig, const std::vector<F> &r_liu);
     F layerMle(int layer, const std::vector<F> &r, int n);
+    // the commitment verifier's two heavy loops on the device (vp_pc_public_evals with the point form / with a general vector, vp_fri_query_digests):
+    // they read public data only — no witness, no committed oracle — and return values; the verifier compares
+    std::vector<F> pcPublicEvals(int n, const std::vector<F> &point, const std::vector<u64> &leaf0);
+    std::vector<F> pcPublicEvalsPub(int n, const std::vector<F> &pub, const std::vector<u64> &leaf0);
+    std::vector<uint8_t> pcOpeningDigests(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes);
+    // with a launch log on (vph_set_profiling), every verifier-side device call above — predicates, liuGr, layerMle, pcPublicEvals(Pub),
+    // pcOpeningDigests — appends the launch table of its call (vp_get_launch_stats), so that a whole verification can be read afterwards
+    void setLaunchLog(bool on) { log_launches = on; verifier_launches_.clear(); }
+    void clearLaunchLog() { verifier_launches_.clear(); }
+    const std::vector<vp_launch_stat> &verifierLaunches() const { return verifier_launches_; }
     hhash_digest friStep(const F &r);
     std::vector<hhash_digest> friCommit(const std::vector<F> &r);   // every step in one device pass (challenges are transcript-independent)
     std::vector<F> friFinal();                           // 2048 elements, reference layout [i << 7 | slice << 1 | hi]
@@ -159,6 +169,9 @@ private:
     int round = 0;
     int sumcheckLayerId = 0;
     timer prove_timer, init_timer, round_timer, fin_timer;
+    void logLaunches();
+    bool log_launches = false;
+    std::vector<vp_launch_stat> verifier_launches_;
     bool masked = false;                                 // the standing private commitment carries a non-zero mask slice
     u64 proof_size = 0;
 };

@@ -1,6 +1,7 @@
 #include "verifier.hpp"
 #include "fft_gkr_verify.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
@@ -142,6 +143,9 @@ bool verifier::check(const std::vector<F> &tape, const std::vector<uint8_t> &tra
 }
 
 bool verifier::run() {                          // verifier.cpp:134-169 (GKR part)
+    // a verification starts here: the launch log of the device its loops run on (prover::verifierLaunches) starts with it
+    if (pred_dev) pred_dev->clearLaunchLog();
+    if (poly_dev && poly_dev != pred_dev) poly_dev->clearLaunchLog();
     for (int i = 0; i < C.circuit[C.size - 1].bitLength; ++i) r_liu[i] = draw();
     F previousSum;
     if (replay) previousSum = nextF();
@@ -389,24 +393,117 @@ struct verifier::RecReader {
     }
 };
 
+// ---- the two heavy loops of the commitment verifier (declared in verifier.hpp) ----
+std::vector<std::vector<F>> pcPublicCoefsHost(int n, const std::vector<F> &pub) {      // public_array_prepare_generic, verifier.cpp:348-361
+    const int ln = n - 6;
+    const u64 N = 1ull << ln;
+    std::vector<std::vector<F>> q_coef(64, std::vector<F>(N));
+    const F inv_root = F::getRootOfUnity(ln).inv();
+    const F inv_n = F::fastPow(F((long long) N), (unsigned __int128) F::mod - 2);
+    for (int j = 0; j < 64; ++j) {
+        std::vector<F> a(pub.begin() + j * N, pub.begin() + (j + 1) * N);
+        host_fft(a, inv_root);
+        for (u64 k = 0; k < N; ++k) q_coef[j][k] = a[k] * inv_n;
+    }
+    return q_coef;
+}
+void pcPublicEvalsAt(const std::vector<std::vector<F>> &q_coef, int n, u64 leaf, F *q0v, F *q1v) {
+    const u64 N = 1ull << (n - 6);
+    const F x0 = F::fastPow(F::getRootOfUnity(n - 1), leaf), x1 = F_ZERO - x0;
+    for (size_t j = 0; j < q_coef.size(); ++j) {
+        F q0 = F_ZERO, q1 = F_ZERO;                          // q_j(x) by Horner from the coefficient form
+        for (u64 k = N; k-- > 0;) { q0 = q0 * x0 + q_coef[j][k]; q1 = q1 * x1 + q_coef[j][k]; }
+        q0v[j] = q0; q1v[j] = q1;
+    }
+}
+std::vector<F> pcPublicEvalsHostPub(int n, const std::vector<F> &pub, const std::vector<u64> &leaf0) {
+    if (n < 7 || pub.size() != (1ull << n)) throw std::runtime_error("pcPublicEvalsHost: a public vector of 2^n entries, n >= 7");
+    const auto q_coef = pcPublicCoefsHost(n, pub);
+    std::vector<F> out(leaf0.size() * 128);
+    for (size_t q = 0; q < leaf0.size(); ++q) pcPublicEvalsAt(q_coef, n, leaf0[q], &out[q * 128], &out[q * 128 + 64]);
+    return out;
+}
+std::vector<F> pcPublicEvalsHost(int n, const std::vector<F> &point, const std::vector<u64> &leaf0) {
+    if (n < 7 || (int) point.size() < n) throw std::runtime_error("pcPublicEvalsHost: a point of n coordinates, n >= 7");
+    std::vector<F> pub;
+    initBetaTable(pub, n, point.begin(), F_ONE);
+    pub.resize(1ull << n);
+    return pcPublicEvalsHostPub(n, pub, leaf0);
+}
+std::vector<F> pcPublicEvalsHostTensor(int n, const std::vector<F> &point, const std::vector<u64> &leaf0) {
+    if (n < 7 || (int) point.size() < n) throw std::runtime_error("pcPublicEvalsHost: a point of n coordinates, n >= 7");
+    const int ln = n - 6;
+    std::vector<F> lo, hi;                                   // eq(point, j N + i) = hi[j] lo[i]
+    initBetaTable(lo, ln, point.begin(), F_ONE);
+    initBetaTable(hi, 6, point.begin() + ln, F_ONE);
+    lo.resize(1ull << ln);
+    host_fft(lo, F::getRootOfUnity(ln).inv());
+    const F inv_n = F::fastPow(F((long long) (1ull << ln)), (unsigned __int128) F::mod - 2);
+    std::vector<std::vector<F>> q_coef(1, std::vector<F>(lo.size()));
+    for (size_t k = 0; k < lo.size(); ++k) q_coef[0][k] = lo[k] * inv_n;
+    std::vector<F> out(leaf0.size() * 128);
+    for (size_t q = 0; q < leaf0.size(); ++q) {
+        F a, b;
+        pcPublicEvalsAt(q_coef, n, leaf0[q], &a, &b);
+        for (int j = 0; j < 64; ++j) { out[q * 128 + j] = hi[j] * a; out[q * 128 + 64 + j] = hi[j] * b; }
+    }
+    return out;
+}
+
+u64 pcQueryAnswerBytes(int n, u64 n_queries) {
+    u64 per = 2 * (2080 + 32ull * (n - 1));
+    for (int k = 0; k < n - 6; ++k) per += 2080 + 32ull * (n - 2 - k);
+    return per * n_queries;
+}
 // Recompute the leaf chain from the opened values (fri.cpp:96-124) and walk the path to the root (vpd_verifier.cpp:9-40).
-bool verifier::checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals,
-                            const std::vector<prover::hhash_digest> &path) {
-    if (vals.size() != 130 || path.empty()) return false;
+void pcOpeningDigest(u64 leaf, const uint8_t *values, const uint8_t *path, size_t depth, uint8_t out[64]) {
     vph::hhash_digest h; memset(&h, 0, sizeof h);
     for (int s = 0; s < 65; ++s) {
-        const uint64_t m[4] = {vals[2 * s].real, vals[2 * s].img, vals[2 * s + 1].real, vals[2 * s + 1].img};
+        uint64_t m[4];
+        memcpy(m, values + 32 * s, 32);
         h = vph::hhash(m, h);
     }
-    const size_t depth = path.size() - 1;
-    if (h != dig(path[depth])) return false;
+    memcpy(out, h.w, 32);
     u64 pos = leaf;
     for (size_t k = 0; k < depth; ++k) {
-        const vph::hhash_digest sib = dig(path[k]);
+        vph::hhash_digest sib; memcpy(sib.w, path + 32 * k, 32);
         h = (pos & 1) ? vph::hhash(sib.w, h) : vph::hhash(h.w, sib);
         pos >>= 1;
     }
-    return h == root;
+    memcpy(out + 32, h.w, 32);
+}
+std::vector<uint8_t> pcOpeningDigestsHost(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes) {
+    if (n < 7 || n_bytes != pcQueryAnswerBytes(n, leaf0.size())) throw std::runtime_error("pcOpeningDigestsHost: not the size of a query answer");
+    const int ln = n - 6;
+    std::vector<uint8_t> out(leaf0.size() * (size_t) (2 + ln) * 64);
+    size_t at = 0, o = 0;
+    for (u64 l0 : leaf0) {
+        u64 D = 1ull << (n - 1), t = l0;
+        for (int oracle = 0; oracle < 2 + ln; ++oracle) {
+            u64 leaf = l0;
+            if (oracle >= 2) { const u64 Dn = D / 2; leaf = t % (Dn / 2); t = leaf; D = Dn; }
+            const size_t plen = (size_t) (oracle < 2 ? n - 1 : n - 2 - (oracle - 2));        // depth + 1 digests; the last is the prover's copy of the leaf digest
+            pcOpeningDigest(leaf, answer + at, answer + at + 2080, plen - 1, &out[o]);
+            at += 2080 + 32 * plen; o += 64;
+        }
+    }
+    return out;
+}
+
+// device_digests: the opening's 64 bytes (leaf digest | root) computed elsewhere (poly_dev); the comparisons are the same
+bool verifier::checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals,
+                            const std::vector<prover::hhash_digest> &path, const uint8_t *device_digests) {
+    if (vals.size() != 130 || path.empty()) return false;
+    const size_t depth = path.size() - 1;
+    uint8_t d[64];
+    if (device_digests) memcpy(d, device_digests, 64);
+    else {
+        digest_timer.start();
+        pcOpeningDigest(leaf, reinterpret_cast<const uint8_t *>(vals.data()), path[0].b, depth, d);
+        digest_timer.stop();
+    }
+    if (memcmp(d, path[depth].b, 32) != 0) return false;
+    return memcmp(d + 32, root.w, 32) == 0;
 }
 
 bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim, int reps) {
@@ -418,19 +515,14 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     // public vector = eq(r_liu, .) over the input layer (verifier.cpp:368-369), and its slices in coefficient form
     // (public_array_prepare_generic, verifier.cpp:348-361)
     poly_timer.start();
+    prover *const dev = poly_dev;
     std::vector<F> pub;
-    initBetaTable(pub, n, r_liu.begin(), F_ONE);
-    pub.resize(1ull << n);
-    std::vector<std::vector<F>> q_coef(64, std::vector<F>(N));
-    {
-        const F inv_root = F::getRootOfUnity(ln).inv();
-        const F inv_n = F::fastPow(F((long long) N), (unsigned __int128) F::mod - 2);
-        for (int j = 0; j < 64; ++j) {
-            std::vector<F> a(pub.begin() + j * N, pub.begin() + (j + 1) * N);
-            host_fft(a, inv_root);
-            for (u64 k = 0; k < N; ++k) q_coef[j][k] = a[k] * inv_n;
-        }
+    if (!(dev && rec)) {                                     // a replay with the device loops needs the point only
+        initBetaTable(pub, n, r_liu.begin(), F_ONE);
+        pub.resize(1ull << n);
     }
+    std::vector<std::vector<F>> q_coef;
+    if (!dev) { pub_eval_timer.start(); q_coef = pcPublicCoefsHost(n, pub); pub_eval_timer.stop(); }
     poly_timer.stop();
     // prover: second oracle
     poly_prove_timer.start();
@@ -512,17 +604,36 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     auto draw_leaf = [&]() { u64 pw; do { pw = (u64) rand() % M; } while (pw < N || (pw & 1)); return pw / 2; };
     // Where the openings come from: one prover::friOpen each (the default), or a block of bytes in vp_fri_query's layout — the answer of ONE
     // prover::friQuery to all positions (batched_openings), or the record's last section (checkFull).  Either way they are kept for the record.
-    const bool positions_first = rec || batched_openings;
+    const bool positions_first = rec || batched_openings || dev;
     std::vector<u64> leaf0((size_t) reps);
     if (positions_first) for (auto &x : leaf0) x = draw_leaf();
     openings_.clear();
     RecReader answer{nullptr, 0, 0}, *src = rec;
-    if (!rec && batched_openings) {
+    if (!rec && (batched_openings || dev)) {
         poly_timer.stop(); open_timer.start();
         openings_ = p->friQuery(leaf0);
         open_timer.stop(); poly_timer.start();
         answer = RecReader{openings_.data(), openings_.size(), 0}; src = &answer;
     }
+    // poly_dev: the q values of every position and the digests of every opening in two device calls over the whole answer block (the record's
+    // remaining bytes, or friQuery's answer); a block that is not the layout's size is rejected here, as the reader below would reject it
+    std::vector<F> dev_q;
+    std::vector<uint8_t> dev_dig;
+    size_t dev_opening = 0;
+    if (dev) {
+        const uint8_t *blk = src->p + src->at;
+        const u64 nb = src->n - src->at;
+        if (nb != pcQueryAnswerBytes(n, (u64) reps)) { fprintf(stderr, "commitment: the query answer is not the size of %d repetitions\n", reps); poly_timer.stop(); return false; }
+        pub_eval_timer.start();
+        dev_q = dev->pcPublicEvals(n, std::vector<F>(r_liu.begin(), r_liu.begin() + n), leaf0);
+        pub_eval_timer.stop();
+        digest_timer.start();
+        dev_dig = dev->pcOpeningDigests(n, leaf0, blk, nb);
+        digest_timer.stop();
+    }
+    auto opening_ok = [&](const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals, const std::vector<prover::hhash_digest> &path) {
+        return checkOpening(root, leaf, vals, path, dev ? &dev_dig[64 * dev_opening++] : nullptr);
+    };
     auto open = [&](int oracle, u64 leaf, std::vector<F> &vals, std::vector<prover::hhash_digest> &path) {
         if (src) {
             vals.resize(130); for (auto &x : vals) x = src->elem();
@@ -541,15 +652,16 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
         const u64 s0 = positions_first ? leaf0[rep] : draw_leaf();
         open(0, s0, vl, pl);
         open(1, s0, vh, ph);
-        if (!checkOpening(root_l, s0, vl, pl) || !checkOpening(root_h, s0, vh, ph)) { fprintf(stderr, "commitment: Merkle opening rejected\n"); return false; }
+        if (!opening_ok(root_l, s0, vl, pl) || !opening_ok(root_h, s0, vh, ph)) { fprintf(stderr, "commitment: Merkle opening rejected\n"); return false; }
         const F x0 = F::fastPow(w, s0), x1 = F_ZERO - x0;
         const F x0n = F::fastPow(x0, N), x1n = F::fastPow(x1, N);
         const F inv_x0 = x0.inv(), inv_x1 = F_ZERO - inv_x0;
         // virtual oracle values at x0 and x1 for every slice (poly_commit.h:301-318 on the prover side)
-        std::vector<F> cur0(64), cur1(64);
+        std::vector<F> cur0(64), cur1(64), q0v(64), q1v(64);
+        if (dev) { std::copy_n(&dev_q[(size_t) rep * 128], 64, q0v.begin()); std::copy_n(&dev_q[(size_t) rep * 128 + 64], 64, q1v.begin()); }
+        else { pub_eval_timer.start(); pcPublicEvalsAt(q_coef, n, s0, q0v.data(), q1v.data()); pub_eval_timer.stop(); }
         for (int j = 0; j < 64; ++j) {
-            F q0 = F_ZERO, q1 = F_ZERO;                          // q_j(x) by Horner from the coefficient form
-            for (u64 k = N; k-- > 0;) { q0 = q0 * x0 + q_coef[j][k]; q1 = q1 * x1 + q_coef[j][k]; }
+            const F &q0 = q0v[j], &q1 = q1v[j];
             cur0[j] = ((vl[2 * j] * q0 - (x0n - F_ONE) * vh[2 * j]) * Nf - all_sum[j]) * inv_x0;
             cur1[j] = ((vl[2 * j + 1] * q1 - (x1n - F_ONE) * vh[2 * j + 1]) * Nf - all_sum[j]) * inv_x1;
         }
@@ -561,7 +673,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
             const u64 Dn = D / 2;                                // next domain size; the folded value sits at index t
             const u64 leaf = t % (Dn / 2);
             open(2 + k, leaf, vb, pb);
-            if (!checkOpening(roots[k], leaf, vb, pb)) { fprintf(stderr, "commitment: FRI Merkle opening rejected (level %d)\n", k); return false; }
+            if (!opening_ok(roots[k], leaf, vb, pb)) { fprintf(stderr, "commitment: FRI Merkle opening rejected (level %d)\n", k); return false; }
             const bool upper = t >= Dn / 2;
             for (int j = 0; j < 64; ++j) {
                 const F expect = inv2 * ((cur0[j] + cur1[j]) + inv_mu * fr[k] * (cur0[j] - cur1[j]));
@@ -639,4 +751,14 @@ bool verifier::checkFull(const std::vector<uint8_t> &record) {
     } catch (const std::runtime_error &) { ok = false; }      // short record / non-canonical element
     rec = nullptr; input_check_by_commitment = false;
     return ok;
+}
+
+// checkFull with the verifier's heavy loops on `device`, on a prover context made for the call (circuit uploaded and evaluated: vp_liu_gr builds its table on an
+// evaluated context; nothing is committed and no prover message is asked of it).  Throws when the context cannot be made.
+bool checkFullOnDevice(const layeredCircuit &c, int device, const std::vector<uint8_t> &record) {
+    prover dev(c, device);
+    F::init();
+    verifier v(nullptr, c);
+    v.pred_dev = &dev; v.poly_dev = &dev;
+    return v.checkFull(record);
 }

@@ -25,6 +25,10 @@ public:
     // reference hard-codes 33).  fullTranscript() is then merkle_root_l | GKR | merkle_root_h | input_0 | all_sum[65].
     bool verifyFull(int reps = 33);
     prover *pred_dev = nullptr;     // when set, the O(|C|) predicate loops run on the device (prover::predicates) instead of the host
+    // when set, the commitment verifier's two heavy loops run on the device: the public polynomials' values at the query points
+    // (prover::pcPublicEvals) and the digests of every opening (prover::pcOpeningDigests).  All positions are drawn first (the same draws), the
+    // device returns values, and every comparison — leaf digest, root, fold consistency, final codeword — stays here.
+    prover *poly_dev = nullptr;
     bool fri_batched = true;        // FRI commit phase as one device pass (prover::friCommit) instead of one friStep per challenge
     // The query phase as one device pass: all `reps` positions are drawn first (the loop draws nothing else between two positions, so they are the ones
     // the default path draws), prover::friQuery answers them in one call, the per-repetition checks then run unchanged over the answer.
@@ -48,6 +52,10 @@ public:
     // Answering the verifier's queries (fri::request_*) is outside that number in the reference and is reported separately here.
     double polyProveTime() const { return poly_prove_timer.elapse_sec(); }
     double polyOpenTime() const { return open_timer.elapse_sec(); }
+    // where polyVerifyTime() goes: the public polynomials (interpolation + evaluation at the query points) and the opening digests (leaf chains +
+    // Merkle paths), by whichever side computed them
+    double publicEvalTime() const { return pub_eval_timer.elapse_sec(); }
+    double openingDigestTime() const { return digest_timer.elapse_sec(); }
     // fft_gkr of the last verifyFull(): its share of polyProveTime() (the reference's p_time_fft, vpd_verifier.cpp:92-94) and its messages
     double fftGkrProveTime() const { return fft_gkr_timer.elapse_sec(); }
     const std::vector<F> &fftGkrMessages() const { return fft_gkr_msgs_; }
@@ -79,7 +87,8 @@ private:
     F getFinalValue(int layer_id, const F &claim_u, const std::vector<F> &claim_v);
     bool checkInput(const F &claim);
     bool verifyPoly(const prover::hhash_digest &root_l, const F &claim, int reps);
-    bool checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals, const std::vector<prover::hhash_digest> &path);
+    bool checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals, const std::vector<prover::hhash_digest> &path,
+                      const uint8_t *device_digests = nullptr);
 
     F draw();
     quadratic_poly nextPoly(int phase, const F &prev);
@@ -106,7 +115,7 @@ private:
     std::vector<F> coeff_r[(int) gateType::SIZE];
     F bias, final_claim_u, assert_random;
     std::vector<std::vector<F>> final_claims_v;
-    timer verify_timer, poly_timer, poly_prove_timer, fft_gkr_timer, open_timer;
+    timer verify_timer, poly_timer, poly_prove_timer, fft_gkr_timer, open_timer, pub_eval_timer, digest_timer;
     std::vector<F> fft_gkr_msgs_;
     std::vector<uint8_t> full_tr;
     std::vector<uint8_t> fri_roots_; std::vector<F> fri_final_, fri_r_;
@@ -119,3 +128,26 @@ private:
 
 // eq table (reference: src/utils.cpp:29-45), host version used by the verifier only
 void initBetaTable(std::vector<F> &beta_g, int gLength, const std::vector<F>::const_iterator &r, const F &init);
+
+// ---- the commitment verifier's two heavy loops, as functions that return values (verifier.cpp; verifyPoly calls them) ----
+// n = bit length of the input layer (>= 7), N = 2^(n-6), M = 2^(n-1), w = the root of unity of order M.
+// pcPublicCoefsHost: the interpolants q_j of the 64 slices of a public vector of 2^n entries, in coefficient form.
+std::vector<std::vector<F>> pcPublicCoefsHost(int n, const std::vector<F> &pub);
+// q0[j] = q_j(w^leaf), q1[j] = q_j(-w^leaf), j < 64, by Horner.
+void pcPublicEvalsAt(const std::vector<std::vector<F>> &q_coef, int n, u64 leaf, F *q0, F *q1);
+// Both for a list of leaves: out[(q 2 + 0) 64 + j] = q_j(w^leaf0[q]), out[(q 2 + 1) 64 + j] = q_j(-w^leaf0[q]) (vp_pc_public_evals' layout).
+// pcPublicEvalsHost: the public vector is eq(point, .) (n coordinates); ...Pub: a general vector of 2^n entries; ...Tensor: eq(point, .) through
+// q_j = eq(point[n-6 .. n), j) q_0' with q_0' the interpolant of eq(point[0 .. n-6), .) — one transform instead of 64, the same values.
+std::vector<F> pcPublicEvalsHost(int n, const std::vector<F> &point, const std::vector<u64> &leaf0);
+std::vector<F> pcPublicEvalsHostPub(int n, const std::vector<F> &pub, const std::vector<u64> &leaf0);
+std::vector<F> pcPublicEvalsHostTensor(int n, const std::vector<F> &point, const std::vector<u64> &leaf0);
+// Bytes of vp_fri_query's answer to n_queries positions at input bit length n, and the (oracle, leaf) of every opening in its order.
+u64 pcQueryAnswerBytes(int n, u64 n_queries);
+// One opening: the leaf-chain digest of its 130 values (65 blocks from the zero state) and the root reached from it through path[0 .. depth).
+void pcOpeningDigest(u64 leaf, const uint8_t *values /* 2080 bytes */, const uint8_t *path /* depth x 32 */, size_t depth, uint8_t out[64]);
+// All openings of an answer block in vp_fri_query's layout: 64 bytes each (leaf digest | root), in the layout's order.  Bytes are hashed as given.
+// Throws std::runtime_error when n_bytes is not the layout's size.
+std::vector<uint8_t> pcOpeningDigestsHost(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes);
+
+// verifier::checkFull (after F::init()) with pred_dev and poly_dev on a context made for the call on `device`; throws std::runtime_error without a usable device
+bool checkFullOnDevice(const layeredCircuit &c, int device, const std::vector<uint8_t> &record);

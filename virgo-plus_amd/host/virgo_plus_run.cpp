@@ -4,6 +4,8 @@
 //     --record FILE: (interactive mode with the commitment) writes the record of the run — everything the prover handed over, layout in vphost.h;
 //         its query phase is then answered in one device pass (verifier::batched_openings)
 //     virgo_plus_run --check-record FILE <file.pws> [--blocks B] [--seed S]: verifies such a record with the host verifier alone, no GPU
+//         --device-verifier [--device D]: the same replay with the verifier's heavy loops (wiring predicates, public polynomial values, opening
+//         digests) on GPU D, as vph_verify_full_record_dev runs it; the comparisons and the verdict stay on the host
 // Loads the circuit, runs the GKR proof on the GPU against the host verifier and prints the
 // reference's result lines (interactive mode runs the whole protocol incl. the Virgo commitment and its verification).
 #include <cstdio>
@@ -19,6 +21,7 @@
 int main(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "usage: %s <file.pws> [--blocks B] [--batched | --fs] [--device D] [--dump out.bin]\n", argv[0]); return 2; }
     int blocks = 1, device = 0; bool batched = false, fsmode = false; const char *dump = nullptr, *record = nullptr, *check_record = nullptr;
+    bool device_verifier = false;
     int first = 2;
     if (!strcmp(argv[1], "--check-record")) {
         if (argc < 4) { fprintf(stderr, "usage: %s --check-record record.bin <file.pws> [--blocks B] [--seed S]\n", argv[0]); return 2; }
@@ -30,6 +33,7 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
         else if (a == "--batched") batched = true;
         else if (a == "--fs") fsmode = true;
+        else if (a == "--device-verifier" && check_record) device_verifier = true;
         else if (a == "--seed" && i + 1 < argc) srandom((unsigned) atol(argv[++i]));      // witness draw (default: glibc's initial state, as the reference)
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
         else if (a == "--record" && i + 1 < argc) record = argv[++i];
@@ -49,7 +53,11 @@ int main(int argc, char **argv) {
         for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) rec.insert(rec.end(), buf, buf + k);
         fclose(f);
         bool ok = false;
-        try { verifier v(nullptr, c); ok = v.checkFull(rec); } catch (const std::exception &) { ok = false; }
+        if (device_verifier) {
+            try { ok = checkFullOnDevice(c, device, rec); } catch (const std::exception &e) { fprintf(stderr, "%s\n", e.what()); return 2; }
+        } else {
+            try { verifier v(nullptr, c); ok = v.checkFull(rec); } catch (const std::exception &) { ok = false; }
+        }
         if (!ok) { fprintf(stderr, "Verification fail\n"); return 1; }
         fprintf(stderr, "Verification pass\n");
         return 0;

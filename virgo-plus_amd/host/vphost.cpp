@@ -19,6 +19,7 @@ struct vph_session {
     std::vector<uint8_t> fri_roots; std::vector<F> fri_final, fri_r;      // FRI commit phase of the last complete-protocol run
     std::vector<uint8_t> full_record;                                     // record of the last accepted complete-protocol run (vph_last_full_record)
     std::vector<F> fft_gkr_msgs; double pc_times[3] = {0, 0, 0};          // fft_gkr messages; {PC prove (reference definition), of which fft_gkr, query answering}
+    double verify_split[4] = {0, 0, 0, 0};                               // vph_last_verify_split
     double t_init = 0, t_round = 0, t_fin = 0;
     std::vector<F> last_point;                                           // r_liu after the last Liu sumcheck of the last complete-protocol run
     std::vector<F> ptape_fft, ptape_fri;                                 // vph_draw_protocol_tape: the draws after the GKR tape (fft_gkr, FRI folds)
@@ -127,7 +128,13 @@ void vph_session_clear_partials(vph_session *s) { if (s) s->p->clearPartials(); 
 void vph_session_drop_rank(vph_session *s, int rank) { if (s) s->p->setDropRank(rank); }
 double vph_session_gather_sec(vph_session *s) { return s ? s->p->gatherTime() : 0; }
 void vph_session_free(vph_session *s) { delete s; }
-int vph_set_profiling(vph_session *s, int level) { return vp_set_profiling(s->p->context(), level); }
+int vph_set_profiling(vph_session *s, int level) { s->p->setLaunchLog(level != 0); return vp_set_profiling(s->p->context(), level); }
+int vph_verifier_launches(vph_session *s, vp_launch_stat *out, int capacity) {
+    if (!s || (capacity > 0 && !out)) return -1;
+    const auto &v = s->p->verifierLaunches();
+    for (int i = 0; i < (int) v.size() && i < capacity; ++i) out[i] = v[i];
+    return (int) v.size();
+}
 void *vph_session_ctx(vph_session *s) { return s ? (void *) s->p->context() : nullptr; }
 
 int vph_layer_values(vph_session *s, int layer, uint64_t *out, uint64_t n) {
@@ -401,6 +408,7 @@ int vph_prove_and_verify_full_ex(vph_session *s, int reps, int flags, uint8_t *t
         F::init();
         verifier v(s->p.get(), s->circ->c);
         v.batched_openings = (flags & VPH_VERIFY_BATCHED_OPENINGS) != 0;
+        if (flags & VPH_VERIFY_DEVICE_LOOPS) { v.pred_dev = s->p.get(); v.poly_dev = s->p.get(); }
         const double t0 = s->p->proveTime();
         const bool ok = v.verifyFull(reps);
         s->full_record = v.fullRecord();
@@ -415,6 +423,8 @@ int vph_prove_and_verify_full_ex(vph_session *s, int reps, int flags, uint8_t *t
         if (gkr_prove_sec) *gkr_prove_sec = s->p->proveTime() - t0;
         if (pc_prove_sec) *pc_prove_sec = v.polyProveTime();
         if (verify_sec) *verify_sec = v.verifyTime() + v.polyVerifyTime();
+        s->verify_split[0] = v.verifyTime(); s->verify_split[1] = v.publicEvalTime(); s->verify_split[2] = v.openingDigestTime();
+        s->verify_split[3] = v.polyVerifyTime() - v.publicEvalTime() - v.openingDigestTime();
         return ok ? 0 : 1;
     } catch (const std::exception &e) {
         set_err(err, errlen, e.what());
@@ -436,6 +446,60 @@ int vph_verify_full_record(vph_circuit *c, const uint8_t *record, uint64_t n) {
         verifier v(nullptr, c->c);
         return v.checkFull(std::vector<uint8_t>(record, record + n)) ? 0 : 1;
     } catch (const std::exception &) { return 1; }
+}
+
+int vph_verify_full_record_dev(vph_circuit *c, int device, const uint8_t *record, uint64_t n, char *err, int errlen) {
+    if (!c || !record) return 1;
+    try { return checkFullOnDevice(c->c, device, std::vector<uint8_t>(record, record + n)) ? 0 : 1; }
+    catch (const std::exception &e) { set_err(err, errlen, e.what()); return -2; }
+}
+void vph_last_verify_split(vph_session *s, double out[4]) { for (int i = 0; i < 4; ++i) out[i] = s ? s->verify_split[i] : 0; }
+
+static bool pc_args_ok(int n, const uint64_t *pairs, uint64_t n_elems, int n_queries, const uint64_t *leaf0) {
+    if (n < 7 || n > 25 || n_queries < 1 || n_queries > 4096 || !leaf0) return false;
+    for (int q = 0; q < n_queries; ++q) if (leaf0[q] < (1ull << (n - 7)) || leaf0[q] >= (1ull << (n - 2))) return false;
+    for (uint64_t i = 0; pairs && i < 2 * n_elems; ++i) if (pairs[i] >= F::mod) return false;
+    return true;
+}
+static std::vector<F> pc_elems(const uint64_t *pairs, uint64_t n_elems) {
+    std::vector<F> v(n_elems);
+    memcpy(static_cast<void *>(v.data()), pairs, n_elems * sizeof(F));
+    return v;
+}
+int vph_pc_public_evals_host(int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int tensor, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs) {
+    if (!out_pairs || (point_pairs == nullptr) == (pub_pairs == nullptr) || (tensor && !point_pairs)) return -1;
+    if (!pc_args_ok(n, point_pairs ? point_pairs : pub_pairs, point_pairs ? (uint64_t) n : 1ull << n, n_queries, leaf0)) return -1;
+    try {
+        const std::vector<u64> lf(leaf0, leaf0 + n_queries);
+        const std::vector<F> in = pc_elems(point_pairs ? point_pairs : pub_pairs, point_pairs ? (uint64_t) n : 1ull << n);
+        const std::vector<F> out = !point_pairs ? pcPublicEvalsHostPub(n, in, lf) : tensor ? pcPublicEvalsHostTensor(n, in, lf) : pcPublicEvalsHost(n, in, lf);
+        memcpy(out_pairs, out.data(), out.size() * sizeof(F));
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+int vph_pc_opening_digests_host(int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out) {
+    if (!answer || !out || !pc_args_ok(n, nullptr, 0, n_queries, leaf0)) return -1;
+    try {
+        const std::vector<uint8_t> d = pcOpeningDigestsHost(n, std::vector<u64>(leaf0, leaf0 + n_queries), answer, n_bytes);
+        memcpy(out, d.data(), d.size());
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+uint64_t vph_pc_query_answer_bytes(int n, int n_queries) { return (n < 7 || n_queries < 0) ? 0 : pcQueryAnswerBytes(n, (u64) n_queries); }
+int vph_pc_public_evals(vph_session *s, int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs,
+                        char *err, int errlen) {
+    // the arguments go to the device library as they are: its refusals are what the caller sees
+    vp_ctx *ctx = s->p->context();
+    const int rc = vp_pc_public_evals(ctx, n, reinterpret_cast<const vp_F *>(point_pairs), reinterpret_cast<const vp_F *>(pub_pairs), n_queries, leaf0,
+                                      reinterpret_cast<vp_F *>(out_pairs));
+    if (rc != VP_OK) set_err(err, errlen, std::string("vp_pc_public_evals: ") + vp_last_error(ctx));
+    return rc;
+}
+int vph_fri_query_digests(vph_session *s, int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out, char *err, int errlen) {
+    vp_ctx *ctx = s->p->context();
+    const int rc = vp_fri_query_digests(ctx, n, n_queries, leaf0, answer, n_bytes, out);
+    if (rc != VP_OK) set_err(err, errlen, std::string("vp_fri_query_digests: ") + vp_last_error(ctx));
+    return rc;
 }
 
 // fft_gkr of the last vph_prove_and_verify_full: its messages ({real,img} pairs, layout of vp_fft_gkr); returns their number or -1

@@ -45,6 +45,10 @@ vph_session *vph_session_create(vph_circuit *, int device, char *err, int errlen
 vph_session *vph_session_create_opts(vph_circuit *, int device, const vp_options *opt /* include/vpgpu.h, NULL = defaults */, char *err, int errlen);
 void vph_session_free(vph_session *);
 int vph_set_profiling(vph_session *, int level);
+/* With profiling on, the launch tables (vp_get_launch_stats) of the VERIFIER-side device calls of the last vph_prove_and_verify_full(_ex) — vp_predicates, vp_liu_gr,
+ * vp_layer_mle, vp_pc_public_evals, vp_fri_query_digests — one after the other, in call order; every verification (verifier::run) starts the log anew, and
+ * vph_set_profiling switches it on and off with the launch tables it reads.  Returns the number of entries (copies up to `capacity`). */
+int vph_verifier_launches(vph_session *, vp_launch_stat *out, int capacity);
 /* the vp_ctx behind the session's prover (for the measurement calls of include/vpgpu.h: vp_get_launch_stats, ...) */
 void *vph_session_ctx(vph_session *);
 /* A session whose interactive sumchecks are sharded by index over world = 1, 2, 4 or 8 ranks (vp_set_round_shard, min_log): one context per entry
@@ -99,7 +103,10 @@ int vph_prove_and_verify_full(vph_session *, int reps, uint8_t *transcript, uint
                               double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen);
 /* The same with flags.  VPH_VERIFY_BATCHED_OPENINGS: the verifier draws all `reps` query positions first and the prover answers them in ONE device
  * pass (vp_fri_query) instead of 2 + (n - 6) vp_fri_open calls per repetition; same positions, same openings, same checks.                     */
-enum { VPH_VERIFY_BATCHED_OPENINGS = 1 };
+/* VPH_VERIFY_DEVICE_LOOPS: the verifier's heavy loops run on the session's device — the wiring predicates (vp_predicates, vp_liu_gr), the public polynomials'
+ * values at the query points (vp_pc_public_evals) and the digests of every opening (vp_fri_query_digests).  Implies positions-first; the device returns values and
+ * every comparison stays on the host: transcript, record and verdict are those of the host mode.                                                        */
+enum { VPH_VERIFY_BATCHED_OPENINGS = 1, VPH_VERIFY_DEVICE_LOOPS = 2 };
 int vph_prove_and_verify_full_ex(vph_session *, int reps, int flags, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                                  double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen);
 /* Record of the last ACCEPTED vph_prove_and_verify_full(_ex) of the session: everything the prover handed over, so that the whole verifier can run
@@ -117,6 +124,27 @@ int vph_prove_and_verify_full_ex(vph_session *, int reps, int flags, uint8_t *tr
  * 1 = rejected (also: short, long, another version, a non-canonical element, any byte changed).                                               */
 int vph_last_full_record(vph_session *, uint8_t *buf, uint64_t cap, uint64_t *n);
 int vph_verify_full_record(vph_circuit *, const uint8_t *record, uint64_t n);
+/* The same replay with the verifier's heavy loops on `device` (VPH_VERIFY_DEVICE_LOOPS), on a context created for the call: the circuit is uploaded and
+ * evaluated there (vp_liu_gr builds its table on an evaluated context); nothing is committed on it and no prover message is asked of it.  0 = accepted,
+ * 1 = rejected (a device call that fails during the replay rejects, like every other exception of the replay), -2 = the context could not be made (err). */
+int vph_verify_full_record_dev(vph_circuit *, int device, const uint8_t *record, uint64_t n, char *err, int errlen);
+/* Where the verifier's time of the last vph_prove_and_verify_full(_ex) went, in seconds: [0] the GKR verifier's O(|C|) loops — wiring predicates, the final value
+ * they give, Liu gr (verifier::verifyTime; the sumcheck round checks are not timed anywhere), [1] public polynomials (interpolation + evaluation at the query
+ * points), [2] opening digests (leaf chains + Merkle paths), [3] the rest of the commitment's verifier. */
+void vph_last_verify_split(vph_session *, double out[4]);
+/* The commitment verifier's two heavy loops by value, on the host (no GPU, no session): the functions verifier::verifyPoly itself calls.
+ * vph_pc_public_evals_host: exactly one of point_pairs (n coordinates: the public vector is eq(point, .)) and pub_pairs (2^n entries); tensor != 0 (point form
+ * only): through q_j = eq(point_hi, j) q' (one transform).  out_pairs: n_queries x 2 x 64 elements in vp_pc_public_evals' layout.
+ * vph_pc_opening_digests_host: `answer` in vp_fri_query's layout for (n, n_queries) — vph_pc_query_answer_bytes gives its size; out: 64 bytes per opening
+ * (recomputed leaf digest | root reached through the path).  0 = done, -1 = refused (sizes, a leaf outside [2^(n-7), 2^(n-2)), a non-canonical limb).     */
+int vph_pc_public_evals_host(int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int tensor, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs);
+int vph_pc_opening_digests_host(int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out);
+uint64_t vph_pc_query_answer_bytes(int n, int n_queries);
+/* The same two on the session's device (vp_pc_public_evals, vp_fri_query_digests on its context, arguments as given). Return the
+ * device library's status: VP_OK, or its refusal with the message in err. */
+int vph_pc_public_evals(vph_session *, int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs,
+                        char *err, int errlen);
+int vph_fri_query_digests(vph_session *, int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out, char *err, int errlen);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
