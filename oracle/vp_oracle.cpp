@@ -1376,13 +1376,34 @@ vector<Digest> leaf_hashes(const vector<F> &evals /* [65][slice_size] */, u64 sl
     return leaves;
 }
 
-// commit_private_array (poly_commit.h:41-124) with the one-element zero mask prover::commit_private passes
-// (src/prover.cpp:526): l_eval[i] = RS encoding (rate 1/32) of slice i of circuitValue[0], mask slice all zero.
-void commit_private_evals(const vector<F> &input, int n_bits, vector<F> &l_eval, u64 &slice_size) {
+// The mask vectors of one commitment (poly_commit.h:55-70, 138-141): mask_position_gap rounded down to a power of two, both vectors zero-padded to
+// slice_size / gap elements.  The protocol's own calls pass one zero each (src/prover.cpp:526, src/verifier.cpp:375-377): gap = slice_size, one element.
+struct Masks { u64 gap = 0; vector<F> pri, pub; u64 ms() const { return pri.size(); } };
+bool mask_geometry(u64 slice_size, u64 n_pri, u64 &gap) {
+    if (n_pri < 1 || n_pri > slice_size) return false;
+    gap = slice_size / n_pri;                                                // poly_commit.h:55
+    for (int j = 0; j < 64; ++j)
+        if ((1ull << j) <= gap && (1ull << (j + 1)) > gap) { gap = 1ull << j; break; }      // :56-61
+    return true;
+}
+Masks make_masks(int n_bits, const F *pri, u64 n_pri, const F *pub, u64 n_pub) {
+    Masks m;
+    const u64 M = 1ull << (n_bits - 1);
+    mask_geometry(M, n_pri, m.gap);
+    m.pri.assign(M / m.gap, F_ZERO); m.pub.assign(M / m.gap, F_ZERO);        // :63-66, :138-141
+    for (u64 i = 0; i < n_pri; ++i) m.pri[i] = pri[i];
+    for (u64 i = 0; i < n_pub; ++i) m.pub[i] = pub[i];
+    return m;
+}
+Masks zero_masks(int n_bits) { const F z = F_ZERO; return make_masks(n_bits, &z, 1, &z, 1); }
+
+// commit_private_array (poly_commit.h:41-124): l_eval[i] = RS encoding (rate 1/32) of slice i of circuitValue[0]; slot 64 = the padded mask interpolated on
+// the ms-th roots and evaluated on the slice's domain (:76-87).  commit_public_array builds q_eval the same way from the public vector and mask (:154-176).
+void commit_private_evals(const vector<F> &input, int n_bits, const vector<F> &mask, vector<F> &l_eval, u64 &slice_size) {
     const u64 slice_real = 1ull << (n_bits - 6);
     slice_size = 1ull << (n_bits - 1);
     l_eval.assign(65 * slice_size, F_ZERO);
-    vector<F> coef(slice_real);
+    vector<F> coef(std::max<u64>(slice_real, mask.size()));
     for (int i = 0; i < 64; ++i) {
         bool all_zero = true;
         for (u64 j = 0; j < slice_real; ++j) if (input[i * slice_real + j] != F_ZERO) { all_zero = false; break; }
@@ -1390,6 +1411,8 @@ void commit_private_evals(const vector<F> &input, int n_bits, vector<F> &l_eval,
         ifft_eval(&input[i * slice_real], slice_real, coef.data());
         fft_eval(coef.data(), slice_real, slice_size, &l_eval[(u64) i * slice_size]);
     }
+    ifft_eval(mask.data(), mask.size(), coef.data());                        // :81-87, no shortcut there
+    fft_eval(coef.data(), mask.size(), slice_size, &l_eval[64 * slice_size]);
 }
 
 }  // namespace
@@ -1421,7 +1444,7 @@ int orc_commit_private(orc_circuit *oc, uint8_t root[32]) {
     vector<F> input(1ull << n_bits, F_ZERO);                                  // circuitValue[0], padded (prover.cpp:30)
     for (u64 g = 0; g < C.circuit[0].size; ++g) input[g] = F((long long) C.circuit[0].gates[g].u);
     vector<F> l_eval; u64 slice_size;
-    commit_private_evals(input, n_bits, l_eval, slice_size);
+    commit_private_evals(input, n_bits, zero_masks(n_bits).pri, l_eval, slice_size);
     Digest r = merkle_root(leaf_hashes(l_eval, slice_size));
     memcpy(root, r.w, 32);
     return 0;
@@ -1429,14 +1452,17 @@ int orc_commit_private(orc_circuit *oc, uint8_t root[32]) {
 
 }  // extern "C"
 
-// ---- commit_public_array (poly_commit.h:126-349) with zero masks ---------------------------------------
+// ---- commit_public_array (poly_commit.h:126-349) ------------------------------------------------------------------------------------------
 namespace {
 struct PublicOut { F inner; F all_sum[65]; Digest root_h; };
-void commit_public_core(const vector<F> &input, const vector<F> &pub, int n_bits, u64 n_used, PublicOut &out, vector<F> *vo = nullptr) {
+// what an opening needs: the 65 codewords of l and h (kept only on request)
+struct Kept { vector<F> l_eval, h_arr; vector<vector<F>> levels; };
+void commit_public_core(const vector<F> &input, const vector<F> &pub, int n_bits, u64 n_used, const Masks &mk, PublicOut &out, vector<F> *vo = nullptr,
+                        vector<F> *vo_msk = nullptr, Kept *keep = nullptr) {
     const u64 N = 1ull << (n_bits - 6);
     vector<F> l_eval, q_eval; u64 M;
-    commit_private_evals(input, n_bits, l_eval, M);                       // the prover still holds l_eval (poly_commit.cpp:4-13)
-    commit_private_evals(pub, n_bits, q_eval, M);                         // poly_commit.h:163-176 (no all-zero shortcut there; same values)
+    commit_private_evals(input, n_bits, mk.pri, l_eval, M);               // the prover still holds l_eval (poly_commit.cpp:4-13)
+    commit_private_evals(pub, n_bits, mk.pub, q_eval, M);                 // poly_commit.h:154-176 (no all-zero shortcut there; same values)
     out.inner = F_ZERO;                                                    // prover::inner_prod, src/prover.cpp:532-540
     for (u64 i = 0; i < n_used; ++i) out.inner = out.inner + input[i] * pub[i];
     vector<F> h_arr(65 * M, F_ZERO), lq_eval(2 * N), lq_coef(2 * N), h_coef(N);
@@ -1465,8 +1491,37 @@ void commit_public_core(const vector<F> &input, const vector<F> &pub, int n_bits
             }
         }
     }
-    out.all_sum[64] = F_ZERO;                                              // mask slice: zero polynomial (:262)
+    {   // the mask slice (poly_commit.h:205-262): l q at 2 ms points of the domain, its 2 ms coefficients, h = the upper half
+        const u64 ms = mk.ms(), half_gap = mk.gap / 2;                     // gap != 1 (:206)
+        vector<F> mq_eval(2 * ms), mq_coef(2 * ms, F_ZERO), mh_coef(ms, F_ZERO);
+        const F *lm = &l_eval[64 * M], *qm = &q_eval[64 * M];
+        F *hm = &h_arr[64 * M];
+        bool all_zero = true;
+        for (u64 id = 0; id < 2 * ms; ++id) {
+            mq_eval[id] = lm[id * half_gap] * qm[id * half_gap];
+            if (mq_eval[id] != F_ZERO) all_zero = false;
+        }
+        if (!all_zero) {                                                   // :216-237; otherwise all three stay zero
+            ifft_eval(mq_eval.data(), 2 * ms, mq_coef.data());
+            for (u64 j = 0; j < ms; ++j) mh_coef[j] = mq_coef[j + ms];
+            fft_eval(mh_coef.data(), ms, M, hm);
+        }
+        const F s0 = mq_coef[0] + mh_coef[0], f_ms((long long) ms);
+        if (vo_msk) {                                                      // :239-261, natural order (the reference stores the pair (j, j + M/2) side by side)
+            vo_msk->assign(M, F_ZERO);
+            const F rou_ms = fpow(rou, ms);
+            F x_n = F_ONE, inv_x = F_ONE;
+            for (u64 j = 0; j < M; ++j) {
+                const F g = lm[j] * qm[j] - (x_n - F_ONE) * hm[j];
+                (*vo_msk)[j] = (g - s0) * f_ms * inv_x;
+                inv_x = inv_x * inv_rou;
+                x_n = x_n * rou_ms;
+            }
+        }
+        out.all_sum[64] = s0 * f_ms;                                       // :262
+    }
     out.root_h = merkle_root(leaf_hashes(h_arr, M));
+    if (keep) { keep->l_eval.swap(l_eval); keep->h_arr.swap(h_arr); }
 }
 }  // namespace
 
@@ -1479,7 +1534,7 @@ int orc_commit_public(const orc_F *input, const orc_F *pub, int n_bits, uint64_t
     vector<F> in(n), pb(n);
     for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
     PublicOut o;
-    commit_public_core(in, pb, n_bits, n_used, o);
+    commit_public_core(in, pb, n_bits, n_used, zero_masks(n_bits), o);
     inner->real = o.inner.re; inner->img = o.inner.im;
     for (int i = 0; i < 65; ++i) { all_sum[i].real = o.all_sum[i].re; all_sum[i].img = o.all_sum[i].im; }
     memcpy(root_h, o.root_h.w, 32);
@@ -1507,7 +1562,7 @@ int64_t orc_prove_full(orc_circuit *oc, uint8_t *transcript, int64_t capacity, o
     init_beta_table(pub, n_bits, v.r_liu.data(), F_ONE);
     oc->last_point.assign(v.r_liu.begin(), v.r_liu.begin() + n_bits);
     PublicOut po;
-    commit_public_core(p.circuitValue[0], pub, n_bits, C.circuit[0].size, po);
+    commit_public_core(p.circuitValue[0], pub, n_bits, C.circuit[0].size, zero_masks(n_bits), po);
     out.insert(out.end(), (unsigned char *) po.root_h.w, (unsigned char *) po.root_h.w + 32);
     v.putF(po.inner);
     for (int i = 0; i < 65; ++i) v.putF(po.all_sum[i]);
@@ -1523,78 +1578,129 @@ int64_t orc_prove_full(orc_circuit *oc, uint8_t *transcript, int64_t capacity, o
 
 }  // extern "C"
 
-// fri::commit_phase_step (fri.cpp:289-424) looped over the n_bits-6 challenges on the virtual oracle vo [64][2^(n_bits-1)], then
-// fri::commit_phase_final's layout: the loop behind orc_fri_commit and orc_commitment_array.
+// fri::commit_phase_step (fri.cpp:289-424) looped over the n_bits-6 challenges on the virtual oracle vo [64][2^(n_bits-1)] and the mask slice's vo_msk
+// [2^(n_bits-1)], then fri::commit_phase_final's layout: the loop behind orc_fri_commit, orc_commitment_array and orc_commitment_array_masked.
 namespace {
-void fri_commit_loop(const vector<F> &vo, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code) {
+void fri_commit_loop(const vector<F> &vo, const vector<F> &vo_msk, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code, orc_F *final_mask,
+                     vector<vector<F>> *levels = nullptr) {
     u64 M = 1ull << (n_bits - 1);
     const int steps = n_bits - 6;
     const F inv2 = finv(F(2ll));
-    vector<F> cur = vo;                                                   // [64][M]
+    vector<F> cur = vo, cur_m = vo_msk;                                   // [64][M], [M]
     F w = root_of_unity(log2_exact(M));
     for (int k = 0; k < steps; ++k) {
         const F rk(r[k].real, r[k].img);
         const u64 half = M / 2;
         const F inv_w = finv(w);
-        vector<F> nxt(64 * half);
-        F inv_mu = F_ONE;                                                 // w^-i  (L_group[(M - i) & (M - 1)], fri.cpp:322)
+        vector<F> padded(65 * half, F_ZERO);                              // the new codeword, the mask slice's in slot 64
+        F inv_mu = F_ONE;                                                 // w^-i  (L_group[(M - i) & (M - 1)], fri.cpp:324, :366)
         for (u64 i = 0; i < half; ++i) {
             const F c = inv_mu * rk;
             for (int s = 0; s < 64; ++s) {
                 const F a = cur[(u64) s * M + i], b = cur[(u64) s * M + i + half];
-                nxt[(u64) s * half + i] = inv2 * ((a + b) + c * (a - b));  // fri.cpp:327-329
+                padded[(u64) s * half + i] = inv2 * ((a + b) + c * (a - b));  // fri.cpp:330-332
             }
+            const F a = cur_m[i], b = cur_m[i + half];
+            padded[64 * half + i] = inv2 * ((a + b) + c * (a - b));       // fri.cpp:369-374
             inv_mu = inv_mu * inv_w;
         }
-        // leaves of the new codeword: pairs (i, i + half/2) chained over the slices, then the (zero) mask pair
-        vector<F> padded(65 * half, F_ZERO);
-        std::copy(nxt.begin(), nxt.end(), padded.begin());
+        // leaves of the new codeword: pairs (i, i + half/2) chained over the slices, then the mask pair (fri.cpp:392-413)
         Digest root = merkle_root(leaf_hashes(padded, half));
         memcpy(roots + 32 * k, root.w, 32);
-        cur.swap(nxt);
+        cur.assign(padded.begin(), padded.begin() + 64 * half);
+        cur_m.assign(padded.begin() + 64 * half, padded.end());
+        if (levels) levels->push_back(std::move(padded));
         M = half;
         w = w * w;
     }
     for (u64 i = 0; i < 16; ++i)
-        for (int s = 0; s < 64; ++s)
-            for (int hi = 0; hi < 2; ++hi) {
+        for (int hi = 0; hi < 2; ++hi) {
+            for (int s = 0; s < 64; ++s) {
                 const F x = cur[(u64) s * 32 + i + 16 * hi];
                 orc_F &o = final_code[(i << 7) | (s << 1) | hi];
                 o.real = x.re; o.img = x.im;
             }
+            if (final_mask) { final_mask[i << 1 | hi].real = cur_m[i + 16 * hi].re; final_mask[i << 1 | hi].img = cur_m[i + 16 * hi].im; }   // fri.cpp:378-380
+        }
+}
+
+// the whole commitment on arrays with the masks mk: what orc_commitment_array and orc_commitment_array_masked both are
+int commitment_array_core(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, const Masks &mk, uint8_t root_l[32], orc_F *inner,
+                          orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots, orc_F *final_code, orc_F *final_mask, int n_open, const int64_t *open_at,
+                          orc_F *open_vals) {
+    const u64 n = 1ull << n_bits;
+    vector<F> in(n), pb(n), vo, vo_msk;
+    for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
+    {   // merkle_root_l, as orc_commit_private
+        vector<F> l_eval; u64 slice_size;
+        commit_private_evals(in, n_bits, mk.pri, l_eval, slice_size);
+        Digest d = merkle_root(leaf_hashes(l_eval, slice_size));
+        memcpy(root_l, d.w, 32);
+    }
+    PublicOut po;
+    Kept keep;
+    commit_public_core(in, pb, n_bits, n_used, mk, po, &vo, &vo_msk, n_open > 0 ? &keep : nullptr);
+    inner->real = po.inner.re; inner->img = po.inner.im;
+    for (int i = 0; i < 65; ++i) { all_sum[i].real = po.all_sum[i].re; all_sum[i].img = po.all_sum[i].im; }
+    memcpy(root_h, po.root_h.w, 32);
+    fri_commit_loop(vo, vo_msk, n_bits, r, roots, final_code, final_mask, n_open > 0 ? &keep.levels : nullptr);
+    for (int q = 0; q < n_open; ++q) {                                     // fri::request_init_value_with_merkle / request_step_commit: the 65 pairs of a leaf
+        const int64_t o = open_at[2 * q], leaf = open_at[2 * q + 1];
+        if (o < 0 || o >= 2 + (n_bits - 6)) return -2;
+        const vector<F> &cw = o == 0 ? keep.l_eval : o == 1 ? keep.h_arr : keep.levels[o - 2];
+        const u64 size = cw.size() / 65;
+        if (leaf < 0 || (u64) leaf >= size / 2) return -2;
+        for (int s = 0; s < 65; ++s)
+            for (int hi = 0; hi < 2; ++hi) {
+                const F &x = cw[(u64) s * size + leaf + hi * (size / 2)];
+                open_vals[(u64) q * 130 + 2 * s + hi].real = x.re; open_vals[(u64) q * 130 + 2 * s + hi].img = x.im;
+            }
+    }
+    return 0;
 }
 }  // namespace
 
 extern "C" int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, const orc_F *r, uint8_t *roots, orc_F *final_code) {
     if (n_bits < 7) return -1;
     const u64 n = 1ull << n_bits;
-    vector<F> in(n), pb(n), vo;
+    vector<F> in(n), pb(n), vo, vo_msk;
     for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
     PublicOut po;
-    commit_public_core(in, pb, n_bits, n, po, &vo);
-    fri_commit_loop(vo, n_bits, r, roots, final_code);
+    commit_public_core(in, pb, n_bits, n, zero_masks(n_bits), po, &vo, &vo_msk);
+    fri_commit_loop(vo, vo_msk, n_bits, r, roots, final_code, nullptr);
     return 0;
 }
 
 extern "C" int orc_commitment_array(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, uint8_t root_l[32],
                                     orc_F *inner, orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots, orc_F *final_code) {
     if (n_bits < 7 || n_used > (1ull << n_bits)) return -1;
-    const u64 n = 1ull << n_bits;
-    vector<F> in(n), pb(n), vo;
-    for (u64 i = 0; i < n; ++i) { in[i] = F(input[i].real, input[i].img); pb[i] = F(pub[i].real, pub[i].img); }
-    {   // merkle_root_l, as orc_commit_private
-        vector<F> l_eval; u64 slice_size;
-        commit_private_evals(in, n_bits, l_eval, slice_size);
-        Digest d = merkle_root(leaf_hashes(l_eval, slice_size));
-        memcpy(root_l, d.w, 32);
-    }
-    PublicOut po;
-    commit_public_core(in, pb, n_bits, n_used, po, &vo);
-    inner->real = po.inner.re; inner->img = po.inner.im;
-    for (int i = 0; i < 65; ++i) { all_sum[i].real = po.all_sum[i].re; all_sum[i].img = po.all_sum[i].im; }
-    memcpy(root_h, po.root_h.w, 32);
-    fri_commit_loop(vo, n_bits, r, roots, final_code);
-    return 0;
+    return commitment_array_core(input, n_used, pub, n_bits, r, zero_masks(n_bits), root_l, inner, all_sum, root_h, roots, final_code, nullptr, 0, nullptr, nullptr);
+}
+
+extern "C" int orc_commitment_array_masked_open(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, const orc_F *pri_mask,
+                                                uint64_t n_pri, const orc_F *pub_mask, uint64_t n_pub, uint8_t root_l[32], orc_F *inner, orc_F all_sum[65],
+                                                uint8_t root_h[32], uint8_t *roots, orc_F *final_code, orc_F final_mask[32], int n_open,
+                                                const int64_t *open_at, orc_F *open_vals) {
+    if (n_bits < 7 || n_bits > 30 || n_used > (1ull << n_bits) || !pri_mask || !pub_mask || n_open < 0) return -1;
+    u64 gap = 0;
+    if (!mask_geometry(1ull << (n_bits - 1), n_pri, gap)) return -1;                      // an empty mask, or one longer than a slice
+    const u64 ms = (1ull << (n_bits - 1)) / gap;
+    if (ms < 8 || gap < 2 || n_pub < 1 || n_pub > ms) return -1;                           // RS_polynomial.cpp:104-133; poly_commit.h:206; :139
+    for (u64 i = 0; i < n_pri; ++i) if (pri_mask[i].real >= P || pri_mask[i].img >= P) return -1;
+    for (u64 i = 0; i < n_pub; ++i) if (pub_mask[i].real >= P || pub_mask[i].img >= P) return -1;
+    for (int i = 0; i < n_bits - 6; ++i) if (r[i].real >= P || r[i].img >= P) return -1;
+    vector<F> pm(n_pri), qm(n_pub);
+    for (u64 i = 0; i < n_pri; ++i) pm[i] = F(pri_mask[i].real, pri_mask[i].img);
+    for (u64 i = 0; i < n_pub; ++i) qm[i] = F(pub_mask[i].real, pub_mask[i].img);
+    return commitment_array_core(input, n_used, pub, n_bits, r, make_masks(n_bits, pm.data(), n_pri, qm.data(), n_pub), root_l, inner, all_sum, root_h, roots,
+                                 final_code, final_mask, n_open, open_at, open_vals);
+}
+
+extern "C" int orc_commitment_array_masked(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, const orc_F *pri_mask,
+                                           uint64_t n_pri, const orc_F *pub_mask, uint64_t n_pub, uint8_t root_l[32], orc_F *inner, orc_F all_sum[65],
+                                           uint8_t root_h[32], uint8_t *roots, orc_F *final_code, orc_F final_mask[32]) {
+    return orc_commitment_array_masked_open(input, n_used, pub, n_bits, r, pri_mask, n_pri, pub_mask, n_pub, root_l, inner, all_sum, root_h, roots, final_code,
+                                            final_mask, 0, nullptr, nullptr);
 }
 
 extern "C" int orc_last_point(const orc_circuit *oc, orc_F *out, int n) {

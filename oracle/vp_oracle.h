@@ -173,9 +173,26 @@ int orc_fri_commit(const orc_F *input, const orc_F *pub, int n_bits, const orc_F
 /* The whole commitment on caller-supplied arrays in one pass: commit_private_array's root (merkle_root_l), commit_public_array's outputs as
  * orc_commit_public gives them (inner product over the first n_used entries) and the FRI commit phase as orc_fri_commit gives it.  input and pub
  * have 2^n_bits entries (input zero from n_used on, as the padded input layer is); r the n_bits-6 fold challenges; roots 32 (n_bits-6) bytes;
- * final_code 2048 elements.  A composition of the functions above: no arithmetic of its own.                                              */
+ * final_code 2048 elements.  A composition: orc_commitment_array_masked's code with the one-element zero masks the protocol passes.                      */
 int orc_commitment_array(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, uint8_t root_l[32], orc_F *inner,
                          orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots, orc_F *final_code);
+
+/* The same commitment with the mask vectors of a hiding commitment: commit_private_array(input, pri_mask), commit_public_array(pub_mask, pub) and the commit
+ * phase restated as written (poly_commit.h:55-86, 138-161, 187-262; fri.cpp:107-122, 358-385, 405-411) — the gap rounding and zero padding of both masks, the
+ * inverse then forward transform into slot 64 of l_eval / q_eval / h, the all-zero shortcut of the mask product, all_sum[64], the mask's virtual oracle, its
+ * fold beside the 64 at every level, leaf chains closed by the mask pair.  final_mask: the mask slice's last codeword, [i << 1 | hi], i < 16 (32 elements).
+ * orc_commitment_array is this code with the protocol's one-element zero masks.  Returns -1 for what the device refuses: a private mask that pads to fewer than
+ * 8 elements or to the whole slice (gap 1), or is empty or longer than a slice; a public mask that is empty or longer than the padded private one; a limb of
+ * a mask or a challenge that is not canonical.                                                                                                              */
+int orc_commitment_array_masked(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, const orc_F *pri_mask, uint64_t n_pri,
+                                const orc_F *pub_mask, uint64_t n_pub, uint8_t root_l[32], orc_F *inner, orc_F all_sum[65], uint8_t root_h[32], uint8_t *roots,
+                                orc_F *final_code, orc_F final_mask[32]);
+/* ... and n_open openings: open_at holds (oracle, leaf) pairs — oracle 0 = l, 1 = h, 2 + k = FRI level k — and open_vals receives 130 elements each, the pairs
+ * (position leaf, position leaf + half the codeword) of the 64 slices, then the mask slice's (fri::request_init_value_with_merkle, request_step_commit).
+ * -2: a request outside the commitment.                                                                                                                      */
+int orc_commitment_array_masked_open(const orc_F *input, uint64_t n_used, const orc_F *pub, int n_bits, const orc_F *r, const orc_F *pri_mask, uint64_t n_pri,
+                                     const orc_F *pub_mask, uint64_t n_pub, uint8_t root_l[32], orc_F *inner, orc_F all_sum[65], uint8_t root_h[32],
+                                     uint8_t *roots, orc_F *final_code, orc_F final_mask[32], int n_open, const int64_t *open_at, orc_F *open_vals);
 
 #ifdef __cplusplus
 }

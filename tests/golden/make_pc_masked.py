@@ -35,6 +35,8 @@ def main():
                       "record": os.path.basename(rec), "fri": os.path.basename(fri), "record_sha256": hashlib.sha256(open(rec, "rb").read()).hexdigest(),
                       "fri_sha256": hashlib.sha256(open(fri, "rb").read()).hexdigest(),
                       "origin": "real reference: oracle/_ref/ref_run --pc-masked (commit_private_array / commit_public_array / commit_phase with the masks of tests/pc_masked_inputs.py)"}
+        if name in pmi.PUB_LEN:
+            meta[name]["n_pub"] = pmi.PUB_LEN[name]             # the public mask's own length: the IN file carries it zero-padded to m
         print(name, r.stdout.strip(), os.path.getsize(rec), os.path.getsize(fri))
     json.dump(meta, open(os.path.join(HERE, "pc_masked.json"), "w"), indent=1, sort_keys=True)
 

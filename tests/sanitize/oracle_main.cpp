@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY.  Sanitizer leg of the CPU build (SURVEY.md §5 "ASan/UBSan CPU targets"): the oracle compiled with
 // -fsanitize=address,undefined (make -C oracle asan -> oracle/_build/oracle_asan) and driven through every code path the parity tests use —
 // loader + replication, randomize, custom circuits with every gate type, GKR proof, Fiat-Shamir proof, the full protocol with the
-// commitment, FRI commit phase, primitives, fft_gkr and the GKR prover on caller's tapes.  Exit code 0 and no sanitizer report = pass (tests/test_sanitizers.py).
+// commitment, FRI commit phase, the commitment with masks, primitives, fft_gkr and the GKR prover on caller's tapes.  Exit code 0 and no sanitizer report = pass (tests/test_sanitizers.py).
 #include "../../oracle/vp_oracle.h"
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +32,32 @@ int main(int argc, char **argv) {
         orc_f_random_next((int) r.size(), r.data());
         std::vector<uint8_t> roots(32 * r.size());
         if (orc_fri_commit(in.data(), pub.data(), nb, r.data(), roots.data(), fin.data()) != 0) return fail("fri_commit");
+        {   // the same commitment with masks: a private mask of 100 elements (pads to 128, more than a slice's message of 8), a shorter public one, three
+            // openings; with zero masks the bytes of the unmasked entry; the entry's refusals
+            std::vector<orc_F> pm(100), qm(37), fm(32), fin2(2048), fm2(32), ov(3 * 130);
+            orc_f_random_seq(11, 100, pm.data());
+            orc_f_random_seq(12, 37, qm.data());
+            uint8_t rl[32], rh[32], rl2[32], rh2[32];
+            orc_F inner, alls[65], inner2, alls2[65];
+            std::vector<uint8_t> roots2(roots.size());
+            const int64_t at[6] = {0, 0, 1, (1 << (nb - 2)) - 1, 2 + nb - 7, 15};
+            if (orc_commitment_array_masked_open(in.data(), in.size(), pub.data(), nb, r.data(), pm.data(), 100, qm.data(), 37, rl, &inner, alls, rh, roots.data(),
+                                                 fin.data(), fm.data(), 3, at, ov.data()) != 0) return fail("commitment_array_masked_open");
+            if (!alls[64].real && !alls[64].img) return fail("masked all_sum[64]");
+            for (auto &x : pm) x = {0, 0};
+            if (orc_commitment_array_masked(in.data(), in.size(), pub.data(), nb, r.data(), pm.data(), 100, pm.data(), 1, rl, &inner, alls, rh, roots.data(),
+                                            fin.data(), fm.data()) != 0) return fail("commitment_array_masked, zero masks");
+            if (orc_commitment_array(in.data(), in.size(), pub.data(), nb, r.data(), rl2, &inner2, alls2, rh2, roots2.data(), fin2.data()) != 0) return fail("commitment_array");
+            if (memcmp(rl, rl2, 32) || memcmp(rh, rh2, 32) || memcmp(alls, alls2, sizeof alls) || roots != roots2 || memcmp(fin.data(), fin2.data(), 2048 * sizeof(orc_F)) ||
+                memcmp(fm.data(), fm2.data(), 32 * sizeof(orc_F)) /* fm2 is zero */) return fail("zero masks differ from the unmasked entry");
+            if (orc_commitment_array_masked(in.data(), in.size(), pub.data(), nb, r.data(), pm.data(), 3, pm.data(), 1, rl, &inner, alls, rh, roots.data(), fin.data(),
+                                            fm.data()) != -1) return fail("a mask that pads to fewer than 8 elements");
+            if (orc_commitment_array_masked(in.data(), in.size(), pub.data(), nb, r.data(), pm.data(), 100, qm.data(), 37, rl, &inner, alls, rh, roots.data(), fin.data(),
+                                            fm.data()) != 0) return fail("commitment_array_masked");
+            qm[36].img = 2305843009213693951ull;
+            if (orc_commitment_array_masked(in.data(), in.size(), pub.data(), nb, r.data(), pm.data(), 100, qm.data(), 37, rl, &inner, alls, rh, roots.data(), fin.data(),
+                                            fm.data()) != -1) return fail("non-canonical mask limb");
+        }
         orc_circuit_free(c);
     }
     {   // tiny and ragged shapes: one-gate layers, single-entry tables

@@ -570,3 +570,79 @@ def test_oracle_gkr_tape_refusals_and_dont_care_draws(ob):
     got = c.prove_gkr_tape(moved)[0]
     assert got != want and got[:-16] == want[:-16]
     c.close()
+
+
+# ---- the oracle's masked commitment (orc_commitment_array_masked) against the REAL reference ------------------------------------------------------------------
+
+def _masked_oracle_vs_record(ob, n, values, pub, pri_mask, pub_mask, rec, fri):
+    """orc_commitment_array_masked_open on the reference's own challenges (read from its FRI record) against a `--dump` / `--dump-fri` pair of
+    `ref_run --pc-masked`: both roots, all_sum[65], the eight openings (3 leaves of l, 3 of h, leaf 3 of FRI levels 0 and 2; 65 pairs each), every FRI root, the
+    final codeword and the mask slice's final codeword, byte for byte"""
+    import pc_masked_inputs as pmi
+    st, M = n - 6, 1 << (n - 1)
+    assert len(rec) == 64 + 65 * 16 + 8 * 130 * 16 and len(fri) == 48 * st + 2048 * 16 + 32 * 16
+    r = np.frombuffer(b"".join(fri[48 * k:48 * k + 16] for k in range(st)), dtype=np.uint64).reshape(st, 2).copy()
+    opens = [(0, 0), (0, 5), (0, M // 2 - 1), (1, 0), (1, 5), (1, M // 2 - 1), (2, 3), (4, 3)]
+    got, vals = pmi.oracle_masked(ob.lib(), values, 1 << n, pub, n, r, pri_mask, pub_mask, opens)
+    f = pmi.split_masked_record(got, n)
+    assert f["root_l"] == rec[:32], "merkle_root_l"
+    assert f["root_h"] == rec[32:64], "merkle_root_h"
+    assert f["public"][16:] == rec[64:64 + 65 * 16], "all_sum[65]"
+    for i, (o, lf) in enumerate(opens):
+        assert vals[i].tobytes() == rec[64 + 65 * 16 + 130 * 16 * i:64 + 65 * 16 + 130 * 16 * (i + 1)], "opening of oracle %d at leaf %d" % (o, lf)
+    for k in range(st):
+        assert f["roots"][k] == fri[48 * k + 16:48 * k + 48], "FRI root %d" % k
+    assert f["final"] == fri[48 * st:48 * st + 2048 * 16], "final codeword"
+    assert f["final_mask"] == fri[48 * st + 2048 * 16:], "final mask codeword"
+
+
+@pytest.mark.parametrize("name", ["n13_zero", "n13_m5", "n13_m64", "n16_m100", "n19_m3000", "n13_m300", "n13_m2000", "n13_m128", "n13_m100_p37", "n13_m200", "n13_m1000"])
+def test_masked_oracle_reproduces_the_real_references_records(ob, name):
+    """All eleven records of the real reference's commitment with masks (tests/golden/pc_masked_*.bin): ms = 8, 64, 128 (= N), 512, 2048 at n = 13, 128 at
+    n = 16, 4096 at n = 19; 2, 4, 8 and 16 blocks of a slice's message; a public mask of 37 elements under a private one of 100.  n13_zero is the protocol's
+    one-element zero mask, which the entry refuses as the device does (it pads to one element): there the entry gets eight zeros, the same polynomial, and
+    orc_commitment_array — the same code on the one-element zero masks — must return the same bytes."""
+    import json
+    import pc_array_inputs as pai
+    import pc_masked_inputs as pmi
+    from conftest import GOLDEN
+    m = json.load(open(os.path.join(GOLDEN, "pc_masked.json")))[name]
+    x = pmi.inputs(name)
+    n = x["n"]
+    assert m.get("n_pub", x["m"]) == x["n_pub"] and not x["pub_mask"][x["n_pub"]:].any()
+    rec, fri = open(os.path.join(GOLDEN, m["record"]), "rb").read(), open(os.path.join(GOLDEN, m["fri"]), "rb").read()
+    pm, qm = x["pri_mask"], x["pub_mask"][:x["n_pub"]]
+    if name == "n13_zero":
+        assert pmi.oracle_masked_rc(ob.lib(), x["values"], 1 << n, x["pub"], n, np.zeros((n - 6, 2), np.uint64), pm, qm)[0] == -1
+        pm = qm = np.zeros((8, 2), np.uint64)
+        st = n - 6
+        r = np.frombuffer(b"".join(fri[48 * k:48 * k + 16] for k in range(st)), dtype=np.uint64).reshape(st, 2).copy()
+        f = pai.split_record(pai.oracle_record(ob.lib(), x["values"], 1 << n, x["pub"], n, r), n)
+        assert (f["root_l"], f["root_h"], f["public"][16:]) == (rec[:32], rec[32:64], rec[64:64 + 65 * 16])
+        assert b"".join(f["roots"]) == b"".join(fri[48 * k + 16:48 * k + 48] for k in range(st)) and f["final"] == fri[48 * st:48 * st + 2048 * 16]
+    _masked_oracle_vs_record(ob, n, x["values"], x["pub"], pm, qm, rec, fri)
+
+
+@pytest.mark.parametrize("fam,ms", [("uniform", 8), ("edges", 16), ("short_pub", 32), ("one_hot", 64), ("pub_zero", 128), ("edges", 256)])
+@pytest.mark.parametrize("n", [10, 11])
+def test_masked_oracle_vs_the_real_reference_live(ob, tmp_path, n, fam, ms):
+    """Where oracle/_ref/ref_run exists: the oracle against `ref_run --pc-masked` on the mask families at n = 10 and 11 (slices of 16 and 32 elements: every
+    transform of the reference has at least the 8 points below which it reads stale scratch, tests/pc_masked_inputs.py).  The reference's output there is a
+    function of its inputs — run twice here, equal bytes asserted — so both lengths stay."""
+    import subprocess
+    import pc_array_inputs as pai
+    import pc_masked_inputs as pmi
+    from conftest import ROOT
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_run")
+    if not os.path.exists(exe):
+        pytest.skip("oracle/_ref/ref_run not built (needs the reference tree at build time)")
+    x, f = pai.inputs("uniform", n), pmi.family(fam, n, ms)
+    inp = str(tmp_path / "in.bin")
+    pmi.write_in_file(inp, n, x["values"], x["pub"], f["pri_mask"], f["pub_mask"])
+    runs = []
+    for k in range(2):
+        rec, fri = str(tmp_path / ("rec%d.bin" % k)), str(tmp_path / ("fri%d.bin" % k))
+        subprocess.run([exe, "--pc-masked", inp, "--dump", rec, "--dump-fri", fri], stdout=subprocess.PIPE, check=True, timeout=600)
+        runs.append((open(rec, "rb").read(), open(fri, "rb").read()))
+    assert runs[0] == runs[1], "the reference's masked commitment is not a function of its inputs here"
+    _masked_oracle_vs_record(ob, n, x["values"], x["pub"], f["pri_mask"], f["pub_mask"], *runs[0])
