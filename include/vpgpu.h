@@ -372,6 +372,15 @@ int vp_fri_query(vp_ctx *, int n_queries, const uint64_t *leaf0, uint8_t *out, u
 int vp_pc_public_evals(vp_ctx *, int n, const vp_F *point /* n, or NULL */, const vp_F *pub /* 2^n, or NULL */, int n_queries, const uint64_t *leaf0,
                        vp_F *out /* n_queries x 2 x 64 */);
 int vp_fri_query_digests(vp_ctx *, int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out /* n_queries x (n - 4) x 64 */);
+/* The mask row of vp_pc_public_evals, for the verifier of a masked commitment (slot 64, vpd_verifier.cpp:82-87,195-205): the public mask polynomial q_msk is the
+ * interpolant of the public mask, zero-padded to ms, on the ms-th roots of unity;
+ *     out[2 q + 0] = q_msk(w^leaf0[q]),   out[2 q + 1] = q_msk(-w^leaf0[q]),   canonical.
+ * Like its sibling: a context without a commitment will do, the same arena, every refusal before any launch and with the context unchanged — those of
+ * vp_pc_public_evals for n, n_queries, leaf0 and limbs, and VP_EINVAL for ms not a power of two in [8, min(2^16, 2^(n-2))] (the padded lengths
+ * vp_commit_private_masked takes) and for n_pub_mask outside 1 .. ms.  Launches: the commitment's inverse transform at ms points, k_pc_poly_eval ONCE over one row of
+ * ms coefficients on the domain of order M (row length and domain are separate arguments of the kernel: ms < 4096 is one partly filled chunk, ms > N is allowed), and
+ * the closing launch k_pc_mask_eval_fin; in the launch table under VP_K_PC_POLY_EVAL and VP_K_PC_POLY_EVAL_FIN.                                                  */
+int vp_pc_mask_evals(vp_ctx *, int n, const vp_F *pub_mask, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, vp_F *out /* n_queries x 2 */);
 /* fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp:833-849), prover side: the self-contained GKR over the inverse-FFT +
  * polynomial-evaluation circuit that verify_poly_commitment runs between commit_public and the FRI commit phase (vpd_verifier.cpp:92,
  * lg = bit_length(layer 0) - 6) and whose prover time the reference adds to "Polynomial commitment: prove time" (:94, src/verifier.cpp:183).
@@ -408,8 +417,8 @@ int vp_fft_gkr_cancel(vp_ctx *);
  * (vp_commit_public_eq), nothing of it crosses PCIe; vp_commit_public_masked's checks and limits, every refusal before the first launch; the mask is copied during the
  * call, which may complete deferred (vp_set_deferred) like vp_commit_public_eq.  Leaf chains of a masked oracle: the generated fixed-register chain with the mask
  * pair as its last block (vp_keccak_asm.h, vp_leaf_chain_mask_asm) under the workgroup rules of the unmasked launches, the compiler's form below 2^17 leaves, with
- * leaf_asm = 0 and in the checked build.  Not built: masks on a sharded commitment, live slices under a mask (a masked commitment transforms all 64 slices), a
- * host verifier for masked commitments (the reference's own verifier decides them, oracle/integration/masked_main.cpp).
+ * leaf_asm = 0 and in the checked build.  Not built: masks on a sharded commitment, live slices under a mask (a masked commitment transforms all 64 slices).
+ * The host verifier checks the mask slice like the other 64 (host/verifier.hpp: verifyFull with masks, pcVerifyCommitment; its device loop is vp_pc_mask_evals).
  * What the reference's VERIFIER makes of it (vpd_verifier.cpp:76-328 with the public mask, oracle/integration/masked_main.cpp): a commitment whose ms is at most a
  * slice's message length 2^(n-6) is accepted; a longer mask is committed exactly as the reference's prover commits it and rejected exactly as the reference's verifier
  * rejects that prover's (its last check, :318-324: n - 6 folds do not reduce the mask slice to a constant).                                                        */

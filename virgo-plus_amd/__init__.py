@@ -169,6 +169,7 @@ def lib_gpu():
         L.vp_fri_query.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
         L.vp_pc_public_evals.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp]
         L.vp_fri_query_digests.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_uint64, vp]
+        L.vp_pc_mask_evals.argtypes = [vp, ctypes.c_int, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, vp]
         L.vp_commit_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.vp_comm_unique_id.argtypes = [vp]
         L.vp_comm_init.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
@@ -246,6 +247,11 @@ def lib_host():
         L.vph_prove_full.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_and_verify_full.argtypes = [vp, ctypes.c_int, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_and_verify_full_ex.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.c_char_p, ctypes.c_int]
+        L.vph_prove_and_verify_full_masked.argtypes = ([vp, ctypes.c_int, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64)] + [ctypes.POINTER(ctypes.c_double)] * 3 +
+                                                       [ctypes.c_char_p, ctypes.c_int])
+        L.vph_pc_mask_evals_host.argtypes = [ctypes.c_int, vp, u64, u64, ctypes.c_int, vp, vp]
+        L.vph_pc_mask_evals.argtypes = [vp, ctypes.c_int, vp, u64, u64, ctypes.c_int, vp, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_verify_commitment.argtypes = [ctypes.c_int, vp, vp, vp, u64, u64] + [vp] * 8 + [ctypes.c_int, vp, vp, u64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_last_full_record.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
         L.vph_verify_full_record.argtypes = [vp, vp, u64]
         L.vph_verifier_launches.argtypes = [vp, ctypes.POINTER(LaunchStat), ctypes.c_int]
@@ -692,6 +698,49 @@ class Circuit:
             raise ValueError("pc_opening_digests_host: refused")
         return out.raw[: len(lf) * (n - 4) * 64]
 
+    @staticmethod
+    def pc_mask_evals_host(n, leaf0, pub_mask, ms):
+        """The mask row of the verifier's public evaluation on the host, by value (no GPU): (n_queries, 2, 2) uint64 — [q, h] = the public mask polynomial (the
+        interpolant of pub_mask, zero-padded to ms, on the ms-th roots of unity) at (-1)^h w^leaf0[q].  Raises ValueError on refused arguments."""
+        import numpy as np
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        pm = np.ascontiguousarray(pub_mask, dtype=np.uint64).reshape(-1, 2)
+        out = np.zeros((max(len(lf), 1), 2, 2), dtype=np.uint64)
+        if lib_host().vph_pc_mask_evals_host(int(n), pm.ctypes.data if pm.shape[0] else None, pm.shape[0], int(ms), len(lf), lf.ctypes.data, out.ctypes.data):
+            raise ValueError("pc_mask_evals_host: refused")
+        return out[: len(lf)]
+
+    @staticmethod
+    def verify_commitment(n, claim, root_l, root_h, all_sum, r, fri_roots, final_code, final_mask, leaf0, answer, point=None, pub=None, pub_mask=None, ms=1,
+                          device=None):
+        """The commitment's verifier by value (vph_verify_commitment, host/vphost.h): no session, no circuit.  Field elements as (k, 2) uint64 arrays (claim:
+        (2,)), roots and the answer block (vp_fri_query's layout for (n, len(leaf0))) as bytes; exactly one of point / pub; pub_mask with ms, the private mask's
+        padded length (1: the zero mask).  device=k: the heavy loops on GPU k, same verdict.  Returns (accepted, reason) — reason names the failed check;
+        raises ValueError on malformed arguments and RuntimeError when the device could not run the loops."""
+        import numpy as np
+        arr = lambda a, rows: np.ascontiguousarray(a, dtype=np.uint64).reshape(rows, 2)
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        pt = None if point is None else arr(point, -1)
+        pb = None if pub is None else arr(pub, -1)
+        pm = None if pub_mask is None else arr(pub_mask, -1)
+        if (pt is not None and pt.shape[0] != n) or (pb is not None and (n < 0 or n > 30 or pb.shape[0] != 1 << n)):
+            raise ValueError("verify_commitment: a point of n coordinates or a vector of 2^n entries")
+        if n < 7 or len(root_l) != 32 or len(root_h) != 32 or len(fri_roots) != 32 * (n - 6):
+            raise ValueError("verify_commitment: n >= 7, roots of 32 bytes, n - 6 FRI roots")
+        cl, sums, rr, fc, fm = arr(claim, 1), arr(all_sum, 65), arr(r, n - 6), arr(final_code, 2048), arr(final_mask, 32)
+        keep = [ctypes.create_string_buffer(bytes(b), max(len(b), 1)) for b in (root_l, root_h, fri_roots, answer)]
+        cp = lambda b: ctypes.cast(b, ctypes.c_void_p)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_verify_commitment(int(n), None if pt is None else pt.ctypes.data, None if pb is None else pb.ctypes.data,
+                                              None if pm is None or not pm.shape[0] else pm.ctypes.data, 0 if pm is None else pm.shape[0], int(ms), cl.ctypes.data,
+                                              cp(keep[0]), cp(keep[1]), sums.ctypes.data, rr.ctypes.data, cp(keep[2]), fc.ctypes.data, fm.ctypes.data, len(lf),
+                                              lf.ctypes.data, cp(keep[3]), len(answer), -1 if device is None else int(device), err, len(err))
+        if rc == -1:
+            raise ValueError("verify_commitment: " + err.value.decode())
+        if rc < 0:
+            raise RuntimeError("verify_commitment: " + err.value.decode())
+        return rc == 0, err.value.decode() if rc else ""
+
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
         buf = ctypes.create_string_buffer(bytes(proof), len(proof))
@@ -1130,17 +1179,27 @@ class Session:
         return (buf.raw[: n.value], roots.raw[:32 * st], fin.copy(),
                 {"total": sec[0], "commit_private": sec[1], "gkr": sec[2], "commit_public": sec[3], "fft_gkr": sec[4], "fri_commit": sec[5]})
 
-    def prove_and_verify_full(self, reps=33, batched_openings=False, device_verifier=False):
+    def prove_and_verify_full(self, reps=33, batched_openings=False, device_verifier=False, mask=None, pub_mask=None):
         """The complete protocol incl. commitment verification: (transcript bytes, accepted, times dict).  batched_openings: the query phase is
         answered in one device pass (vp_fri_query) instead of one vp_fri_open per opening; same positions, openings and checks.  device_verifier: the
         verifier's heavy loops — wiring predicates, public polynomial values, opening digests — run on the session's device (VPH_VERIFY_DEVICE_LOOPS;
-        implies the one-pass query phase); every comparison stays on the host, and transcript, record and verdict are the host mode's."""
+        implies the one-pass query phase); every comparison stays on the host, and transcript, record and verdict are the host mode's.
+        mask / pub_mask: (k, 2) uint64 mask vectors of a hiding commitment (vph_prove_and_verify_full_masked): the 65th slice is proved and verified like the
+        other 64, and last_full_record() is then a version-2 record; an all-zero mask is the run without one.  A mask the device refuses raises RuntimeError."""
         cap = self._cap + 32 + 32 + 16 + 65 * 16
         buf = ctypes.create_string_buffer(cap)
         n = ctypes.c_uint64(0)
         t = [ctypes.c_double(0) for _ in range(3)]
         err = ctypes.create_string_buffer(512)
-        if batched_openings or device_verifier:
+        if mask is not None:
+            import numpy as np
+            mk = np.ascontiguousarray(mask, dtype=np.uint64).reshape(-1, 2)
+            pm = np.ascontiguousarray(pub_mask if pub_mask is not None else np.zeros((0, 2)), dtype=np.uint64).reshape(-1, 2)
+            rc = lib_host().vph_prove_and_verify_full_masked(self.h, reps, (1 if batched_openings else 0) | (2 if device_verifier else 0),
+                                                             mk.ctypes.data if mk.shape[0] else None, mk.shape[0], pm.ctypes.data if pm.shape[0] else None, pm.shape[0],
+                                                             ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n), ctypes.byref(t[0]), ctypes.byref(t[1]),
+                                                             ctypes.byref(t[2]), err, len(err))
+        elif batched_openings or device_verifier:
             rc = lib_host().vph_prove_and_verify_full_ex(self.h, reps, (1 if batched_openings else 0) | (2 if device_verifier else 0), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(n),
                                                          ctypes.byref(t[0]), ctypes.byref(t[1]), ctypes.byref(t[2]), err, len(err))
         else:
@@ -1181,6 +1240,22 @@ class Session:
                                             lf.ctypes.data, out.ctypes.data, err, len(err))
         if rc:
             raise RuntimeError("vp_pc_public_evals failed: %d %s" % (rc, err.value.decode()))
+        return out[: len(lf)]
+
+    def pc_mask_evals(self, leaf0, pub_mask, ms, n=None):
+        """vp_pc_mask_evals on the session's device: the public mask polynomial's values at the query points, (n_queries, 2, 2) uint64 as
+        Circuit.pc_mask_evals_host; n defaults to the circuit's input bit length.  Raises RuntimeError with the library's status and message on a refusal."""
+        import numpy as np
+        if n is None:
+            n = self.circuit.layer_bitlen(0)
+        lf = np.ascontiguousarray(leaf0, dtype=np.uint64).reshape(-1)
+        pm = np.ascontiguousarray(pub_mask, dtype=np.uint64).reshape(-1, 2)
+        out = np.zeros((max(len(lf), 1), 2, 2), dtype=np.uint64)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_pc_mask_evals(self.h, int(n), pm.ctypes.data if pm.shape[0] else None, pm.shape[0], int(ms), len(lf), lf.ctypes.data, out.ctypes.data,
+                                          err, len(err))
+        if rc:
+            raise RuntimeError("vp_pc_mask_evals failed: %d %s" % (rc, err.value.decode()))
         return out[: len(lf)]
 
     def fri_query_digests(self, leaf0, answer, n=None):

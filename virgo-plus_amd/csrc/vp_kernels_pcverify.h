@@ -67,6 +67,20 @@ __global__ void __launch_bounds__(VP_BLOCK) k_pc_poly_eval_fin(PolyEvalArgs a, c
     out[((size_t) q * 2 + 1) * 64 + j] = v1;
 }
 
+// The closing launch of the mask row (vp_pc_mask_evals): k_pc_poly_eval ran over ONE row of 2^a.ln coefficients (the public mask polynomial; its length is
+// independent of the domain 2 a.half_m), thread q adds that row's partial sums and writes out[2 q] = E + x O, out[2 q + 1] = E - x O, canonical.
+__global__ void __launch_bounds__(VP_BLOCK) k_pc_mask_eval_fin(PolyEvalArgs a, F *__restrict__ out) {
+    const u32 q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.n_q) return;
+    const F *src = a.part + (size_t) q * a.chunks * 2;
+    F e = f_zero(), o = f_zero();
+    for (u32 c = 0; c < a.chunks; ++c) { e = f_add(e, src[2 * c]); o = f_add(o, src[2 * c + 1]); }
+    const F x = root_pow(a.RT, a.half_m, (u32) (a.leaf[q] & (2 * a.half_m - 1)));
+    const F xo = f_mad_c(x, o, f_zero());
+    out[2 * (size_t) q] = f_add(e, xo);
+    out[2 * (size_t) q + 1] = f_sub(e, xo);
+}
+
 // ---- digests of every opening of a query answer ------------------------------------------------------------------------------------------
 // `buf` = leaf0[n_q] (8 bytes each) followed by the answer in vp_fri_query's layout: per query, oracle 0, oracle 1, level 0 .. ln - 1, each 130
 // values (2080 bytes) + its path (n - 1 digests for the two first oracles, n - 2 - k for level k; the last one, the prover's copy of the leaf

@@ -112,9 +112,64 @@ int pv_public_evals(vp_ctx *ctx, int n, const vp_F *point, const vp_F *pub, int 
     return rc;
 }
 
+// the mask row: one row of ms values (the public mask, zero-padded) -> its interpolant on the ms-th roots by the commitment's inverse transform of that size (as
+// pc_mask_lde runs it) -> k_pc_poly_eval over that one row on the domain of order M -> k_pc_mask_eval_fin.  The row length (lg) and the domain (lm) are independent.
+int pv_mask_evals(vp_ctx *ctx, int n, const vp_F *pub_mask, u64 n_pub_mask, u32 ms, int n_queries, const uint64_t *leaf0, vp_F *out) {
+    const int lm = n - 1, lg = ilog2(ms);
+    const u32 nq = (u32) n_queries, NP = ms / 2, chunks = (NP + PEV_PAIRS - 1) / PEV_PAIRS;
+    // one arena: values | coefficients | partial sums | results | leaves
+    const size_t n_part = (size_t) nq * chunks * 2, n_out = (size_t) nq * 2;
+    VPCHK(pv_reserve(ctx, 2 * (size_t) ms + n_part + n_out + (nq + 1) / 2));
+    F *d_in = ctx->pv_buf, *d_coef = d_in + ms, *d_part = d_coef + ms, *d_out = d_part + n_part;
+    u64 *d_leaf = reinterpret_cast<u64 *>(d_out + n_out);
+    F *rt = nullptr;
+    VPCHK(pv_root_table(ctx, lm, &rt));
+    if (ctx->profiling) ensure_event_pool(ctx);
+    ctx->ev_used = 0;
+    F *h_mask = nullptr;                                // pinned until the stream has taken it (ms <= 2^16: 1 MB, the ring's largest single request)
+    u64 *h_leaf = nullptr;
+    VPCHK(ring_alloc(ctx, (size_t) ms * sizeof(F), (void **) &h_mask));
+    VPCHK(ring_alloc(ctx, (size_t) nq * 8, (void **) &h_leaf));
+    for (u32 i = 0; i < ms; ++i) h_mask[i] = i < n_pub_mask ? f_make(pub_mask[i].real, pub_mask[i].img) : f_zero();
+    for (u32 q = 0; q < nq; ++q) h_leaf[q] = leaf0[q];
+    HIPCHK(hipMemcpyAsync(d_in, h_mask, (size_t) ms * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_leaf, h_leaf, (size_t) nq * 8, hipMemcpyHostToDevice, ctx->stream));
+    {
+        PvRootScope scope(ctx, rt, lm);
+        VPCHK(pc_launch_ntt(ctx, d_in, d_coef, lg, lm, 1, 1, 1, ms));
+    }
+    PolyEvalArgs a{};
+    a.coef = d_coef; a.RT = rt; a.half_m = 1u << (lm - 1); a.leaf = d_leaf; a.part = d_part; a.ln = (u32) lg; a.n_q = nq; a.chunks = chunks;
+    u32 groups = std::min<u32>(nq, std::max<u32>(1, 1024 / chunks));
+    a.q_per_group = (nq + groups - 1) / groups;
+    groups = (nq + a.q_per_group - 1) / a.q_per_group;
+    const dim3 g(chunks, 1, groups);
+    PC_PROF(VP_K_PC_POLY_EVAL, g.x * g.y * g.z, 1, 16ull * ms * groups, (u64) nq * 2ull * PEV_PAIRS * chunks,
+            hipLaunchKernelGGL(k_pc_poly_eval, g, dim3(VP_BLOCK), 0, ctx->stream, a));
+    PC_PROF(VP_K_PC_POLY_EVAL_FIN, nblk((u64) nq), 1, 32ull * n_part / 2 + 16ull * n_out, (u64) nq,
+            hipLaunchKernelGGL(k_pc_mask_eval_fin, dim3(nblk((u64) nq)), dim3(VP_BLOCK), 0, ctx->stream, a, d_out));
+    HIPCHK(hipMemcpyAsync(out, d_out, n_out * sizeof(F), hipMemcpyDeviceToHost, ctx->stream));
+    const int rc = check_stream(ctx);
+    if (rc == VP_OK && ctx->profiling) prof_collect(ctx);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vp_pc_mask_evals(vp_ctx *ctx, int n, const vp_F *pub_mask, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, vp_F *out) {
+    if (!ctx) return VP_EINVAL;
+    if (n < 7) { ctx->err = "vp_pc_mask_evals: the commitment needs an input layer of at least 2^7 wires"; return VP_EINVAL; }
+    if (n > PC_MAX_N) { ctx->err = "vp_pc_mask_evals: input layer above 2^25 wires"; return VP_ELIMIT; }
+    if (!out || !leaf0 || n_queries < 1 || n_queries > 4096) { ctx->err = "vp_pc_mask_evals: 1 .. 4096 queries, leaf0 and out"; return VP_EINVAL; }
+    if (!pv_leaves_ok(n, n_queries, leaf0)) { ctx->err = "vp_pc_mask_evals: a leaf outside [N / 2, M / 2)"; return VP_EINVAL; }
+    if (ms < 8 || (ms & (ms - 1)) || ms > (1ull << 16) || ms > (1ull << (n - 2))) { ctx->err = "vp_pc_mask_evals: ms is no power of two in [8, min(2^16, 2^(n-2))]"; return VP_EINVAL; }
+    if (!pub_mask || n_pub_mask < 1 || n_pub_mask > ms) { ctx->err = "vp_pc_mask_evals: a public mask of 1 .. ms elements"; return VP_EINVAL; }
+    for (u64 i = 0; i < n_pub_mask; ++i) if (pub_mask[i].real >= P61 || pub_mask[i].img >= P61) { ctx->err = "vp_pc_mask_evals: non-canonical limb in the public mask"; return VP_EINVAL; }
+    VP_ENTER(ctx);
+    return pv_mask_evals(ctx, n, pub_mask, n_pub_mask, (u32) ms, n_queries, leaf0, out);
+}
 
 int vp_pc_public_evals(vp_ctx *ctx, int n, const vp_F *point, const vp_F *pub, int n_queries, const uint64_t *leaf0, vp_F *out) {
     if (!ctx) return VP_EINVAL;

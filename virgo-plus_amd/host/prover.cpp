@@ -532,6 +532,12 @@ std::vector<uint8_t> prover::pcOpeningDigests(int n, const std::vector<u64> &lea
     logLaunches();
     return out;
 }
+std::vector<F> prover::pcMaskEvals(int n, const std::vector<F> &pub_mask, u64 ms, const std::vector<u64> &leaf0) {
+    std::vector<F> out(leaf0.size() * 2);
+    check(vp_pc_mask_evals(ctx, n, cF(pub_mask.data()), pub_mask.size(), ms, (int) leaf0.size(), reinterpret_cast<const uint64_t *>(leaf0.data()), mF(out.data())), "vp_pc_mask_evals");
+    logLaunches();
+    return out;
+}
 prover::hhash_digest prover::friStep(const F &r) {
     hhash_digest d;
     if (shard_pc) {

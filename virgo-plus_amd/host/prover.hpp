@@ -70,6 +70,9 @@ public:
     // the same two with the mask vectors lib/virgo's commit_private_array / commit_public_array take (poly_commit.h:41-42,126-128; the reference's own
     // prover passes one zero, src/prover.cpp:526, and its commit_public has this signature, src/prover.cpp:542): a non-zero private mask puts content into the
     // 65th slice of every oracle (vp_commit_private_masked / vp_commit_public_masked); an all-zero one is the call above
+    // Limits (include/vpgpu.h): the private mask pads to ms = M / gap, M = 2^(n-1), gap = the largest power of two <= M / its length; 8 <= ms <= min(2^16, M / 2);
+    // the public mask has at most ms elements; not on a sharded commitment.  The library's refusal is the exception's message.  The verifier (verifier.hpp)
+    // accepts such a commitment when ms <= 2^(n-6), a slice's message length, and rejects a longer mask at the final mask codeword, as the reference's does.
     hhash_digest commit_private(const std::vector<F> &mask);
     hhash_digest commit_public(std::vector<F> &pub, F &inner_product_sum, std::vector<F> &mask, std::vector<F> &all_sum);
     std::vector<F> friFinalMask();                       // fri::cpd.rs_codeword_msk[last] (vpd_verifier.cpp:321-325)
@@ -92,7 +95,10 @@ public:
     std::vector<F> pcPublicEvals(int n, const std::vector<F> &point, const std::vector<u64> &leaf0);
     std::vector<F> pcPublicEvalsPub(int n, const std::vector<F> &pub, const std::vector<u64> &leaf0);
     std::vector<uint8_t> pcOpeningDigests(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes);
-    // with a launch log on (vph_set_profiling), every verifier-side device call above — predicates, liuGr, layerMle, pcPublicEvals(Pub),
+    // the mask row of pcPublicEvals (vp_pc_mask_evals): out[2 q + h] = the public mask polynomial — the interpolant of pub_mask, zero-padded to ms, on the ms-th
+    // roots — at (-1)^h w^leaf0[q].  Limits: ms a power of two in [8, min(2^16, 2^(n-2))], 1 .. ms mask elements (the library refuses anything else)
+    std::vector<F> pcMaskEvals(int n, const std::vector<F> &pub_mask, u64 ms, const std::vector<u64> &leaf0);
+    // with a launch log on (vph_set_profiling), every verifier-side device call above — predicates, liuGr, layerMle, pcPublicEvals(Pub), pcMaskEvals,
     // pcOpeningDigests — appends the launch table of its call (vp_get_launch_stats), so that a whole verification can be read afterwards
     void setLaunchLog(bool on) { log_launches = on; verifier_launches_.clear(); }
     void clearLaunchLog() { verifier_launches_.clear(); }

@@ -450,6 +450,32 @@ std::vector<F> pcPublicEvalsHostTensor(int n, const std::vector<F> &point, const
     return out;
 }
 
+std::vector<F> pcMaskCoefsHost(const std::vector<F> &pub_mask, u64 ms) {                 // vpd_verifier.cpp:82-87
+    if (ms < 1 || (ms & (ms - 1)) || pub_mask.size() > ms) throw std::runtime_error("pcMaskCoefsHost: a power of two ms, at most ms mask elements");
+    std::vector<F> a(ms, F_ZERO);
+    std::copy(pub_mask.begin(), pub_mask.end(), a.begin());
+    if (ms == 1) return a;
+    int lg = 0;
+    while ((1ull << lg) < ms) ++lg;
+    host_fft(a, F::getRootOfUnity(lg).inv());
+    const F inv_n = F::fastPow(F((long long) ms), (unsigned __int128) F::mod - 2);
+    for (auto &x : a) x = x * inv_n;
+    return a;
+}
+static void pcMaskEvalsAt(const std::vector<F> &coef, int n, u64 leaf, F *out /* 2 */) {
+    const F x0 = F::fastPow(F::getRootOfUnity(n - 1), leaf), x1 = F_ZERO - x0;
+    F q0 = F_ZERO, q1 = F_ZERO;
+    for (size_t k = coef.size(); k-- > 0;) { q0 = q0 * x0 + coef[k]; q1 = q1 * x1 + coef[k]; }
+    out[0] = q0; out[1] = q1;
+}
+std::vector<F> pcMaskEvalsHost(int n, const std::vector<F> &pub_mask, u64 ms, const std::vector<u64> &leaf0) {
+    if (n < 7) throw std::runtime_error("pcMaskEvalsHost: n >= 7");
+    const std::vector<F> coef = pcMaskCoefsHost(pub_mask, ms);
+    std::vector<F> out(leaf0.size() * 2);
+    for (size_t q = 0; q < leaf0.size(); ++q) pcMaskEvalsAt(coef, n, leaf0[q], &out[2 * q]);
+    return out;
+}
+
 u64 pcQueryAnswerBytes(int n, u64 n_queries) {
     u64 per = 2 * (2080 + 32ull * (n - 1));
     for (int k = 0; k < n - 6; ++k) per += 2080 + 32ull * (n - 2 - k);
@@ -489,6 +515,81 @@ std::vector<uint8_t> pcOpeningDigestsHost(int n, const std::vector<u64> &leaf0, 
     }
     return out;
 }
+
+// ---- the algebra of the commitment's verifier over all 65 slices (vpd_verifier.cpp:99-325), shared by verifyPoly and pcVerifyCommitment -------------------
+// Slots 0 .. 63 are the witness slices on the N-th roots; slot 64 is the mask slice on the ms-th roots, with the public mask polynomial in q's place, x^ms in
+// x^N's and ms in N's (:177-238).  The reference's own protocol is ms = 1 with one zero: q_msk = 0, and every value of slot 64 must then be zero.  Every
+// function returns the name of the failed check, or an empty string.
+namespace {
+struct PcSliceCheck {
+    int n, ln;
+    u64 N, M, ms;
+    const std::vector<F> &all_sum, &fr;
+    F w, inv2, Nf, msf;
+    std::vector<F> final_val, cur0, cur1;
+    u64 D = 0, t = 0;
+    PcSliceCheck(int n_, u64 ms_, const std::vector<F> &sums, const std::vector<F> &challenges)
+        : n(n_), ln(n_ - 6), N(1ull << (n_ - 6)), M(1ull << (n_ - 1)), ms(ms_), all_sum(sums), fr(challenges), w(F::getRootOfUnity(n_ - 1)), inv2(F(2ll).inv()),
+          Nf((long long) N), msf((long long) ms_), final_val(65), cur0(65), cur1(65) {}
+    // The 64 witness slices' sums must add up to the claimed inner product.  Slot 64 is no part of it: input_0 is <witness, pub> alone (src/prover.cpp:544), and
+    // all_sum[64] = <private mask, public mask> comes on top (poly_commit.h:262).  The sum over all 65 slots that stood here before let claim and all_sum[64]
+    // move together; all_sum[64] now meets only the mask slice's own checks below, as in the reference (vpd_verifier.cpp:228-238), and cannot reach the claim.
+    std::string sums(const F &claim) const {
+        F s = F_ZERO;
+        for (int j = 0; j < 64; ++j) s = s + all_sum[j];
+        return s == claim ? "" : "commitment: slice sums do not match the inner product";
+    }
+    // the last codeword must be constant on its 32-point domain, per slice (vpd_verifier.cpp:309-325)
+    std::string finalCodes(const std::vector<F> &final_code, const std::vector<F> &final_mask) {
+        for (int s = 0; s < 64; ++s) {
+            final_val[s] = final_code[(0 << 7) | (s << 1) | 0];
+            for (int i = 0; i < 16; ++i)
+                for (int hi = 0; hi < 2; ++hi)
+                    if (final_code[(i << 7) | (s << 1) | hi] != final_val[s]) return "Fri rs code check fail";
+        }
+        final_val[64] = final_mask[0];
+        for (int j = 1; j < 32; ++j) if (final_mask[j] != final_val[64]) return "Fri msk rs code check fail";
+        return "";
+    }
+    // virtual oracle values at x0 = w^s0 and x1 = -x0 for every slice (poly_commit.h:301-318 on the prover side); q0v / q1v: the 64 public polynomials
+    // there, qm: the public mask polynomial at the two points
+    void first(u64 s0, const std::vector<F> &vl, const std::vector<F> &vh, const F *q0v, const F *q1v, const F *qm) {
+        const F x0 = F::fastPow(w, s0), x1 = F_ZERO - x0;
+        const F x0n = F::fastPow(x0, N), x1n = F::fastPow(x1, N), x0m = F::fastPow(x0, ms), x1m = F::fastPow(x1, ms);
+        const F inv_x0 = x0.inv(), inv_x1 = F_ZERO - inv_x0;
+        for (int j = 0; j < 64; ++j) {
+            cur0[j] = ((vl[2 * j] * q0v[j] - (x0n - F_ONE) * vh[2 * j]) * Nf - all_sum[j]) * inv_x0;
+            cur1[j] = ((vl[2 * j + 1] * q1v[j] - (x1n - F_ONE) * vh[2 * j + 1]) * Nf - all_sum[j]) * inv_x1;
+        }
+        cur0[64] = ((vl[128] * qm[0] - (x0m - F_ONE) * vh[128]) * msf - all_sum[64]) * inv_x0;
+        cur1[64] = ((vl[129] * qm[1] - (x1m - F_ONE) * vh[129]) * msf - all_sum[64]) * inv_x1;
+        D = M; t = s0;                               // D: domain size of the codeword cur0 / cur1 come from; cur0 is its value at index t, cur1 at t + D / 2
+    }
+    u64 levelLeaf() const { return t % (D / 4); }    // the folded value sits at index t of the next domain (D / 2 points), whose leaves pair i with i + D / 4
+    // fold consistency of level k against its opening (vpd_verifier.cpp:167-306)
+    std::string level(int k, const std::vector<F> &vb) {
+        const F inv_mu = F::fastPow(F::fastPow(w, 1ull << k), t).inv();      // (w_D^t)^-1, w_D = w^(2^k)
+        const u64 Dn = D / 2, leaf = t % (Dn / 2);
+        const bool upper = t >= Dn / 2;
+        for (int j = 0; j < 65; ++j) {
+            const F expect = inv2 * ((cur0[j] + cur1[j]) + inv_mu * fr[k] * (cur0[j] - cur1[j]));
+            if (expect != vb[2 * j + (upper ? 1 : 0)]) {
+                char b[64];
+                snprintf(b, sizeof b, j < 64 ? "Fri check consistency %d round fail" : "Fri msk check consistency %d round fail", k);
+                return b;
+            }
+            cur0[j] = vb[2 * j]; cur1[j] = vb[2 * j + 1];
+        }
+        D = Dn; t = leaf;
+        return "";
+    }
+    std::string last() const {                       // the last level's pairs are the final codewords' constants
+        for (int j = 0; j < 65; ++j)
+            if (cur0[j] != final_val[j] || cur1[j] != final_val[j]) return j < 64 ? "Fri final codeword mismatch" : "Fri msk final codeword mismatch";
+        return "";
+    }
+};
+}  // namespace
 
 // device_digests: the opening's 64 bytes (leaf digest | root) computed elsewhere (poly_dev); the comparisons are the same
 bool verifier::checkOpening(const vph::hhash_digest &root, u64 leaf, const std::vector<F> &vals,
@@ -530,6 +631,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     std::vector<F> all_sum;
     prover::hhash_digest root_h_raw;
     if (rec) { rec->bytes(root_h_raw.b, 32); input_0 = rec->elem(); all_sum.resize(65); for (auto &x : all_sum) x = rec->elem(); }
+    else if (mask_ms > 1) root_h_raw = p->commit_public_eq(std::vector<F>(r_liu.begin(), r_liu.begin() + n), pub_mask_, input_0, all_sum);
     else root_h_raw = p->commit_public(pub, input_0, all_sum);
     poly_prove_timer.stop();
     full_tr.insert(full_tr.end(), root_h_raw.b, root_h_raw.b + 32);
@@ -538,11 +640,10 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     const vph::hhash_digest root_h = dig(root_h_raw);
     poly_timer.start();
     if (claim != input_0) { fprintf(stderr, "Verification fail, final input check fail.\n"); return false; }   // verifier.cpp:383
-    {   // the slice sums must add up to the claimed inner product
-        F s = F_ZERO;
-        for (int j = 0; j < 65; ++j) s = s + all_sum[j];
-        if (s != input_0) { fprintf(stderr, "commitment: slice sums do not match the inner product\n"); return false; }
-    }
+    std::vector<F> fr(ln);
+    PcSliceCheck chk(n, mask_ms, all_sum, fr);
+    auto failed = [&](const std::string &why) { if (why.empty()) return false; fprintf(stderr, "%s\n", why.c_str()); return true; };
+    if (failed(chk.sums(input_0))) return false;
     poly_timer.stop();
     // verify_poly_commitment runs fft_circuit_gkr::fft_gkr(ln) here (vpd_verifier.cpp:92): a self-contained GKR over the inverse-FFT +
     // polynomial-evaluation circuit whose verifier draws come from the same glibc stream.  Its prover runs on the device (vp_fft_gkr) on
@@ -567,14 +668,19 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
         if (!okf) { fprintf(stderr, "Error, fft gkr failed\n"); return false; }     // (the reference prints this and carries on, fft_circuit_GKR.cpp:843-844)
     }
     // FRI commit phase (vpd_verifier.cpp:44-74): the fold challenges are drawn here
-    std::vector<F> fr(ln);
     std::vector<vph::hhash_digest> roots(ln);
     poly_prove_timer.start();
-    std::vector<F> final_code;
+    std::vector<F> final_code, final_mask(32, F_ZERO);          // the zero mask's last codeword is zero: nothing is asked of the prover
     if (rec) {                  // the same draws; roots and final codeword from the record
         for (int k = 0; k < ln; ++k) fr[k] = F::random();
         for (int k = 0; k < ln; ++k) rec->bytes(roots[k].w, 32);
         final_code.resize(2048); for (auto &x : final_code) x = rec->elem();
+        if (mask_ms > 1) {      // version 2: the mask section (its two lengths were read and checked by checkFull, which looked ahead for them)
+            uint32_t lens[2]; rec->bytes(lens, sizeof lens);
+            if (lens[0] != mask_ms || lens[1] < 1 || lens[1] > mask_ms) throw std::runtime_error("record: mask section");
+            pub_mask_.resize(lens[1]); for (auto &x : pub_mask_) x = rec->elem();
+            for (auto &x : final_mask) x = rec->elem();
+        }
     } else {
     if (fri_batched) {          // same draws in the same order; the device runs the whole commit phase in one pass
         for (int k = 0; k < ln; ++k) fr[k] = F::random();
@@ -583,21 +689,17 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     } else
         for (int k = 0; k < ln; ++k) { fr[k] = F::random(); roots[k] = dig(p->friStep(fr[k])); }
     final_code = p->friFinal();
+    if (mask_ms > 1) final_mask = p->friFinalMask();
     }
     fri_roots_.clear();
     for (int k = 0; k < ln; ++k) { const uint8_t *b = reinterpret_cast<const uint8_t *>(roots[k].w); fri_roots_.insert(fri_roots_.end(), b, b + 32); }
-    fri_final_ = final_code; fri_r_ = fr;
+    fri_final_ = final_code; fri_r_ = fr; fri_final_mask_ = final_mask;
     poly_prove_timer.stop();
     poly_timer.start();
-    // the last codeword must be constant on its 32-point domain, per slice (vpd_verifier.cpp:309-324)
-    std::vector<F> final_val(64);
-    for (int s = 0; s < 64; ++s) {
-        final_val[s] = final_code[(0 << 7) | (s << 1) | 0];
-        for (int i = 0; i < 16; ++i)
-            for (int hi = 0; hi < 2; ++hi)
-                if (final_code[(i << 7) | (s << 1) | hi] != final_val[s]) { fprintf(stderr, "Fri rs code check fail\n"); return false; }
-    }
-    const F w = F::getRootOfUnity(lm), inv2 = F(2ll).inv(), Nf((long long) N);
+    if (failed(chk.finalCodes(final_code, final_mask))) return false;
+    // the public mask polynomial (vpd_verifier.cpp:82-87); the zero mask's is zero
+    std::vector<F> mask_coef;
+    if (mask_ms > 1 && !dev) { pub_eval_timer.start(); mask_coef = pcMaskCoefsHost(pub_mask_, mask_ms); pub_eval_timer.stop(); }
     std::vector<F> vl, vh, vb;
     std::vector<prover::hhash_digest> pl, ph, pb;
     // query point x0 = w^(pow/2), pow even in [N, M) (vpd_verifier.cpp:119-123); pow / 2 is the leaf of the two first oracles (x1 = -x0 sits in the same leaf)
@@ -617,7 +719,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     }
     // poly_dev: the q values of every position and the digests of every opening in two device calls over the whole answer block (the record's
     // remaining bytes, or friQuery's answer); a block that is not the layout's size is rejected here, as the reader below would reject it
-    std::vector<F> dev_q;
+    std::vector<F> dev_q, dev_qm;
     std::vector<uint8_t> dev_dig;
     size_t dev_opening = 0;
     if (dev) {
@@ -626,6 +728,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
         if (nb != pcQueryAnswerBytes(n, (u64) reps)) { fprintf(stderr, "commitment: the query answer is not the size of %d repetitions\n", reps); poly_timer.stop(); return false; }
         pub_eval_timer.start();
         dev_q = dev->pcPublicEvals(n, std::vector<F>(r_liu.begin(), r_liu.begin() + n), leaf0);
+        if (mask_ms > 1) dev_qm = dev->pcMaskEvals(n, pub_mask_, mask_ms, leaf0);
         pub_eval_timer.stop();
         digest_timer.start();
         dev_dig = dev->pcOpeningDigests(n, leaf0, blk, nb);
@@ -653,41 +756,97 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
         open(0, s0, vl, pl);
         open(1, s0, vh, ph);
         if (!opening_ok(root_l, s0, vl, pl) || !opening_ok(root_h, s0, vh, ph)) { fprintf(stderr, "commitment: Merkle opening rejected\n"); return false; }
-        const F x0 = F::fastPow(w, s0), x1 = F_ZERO - x0;
-        const F x0n = F::fastPow(x0, N), x1n = F::fastPow(x1, N);
-        const F inv_x0 = x0.inv(), inv_x1 = F_ZERO - inv_x0;
-        // virtual oracle values at x0 and x1 for every slice (poly_commit.h:301-318 on the prover side)
-        std::vector<F> cur0(64), cur1(64), q0v(64), q1v(64);
-        if (dev) { std::copy_n(&dev_q[(size_t) rep * 128], 64, q0v.begin()); std::copy_n(&dev_q[(size_t) rep * 128 + 64], 64, q1v.begin()); }
-        else { pub_eval_timer.start(); pcPublicEvalsAt(q_coef, n, s0, q0v.data(), q1v.data()); pub_eval_timer.stop(); }
-        for (int j = 0; j < 64; ++j) {
-            const F &q0 = q0v[j], &q1 = q1v[j];
-            cur0[j] = ((vl[2 * j] * q0 - (x0n - F_ONE) * vh[2 * j]) * Nf - all_sum[j]) * inv_x0;
-            cur1[j] = ((vl[2 * j + 1] * q1 - (x1n - F_ONE) * vh[2 * j + 1]) * Nf - all_sum[j]) * inv_x1;
+        // the public polynomials at x0 = w^s0 and x1 = -x0: the 64 slices', and the mask's
+        std::vector<F> q0v(64), q1v(64);
+        F qm[2] = {F_ZERO, F_ZERO};
+        if (dev) {
+            std::copy_n(&dev_q[(size_t) rep * 128], 64, q0v.begin()); std::copy_n(&dev_q[(size_t) rep * 128 + 64], 64, q1v.begin());
+            if (mask_ms > 1) { qm[0] = dev_qm[2 * (size_t) rep]; qm[1] = dev_qm[2 * (size_t) rep + 1]; }
+        } else {
+            pub_eval_timer.start();
+            pcPublicEvalsAt(q_coef, n, s0, q0v.data(), q1v.data());
+            if (mask_ms > 1) pcMaskEvalsAt(mask_coef, n, s0, qm);
+            pub_eval_timer.stop();
         }
-        // fold consistency level by level (vpd_verifier.cpp:167-306)
-        u64 D = M;                                               // domain size of the codeword cur0/cur1 come from
-        u64 t = s0;                                              // cur0 is its value at index t, cur1 at t + D/2
+        chk.first(s0, vl, vh, q0v.data(), q1v.data(), qm);
         for (int k = 0; k < ln; ++k) {
-            const F inv_mu = F::fastPow(F::fastPow(w, 1ull << k), t).inv();      // (w_D^t)^-1, w_D = w^(2^k)
-            const u64 Dn = D / 2;                                // next domain size; the folded value sits at index t
-            const u64 leaf = t % (Dn / 2);
+            const u64 leaf = chk.levelLeaf();
             open(2 + k, leaf, vb, pb);
             if (!opening_ok(roots[k], leaf, vb, pb)) { fprintf(stderr, "commitment: FRI Merkle opening rejected (level %d)\n", k); return false; }
-            const bool upper = t >= Dn / 2;
-            for (int j = 0; j < 64; ++j) {
-                const F expect = inv2 * ((cur0[j] + cur1[j]) + inv_mu * fr[k] * (cur0[j] - cur1[j]));
-                if (expect != vb[2 * j + (upper ? 1 : 0)]) { fprintf(stderr, "Fri check consistency %d round fail\n", k); return false; }
-                cur0[j] = vb[2 * j]; cur1[j] = vb[2 * j + 1];
-            }
-            D = Dn; t = leaf;
+            if (failed(chk.level(k, vb))) return false;
         }
-        for (int j = 0; j < 64; ++j)
-            if (cur0[j] != final_val[j] || cur1[j] != final_val[j]) { fprintf(stderr, "Fri final codeword mismatch\n"); return false; }
+        if (failed(chk.last())) return false;
     }
     poly_timer.stop();
     if (src == &answer && answer.at != answer.n) { fprintf(stderr, "commitment: the query answer has bytes left over\n"); return false; }
     return true;
+}
+
+// The commitment's verifier on arrays: verifyPoly's checks behind fft_gkr, in its order, with every challenge, position and prover message an argument.
+int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev) {
+    const int n = c.n;
+    auto bad = [&](const char *m) { why = m; return -1; };
+    if (n < 7 || n > 30) return bad("n outside 7 .. 30");
+    const int ln = n - 6;
+    const u64 reps = c.leaf0.size();
+    if (c.point.empty() == c.pub.empty()) return bad("exactly one of point and pub");
+    if (!c.point.empty() ? c.point.size() != (size_t) n : c.pub.size() != (1ull << n)) return bad("a point of n coordinates or a public vector of 2^n entries");
+    // the padded lengths a commitment can have: the zero mask's 1, or what vp_commit_private_masked takes
+    if (c.ms != 1 && (c.ms < 8 || (c.ms & (c.ms - 1)) || c.ms > (1ull << 16) || c.ms > (1ull << (n - 2)))) return bad("ms is neither 1 nor a power of two in [8, min(2^16, 2^(n-2))]");
+    if (c.pub_mask.size() > c.ms) return bad("public mask longer than ms");
+    if (c.all_sum.size() != 65 || c.fr.size() != (size_t) ln || c.fri_roots.size() != (size_t) 32 * ln || c.final_code.size() != 2048 || c.final_mask.size() != 32)
+        return bad("all_sum[65], n - 6 challenges and roots, final_code[2048], final_mask[32]");
+    if (reps < 1 || reps > 4096) return bad("1 .. 4096 repetitions");
+    for (u64 l : c.leaf0) if (l < (1ull << (n - 7)) || l >= (1ull << (n - 2))) return bad("a leaf outside [N / 2, M / 2)");
+    if (!c.answer || c.n_bytes != pcQueryAnswerBytes(n, reps)) return bad("the answer block is not the size of vp_fri_query's answer");
+    auto rejected = [&](const std::string &m) { if (m.empty()) return false; why = m; return true; };
+    PcSliceCheck chk(n, c.ms, c.all_sum, c.fr);
+    if (rejected(chk.sums(c.claim))) return 1;
+    if (rejected(chk.finalCodes(c.final_code, c.final_mask))) return 1;
+    // the two heavy loops, and the mask row, over all positions: on the device or on the host
+    std::vector<F> q, qm(2 * reps, F_ZERO);
+    std::vector<uint8_t> dg;
+    if (dev) {
+        auto call = [&](int rc, const char *what) { if (rc != VP_OK) throw std::runtime_error(std::string(what) + ": " + vp_last_error(dev)); };
+        q.resize(128 * reps); dg.resize(reps * (size_t) (n - 4) * 64);
+        const uint64_t *lf = reinterpret_cast<const uint64_t *>(c.leaf0.data());
+        call(vp_pc_public_evals(dev, n, c.point.empty() ? nullptr : reinterpret_cast<const vp_F *>(c.point.data()), c.pub.empty() ? nullptr : reinterpret_cast<const vp_F *>(c.pub.data()),
+                                (int) reps, lf, reinterpret_cast<vp_F *>(q.data())), "vp_pc_public_evals");
+        const std::vector<F> one_zero(1, F_ZERO), &pm = c.pub_mask.empty() ? one_zero : c.pub_mask;
+        if (c.ms > 1) call(vp_pc_mask_evals(dev, n, reinterpret_cast<const vp_F *>(pm.data()), pm.size(), c.ms, (int) reps, lf, reinterpret_cast<vp_F *>(qm.data())), "vp_pc_mask_evals");
+        call(vp_fri_query_digests(dev, n, (int) reps, lf, c.answer, c.n_bytes, dg.data()), "vp_fri_query_digests");
+    } else {
+        q = c.point.empty() ? pcPublicEvalsHostPub(n, c.pub, c.leaf0) : pcPublicEvalsHostTensor(n, c.point, c.leaf0);
+        if (c.ms > 1) qm = pcMaskEvalsHost(n, c.pub_mask, c.ms, c.leaf0);
+        dg = pcOpeningDigestsHost(n, c.leaf0, c.answer, c.n_bytes);
+    }
+    std::vector<F> vl(130), vh(130), vb(130);
+    size_t at = 0, opening = 0;                      // (the block has the layout's size: every read below stays inside it)
+    // one opening of the block: its values (canonical), then the comparisons of checkOpening on its 64 digest bytes
+    auto open = [&](std::vector<F> &vals, size_t plen, const uint8_t *root) {
+        for (auto &x : vals) {
+            unsigned long long w[2]; memcpy(w, c.answer + at, 16); at += 16;
+            if (w[0] >= F::mod || w[1] >= F::mod) throw std::runtime_error("non-canonical field element among the opened values");
+            x.real = w[0]; x.img = w[1];
+        }
+        const uint8_t *path = c.answer + at;
+        at += 32 * plen;
+        const uint8_t *d = &dg[64 * opening++];
+        return memcmp(d, path + 32 * (plen - 1), 32) == 0 && memcmp(d + 32, root, 32) == 0;
+    };
+    try {
+        for (u64 rep = 0; rep < reps; ++rep) {
+            const bool okl = open(vl, (size_t) n - 1, c.root_l), okh = open(vh, (size_t) n - 1, c.root_h);
+            if (!okl || !okh) { why = "commitment: Merkle opening rejected"; return 1; }
+            chk.first(c.leaf0[rep], vl, vh, &q[128 * rep], &q[128 * rep + 64], &qm[2 * rep]);
+            for (int k = 0; k < ln; ++k) {
+                if (!open(vb, (size_t) (n - 2 - k), &c.fri_roots[32 * (size_t) k])) { why = "commitment: FRI Merkle opening rejected (level " + std::to_string(k) + ")"; return 1; }
+                if (rejected(chk.level(k, vb))) return 1;
+            }
+            if (rejected(chk.last())) return 1;
+        }
+    } catch (const std::runtime_error &e) { why = e.what(); return 1; }      // a non-canonical element among the opened values
+    return 0;
 }
 
 // F::random() draws of fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp): r[lg] (:840), eval_points[64] (:84),
@@ -695,12 +854,21 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
 // layer's of lg (:394-395), and per iFFT depth (lg of them) r_u / r_v of lg plus alpha and beta (:563-564, :763-764).
 int verifier::fftGkrDraws(int lg) { return lg + 64 + 2 * (lg + 10) + 2 * (lg + 6) + 2 * lg + lg * (2 * lg + 2); }
 
-bool verifier::verifyFull(int reps) {
+bool verifier::verifyFull(int reps) { return verifyFull(reps, {}, {}); }
+bool verifier::verifyFull(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask) {
     if (!p) throw std::runtime_error("verifyFull(): no prover attached");
     full_tr.clear();
     poly_prove_timer.start();
-    const prover::hhash_digest root_l = p->commit_private();               // verifier.cpp:137
+    const prover::hhash_digest root_l = p->commit_private(pri_mask);       // verifier.cpp:137 (an empty or all-zero mask: commit_private())
     poly_prove_timer.stop();
+    mask_ms = 1; pub_mask_.clear();
+    if (p->isMasked()) {                                                   // the padded length is public: M / the largest power of two <= M / length (poly_commit.h:55-63)
+        const u64 M = 1ull << (C.circuit[0].bitLength - 1);
+        u64 gap = 1;
+        while (gap * 2 <= M / pri_mask.size()) gap *= 2;
+        mask_ms = M / gap;
+        pub_mask_ = pub_mask.empty() ? std::vector<F>(1, F_ZERO) : pub_mask;
+    }
     full_tr.insert(full_tr.end(), root_l.b, root_l.b + 32);
     replay = false; tape_.clear(); tr.clear();
     input_check_by_commitment = true;
@@ -711,13 +879,21 @@ bool verifier::verifyFull(int reps) {
     if (!ok) return false;
     if (!verifyPoly(root_l, last_claim, reps)) return false;
     // the record (vphost.h): header, transcript in the golden layout, fft_gkr messages, FRI roots, final codeword, openings
-    const uint32_t head[4] = {RECORD_MAGIC, RECORD_VERSION, (uint32_t) C.circuit[0].bitLength, (uint32_t) reps};
+    // (version 2, a masked run: the mask section in front of the openings)
+    const bool masked = mask_ms > 1;
+    const uint32_t head[4] = {RECORD_MAGIC, masked ? RECORD_VERSION_MASKED : RECORD_VERSION, (uint32_t) C.circuit[0].bitLength, (uint32_t) reps};
     auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); record_.insert(record_.end(), q, q + k); };
     put(head, sizeof head);
     put(full_tr.data(), full_tr.size());
     put(fft_gkr_msgs_.data(), fft_gkr_msgs_.size() * sizeof(F));
     put(fri_roots_.data(), fri_roots_.size());
     put(fri_final_.data(), fri_final_.size() * sizeof(F));
+    if (masked) {
+        const uint32_t lens[2] = {(uint32_t) mask_ms, (uint32_t) pub_mask_.size()};
+        put(lens, sizeof lens);
+        put(pub_mask_.data(), pub_mask_.size() * sizeof(F));
+        put(fri_final_mask_.data(), fri_final_mask_.size() * sizeof(F));
+    }
     put(openings_.data(), openings_.size());
     return true;
 }
@@ -731,7 +907,8 @@ bool verifier::checkFull(const std::vector<uint8_t> &record) {
     try {
         uint32_t head[4];
         r.bytes(head, sizeof head);
-        if (head[0] != RECORD_MAGIC || head[1] != RECORD_VERSION || head[2] != (uint32_t) n || head[3] < 1 || head[3] > 4096) return false;
+        if (head[0] != RECORD_MAGIC || (head[1] != RECORD_VERSION && head[1] != RECORD_VERSION_MASKED) || head[2] != (uint32_t) n || head[3] < 1 || head[3] > 4096) return false;
+        mask_ms = 1; pub_mask_.clear();
         prover::hhash_digest root_l;
         r.bytes(root_l.b, 32);
         // GKR slice: the replay of check(), on the tape redrawn here; it ends where run() stops reading
@@ -745,6 +922,20 @@ bool verifier::checkFull(const std::vector<uint8_t> &record) {
             r.at += tr_pos;
             full_tr.assign(root_l.b, root_l.b + 32);
             full_tr.insert(full_tr.end(), tr.begin(), tr.end());
+            if (head[1] == RECORD_VERSION_MASKED) {
+                // the mask's padded length decides slot 64's algebra from the first check on: read it ahead, at its place behind the final codeword (the
+                // sections in between have fixed sizes), under a masked run's own limits — a power of two in [8, min(2^16, 2^(n-2))]
+                RecReader ahead = r;
+                ahead.at += 32 + 16 + 65 * 16;
+                for (size_t skip : {vph::FftGkrLayout(n - 6).n_msgs * sizeof(F), (size_t) 32 * (n - 6), (size_t) 2048 * sizeof(F)}) {
+                    if (skip > ahead.n - std::min(ahead.at, ahead.n)) throw std::runtime_error("record too short");
+                    ahead.at += skip;
+                }
+                uint32_t lens[2]; ahead.bytes(lens, sizeof lens);
+                const u64 ms = lens[0];
+                if (ms < 8 || (ms & (ms - 1)) || ms > (1ull << 16) || ms > (1ull << (n - 2))) throw std::runtime_error("record: mask length");
+                mask_ms = ms;
+            }
             rec = &r;
             ok = verifyPoly(root_l, last_claim, (int) head[3]) && r.at == r.n;
         }

@@ -8,6 +8,7 @@
 // Both record the prover's messages in the golden transcript layout (GKR slice).
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "circuit.hpp"
@@ -24,6 +25,11 @@ public:
     // verifyPoly = commit_public + FRI commit phase + `reps` query repetitions (vpd_verifier.cpp:76-328; the
     // reference hard-codes 33).  fullTranscript() is then merkle_root_l | GKR | merkle_root_h | input_0 | all_sum[65].
     bool verifyFull(int reps = 33);
+    // The same with the mask vectors of a hiding commitment: prover::commit_private(pri_mask), and prover::commit_public_eq(r_liu, pub_mask, ..) behind it.  The 65th
+    // slice is then verified like the other 64 (verifyPoly; ms = the private mask's padded length, poly_commit.h:55-63) and an accepted run writes a version-2
+    // record.  A null or all-zero private mask is verifyFull(reps): the reference's one-element zero mask, ms = 1.  Limits: prover.hpp, at commit_private(mask);
+    // a mask the device refuses throws with the library's message.
+    bool verifyFull(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask);
     prover *pred_dev = nullptr;     // when set, the O(|C|) predicate loops run on the device (prover::predicates) instead of the host
     // when set, the commitment verifier's two heavy loops run on the device: the public polynomials' values at the query points
     // (prover::pcPublicEvals) and the digests of every opening (prover::pcOpeningDigests).  All positions are drawn first (the same draws), the
@@ -39,12 +45,14 @@ public:
     // with a non-canonical element or with any byte changed is rejected.
     const std::vector<uint8_t> &fullRecord() const { return record_; }
     bool checkFull(const std::vector<uint8_t> &record);
-    static constexpr uint32_t RECORD_MAGIC = 0x52465056u /* "VPFR" */, RECORD_VERSION = 1;
+    // version 1: the zero mask; version 2: one more section in front of the openings — u32 ms | u32 public mask length | the public mask | the final mask codeword [32]
+    static constexpr uint32_t RECORD_MAGIC = 0x52465056u /* "VPFR" */, RECORD_VERSION = 1, RECORD_VERSION_MASKED = 2;
     const std::vector<uint8_t> &fullTranscript() const { return full_tr; }
     // FRI commit phase of the last verifyFull(): Merkle root per fold step (32 bytes each), final codeword (2048), fold challenges
     const std::vector<uint8_t> &friRoots() const { return fri_roots_; }
     const std::vector<F> &friFinalCode() const { return fri_final_; }
     const std::vector<F> &friChallenges() const { return fri_r_; }
+    const std::vector<F> &friFinalMask() const { return fri_final_mask_; }      // the mask slice's last codeword (32; zeros for the zero mask)
     static int fftGkrDraws(int lg);
     double polyVerifyTime() const { return poly_timer.elapse_sec(); }
     // "Polynomial commitment: prove time" by the REFERENCE's definition (src/verifier.cpp:183): poly_prover.total_time = commit_private +
@@ -118,7 +126,9 @@ private:
     timer verify_timer, poly_timer, poly_prove_timer, fft_gkr_timer, open_timer, pub_eval_timer, digest_timer;
     std::vector<F> fft_gkr_msgs_;
     std::vector<uint8_t> full_tr;
-    std::vector<uint8_t> fri_roots_; std::vector<F> fri_final_, fri_r_;
+    std::vector<uint8_t> fri_roots_; std::vector<F> fri_final_, fri_r_, fri_final_mask_;
+    u64 mask_ms = 1;                                   // padded length of the run's mask; 1 = the zero mask (nothing of the prover is asked for slot 64)
+    std::vector<F> pub_mask_;                          // the run's public mask (at most mask_ms elements)
     struct RecReader;                                  // bounds- and canonicity-checked cursor over a record (verifier.cpp)
     RecReader *rec = nullptr;                          // checkFull(): where verifyPoly reads the prover's side from
     std::vector<uint8_t> openings_, record_;           // the query phase's answers in vp_fri_query's layout; the whole record
@@ -148,6 +158,30 @@ void pcOpeningDigest(u64 leaf, const uint8_t *values /* 2080 bytes */, const uin
 // All openings of an answer block in vp_fri_query's layout: 64 bytes each (leaf digest | root), in the layout's order.  Bytes are hashed as given.
 // Throws std::runtime_error when n_bytes is not the layout's size.
 std::vector<uint8_t> pcOpeningDigestsHost(int n, const std::vector<u64> &leaf0, const uint8_t *answer, u64 n_bytes);
+
+// ---- the mask slice (slot 64) --------------------------------------------------------------------------------------------------------------------
+// The public mask polynomial: the interpolant of the public mask, zero-padded to ms (a power of two), on the ms-th roots of unity (vpd_verifier.cpp:82-87), in
+// coefficient form; and its values at the query points, out[2 q + h] = q_msk((-1)^h w^leaf0[q]) (vp_pc_mask_evals' layout).  ms = 1 with one zero: q_msk = 0.
+std::vector<F> pcMaskCoefsHost(const std::vector<F> &pub_mask, u64 ms);
+std::vector<F> pcMaskEvalsHost(int n, const std::vector<F> &pub_mask, u64 ms, const std::vector<u64> &leaf0);
+
+// ---- the commitment's verifier by value: everything verifyPoly checks after fft_gkr, on arrays -------------------------------------------------------
+struct PcCommitment {
+    int n = 0;                                   // bit length of the committed vector (>= 7)
+    std::vector<F> point, pub;                   // exactly one: n coordinates (the public vector is eq(point, .)) or 2^n entries
+    std::vector<F> pub_mask; u64 ms = 1;         // at most ms elements; ms = 1 (the zero mask) or a power of two in [8, min(2^16, 2^(n-2))]
+    F claim;
+    uint8_t root_l[32], root_h[32];
+    std::vector<F> all_sum;                      // 65
+    std::vector<F> fr;                           // n - 6 fold challenges
+    std::vector<uint8_t> fri_roots;              // 32 (n - 6)
+    std::vector<F> final_code, final_mask;       // 2048, 32
+    std::vector<u64> leaf0;                      // one per repetition, in [2^(n-7), 2^(n-2))
+    const uint8_t *answer = nullptr; u64 n_bytes = 0;      // vp_fri_query's layout for (n, leaf0.size())
+};
+// 0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).  dev: a device context for the heavy loops (vp_pc_public_evals, vp_pc_mask_evals,
+// vp_fri_query_digests), or null for the host's; a device call that fails throws std::runtime_error.
+int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev = nullptr);
 
 // verifier::checkFull (after F::init()) with pred_dev and poly_dev on a context made for the call on `device`; throws std::runtime_error without a usable device
 bool checkFullOnDevice(const layeredCircuit &c, int device, const std::vector<uint8_t> &record);

@@ -398,19 +398,28 @@ int vph_fri_query(vph_session *s, int n_queries, const uint64_t *leaf0, uint8_t 
     }
 }
 
+static std::vector<F> pc_elems(const uint64_t *pairs, uint64_t n_elems);
 int vph_prove_and_verify_full(vph_session *s, int reps, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                               double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen) {
     return vph_prove_and_verify_full_ex(s, reps, 0, transcript, capacity, n_written, gkr_prove_sec, pc_prove_sec, verify_sec, err, errlen);
 }
 int vph_prove_and_verify_full_ex(vph_session *s, int reps, int flags, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                                  double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen) {
+    return vph_prove_and_verify_full_masked(s, reps, flags, nullptr, 0, nullptr, 0, transcript, capacity, n_written, gkr_prove_sec, pc_prove_sec, verify_sec, err, errlen);
+}
+int vph_prove_and_verify_full_masked(vph_session *s, int reps, int flags, const uint64_t *pri_mask_pairs, uint64_t n_pri, const uint64_t *pub_mask_pairs, uint64_t n_pub,
+                                     uint8_t *transcript, uint64_t capacity, uint64_t *n_written, double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec,
+                                     char *err, int errlen) {
     try {
+        for (uint64_t i = 0; pri_mask_pairs && i < 2 * n_pri; ++i) if (pri_mask_pairs[i] >= F::mod) throw std::runtime_error("vph_prove_and_verify_full_masked: non-canonical mask element");
+        for (uint64_t i = 0; pub_mask_pairs && i < 2 * n_pub; ++i) if (pub_mask_pairs[i] >= F::mod) throw std::runtime_error("vph_prove_and_verify_full_masked: non-canonical mask element");
+        const std::vector<F> pri_mask = pc_elems(pri_mask_pairs, pri_mask_pairs ? n_pri : 0), pub_mask = pc_elems(pub_mask_pairs, pub_mask_pairs ? n_pub : 0);
         F::init();
         verifier v(s->p.get(), s->circ->c);
         v.batched_openings = (flags & VPH_VERIFY_BATCHED_OPENINGS) != 0;
         if (flags & VPH_VERIFY_DEVICE_LOOPS) { v.pred_dev = s->p.get(); v.poly_dev = s->p.get(); }
         const double t0 = s->p->proveTime();
-        const bool ok = v.verifyFull(reps);
+        const bool ok = v.verifyFull(reps, pri_mask, pub_mask);
         s->full_record = v.fullRecord();
         s->fri_roots = v.friRoots(); s->fri_final = v.friFinalCode(); s->fri_r = v.friChallenges();
         s->fft_gkr_msgs = v.fftGkrMessages();
@@ -463,7 +472,7 @@ static bool pc_args_ok(int n, const uint64_t *pairs, uint64_t n_elems, int n_que
 }
 static std::vector<F> pc_elems(const uint64_t *pairs, uint64_t n_elems) {
     std::vector<F> v(n_elems);
-    memcpy(static_cast<void *>(v.data()), pairs, n_elems * sizeof(F));
+    if (n_elems) memcpy(static_cast<void *>(v.data()), pairs, n_elems * sizeof(F));
     return v;
 }
 int vph_pc_public_evals_host(int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int tensor, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs) {
@@ -500,6 +509,68 @@ int vph_fri_query_digests(vph_session *s, int n, int n_queries, const uint64_t *
     const int rc = vp_fri_query_digests(ctx, n, n_queries, leaf0, answer, n_bytes, out);
     if (rc != VP_OK) set_err(err, errlen, std::string("vp_fri_query_digests: ") + vp_last_error(ctx));
     return rc;
+}
+
+int vph_pc_mask_evals_host(int n, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs) {
+    if (!out_pairs || !pub_mask_pairs || ms < 1 || (ms & (ms - 1)) || n_pub_mask < 1 || n_pub_mask > ms || n < 7 || n > 25 || ms > (1ull << (n - 2))) return -1;
+    if (!pc_args_ok(n, pub_mask_pairs, n_pub_mask, n_queries, leaf0)) return -1;
+    try {
+        const std::vector<F> out = pcMaskEvalsHost(n, pc_elems(pub_mask_pairs, n_pub_mask), ms, std::vector<u64>(leaf0, leaf0 + n_queries));
+        memcpy(out_pairs, out.data(), out.size() * sizeof(F));
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+int vph_pc_mask_evals(vph_session *s, int n, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs,
+                      char *err, int errlen) {
+    vp_ctx *ctx = s->p->context();
+    const int rc = vp_pc_mask_evals(ctx, n, reinterpret_cast<const vp_F *>(pub_mask_pairs), n_pub_mask, ms, n_queries, leaf0, reinterpret_cast<vp_F *>(out_pairs));
+    if (rc != VP_OK) set_err(err, errlen, std::string("vp_pc_mask_evals: ") + vp_last_error(ctx));
+    return rc;
+}
+
+int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms,
+                          const uint64_t *claim_pair, const uint8_t *root_l, const uint8_t *root_h, const uint64_t *all_sum_pairs, const uint64_t *r_pairs,
+                          const uint8_t *fri_roots, const uint64_t *final_code_pairs, const uint64_t *final_mask_pairs, int reps, const uint64_t *leaf0,
+                          const uint8_t *answer, uint64_t n_bytes, int device, char *err, int errlen) {
+    auto bad = [&](const char *m) { set_err(err, errlen, m); return -1; };
+    if (n < 7 || n > 25) return bad("vph_verify_commitment: n outside 7 .. 25");
+    if ((point_pairs == nullptr) == (pub_pairs == nullptr)) return bad("vph_verify_commitment: exactly one of point and pub");
+    if (!claim_pair || !root_l || !root_h || !all_sum_pairs || !r_pairs || !fri_roots || !final_code_pairs || !final_mask_pairs || !leaf0 || !answer)
+        return bad("vph_verify_commitment: a null argument");
+    if (reps < 1 || reps > 4096) return bad("vph_verify_commitment: 1 .. 4096 repetitions");
+    if (pub_mask_pairs && n_pub_mask > ms) return bad("vph_verify_commitment: public mask longer than ms");
+    const uint64_t n_mask = pub_mask_pairs ? n_pub_mask : 0;
+    const struct { const uint64_t *p; uint64_t n; } elems[] = {{point_pairs, (uint64_t) n}, {pub_pairs, 1ull << n}, {pub_mask_pairs, n_mask}, {claim_pair, 1}, {all_sum_pairs, 65},
+                                                                {r_pairs, (uint64_t) (n - 6)}, {final_code_pairs, 2048}, {final_mask_pairs, 32}};
+    for (const auto &e : elems)
+        for (uint64_t i = 0; e.p && i < 2 * e.n; ++i) if (e.p[i] >= F::mod) return bad("vph_verify_commitment: non-canonical field element in an argument");
+    vp_ctx *ctx = nullptr;
+    try {
+        PcCommitment c;
+        c.n = n;
+        if (point_pairs) c.point = pc_elems(point_pairs, (uint64_t) n); else c.pub = pc_elems(pub_pairs, 1ull << n);
+        c.pub_mask = pc_elems(pub_mask_pairs, n_mask);
+        c.ms = ms;
+        c.claim = pc_elems(claim_pair, 1)[0];
+        memcpy(c.root_l, root_l, 32); memcpy(c.root_h, root_h, 32);
+        c.all_sum = pc_elems(all_sum_pairs, 65);
+        c.fr = pc_elems(r_pairs, (uint64_t) (n - 6));
+        c.fri_roots.assign(fri_roots, fri_roots + 32 * (size_t) (n - 6));
+        c.final_code = pc_elems(final_code_pairs, 2048);
+        c.final_mask = pc_elems(final_mask_pairs, 32);
+        c.leaf0.assign(leaf0, leaf0 + reps);
+        c.answer = answer; c.n_bytes = n_bytes;
+        if (device >= 0 && vp_create(device, &ctx) != VP_OK) { ctx = nullptr; throw std::runtime_error("vph_verify_commitment: no context on the device"); }
+        std::string why;
+        const int rc = pcVerifyCommitment(c, why, ctx);
+        if (ctx) vp_destroy(ctx);
+        if (rc) set_err(err, errlen, why);
+        return rc;
+    } catch (const std::exception &e) {
+        if (ctx) vp_destroy(ctx);
+        set_err(err, errlen, e.what());
+        return -2;
+    }
 }
 
 // fft_gkr of the last vph_prove_and_verify_full: its messages ({real,img} pairs, layout of vp_fft_gkr); returns their number or -1

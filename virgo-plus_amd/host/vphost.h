@@ -46,7 +46,7 @@ vph_session *vph_session_create_opts(vph_circuit *, int device, const vp_options
 void vph_session_free(vph_session *);
 int vph_set_profiling(vph_session *, int level);
 /* With profiling on, the launch tables (vp_get_launch_stats) of the VERIFIER-side device calls of the last vph_prove_and_verify_full(_ex) — vp_predicates, vp_liu_gr,
- * vp_layer_mle, vp_pc_public_evals, vp_fri_query_digests — one after the other, in call order; every verification (verifier::run) starts the log anew, and
+ * vp_layer_mle, vp_pc_public_evals, vp_pc_mask_evals (a masked run), vp_fri_query_digests — one after the other, in call order; every verification (verifier::run) starts the log anew, and
  * vph_set_profiling switches it on and off with the launch tables it reads.  Returns the number of entries (copies up to `capacity`). */
 int vph_verifier_launches(vph_session *, vp_launch_stat *out, int capacity);
 /* the vp_ctx behind the session's prover (for the measurement calls of include/vpgpu.h: vp_get_launch_stats, ...) */
@@ -109,14 +109,25 @@ int vph_prove_and_verify_full(vph_session *, int reps, uint8_t *transcript, uint
 enum { VPH_VERIFY_BATCHED_OPENINGS = 1, VPH_VERIFY_DEVICE_LOOPS = 2 };
 int vph_prove_and_verify_full_ex(vph_session *, int reps, int flags, uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
                                  double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec, char *err, int errlen);
-/* Record of the last ACCEPTED vph_prove_and_verify_full(_ex) of the session: everything the prover handed over, so that the whole verifier can run
+/* The same with the mask vectors of a hiding commitment (flags as _ex): prover::commit_private(pri_mask), commit_public_eq(r_liu, pub_mask; null or n_pub = 0: one
+ * zero) behind it, and the verifier checks the 65th slice like the other 64 — the public mask polynomial at the query points, the slice's virtual oracle, its fold
+ * consistency on every level, its final codeword (vp_fri_final_mask) constant and equal to the last level's pair.  As the reference's verifier, it accepts a mask
+ * that pads to at most 2^(n-6) elements and rejects a longer one at the final mask codeword.  With VPH_VERIFY_DEVICE_LOOPS the mask polynomial's values come from
+ * vp_pc_mask_evals.  A null or all-zero private mask is vph_prove_and_verify_full_ex, byte for byte.  A mask the device refuses (lengths: include/vpgpu.h; a sharded
+ * commitment) is -2 with the library's message, not a verdict.  An accepted masked run leaves a version-2 record.                                              */
+int vph_prove_and_verify_full_masked(vph_session *, int reps, int flags, const uint64_t *pri_mask_pairs, uint64_t n_pri, const uint64_t *pub_mask_pairs, uint64_t n_pub,
+                                     uint8_t *transcript, uint64_t capacity, uint64_t *n_written, double *gkr_prove_sec, double *pc_prove_sec, double *verify_sec,
+                                     char *err, int errlen);
+/* Record of the last ACCEPTED vph_prove_and_verify_full(_ex, _masked) of the session: everything the prover handed over, so that the whole verifier can run
  * again later without a GPU.  All integers little-endian, field elements as {real, img} u64 pairs (canonical), n = bit length of the input layer:
- *     header       16 bytes   u32 magic 0x52465056 ("VPFR") | u32 version = 1 | u32 n | u32 reps (1 .. 4096)
+ *     header       16 bytes   u32 magic 0x52465056 ("VPFR") | u32 version = 1, or 2 for a masked run | u32 n | u32 reps (1 .. 4096)
  *     transcript              merkle_root_l[32] | GKR slice | merkle_root_h[32] | input_0[16] | all_sum[65 x 16]      (the golden layout)
  *     fft_gkr      16 x (64 + 3 (2 lg^2 + 2 lg + 6) + 2 + 2 lg) bytes, lg = n - 6                                     (vp_fft_gkr's message layout)
  *     FRI roots    32 x (n - 6) bytes
  *     final code   2048 x 16 bytes                                                                                    (vp_fri_final's layout)
- *     openings     vp_fri_query's bytes for the `reps` positions the verifier drew: per repetition oracle 0, oracle 1, level 0 .. n - 7, each
+ *     mask         VERSION 2 ONLY: u32 ms (the private mask's padded length, a power of two in [8, min(2^16, 2^(n-2))]) | u32 n_pub (1 .. ms) | the public
+ *                  mask, n_pub x 16 bytes | the final mask codeword, 32 x 16 bytes                                    (vp_fri_final_mask's layout)
+ *     openings   vp_fri_query's bytes for the `reps` positions the verifier drew: per repetition oracle 0, oracle 1, level 0 .. n - 7, each
  *                  130 values (2080 bytes) + its path at the true length (n - 1 digests for l and h, n - 2 - k for level k)
  * vph_last_full_record: copies it to buf (*n = its size; -1 if there is none or cap is too small, *n still set).
  * vph_verify_full_record: no GPU, no session.  F::init(), then verifier::checkFull: the GKR part as vph_verify_transcript, then the commitment's
@@ -145,6 +156,27 @@ uint64_t vph_pc_query_answer_bytes(int n, int n_queries);
 int vph_pc_public_evals(vph_session *, int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs,
                         char *err, int errlen);
 int vph_fri_query_digests(vph_session *, int n, int n_queries, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, uint8_t *out, char *err, int errlen);
+/* The mask row of the public evaluation (slot 64 of a masked commitment): out_pairs[2 q + h] = the public mask polynomial — the interpolant of the public mask,
+ * zero-padded to ms, on the ms-th roots of unity — at (-1)^h w^leaf0[q].  _host: on the host, any power of two ms in 1 .. 2^(n-2), 1 .. ms mask elements; -1 = refused.
+ * vph_pc_mask_evals: vp_pc_mask_evals on the session's context, arguments as given; the device library's status, its refusal in err.                             */
+int vph_pc_mask_evals_host(int n, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs);
+int vph_pc_mask_evals(vph_session *, int n, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms, int n_queries, const uint64_t *leaf0, uint64_t *out_pairs,
+                      char *err, int errlen);
+/* The commitment's verifier by value (no session, no circuit): everything verifier::verifyPoly checks behind fft_gkr, all 65 slices, on the caller's arrays.
+ * n: bit length of the committed vector; exactly one of point_pairs (n coordinates: the public vector is eq(point, .)) and pub_pairs (2^n entries); pub_mask_pairs
+ * (n_pub_mask <= ms elements, or null: zeros) and ms, the private mask's padded length — 1 for the zero mask, else a power of two in [8, min(2^16, 2^(n-2))];
+ * claim; root_l, root_h; all_sum[65]; the n - 6 fold challenges and FRI roots; final_code[2048] (vp_fri_final), final_mask[32] (vp_fri_final_mask; zeros for the
+ * zero mask); reps positions leaf0 in [2^(n-7), 2^(n-2)); answer: n_bytes in vp_fri_query's layout for (n, reps).  device >= 0: the heavy loops (vp_pc_public_evals,
+ * vp_pc_mask_evals, vp_fri_query_digests) run there on a context made for the call; -1: on the host.  Same verdict either way.
+ * 0 = accepted; 1 = rejected, err names the failed check ("commitment: slice sums ...", "Fri rs code check fail", "Fri msk rs code check fail", "commitment: Merkle
+ * opening rejected", "commitment: FRI Merkle opening rejected (level k)", "Fri check consistency k round fail", "Fri msk check consistency k round fail", "Fri final
+ * codeword mismatch", "Fri msk final codeword mismatch", a non-canonical opened value); -1 = malformed arguments (err); -2 = the device could not run the loops (err).
+ * fft_gkr is not part of it: it is independent of the commitment (vph_prove_and_verify_full covers it).                                                            */
+int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pub_pairs, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint64_t ms,
+                          const uint64_t *claim_pair, const uint8_t root_l[32], const uint8_t root_h[32], const uint64_t *all_sum_pairs /* 65 */,
+                          const uint64_t *r_pairs /* n - 6 */, const uint8_t *fri_roots /* 32 (n - 6) */, const uint64_t *final_code_pairs /* 2048 */,
+                          const uint64_t *final_mask_pairs /* 32 */, int reps, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, int device,
+                          char *err, int errlen);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
