@@ -318,6 +318,20 @@ int vp_fri_step(vp_ctx *, const vp_F *r, uint8_t root[32]);
  * leaf launch, and the roots come back in one copy; vp_fri_final_mask and a vp_fri_step after a partial phase
  * (n_steps < n - 6) continue from there.                                                                             */
 int vp_fri_commit(vp_ctx *, const vp_F *r, int n_steps, uint8_t *roots);
+/* The commit phase of a NON-INTERACTIVE commitment: steps 8 and 9 of the Fiat-Shamir chain written out in host/vphost.h ("The transcript chain").  The device
+ * draws every fold challenge itself from the root it has just computed: state_in is the chain's state after D(1, root_h); r_0 = C(0); level k is folded by
+ * r_k, hashed by the rules of vp_fri_step (leaf chains closed by the mask slice's pair under a masked commitment, one tree), and its tree top performs
+ * D(2 + k, root_k) and, for k + 1 < n - 6, r_(k+1) = C(k + 1) on one lane.  state_out is the state after the last D.  State and challenges live in device
+ * memory and the folds read their challenge through a pointer (k_fri_fold0_vo_p, k_fri_fold_p, k_fri_fold_one_p: the same device bodies as the by-value
+ * kernels, so the same bytes); the fused three-level fold and the merged leaf launch of vp_fri_commit cannot be used, since they need every challenge up
+ * front.  The call always runs the complete phase, all n - 6 levels, queued without a host wait between the first fold and the one pinned copy that brings
+ * back roots (32 (n - 6) bytes), r_out (n - 6 elements) and state_out.  Afterwards vp_fri_final, vp_fri_final_mask, vp_fri_open(_many) and vp_fri_query
+ * behave as after vp_fri_commit.  Live slices as in vp_fri_step; under vp_pc_hash_late an outstanding l or h is hashed first.
+ * Refused with VP_EINVAL before anything is queued, the reason in vp_last_error and the context usable afterwards: a null argument; a call before
+ * vp_commit_public*; a call after a vp_fri_step, vp_fri_commit or vp_fri_commit_fs of the same commitment; a sharded commitment (vp_pc_set_shard), for
+ * which this call is not built.  With vp_set_profiling(1) the launch table holds per level one k_fri_fold row (two under a mask), one k_leaf_hash row and
+ * the level's k_merkle rows, the last of which is the drawing tree top: rounds = 1, first_round = the level, 1-based like every first_round.            */
+int vp_fri_commit_fs(vp_ctx *, const uint8_t state_in[32], uint8_t *roots /* 32 (n - 6) */, vp_F *r_out /* n - 6 */, uint8_t state_out[32]);
 /* fri::commit_phase_final() (fri.cpp:426-431): the last codeword, 2048 elements in the reference's interleaved
  * layout [i << 7 | slice << 1 | hi], i < 16.                                                            */
 int vp_fri_final(vp_ctx *, vp_F *final_code);
@@ -618,6 +632,10 @@ int vp_test_sha3(vp_ctx *, const uint8_t *in, uint8_t *out, uint64_t n);
  * (RS_polynomial.cpp:26-220), natural order in and out.  order/coef_len must be 1 or 32 for the forward
  * transform (the two shapes the commitment uses); sizes up to 2^19 per transform (VP_ELIMIT above).       */
 int vp_test_fft(vp_ctx *, const vp_F *coefs, int coef_len, int order, int inverse, vp_F *out);
+/* The device side of the commitment's Fiat-Shamir chain (vp_fri_commit_fs).  op 0: one lane performs D(label, root) and C(counter) on `state` — the new
+ * state -> state_out, the challenge -> r_out.  op 1: the reduction of digest words to limbs alone, on raw words: the four words of `root`, each reduced
+ * (low 61 bits, p -> 0) -> state_out, the first two also -> r_out; state, label and counter are not read.                                             */
+int vp_test_fs_draw(vp_ctx *, int op, const uint8_t state[32], const uint8_t root[32], uint64_t label, uint64_t counter, uint8_t state_out[32], vp_F *r_out);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@ GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vp
     os.path.join(ROOT, "include", "vpgpu.h")]
 HOST_SRC = [os.path.join(HOST, f) for f in ("circuit.cpp", "prover.cpp", "verifier.cpp", "vphost.cpp")]
 HOST_HDR = [os.path.join(HOST, f) for f in ("circuit.hpp", "prover.hpp", "verifier.hpp", "vphost.h", "field.hpp",
-                                              "polynomial.hpp")]
+                                              "polynomial.hpp", "sha3.hpp", "pc_fs.hpp")]
 
 
 def _stale(target, sources):
@@ -158,6 +158,8 @@ def lib_gpu():
         L.vp_commit_public_masked.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp]
         L.vp_fri_final_mask.argtypes = [vp, vp]
         L.vp_fri_commit.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.vp_fri_commit_fs.argtypes = [vp, vp, vp, vp, vp]
+        L.vp_test_fs_draw.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp]
         L.vp_fri_step.argtypes = [vp, vp, vp]
         L.vp_commit_private_masked.argtypes = [vp, vp, ctypes.c_uint64, vp]
         L.vp_shard_pending.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
@@ -252,6 +254,11 @@ def lib_host():
         L.vph_pc_mask_evals_host.argtypes = [ctypes.c_int, vp, u64, u64, ctypes.c_int, vp, vp]
         L.vph_pc_mask_evals.argtypes = [vp, ctypes.c_int, vp, u64, u64, ctypes.c_int, vp, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_verify_commitment.argtypes = [ctypes.c_int, vp, vp, vp, u64, u64] + [vp] * 8 + [ctypes.c_int, vp, vp, u64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_commit_fs.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, u64, vp, u64, ctypes.c_int, vp, u64, ctypes.POINTER(u64), ctypes.c_char_p, ctypes.c_int]
+        L.vph_last_commit_fs_times.restype = None
+        L.vph_last_commit_fs_times.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        L.vph_verify_commitment_fs.argtypes = [vp, u64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_commitment_fs_challenges.argtypes = [vp, u64, vp, vp]
         L.vph_last_full_record.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
         L.vph_verify_full_record.argtypes = [vp, vp, u64]
         L.vph_verifier_launches.argtypes = [vp, ctypes.POINTER(LaunchStat), ctypes.c_int]
@@ -741,6 +748,39 @@ class Circuit:
             raise RuntimeError("verify_commitment: " + err.value.decode())
         return rc == 0, err.value.decode() if rc else ""
 
+    @staticmethod
+    def verify_commitment_fs(proof, device=None):
+        """Verify a non-interactive commitment proof (Session.commit_fs; layout and chain: host/vphost.h): no tape, no session, no circuit.  The fold challenges
+        and query positions are derived from the proof itself, then verify_commitment's checks run unchanged.  device=k: the heavy loops on GPU k.  Returns
+        (accepted, reason); raises ValueError on a malformed proof and RuntimeError when the device could not run the loops."""
+        proof = bytes(proof)
+        buf = ctypes.create_string_buffer(proof, max(len(proof), 1))
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_verify_commitment_fs(ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), err, len(err))
+        if rc == -1:
+            raise ValueError("verify_commitment_fs: " + err.value.decode())
+        if rc < 0:
+            raise RuntimeError("verify_commitment_fs: " + err.value.decode())
+        return rc == 0, err.value.decode() if rc else ""
+
+    @staticmethod
+    def commitment_fs_challenges(proof):
+        """The derivation alone: (r, leaf0) of a well-formed commitment proof — the n - 6 fold challenges as an (n - 6, 2) uint64 array and the positions as a
+        list.  Raises ValueError on a malformed proof."""
+        import struct
+        import numpy as np
+        proof = bytes(proof)
+        if len(proof) < 32:
+            raise ValueError("commitment_fs_challenges: malformed proof")
+        n, reps = struct.unpack_from("<II", proof, 8)
+        if not (7 <= n <= 30 and 1 <= reps <= 4096):
+            raise ValueError("commitment_fs_challenges: malformed proof")
+        buf = ctypes.create_string_buffer(proof, len(proof))
+        r, lf = np.zeros((n - 6, 2), np.uint64), np.zeros(reps, np.uint64)
+        if lib_host().vph_commitment_fs_challenges(ctypes.cast(buf, ctypes.c_void_p), len(proof), r.ctypes.data, lf.ctypes.data):
+            raise ValueError("commitment_fs_challenges: malformed proof")
+        return r, [int(x) for x in lf]
+
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
         buf = ctypes.create_string_buffer(bytes(proof), len(proof))
@@ -1129,6 +1169,33 @@ class Session:
         if rc:
             raise RuntimeError("vp_commit_public_eq failed: %d %s" % (rc, (lib_gpu().vp_last_error(ctx) or b"").decode()))
         return out.raw[:32], out.raw[32:48], out.raw[48:], self.commit_device_ms()
+
+    def commit_fs(self, point, reps=33, mask=None, pub_mask=None, device_draws=True):
+        """The non-interactive commitment proof of the session's input layer at `point` (vph_commit_fs, host/vphost.h): one block of bytes for
+        Circuit.verify_commitment_fs.  mask / pub_mask: the vectors of a hiding commitment, as for commit_private(mask) and commit_public_eq(pub_mask=).
+        device_draws: the commit phase draws every fold challenge on the device (vp_fri_commit_fs); False: the vp_fri_step loop with the chain on the host —
+        the same bytes.  Not on a session with a sharded commitment."""
+        import numpy as np
+        arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 2)
+        pt, m, pm = arr(point), arr(mask), arr(pub_mask)
+        ptr = lambda a: a.ctypes.data if a is not None and a.shape[0] else None
+        cnt = lambda a: 0 if a is None else a.shape[0]
+        n = pt.shape[0]
+        cap = 4096 + 16 * (n + cnt(pm)) + 32 * n + (2048 + 32) * 16 + int(reps) * ((n - 4) * 2080 + 32 * (n * n))
+        buf = ctypes.create_string_buffer(cap)
+        ln = ctypes.c_uint64(0)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_commit_fs(self.h, pt.ctypes.data, n, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), 0 if device_draws else 1, ctypes.cast(buf, ctypes.c_void_p), cap,
+                                      ctypes.byref(ln), err, len(err))
+        if rc:
+            raise RuntimeError("commit_fs failed: " + err.value.decode())
+        return buf.raw[: ln.value]
+
+    def last_commit_fs_times(self):
+        """(host seconds, device milliseconds) of the last commit_fs's commit phase alone"""
+        out = (ctypes.c_double * 2)()
+        lib_host().vph_last_commit_fs_times(self.h, out)
+        return out[0], out[1]
 
     def warm(self):
         """vp_warm(VP_WARM_COMMITMENT | VP_WARM_FFT_GKR): the commitment's tables, buffers and pinned staging (and fft_gkr's arrays) exist before the first prover call (include/vpgpu.h)."""

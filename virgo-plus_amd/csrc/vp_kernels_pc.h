@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(VP_BLOCK) k_merkle_level(MerkleArgs a) {
     const Dig l = tree[2 * (c + i)], r = tree[2 * (c + i) + 1];
     tree[c + i] = hhash64(l.w[0], l.w[1], l.w[2], l.w[3], r);
 }
-__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top(MerkleArgs a, Dig *roots) {
+__device__ __forceinline__ void merkle_top_body(const MerkleArgs &a, Dig *roots) {
     Dig *tree = a.tree[blockIdx.x];
     for (u32 c = a.count[blockIdx.x] >> 1; c >= 1; c >>= 1) {
         for (u32 i = threadIdx.x; i < c; i += blockDim.x) {
@@ -330,6 +330,47 @@ __global__ void __launch_bounds__(VP_BLOCK) k_merkle_top(MerkleArgs a, Dig *root
         __syncthreads();
     }
     if (roots && threadIdx.x == 0) roots[blockIdx.x] = tree[1];
+}
+__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top(MerkleArgs a, Dig *roots) { merkle_top_body(a, roots); }
+
+// ---- the Fiat-Shamir chain of the commitment on the device (vp_fri_commit_fs; the chain's text: host/vphost.h) ----------------------------------------------
+// A step is state = SHA3-256(m0..m3 || state), the block function of the leaf chains.  D(label, digest) is two steps, {label, 0, 0, 0x44} and the digest's four
+// words; C(counter) is the step {counter, 0, 0, 0x43}, and the challenge is the first two words of the new state, each reduced by fs_limb.
+// fs_limb: a digest word -> a limb of F: the low 61 bits, with p itself mapped to 0 (verifier::draw()'s rule; p is reached with probability 2^-61, so only a
+// test that hands in raw words sees that branch: vp_test_fs_draw, op 1)
+__device__ __forceinline__ u64 fs_limb(u64 w) {
+    const u64 p = 0x1FFFFFFFFFFFFFFFull;
+    w &= p;
+    return w == p ? 0 : w;
+}
+// One lane: D(label, *root) unless root is null, then C(counter) into *r_out unless r_out is null.  The state lives in device memory.
+__device__ __forceinline__ void fs_absorb_draw(Dig *state, const Dig *root, u64 label, u64 counter, F *r_out) {
+    Dig s = *state;
+    if (root) {
+        const Dig d = *root;
+        s = hhash64(label, 0, 0, 0x44, s);
+        s = hhash64(d.w[0], d.w[1], d.w[2], d.w[3], s);
+    }
+    if (r_out) {
+        s = hhash64(counter, 0, 0, 0x43, s);
+        F r; r.re = fs_limb(s.w[0]); r.im = fs_limb(s.w[1]);
+        *r_out = r;
+    }
+    *state = s;
+}
+// k_merkle_top of ONE tree that also continues the chain: the root goes to roots[0], D(label, root) follows, and C(counter) -> *r_next unless r_next is null
+// (the last level draws nothing).  The fold of the next level reads *r_next in stream order.
+__global__ void __launch_bounds__(VP_BLOCK) k_merkle_top_fs(MerkleArgs a, Dig *roots, Dig *state, u64 label, u64 counter, F *r_next) {
+    merkle_top_body(a, roots);
+    if (blockIdx.x == 0 && threadIdx.x == 0) fs_absorb_draw(state, a.tree[0] + 1, label, counter, r_next);       // (thread 0 wrote tree[1] itself)
+}
+// the chain's steps alone: the first challenge C(0) of vp_fri_commit_fs (root null) and the test hook (vp_test_fs_draw)
+__global__ void k_fs_draw(Dig *state, const Dig *root, u64 label, u64 counter, F *r_out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) fs_absorb_draw(state, root, label, counter, r_out);
+}
+__global__ void k_test_fs_limbs(const u64 *__restrict__ in, u64 *__restrict__ out, u32 n) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = fs_limb(in[i]);
 }
 
 // Round 4: the same leaf chains by the generated fixed-register block (vp_keccak_asm.h, tools/gen_keccak_asm.py): workgroups of 1024 threads, one per
@@ -474,8 +515,9 @@ k_pc_virtual_oracle(const F *__restrict__ lcw, F *__restrict__ qcw, const F *__r
 // that hold a live slice (vp_fold_groups).  64: every slice.
 #define VP_FOLD_SPT 4
 __host__ __device__ inline u32 vp_fold_groups(u32 live, u32 spt) { return (live + spt - 1) / spt; }
-__global__ void __launch_bounds__(VP_BLOCK)
-k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2, int lw, u32 rank, u32 live) {
+// (the body of both forms: the challenge by value, k_fri_fold, or read once per thread from device memory, k_fri_fold_p — the same field operations)
+__device__ __forceinline__ void
+fri_fold_body(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, const F r, F inv2, int lw, u32 rank, u32 live) {
     const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     const u32 No = Nk >> 1;                                   // per-coset length of the output (>= 1)
     if (t >= (size_t) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No) return;
@@ -499,6 +541,15 @@ k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F
         if (ig * VP_FOLD_SPT + j < live) out[sb * No + al] = f_add(f_half(f_add(p[j], q[j])), f_mul(c, f_sub(p[j], q[j])));      // 1/2 ((p + q) + mu^-1 r (p - q))
     }
 }
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2, int lw, u32 rank, u32 live) {
+    fri_fold_body(in, out, Nk, k, RT, half_m, r, inv2, lw, rank, live);
+}
+// the challenge in device memory (vp_fri_commit_fs: the device drew it from the root of the level before)
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold_p(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, const F *__restrict__ r, F inv2, int lw, u32 rank, u32 live) {
+    fri_fold_body(in, out, Nk, k, RT, half_m, *r, inv2, lw, rank, live);
+}
 // Round 4: the FIRST fold straight from the three committed codewords — the virtual oracle (k_pc_virtual_oracle) is never written.  With
 // G(a) = l q - (x^N - 1) h - S0 at position (b, a) and X = N x^-1, the oracle is G X; its partner at a + N/2 sits at -x (w_M^(16 N) = -1), so
 //   p = G(a) X,  q' = -G(a') X   and   1/2 ((p + q') + mu^-1 r (p - q')) = (X / 2) ((G(a) - G(a')) + x^-1 r (G(a) + G(a'))),  mu = x at level 0
@@ -510,9 +561,9 @@ k_fri_fold(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F
 #ifndef VP_VO_SPT
 #define VP_VO_SPT 4
 #endif
-__global__ void __launch_bounds__(VP_BLOCK)
-k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out, u32 N,
-               const F *__restrict__ RTn /* w_N^k, k < N */, const F *__restrict__ cb /* [b] = w_M^-b, [32 + b] = w_32^b - 1 */, F r, F half_n /* N / 2 */,
+__device__ __forceinline__ void
+fri_fold0_vo_body(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out, u32 N,
+               const F *__restrict__ RTn /* w_N^k, k < N */, const F *__restrict__ cb /* [b] = w_M^-b, [32 + b] = w_32^b - 1 */, const F r, F half_n /* N / 2 */,
                const F *__restrict__ q0, const F *__restrict__ qscal, u32 live /* slices >= live: neither read nor written, see k_fri_fold */) {
     const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     const u32 No = N >> 1;
@@ -544,6 +595,16 @@ k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__
         const F D = f_sub(Ga, Gb), S = f_add(Ga, Gb);
         out[((size_t) i * 32 + b) * No + al] = f_mul(hx, f_add(D, f_mul(xr, S)));
     }
+}
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold0_vo(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out, u32 N,
+               const F *__restrict__ RTn, const F *__restrict__ cb, F r, F half_n, const F *__restrict__ q0, const F *__restrict__ qscal, u32 live) {
+    fri_fold0_vo_body(lcw, qcw, hcw, S0, out, N, RTn, cb, r, half_n, q0, qscal, live);
+}
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold0_vo_p(const F *__restrict__ lcw, const F *__restrict__ qcw, const F *__restrict__ hcw, const F *__restrict__ S0, F *__restrict__ out, u32 N,
+                 const F *__restrict__ RTn, const F *__restrict__ cb, const F *__restrict__ r, F half_n, const F *__restrict__ q0, const F *__restrict__ qscal, u32 live) {
+    fri_fold0_vo_body(lcw, qcw, hcw, S0, out, N, RTn, cb, *r, half_n, q0, qscal, live);
 }
 // Round 5: the first THREE folds in one pass (vp_fri_commit has every challenge before it starts).  A workgroup owns 64 consecutive positions al of one coset at
 // the eight offsets al + j N/8: wave v (of four) does fold 0 on the pair (v, v + 4) exactly as k_fri_fold0_vo does — same loads, 1 KB contiguous per wave and
@@ -855,8 +916,8 @@ k_mask_vo(const F *__restrict__ lm, const F *qm, const F *__restrict__ hm, const
     out[t] = f_mul(f_sub(g, *S0), inv_x);
 }
 // One FRI fold of ONE slice (k_fri_fold's arithmetic on a single coset-major codeword): fri.cpp:366-374
-__global__ void __launch_bounds__(VP_BLOCK)
-k_fri_fold_one(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2) {
+__device__ __forceinline__ void
+fri_fold_one_body(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, const F r, F inv2) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 No = Nk >> 1;
     if (t >= 32 * No) return;
@@ -866,6 +927,14 @@ k_fri_fold_one(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, con
     const F p = in[(size_t) b * Nk + a], q = in[(size_t) b * Nk + a + No];
     const F c = f_mul(inv2, f_mul(inv_mu, r));
     out[(size_t) b * No + a] = f_add(f_half(f_add(p, q)), f_mul(c, f_sub(p, q)));
+}
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold_one(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, F r, F inv2) {
+    fri_fold_one_body(in, out, Nk, k, RT, half_m, r, inv2);
+}
+__global__ void __launch_bounds__(VP_BLOCK)
+k_fri_fold_one_p(const F *__restrict__ in, F *__restrict__ out, u32 Nk, int k, const F *__restrict__ RT, u32 half_m, const F *__restrict__ r, F inv2) {
+    fri_fold_one_body(in, out, Nk, k, RT, half_m, *r, inv2);
 }
 }  // namespace vp
 #undef f_mul

@@ -237,6 +237,7 @@ struct vp_ctx {
     // vp_fri_open_many / vp_fri_query: records on the device, descriptor table + request list on the device, pinned staging of both directions
     PcOpenRec *pc_many_buf = nullptr; unsigned char *pc_many_in = nullptr; u32 pc_many_cap = 0; unsigned char *h_many = nullptr; size_t h_many_cap = 0;
     Dig *pc_fri_roots = nullptr;
+    Dig *pc_fs = nullptr;                                 // vp_fri_commit_fs: roots[VP_FRI_MAX] | challenges (VP_FRI_MAX elements of F) | the chain's state, one block for one copy
     Dig *pc_fri_tree = nullptr; int fri_step = -1; bool pc_public_done = false;       // fri_step: FRI levels committed (openable); -1: no FRI phase begun
     // the mask slice with content (vp_commit_private_masked / vp_commit_public_masked; 0 = the protocol's zero mask, nothing below is touched): padded mask length,
     // the slice's l / q / h codewords and its FRI levels end to end (M elements each, coset-major), scratch of its small transforms
@@ -391,7 +392,7 @@ void pc_forget(vp_ctx *ctx) {
     ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
     ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
     ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0;
-    ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
+    ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->pc_fs = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
     ctx->pc_lv = PcLive(); ctx->pc_zf_cw = ctx->pc_zf_hcw = ctx->pc_zf_fri = 64;
 }

@@ -391,7 +391,10 @@ static int pc_hash_leaves(vp_ctx *ctx, FriLeafArgs &la, bool profiled) {
 // Merkle trees over leaves already in place: ma.tree / count / n filled in, count[q] leaves at tree[q][count .. 2 count) (at least 2).  One k_merkle_level
 // launch per height while any tree has more than 512 nodes there, then one k_merkle_top launch for all trees; root q also lands in d_roots[q] unless d_roots
 // is null.  levels >= 0: exactly that many level launches whatever the width, and no top (the local part of a sharded tree).  ma.count is used up.
-static int pc_merkle_trees(vp_ctx *ctx, MerkleArgs &ma, Dig *d_roots, int levels = -1) {
+// fs (vp_fri_commit_fs, one tree): the top is k_merkle_top_fs, which continues the Fiat-Shamir chain behind the root — D(label, root), then C(counter) into
+// *r_next unless that is null; its launch-table row is a k_merkle row with rounds = 1 and first_round = label - 1: the level, 1-based.
+struct PcFsTop { Dig *state; u64 label, counter; F *r_next; };
+static int pc_merkle_trees(vp_ctx *ctx, MerkleArgs &ma, Dig *d_roots, int levels = -1, const PcFsTop *fs = nullptr) {
     for (int h = 0; levels < 0 || h < levels; ++h) {
         MerkleArgs lv{}; u32 b = 0; u64 hs = 0;
         for (int q = 0; q < ma.n; ++q) {
@@ -407,6 +410,13 @@ static int pc_merkle_trees(vp_ctx *ctx, MerkleArgs &ma, Dig *d_roots, int levels
     if (levels >= 0) return VP_OK;
     u64 hs = 0;
     for (int q = 0; q < ma.n; ++q) hs += ma.count[q] - 1;
+    if (fs) {
+        if (ma.n != 1) { ctx->err = "internal: the drawing tree top takes one tree"; return VP_EINVAL; }
+        const int sl_ = prof_begin(ctx, ctx->stream, VP_K_MERKLE, 1, 1, 96ull * hs + 3 * 64, hs + 3, 1, (u32) (fs->label - 1));
+        hipLaunchKernelGGL(k_merkle_top_fs, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots, fs->state, fs->label, fs->counter, fs->r_next);
+        prof_end(ctx, ctx->stream, sl_);
+        return VP_OK;
+    }
     // (the row's bytes: 96 per hash where the roots are collected, 96 per node of the widest level where they are not — the two forms this launch had)
     PC_PROF(VP_K_MERKLE, ma.n, ma.n, 96ull * (d_roots ? hs : hs + ma.n), hs, hipLaunchKernelGGL(k_merkle_top, dim3(ma.n), dim3(VP_BLOCK), 0, ctx->stream, ma, d_roots));
     return VP_OK;
@@ -647,14 +657,15 @@ static void pc_mask_vo(vp_ctx *ctx, bool profiled) {
                hipLaunchKernelGGL(k_mask_vo, dim3(nblk(M)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) ctx->pc_lm_cw, (const F *) ctx->pc_qm_cw, (const F *) ctx->pc_hm_cw,
                                   (const F *) pc_mask_S0(ctx), N, ctx->pc_rt, M >> 1, f_make(ctx->pc_mask_ms, 0), ctx->pc_mask_ms, ctx->pc_qm_cw));
 }
-static const F *pc_mask_fold(vp_ctx *ctx, int k, F r, bool profiled) {
+static const F *pc_mask_fold(vp_ctx *ctx, int k, F r, bool profiled, const F *d_r = nullptr /* the challenge in device memory instead (vp_fri_commit_fs) */) {
     const int n = ctx->L[0].bl;
     const FriLayout fl(n - 6, 0);
     const u32 M = 1u << (n - 1), Nk = (1u << (n - 6)) >> k, No = Nk >> 1;
     const F *in_m = k == 0 ? ctx->pc_qm_cw : ctx->pc_fm + fl.mask(k - 1);
     F *out_m = ctx->pc_fm + fl.mask(k);
     PC_PROF_IF(profiled, VP_K_FRI_FOLD, nblk((u64) 32 * No), 1, 48ull * 32 * No, (u64) 3 * 32 * No,
-               hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, r, host_inv_real(2)));
+               if (d_r) hipLaunchKernelGGL(k_fri_fold_one_p, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, d_r, host_inv_real(2));
+               else hipLaunchKernelGGL(k_fri_fold_one, dim3(nblk((u64) 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in_m, out_m, Nk, k, ctx->pc_rt, M >> 1, r, host_inv_real(2)));
     return out_m;
 }
 // the last level's codeword ([slice][32], one value per coset) in the reference's order: out[(i << 7) | (slice << 1) | hi] = value at position i + 16 hi
@@ -1278,6 +1289,113 @@ int vp_fri_commit(vp_ctx *ctx, const vp_F *r, int n_steps, uint8_t *roots) {
         ctx->commit_ms = ms;
         return VP_OK;
     });
+}
+
+// The commit phase of a NON-INTERACTIVE commitment (steps 8 and 9 of the chain in host/vphost.h): challenge k + 1 is drawn from the root of level k, so the
+// levels cannot share a leaf launch or a fused fold as in vp_fri_commit — but nothing of that needs the host.  The state and the challenges live in device
+// memory (vp_ctx::pc_fs); k_fs_draw draws r_0, every fold reads its challenge through a pointer (k_fri_fold0_vo_p, k_fri_fold_p, k_fri_fold_one_p: the bodies
+// of the by-value kernels), every level is hashed by pc_hash_level's rules and its tree top (k_merkle_top_fs) performs D(2 + k, root) and C(k + 1).  The whole
+// phase is queued without a host wait; roots, challenges and the closing state come back in one pinned copy.
+int vp_fri_commit_fs(vp_ctx *ctx, const uint8_t state_in[32], uint8_t *roots, vp_F *r_out, uint8_t state_out[32]) {
+    if (!ctx) return VP_EINVAL;
+    VP_ENTER(ctx);
+    // every refusal before anything is queued
+    if (!state_in || !roots || !r_out || !state_out) { ctx->err = "vp_fri_commit_fs: a null argument"; return VP_EINVAL; }
+    if (ctx->pcs) { ctx->err = "vp_fri_commit_fs: not built for a sharded commitment (vp_pc_set_shard)"; return VP_EINVAL; }
+    if (ctx->L.empty() || !ctx->pc_public_done) { ctx->err = "vp_fri_commit_fs: vp_commit_public first"; return VP_EINVAL; }
+    if (ctx->fri_step >= 0) { ctx->err = "vp_fri_commit_fs after vp_fri_step or vp_fri_commit of the same commitment"; return VP_EINVAL; }
+    const int n = ctx->L[0].bl, ln = n - 6, lm = n - 1;
+    if (ln < 1 || ln > VP_FRI_MAX) { ctx->err = "vp_fri_commit_fs: too many FRI steps"; return VP_ELIMIT; }
+    const u32 N = 1u << ln, M = 1u << lm;
+    VPCHK(pc_hash_outstanding(ctx, 3u));                  // (vp_pc_hash_late: only the one-pass vp_fri_commit merges)
+    const bool masked = ctx->pc_mask_ms != 0;
+    if (!ctx->pc_fri_all) {
+        VPCHK(dalloc(ctx, &ctx->pc_fri_all, (size_t) 64 * M));
+        VPCHK(dalloc(ctx, &ctx->pc_fri_tree, (size_t) M));
+    }
+    constexpr size_t FS_DIGS = VP_FRI_MAX + VP_FRI_MAX / 2 + 1;          // roots | challenges | state
+    if (!ctx->pc_fs) VPCHK(dalloc(ctx, &ctx->pc_fs, FS_DIGS));
+    Dig *d_roots = ctx->pc_fs, *d_state = ctx->pc_fs + VP_FRI_MAX + VP_FRI_MAX / 2;
+    F *d_r = reinterpret_cast<F *>(ctx->pc_fs + VP_FRI_MAX);
+    const F *rtn = nullptr;
+    VPCHK(pc_circle_roots(ctx, lm, ln, &rtn));
+    VPCHK(pc_fold0_consts(ctx, lm));
+    unsigned char *h_in = nullptr, *st = nullptr;         // pinned: the state on its way in, the block on its way out
+    VPCHK(ring_alloc(ctx, 32, (void **) &h_in));
+    VPCHK(ring_alloc(ctx, FS_DIGS * sizeof(Dig), (void **) &st));
+    memcpy(h_in, state_in, 32);
+    ctx->ev_used = 0;
+    hipEvent_t ev_a = nullptr;
+    VPCHK(defer_begin(ctx, &ev_a));
+    EvGuard ev_guard{ctx, &ev_a};
+    HIPCHK(hipMemsetAsync(ctx->pc_fs, 0, FS_DIGS * sizeof(Dig), ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_state, h_in, 32, hipMemcpyHostToDevice, ctx->stream));
+    ctx->fri_step = 0;
+    const u32 live = masked ? 64u : ctx->pc_lv.live;     // slices >= live: a zero oracle and zero levels (vp_pc_live.h), kept as zero bytes
+    VPCHK(pc_live_zero_fri(ctx));
+    const FriLayout fl(ln, 0);
+    const PcSlices v = pc_slices(ctx, live);
+    hipLaunchKernelGGL(k_fs_draw, dim3(1), dim3(64), 0, ctx->stream, d_state, (const Dig *) nullptr, (u64) 0, (u64) 0, d_r);      // r_0 = C(0)
+    if (masked) pc_mask_vo(ctx, true);
+    for (int k = 0; k < ln; ++k) {
+        const u32 Nk = N >> k, No = Nk >> 1;
+        const F *in = k == 0 ? ctx->pc_qcw : ctx->pc_fri_all + fl.cw(k - 1);
+        F *out = ctx->pc_fri_all + fl.cw(k);
+        const F *rk = d_r + k;
+        if (k == 0)       // the virtual oracle is consumed by the first fold only: fused into it, as in vp_fri_commit
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No), 1, (v.tensor ? 80ull : 112ull) * live * 32 * No, (u64) (v.tensor ? 9 : 7) * live * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold0_vo_p, dim3(nblk((u64) vp_fold_groups(live, VP_VO_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, (const F *) v.lcw, (const F *) v.qcw,
+                                       (const F *) v.hcw, (const F *) v.S0(), out, N, rtn, (const F *) ctx->pc_cbuf, rk,
+                                       f_mul(f_make(N, 0), host_inv_real(2)), v.q0_arg(), v.qs_arg(), live));
+        else
+            PC_PROF(VP_K_FRI_FOLD, nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No), 1, 48ull * live * 32 * No, (u64) 3 * live * 32 * No,
+                    hipLaunchKernelGGL(k_fri_fold_p, dim3(nblk((u64) vp_fold_groups(live, VP_FOLD_SPT) * 32 * No)), dim3(VP_BLOCK), 0, ctx->stream, in, out, Nk, k, ctx->pc_rt, M >> 1, rk,
+                                       host_inv_real(2), 0, 0u, live));
+        // the mask slice folds behind the 64 on the same stream, and its pair closes every leaf chain of the level
+        const F *out_m = masked ? pc_mask_fold(ctx, k, f_zero(), true, rk) : nullptr;
+        const u32 n_leaves = 16 * No;
+        Dig *tree = ctx->pc_fri_tree + fl.tree(k);
+        FriLeafArgs la{};
+        la.cw[0] = out; la.leaves[0] = tree + n_leaves; la.N[0] = No; la.mask[0] = out_m; la.n = 1;
+        VPCHK(pc_hash_leaves(ctx, la, true));
+        MerkleArgs ma{};
+        ma.tree[0] = tree; ma.count[0] = n_leaves; ma.n = 1;
+        const PcFsTop top{d_state, (u64) (2 + k), (u64) (k + 1), k + 1 < ln ? d_r + k + 1 : nullptr};
+        VPCHK(pc_merkle_trees(ctx, ma, d_roots + k, -1, &top));
+    }
+    HIPCHK(hipMemcpyAsync(st, ctx->pc_fs, FS_DIGS * sizeof(Dig), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->fri_step = ln;
+    return defer_end(ctx, ev_a, VP_PH_FRI, [ctx, st, roots, r_out, state_out, ln](float ms) {
+        memcpy(roots, st, (size_t) 32 * ln);
+        memcpy(r_out, st + 32 * (size_t) VP_FRI_MAX, sizeof(F) * (size_t) ln);
+        memcpy(state_out, st + 32 * (size_t) (VP_FRI_MAX + VP_FRI_MAX / 2), 32);
+        ctx->commit_ms = ms;
+        return VP_OK;
+    });
+}
+
+// Test hook of the chain's device side.  op 0: one lane performs D(label, root) and C(counter) on `state`: the new state -> state_out, the challenge -> r_out.
+// op 1: the reduction alone on raw words: the four words of `root` through fs_limb -> state_out, the first two also -> r_out (state, label, counter unused).
+int vp_test_fs_draw(vp_ctx *ctx, int op, const uint8_t state[32], const uint8_t root[32], uint64_t label, uint64_t counter, uint8_t state_out[32], vp_F *r_out) {
+    if (!ctx || !root || !state_out || !r_out || (op != 0 && op != 1) || (op == 0 && !state)) return VP_EINVAL;
+    VP_ENTER(ctx);
+    u64 *d = nullptr;                                      // state | root | out (4 words each) | r (2 words)
+    HIPCHK(hipMalloc((void **) &d, 14 * sizeof(u64)));
+    u64 h[14] = {0};
+    if (op == 0) memcpy(h, state, 32);
+    memcpy(h + 4, root, 32);
+    int rc = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess ? VP_OK : VP_EHIP;
+    if (rc == VP_OK) {
+        if (op == 0) hipLaunchKernelGGL(k_fs_draw, dim3(1), dim3(64), 0, ctx->stream, reinterpret_cast<Dig *>(d), reinterpret_cast<const Dig *>(d + 4), (u64) label, (u64) counter, reinterpret_cast<F *>(d + 12));
+        else hipLaunchKernelGGL(k_test_fs_limbs, dim3(1), dim3(64), 0, ctx->stream, (const u64 *) (d + 4), d + 8, 4u);
+        rc = check_stream(ctx);
+    }
+    if (rc == VP_OK && hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) rc = VP_EHIP;
+    (void) hipFree(d);
+    if (rc != VP_OK) return rc;
+    if (op == 0) { memcpy(state_out, h, 32); memcpy(r_out, h + 12, 16); }
+    else { memcpy(state_out, h + 8, 32); memcpy(r_out, h + 8, 16); }
+    return VP_OK;
 }
 
 int vp_fri_final(vp_ctx *ctx, vp_F *final_code) {

@@ -1,0 +1,42 @@
+// The fixed parts of the non-interactive commitment proof's Fiat-Shamir chain (its text: vphost.h, "The transcript chain"), shared by prover::commitFS and
+// pcParseCommitmentFS: one piece of code walks the chain on both sides.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "circuit.hpp"
+#include "field.hpp"
+#include "sha3.hpp"
+
+constexpr uint32_t PCFS_MAGIC = 0x46435056u, PCFS_VERSION = 1;      // the proof's header: "VPCF", version 1
+
+// steps 1 .. 7: the chain up to D(1, root_h), what both sides absorb before the commit phase
+inline void pcFsAbsorbHead(vph::fs_chain &ch, int n, u64 reps, u64 ms, const std::vector<F> &point, const std::vector<F> &pub_mask, const F &claim, const uint8_t root_l[32],
+                    const uint8_t root_h[32], const std::vector<F> &all_sum) {
+    const u64 n_pub = ms == 1 ? 0 : pub_mask.size();
+    ch.param((u64) n, reps, ms, n_pub);
+    ch.digest(0, root_l);
+    for (int i = 0; i < n; ++i) ch.elem(point[i].real, point[i].img);
+    for (u64 i = 0; i < n_pub; ++i) ch.elem(pub_mask[i].real, pub_mask[i].img);
+    ch.elem(claim.real, claim.img);
+    for (int i = 0; i < 65; ++i) ch.elem(all_sum[i].real, all_sum[i].img);
+    ch.digest(1, root_h);
+}
+// steps 8 and 9 on the host: r_0 = C(0); then per level D(2 + k, root_k) and, for k + 1 < ln, r_(k+1) = C(k + 1) (true: *next was drawn)
+inline F pcFsFirstChallenge(vph::fs_chain &ch) { uint64_t a, b; ch.challenge(0, a, b); F r; r.real = a; r.img = b; return r; }
+inline bool pcFsLevel(vph::fs_chain &ch, int k, int ln, const uint8_t root[32], F *next) {
+    ch.digest(2 + (u64) k, root);
+    if (k + 1 >= ln) return false;
+    uint64_t a, b;
+    ch.challenge((u64) k + 1, a, b);
+    next->real = a; next->img = b;
+    return true;
+}
+// steps 10 .. 12: the final codewords, then the positions
+inline std::vector<u64> pcFsPositions(vph::fs_chain &ch, int n, u64 reps, const std::vector<F> &final_code, const std::vector<F> &final_mask) {
+    for (const F &x : final_code) ch.elem(x.real, x.img);
+    for (const F &x : final_mask) ch.elem(x.real, x.img);
+    std::vector<u64> lf(reps);
+    for (u64 q = 0; q < reps; ++q) lf[q] = ch.position(q, n);
+    return lf;
+}

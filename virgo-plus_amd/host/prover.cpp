@@ -1,4 +1,5 @@
 #include "prover.hpp"
+#include "pc_fs.hpp"
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -536,6 +537,72 @@ std::vector<F> prover::pcMaskEvals(int n, const std::vector<F> &pub_mask, u64 ms
     std::vector<F> out(leaf0.size() * 2);
     check(vp_pc_mask_evals(ctx, n, cF(pub_mask.data()), pub_mask.size(), ms, (int) leaf0.size(), reinterpret_cast<const uint64_t *>(leaf0.data()), mF(out.data())), "vp_pc_mask_evals");
     logLaunches();
+    return out;
+}
+std::vector<uint8_t> prover::commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_draws) {
+    if (shard_pc) throw std::runtime_error("commitFS: not built for a sharded commitment");
+    const int n = C.circuit[0].bitLength, ln = n - 6;
+    if (n < 7 || (int) point.size() != n) throw std::runtime_error("commitFS: a point of n >= 7 coordinates, n the input layer's bit length");
+    if (reps < 1 || reps > 4096) throw std::runtime_error("commitFS: 1 .. 4096 repetitions");
+    const hhash_digest root_l = commit_private(pri_mask);
+    u64 ms = 1;
+    if (masked) {                                          // the padded length is public: M / the largest power of two <= M / length (poly_commit.h:55-63)
+        const u64 M = 1ull << (n - 1);
+        u64 gap = 1;
+        while (gap * 2 <= M / pri_mask.size()) gap *= 2;
+        ms = M / gap;
+    }
+    const std::vector<F> pm = masked ? pub_mask : std::vector<F>();
+    F claim;
+    std::vector<F> all_sum;
+    const hhash_digest root_h = commit_public_eq(point, pm, claim, all_sum);
+    vph::fs_chain ch;
+    pcFsAbsorbHead(ch, n, (u64) reps, ms, point, pm, claim, root_l.b, root_h.b, all_sum);
+    std::vector<uint8_t> roots(32 * (size_t) ln);
+    std::vector<F> fr((size_t) ln);
+    fs_phase_ms = 0;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    if (device_draws) {
+        uint8_t st_in[32], st_out[32];
+        memcpy(st_in, ch.s.w, 32);
+        check(vp_fri_commit_fs(ctx, st_in, roots.data(), mF(fr.data()), st_out), "vp_fri_commit_fs");
+        fs_phase_sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        fs_phase_ms = commitDeviceMs();
+        // the host's chain over the returned roots: the device's challenges and closing state must be its own
+        F r = pcFsFirstChallenge(ch);
+        for (int k = 0; k < ln; ++k) {
+            if (memcmp(&r, &fr[k], sizeof(F))) throw std::runtime_error("vp_fri_commit_fs: challenge " + std::to_string(k) + " is not the chain's");
+            pcFsLevel(ch, k, ln, &roots[32 * (size_t) k], &r);
+        }
+        if (memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_fri_commit_fs: the closing state is not the chain's");
+    } else {
+        F r = pcFsFirstChallenge(ch);
+        for (int k = 0; k < ln; ++k) {
+            fr[k] = r;
+            const hhash_digest d = friStep(r);
+            fs_phase_ms += commitDeviceMs();
+            memcpy(&roots[32 * (size_t) k], d.b, 32);
+            pcFsLevel(ch, k, ln, d.b, &r);
+        }
+        fs_phase_sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    }
+    const std::vector<F> fin = friFinal(), fm = friFinalMask();
+    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm);
+    const std::vector<uint8_t> ans = friQuery(lf);
+    std::vector<uint8_t> out;
+    auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); out.insert(out.end(), q, q + k); };
+    const uint32_t h32[4] = {PCFS_MAGIC, PCFS_VERSION, (uint32_t) n, (uint32_t) reps};
+    const uint64_t h64[2] = {ms, ms == 1 ? 0 : pm.size()};
+    put(h32, sizeof h32); put(h64, sizeof h64);
+    put(point.data(), point.size() * sizeof(F));
+    if (ms != 1) put(pm.data(), pm.size() * sizeof(F));
+    put(&claim, sizeof(F));
+    put(root_l.b, 32); put(root_h.b, 32);
+    put(all_sum.data(), 65 * sizeof(F));
+    put(roots.data(), roots.size());
+    put(fin.data(), fin.size() * sizeof(F));
+    put(fm.data(), fm.size() * sizeof(F));
+    put(ans.data(), ans.size());
     return out;
 }
 prover::hhash_digest prover::friStep(const F &r) {

@@ -103,6 +103,14 @@ public:
     void setLaunchLog(bool on) { log_launches = on; verifier_launches_.clear(); }
     void clearLaunchLog() { verifier_launches_.clear(); }
     const std::vector<vp_launch_stat> &verifierLaunches() const { return verifier_launches_; }
+    // The non-interactive commitment proof (layout and chain: vphost.h): commit_private(pri_mask), commit_public_eq(point[, pub_mask]), the FRI commit phase with
+    // every fold challenge drawn from the transcript, the final codewords, the positions drawn from the chain, and their openings (vp_fri_query) — one block
+    // of bytes that pcVerifyCommitmentFS checks with no tape and no session.  device_draws: the commit phase is vp_fri_commit_fs, the device drawing each
+    // challenge from the root it has just computed (checked here against the host's chain over the returned roots); false: the vp_fri_step loop with the chain on
+    // the host, one wait per level — a second implementation with the same bytes.  Throws on a sharded commitment (not built).
+    std::vector<uint8_t> commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_draws = true);
+    double fsPhaseSec() const { return fs_phase_sec; }      // host wall clock of the last commitFS's commit phase (step 5 alone)
+    double fsPhaseDeviceMs() const { return fs_phase_ms; }  // its device time (the levels' sum in the vp_fri_step loop)
     hhash_digest friStep(const F &r);
     std::vector<hhash_digest> friCommit(const std::vector<F> &r);   // every step in one device pass (challenges are transcript-independent)
     std::vector<F> friFinal();                           // 2048 elements, reference layout [i << 7 | slice << 1 | hi]
@@ -180,4 +188,5 @@ private:
     std::vector<vp_launch_stat> verifier_launches_;
     bool masked = false;                                 // the standing private commitment carries a non-zero mask slice
     u64 proof_size = 0;
+    double fs_phase_sec = 0, fs_phase_ms = 0;
 };

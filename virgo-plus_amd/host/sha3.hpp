@@ -55,6 +55,21 @@ inline hhash_digest hhash(const uint64_t m[4], const hhash_digest &prev) {
     return d;
 }
 
+// The Fiat-Shamir chain of proveFS / checkFS and of the non-interactive commitment proof (its text: vphost.h, "The transcript chain"): every step is
+// state = hhash(m, state) from the all-zero state.  One implementation for the prover's and the verifier's side.
+struct fs_chain {
+    hhash_digest s{};
+    void step(uint64_t a, uint64_t b, uint64_t c, uint64_t d) { const uint64_t m[4] = {a, b, c, d}; s = hhash(m, s); }
+    void param(uint64_t a, uint64_t b, uint64_t c, uint64_t d) { step(1, 0, 0, 0x50); step(a, b, c, d); }          // P(a, b, c, d)
+    void elem(uint64_t re, uint64_t im) { step(re, im, 0, 0x4d); }                                                     // E(x)
+    void digest(uint64_t label, const uint8_t d[32]) { uint64_t w[4]; memcpy(w, d, 32); step(label, 0, 0, 0x44); step(w[0], w[1], w[2], w[3]); }   // D(t, d)
+    // a digest word -> a limb: the low 61 bits, p itself mapped to 0 (the bias is 2^-61)
+    static uint64_t limb(uint64_t w) { const uint64_t P = 2305843009213693951ull; w &= P; return w == P ? 0 : w; }
+    void challenge(uint64_t c, uint64_t &re, uint64_t &im) { step(c, 0, 0, 0x43); re = limb(s.w[0]); im = limb(s.w[1]); }   // C(c)
+    // Q(q): a leaf in [2^(n-7), 2^(n-2)), the range pcVerifyCommitment accepts
+    uint64_t position(uint64_t q, int n) { step(q, 0, 0, 0x51); const uint64_t lo = 1ull << (n - 7); return lo + s.w[0] % ((1ull << (n - 2)) - lo); }
+};
+
 // Streaming SHA3-256 (FIPS 202 sponge, rate 136 bytes): the statement digest of the Fiat-Shamir mode absorbs the whole
 // serialised circuit and its input values through it (verifier::fsInit).
 class sha3_256 {

@@ -42,25 +42,19 @@ verifier::verifier(prover *pr, const layeredCircuit &cir) : p(pr), C(cir) {     
 // absorb a prover message:  block = {real, img, 0, 0x4d};  squeeze challenge number c:  block = {c, 0, 0, 0x43}, then the two
 // limbs are the first two digest words reduced to 61 bits (p itself maps to 0; the bias is 2^-61).
 void verifier::fsInit() {
-    fs_state = vph::hhash_digest{};
+    fs_state = vph::fs_chain{};
     fs_ctr = 0;
     // statement: SHA3-256 over the serialised levelised circuit, subset tables and input values (layeredCircuit::statementDigest);
     // the non-cryptographic structuralHash is a test fingerprint only and is not used here
     u64 h[4];
     C.statementDigest(h);
-    const uint64_t m[4] = {h[0], h[1], h[2], h[3]};
-    fs_state = vph::hhash(m, fs_state);
-    const uint64_t m2[4] = {(uint64_t) C.size, 0, 0, 0x53};
-    fs_state = vph::hhash(m2, fs_state);
+    fs_state.step(h[0], h[1], h[2], h[3]);
+    fs_state.step((uint64_t) C.size, 0, 0, 0x53);
 }
 F verifier::draw() {
     if (fs) {
-        const uint64_t m[4] = {fs_ctr++, 0, 0, 0x43};
-        fs_state = vph::hhash(m, fs_state);
-        const uint64_t P = 2305843009213693951ull;
-        uint64_t a = fs_state.w[0] & P, b = fs_state.w[1] & P;
-        if (a == P) a = 0;
-        if (b == P) b = 0;
+        uint64_t a, b;
+        fs_state.challenge(fs_ctr++, a, b);
         F x; x.real = a; x.img = b;
         tape_.push_back(x);
         return x;
@@ -75,8 +69,7 @@ void verifier::putF(const F &x) {
     const uint8_t *b = reinterpret_cast<const uint8_t *>(w);
     tr.insert(tr.end(), b, b + 16);
     if (fs) {
-        const uint64_t m[4] = {x.real, x.img, 0, 0x4d};
-        fs_state = vph::hhash(m, fs_state);
+        fs_state.elem(x.real, x.img);
     }
 }
 F verifier::nextF() {
@@ -847,6 +840,62 @@ int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev) {
         }
     } catch (const std::runtime_error &e) { why = e.what(); return 1; }      // a non-canonical element among the opened values
     return 0;
+}
+
+// ---- the non-interactive commitment proof: the chain's fixed parts, the parser and the verifier (no algebra here: pcVerifyCommitment decides) ----------------
+int pcParseCommitmentFS(const uint8_t *proof, u64 len, PcCommitment &c, std::string &why) {
+    auto bad = [&](const char *m) { why = m; return -1; };
+    if (!proof) return bad("no proof");
+    u64 at = 0;
+    auto have = [&](u64 k) { return k <= len - at; };            // (at <= len throughout)
+    if (!have(32)) return bad("proof shorter than its header");
+    uint32_t h32[4]; u64 h64[2];
+    memcpy(h32, proof, 16); memcpy(h64, proof + 16, 16); at = 32;
+    if (h32[0] != PCFS_MAGIC) return bad("not a commitment proof (magic)");
+    if (h32[1] != PCFS_VERSION) return bad("a commitment proof of another version");
+    const u64 n = h32[2], reps = h32[3], ms = h64[0], n_pub = h64[1];
+    if (n < 7 || n > 30) return bad("n outside 7 .. 30");
+    if (reps < 1 || reps > 4096) return bad("1 .. 4096 repetitions");
+    if (ms != 1 && (ms < 8 || (ms & (ms - 1)) || ms > (1ull << 16) || ms > (1ull << (n - 2)))) return bad("ms is neither 1 nor a power of two in [8, min(2^16, 2^(n-2))]");
+    if (ms == 1 ? n_pub != 0 : n_pub > ms) return bad("public mask longer than ms (none with the zero mask)");
+    const u64 ln = n - 6;
+    bool canon = true;
+    auto elems = [&](std::vector<F> &v, u64 k) {
+        if (!have(16 * k)) return false;
+        v.resize(k);
+        for (u64 i = 0; i < k; ++i) {
+            unsigned long long w[2]; memcpy(w, proof + at, 16); at += 16;
+            if (w[0] >= F::mod || w[1] >= F::mod) canon = false;
+            v[i].real = w[0]; v[i].img = w[1];
+        }
+        return true;
+    };
+    auto bytes = [&](uint8_t *dst, u64 k) { if (!have(k)) return false; memcpy(dst, proof + at, k); at += k; return true; };
+    c = PcCommitment{};
+    c.n = (int) n; c.ms = ms;
+    std::vector<F> claim;
+    c.fri_roots.resize(32 * ln);
+    if (!elems(c.point, n) || !elems(c.pub_mask, n_pub) || !elems(claim, 1) || !bytes(c.root_l, 32) || !bytes(c.root_h, 32) || !elems(c.all_sum, 65) ||
+        !bytes(c.fri_roots.data(), 32 * ln) || !elems(c.final_code, 2048) || !elems(c.final_mask, 32))
+        return bad("proof shorter than its sections");
+    if (!canon) return bad("non-canonical field element in the proof");
+    c.claim = claim[0];
+    c.n_bytes = pcQueryAnswerBytes((int) n, reps);
+    if (len - at != c.n_bytes) return bad("the proof does not end where the answer ends");
+    c.answer = proof + at;
+    // the challenges and positions: nobody hands them over
+    vph::fs_chain ch;
+    pcFsAbsorbHead(ch, (int) n, reps, ms, c.point, c.pub_mask, c.claim, c.root_l, c.root_h, c.all_sum);
+    c.fr.resize(ln);
+    c.fr[0] = pcFsFirstChallenge(ch);
+    for (u64 k = 0; k < ln; ++k) { F next; if (pcFsLevel(ch, (int) k, (int) ln, &c.fri_roots[32 * k], &next)) c.fr[k + 1] = next; }
+    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask);
+    return 0;
+}
+int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev) {
+    PcCommitment c;
+    if (pcParseCommitmentFS(proof, len, c, why) != 0) return -1;
+    return pcVerifyCommitment(c, why, dev);
 }
 
 // F::random() draws of fft_circuit_gkr::fft_gkr(lg) (lib/virgo/src/fft_circuit_GKR.cpp): r[lg] (:840), eval_points[64] (:84),

@@ -15,6 +15,7 @@
 #include "polynomial.hpp"
 #include "prover.hpp"
 #include "sha3.hpp"
+#include "pc_fs.hpp"
 
 class verifier {
 public:
@@ -107,7 +108,7 @@ private:
     const layeredCircuit &C;
     bool replay = false;
     bool fs = false;                                   // challenges derived from the transcript
-    vph::hhash_digest fs_state{};
+    vph::fs_chain fs_state{};
     uint64_t fs_ctr = 0;
     void fsInit();
     const std::vector<F> *rtape = nullptr;
@@ -182,6 +183,13 @@ struct PcCommitment {
 // 0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).  dev: a device context for the heavy loops (vp_pc_public_evals, vp_pc_mask_evals,
 // vp_fri_query_digests), or null for the host's; a device call that fails throws std::runtime_error.
 int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev = nullptr);
+
+// ---- the non-interactive commitment proof (layout and chain: vphost.h) ---------------------------------------------------------------------------------
+// Parses a proof under checkFull's rules (bounds on every read, canonical limbs, the proof ends where the answer ends; ms and n_pub by vph_verify_commitment's
+// rules) and derives fr and leaf0 from the chain: c is ready for pcVerifyCommitment, its answer pointing into `proof`.  0, or -1 with the reason.
+int pcParseCommitmentFS(const uint8_t *proof, u64 len, PcCommitment &c, std::string &why);
+// Parse, derive, pcVerifyCommitment unchanged: no algebra of its own.  0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).
+int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr);
 
 // verifier::checkFull (after F::init()) with pred_dev and poly_dev on a context made for the call on `device`; throws std::runtime_error without a usable device
 bool checkFullOnDevice(const layeredCircuit &c, int device, const std::vector<uint8_t> &record);

@@ -573,6 +573,52 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
     }
 }
 
+// ---- the non-interactive commitment proof (vphost.h: "The transcript chain", "Proof bytes") ----------------------------------------------------------------
+int vph_commit_fs(vph_session *s, const uint64_t *point_pairs, int n_point, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs,
+                  uint64_t n_pub_mask, int flags, uint8_t *out, uint64_t cap, uint64_t *len, char *err, int errlen) {
+    if (!s || !point_pairs || n_point < 1 || !len || (n_mask && !mask_pairs) || (n_pub_mask && !pub_mask_pairs)) { set_err(err, errlen, "vph_commit_fs: a null argument"); return -1; }
+    for (uint64_t i = 0; i < 2 * (uint64_t) n_point; ++i) if (point_pairs[i] >= F::mod) { set_err(err, errlen, "vph_commit_fs: non-canonical coordinate"); return -1; }
+    try {
+        const std::vector<uint8_t> proof = s->p->commitFS(pc_elems(point_pairs, (uint64_t) n_point), reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask),
+                                                          !(flags & VPH_FS_HOST_DRAWS));
+        *len = proof.size();
+        if (!out || cap < proof.size()) { set_err(err, errlen, "vph_commit_fs: output buffer too small (*len: the proof's size)"); return -1; }
+        memcpy(out, proof.data(), proof.size());
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+void vph_last_commit_fs_times(vph_session *s, double out[2]) { out[0] = s ? s->p->fsPhaseSec() : 0; out[1] = s ? s->p->fsPhaseDeviceMs() : 0; }
+int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen) {
+    vp_ctx *ctx = nullptr;
+    try {
+        PcCommitment c;
+        std::string why;
+        if (pcParseCommitmentFS(proof, len, c, why) != 0) { set_err(err, errlen, why); return -1; }      // malformed: before a context is made
+        if (device >= 0 && vp_create(device, &ctx) != VP_OK) { ctx = nullptr; throw std::runtime_error("vph_verify_commitment_fs: no context on the device"); }
+        const int rc = pcVerifyCommitment(c, why, ctx);
+        if (ctx) vp_destroy(ctx);
+        if (rc) set_err(err, errlen, why);
+        return rc;
+    } catch (const std::exception &e) {
+        if (ctx) vp_destroy(ctx);
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r_pairs, uint64_t *leaf0) {
+    try {
+        PcCommitment c;
+        std::string why;
+        if (!r_pairs || !leaf0 || pcParseCommitmentFS(proof, len, c, why) != 0) return -1;
+        memcpy(r_pairs, c.fr.data(), c.fr.size() * sizeof(F));
+        for (size_t q = 0; q < c.leaf0.size(); ++q) leaf0[q] = c.leaf0[q];
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+
 // fft_gkr of the last vph_prove_and_verify_full: its messages ({real,img} pairs, layout of vp_fft_gkr); returns their number or -1
 int64_t vph_last_fft_gkr(vph_session *s, uint64_t *pairs, uint64_t cap_elems) {
     if (!s || s->fft_gkr_msgs.empty() || cap_elems < s->fft_gkr_msgs.size()) return -1;

@@ -177,6 +177,54 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
                           const uint64_t *r_pairs /* n - 6 */, const uint8_t *fri_roots /* 32 (n - 6) */, const uint64_t *final_code_pairs /* 2048 */,
                           const uint64_t *final_mask_pairs /* 32 */, int reps, const uint64_t *leaf0, const uint8_t *answer, uint64_t n_bytes, int device,
                           char *err, int errlen);
+/* ---- The non-interactive commitment proof: Fiat-Shamir over the commitment by value ---------------------------------------------------------------------------
+ * One block of bytes that anyone checks with no tape and no session: the level of vph_verify_commitment, with the fold challenges and the query positions
+ * derived from the prover's own messages instead of handed over.  What it proves: that the committed vector's inner product with eq(point, .) is the claim, with
+ * the reference's soundness per repetition (no proof of work on top); the multiple-of-32 corner of h is what it is for vph_verify_commitment.  Limits: unsharded
+ * sessions, the point form of the public vector, masks within vp_commit_private_masked's limits (the verifier accepts ms <= 2^(n-6)).  Joining it to vph_prove_fs
+ * and fft_gkr into one proof of the whole protocol is the next step and not part of this.
+ *
+ * The transcript chain.  The primitive is the one of vph_prove_fs: H(m, s) = SHA3-256 of 64 bytes, four little-endian u64 words m0..m3 followed by the 32-byte
+ * state s.  The state starts as 32 zero bytes and every step is s = H(m, s), with m as follows:
+ *     P(a, b, c, d)  a parameter block: two steps, {1, 0, 0, 0x50}, then {a, b, c, d}
+ *     E(x)           a field element: {x.re, x.im, 0, 0x4d}
+ *     D(t, d)        a digest under label t: two steps, {t, 0, 0, 0x44}, then the digest's four words
+ *     C(c)           challenge number c: {c, 0, 0, 0x43}; the element is (s.w0 & P, s.w1 & P), P = 2^61 - 1, with a limb equal to P mapped to 0
+ *     Q(q)           position number q: {q, 0, 0, 0x51}; leaf0 = 2^(n-7) + (s.w0 mod (2^(n-2) - 2^(n-7))), the range vph_verify_commitment accepts
+ * With ln = n - 6 the order is:
+ *      1. P(n, reps, ms, n_pub)
+ *      2. D(0, root_l)
+ *      3. E(point[i]), i < n
+ *      4. E(pub_mask[i]), i < n_pub; n_pub = 0 when ms = 1
+ *      5. E(claim)
+ *      6. E(all_sum[i]), i < 65
+ *      7. D(1, root_h)
+ *      8. r_0 = C(0)
+ *      9. for k = 0 .. ln - 1: fold by r_k, which gives root_k; D(2 + k, root_k); for k + 1 < ln also r_(k+1) = C(k + 1)
+ *     10. E over the 2048 elements of vp_fri_final
+ *     11. E over the 32 elements of vp_fri_final_mask (zeros for the zero mask)
+ *     12. Q(q), q < reps
+ * Positions may repeat.  The point comes after root_l, so the committer cannot choose the witness after seeing it.
+ *
+ * Proof bytes, little-endian.  Header, 32 bytes: u32 magic 0x46435056 ("VPCF") | u32 version = 1 | u32 n | u32 reps | u64 ms | u64 n_pub.  Then, in this order:
+ * the point (16 n bytes) | the public mask (16 n_pub) | the claim (16) | root_l (32) | root_h (32) | all_sum (65 x 16) | the FRI roots (32 ln) | the final codeword
+ * (2048 x 16) | the final mask (32 x 16) | the answer in vp_fri_query's layout for (n, reps).
+ *
+ * vph_commit_fs: prover::commitFS on the session — commit_private(mask; null or all zero: the zero mask), commit_public_eq(point[, pub_mask]), the commit phase,
+ * the final codewords, the positions, vp_fri_query.  flags 0: the commit phase is vp_fri_commit_fs (the device draws every challenge from the root it has just
+ * computed, no host wait between the levels); VPH_FS_HOST_DRAWS: the vp_fri_step loop with the chain on the host — a second implementation, the same bytes.
+ * *len is set to the proof's size whenever it is known.  0 = done; -1 = a bad argument or cap too small (err); -2 = refused or failed (err: a sharded session,
+ * the device library's refusal of a mask, ...).  vph_last_commit_fs_times: [0] host seconds, [1] device milliseconds of the last proof's commit phase alone.
+ * vph_verify_commitment_fs: parses under vph_verify_full_record's rules (bounds on every read, canonical limbs, the proof ends where the answer ends; ms and
+ * n_pub by vph_verify_commitment's rules), derives the challenges and positions from the chain and runs vph_verify_commitment's checks unchanged (device as
+ * there).  Return codes of vph_verify_commitment: 0 accepted, 1 rejected (err: the failed check), -1 malformed (err), -2 no device.
+ * vph_commitment_fs_challenges: the derivation alone — the n - 6 challenges and the reps positions of a well-formed proof; -1 otherwise.                       */
+enum { VPH_FS_HOST_DRAWS = 1 };
+int vph_commit_fs(vph_session *, const uint64_t *point_pairs, int n_point, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs,
+                  uint64_t n_pub_mask, int flags, uint8_t *out, uint64_t cap, uint64_t *len, char *err, int errlen);
+void vph_last_commit_fs_times(vph_session *, double out[2]);
+int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen);
+int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r_pairs /* n - 6 */, uint64_t *leaf0 /* reps */);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
