@@ -417,6 +417,30 @@ int vp_fft_gkr_end(vp_ctx *, vp_F *msgs, uint64_t capacity, uint64_t *n_written)
 /* Drop a run begun with vp_fft_gkr_begin without reading its messages (the caller's pass failed between begin and end); VP_OK when none is pending.
  * vp_fft_gkr_begin itself drains and drops a run that was never collected, so a failed pass cannot wedge the context. */
 int vp_fft_gkr_cancel(vp_ctx *);
+/* fft_gkr NON-INTERACTIVE: the same circuit, message layout and tape layout, but the tape is not an argument — the device draws every slot from the
+ * Fiat-Shamir chain (host/vphost.h, "The transcript chain": steps E and C; a slot's counter is its index in the tape layout) as soon as the messages it
+ * depends on exist, and returns the tape it drew.  From state_in:
+ *     r[i] = C(slot), i < lg; x[i] = C(slot), i < 64; E(O[i]), i < 64; every slot of r_0 and of r_1 = C(slot) (lg + 10 each);
+ *     addition layer: per round k < lg + 6: E(a), E(b), E(c), r_u[k] = C(slot); E(v_u); every r_v[k] = C(slot) (they multiply beta = 0: don't-cares that
+ *     fft_gkr_check still reads);  multiplication layer: the same with lg rounds;
+ *     per inverse-FFT depth: phase 1 per round E(a), E(b), E(c), r_u[k] = C(slot); E(v_u); phase 2 per round E(a), E(b), E(c), r_v[k] = C(slot); E(v_v);
+ *     alpha = C(slot), beta = C(slot).
+ * A draw never precedes the polynomial it challenges, so the rounds cannot share launches as in vp_fft_gkr: while a sumcheck's tables have more than
+ * 2^VP_FFT_GKR_FS_TAIL_LOG entries a round is one launch over every workgroup (fold by the challenge in its tape slot + the round's sums) and a closing launch
+ * of one workgroup (polynomial, absorb, draw); from 2^VP_FFT_GKR_FS_TAIL_LOG entries on ONE launch of one workgroup keeps V, M and A in LDS (3 tables x 16 bytes
+ * x 2^11 = 96 KB of the 160 KB) and runs every round that is left.  The inverse-FFT depths run one after the other (fft_gkr_batched does not apply).  Nothing
+ * waits on the host between the first draw and the one pinned copy that returns msgs, tape_out and the closing state.
+ * msgs: capacity >= n_msgs, tape_out: n_tape elements (vp_fft_gkr_sizes).  lg in 1..19 (VP_ELIMIT outside); a null argument, a recording plan and a pending
+ * vp_fft_gkr_begin are VP_EINVAL; every refusal comes before the first launch and leaves the context as it was.
+ * vp_get_stats after the call: rounds = the 2 lg^2 + 2 lg + 6 rounds, launches = the drawing, round, closing and tail launches (the circuit and table kernels between
+ * them, unchanged from vp_fft_gkr, are not counted).
+ * Launch table (vp_set_profiling(1); at most 694 rows, at lg = 19, of the 1 024 a call can log); no kernel ids of its own: the draws alone (k_fg_fs_draw, two launches) are VP_K_MERKLE rows with work = chain steps, as
+ * vp_fri_commit_fs logs its drawing tree top; a round above the tail (k_fg_fs_round) is a VP_K_ROUND row (jobs = 1, rounds = 1, first_round = the round,
+ * work = pairs), its closing launch (k_fg_fs_close) a VP_K_EMIT row (rounds = 1, work = 4 chain steps); the tail (k_fg_fs_tail) is a VP_K_SEG row (rounds = the
+ * rounds it runs, first_round = its first, work = chain steps).  Rows follow the sumchecks' order: addition, multiplication, depth 0 phase 1, phase 2, ...   */
+#define VP_FFT_GKR_FS_TAIL_LOG 11
+int vp_fft_gkr_fs(vp_ctx *, int lg, const uint8_t state_in[32], vp_F *msgs, uint64_t capacity, uint64_t *n_written,
+                  vp_F *tape_out /* vp_fft_gkr_sizes' n_tape */, uint8_t state_out[32]);
 /* ---- the mask slice with CONTENT (round 6) ------------------------------------------------------------------------------------------------
  * lib/virgo's commit_private_array / commit_public_array take a mask vector that fills the 65th slice (lib/virgo/src/poly_commit.h:42,55-86,138-161,187-247).
  * The reference's own prover and verifier only ever pass one zero (src/prover.cpp:526, src/verifier.cpp:375-377): vp_commit_private / vp_commit_public.  These

@@ -31,7 +31,7 @@ GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vp
     os.path.join(ROOT, "include", "vpgpu.h")]
 HOST_SRC = [os.path.join(HOST, f) for f in ("circuit.cpp", "prover.cpp", "verifier.cpp", "vphost.cpp")]
 HOST_HDR = [os.path.join(HOST, f) for f in ("circuit.hpp", "prover.hpp", "verifier.hpp", "vphost.h", "field.hpp",
-                                              "polynomial.hpp", "sha3.hpp", "pc_fs.hpp")]
+                                              "polynomial.hpp", "sha3.hpp", "pc_fs.hpp", "fft_gkr_fs.hpp", "fft_gkr_verify.hpp")]
 
 
 def _stale(target, sources):
@@ -139,6 +139,7 @@ def lib_gpu():
         L.vp_fft_gkr_begin.argtypes = [vp, ctypes.c_int, vp, u64_]
         L.vp_fft_gkr_end.argtypes = [vp, vp, u64_, vp]
         L.vp_fft_gkr_cancel.argtypes = [vp]
+        L.vp_fft_gkr_fs.argtypes = [vp, ctypes.c_int, vp, vp, u64_, vp, vp, vp]
         L.vp_options_default.restype = None
         L.vp_destroy.argtypes = [vp]
         L.vp_last_error.argtypes = [vp]
@@ -259,6 +260,11 @@ def lib_host():
         L.vph_last_commit_fs_times.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         L.vph_verify_commitment_fs.argtypes = [vp, u64, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_commitment_fs_challenges.argtypes = [vp, u64, vp, vp]
+        L.vph_prove_full_fs.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_verify_full_fs.argtypes = [vp, vp, u64, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_fft_gkr_fs_tape.argtypes = [ctypes.c_int, vp, vp, u64, vp, vp]
+        L.vph_fft_gkr_check.argtypes = [ctypes.c_int, vp, u64, vp, u64]
+        L.vph_fft_gkr_fs.argtypes = [vp, ctypes.c_int, vp, vp, u64, vp, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_last_full_record.argtypes = [vp, vp, u64, ctypes.POINTER(u64)]
         L.vph_verify_full_record.argtypes = [vp, vp, u64]
         L.vph_verifier_launches.argtypes = [vp, ctypes.POINTER(LaunchStat), ctypes.c_int]
@@ -781,6 +787,53 @@ class Circuit:
             raise ValueError("commitment_fs_challenges: malformed proof")
         return r, [int(x) for x in lf]
 
+    def verify_full_fs(self, proof, device=None, return_point=False):
+        """Verify a joined non-interactive proof of the whole protocol (Session.prove_full_fs; chain and layout: host/vphost.h, "The joined proof") holding only this
+        circuit: no tape, no session, no input values.  device=k: the commitment's heavy loops on GPU k.  Returns (accepted, reason) — with return_point also the
+        derived point as an (n, 2) uint64 array (a rejected GKR part: as far as its replay got); raises ValueError on a malformed proof and RuntimeError without the device."""
+        import numpy as np
+        proof = bytes(proof)
+        buf = ctypes.create_string_buffer(proof, max(len(proof), 1))
+        err = ctypes.create_string_buffer(512)
+        n = self.layer_bitlen(0)
+        pt = np.full((max(n, 1), 2), (1 << 64) - 1, np.uint64)
+        rc = lib_host().vph_verify_full_fs(self.h, ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), pt.ctypes.data, err, len(err))
+        if rc == -1:
+            raise ValueError("verify_full_fs: " + err.value.decode())
+        if rc < 0:
+            raise RuntimeError("verify_full_fs: " + err.value.decode())
+        out = (rc == 0, err.value.decode() if rc else "")
+        return out + (None if int(pt[0, 0]) == (1 << 64) - 1 else pt,) if return_point else out
+
+    @staticmethod
+    def fft_gkr_fs_tape(lg, state, msgs):
+        """fft_gkr's part of the Fiat-Shamir chain, the derivation alone (vph_fft_gkr_fs_tape, host/vphost.h): from the 32-byte chain state and the messages
+        of fft_gkr(lg) in vp_fft_gkr's layout, the tape the device drew as an (n_tape, 2) uint64 array and the closing state.  No GPU.  Raises ValueError on
+        lg outside 1..19, a wrong message count or a non-canonical limb."""
+        import numpy as np
+        state = bytes(state)
+        m = np.ascontiguousarray(msgs, dtype=np.uint64).reshape(-1, 2)
+        lg = int(lg)
+        if len(state) != 32 or not 1 <= lg <= 19:
+            raise ValueError("fft_gkr_fs_tape: bad arguments")
+        tape = np.zeros((2 * lg * lg + 9 * lg + 96, 2), np.uint64)
+        st_in, st_out = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32)
+        if lib_host().vph_fft_gkr_fs_tape(lg, ctypes.cast(st_in, ctypes.c_void_p), m.ctypes.data, m.shape[0], tape.ctypes.data, ctypes.cast(st_out, ctypes.c_void_p)):
+            raise ValueError("fft_gkr_fs_tape: malformed messages")
+        return tape, st_out.raw
+
+    @staticmethod
+    def fft_gkr_check(lg, tape, msgs):
+        """The host verifier of fft_gkr (fft_gkr_check, host/fft_gkr_verify.hpp) on a tape and messages by value: True iff every check holds.  Raises
+        ValueError on malformed arrays."""
+        import numpy as np
+        t = np.ascontiguousarray(tape, dtype=np.uint64).reshape(-1, 2)
+        m = np.ascontiguousarray(msgs, dtype=np.uint64).reshape(-1, 2)
+        rc = lib_host().vph_fft_gkr_check(int(lg), t.ctypes.data, t.shape[0], m.ctypes.data, m.shape[0])
+        if rc < 0:
+            raise ValueError("fft_gkr_check: malformed tape or messages")
+        return rc == 0
+
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
         buf = ctypes.create_string_buffer(bytes(proof), len(proof))
@@ -1190,6 +1243,51 @@ class Session:
         if rc:
             raise RuntimeError("commit_fs failed: " + err.value.decode())
         return buf.raw[: ln.value]
+
+    def prove_full_fs(self, reps=33, mask=None, pub_mask=None, return_point=False):
+        """The joined non-interactive proof of the whole protocol on the session's circuit and input (vph_prove_full_fs, host/vphost.h): commit_private(mask), the GKR
+        part as prove_fs with the input check left to the commitment, commit_public_eq at the derived point, fft_gkr with its challenges drawn on the device, the
+        FRI commit phase, final codewords, derived positions and their openings, on one Fiat-Shamir chain — one block of bytes for Circuit.verify_full_fs.
+        Not on a sharded session."""
+        import numpy as np
+        arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 2)
+        m, pm = arr(mask), arr(pub_mask)
+        ptr = lambda a: a.ctypes.data if a is not None and a.shape[0] else None
+        cnt = lambda a: 0 if a is None else a.shape[0]
+        err = ctypes.create_string_buffer(512)
+        ln = ctypes.c_uint64(0)
+        pt = np.zeros((32, 2), np.uint64)
+        cap = 1 << 22
+        for _ in range(2):                                     # a proof larger than the first buffer: the call reports its size and is made again
+            buf = ctypes.create_string_buffer(cap)
+            rc = lib_host().vph_prove_full_fs(self.h, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), pt.ctypes.data,
+                                              err, len(err))
+            if rc != -1 or ln.value <= cap:
+                break
+            cap = ln.value
+        if rc:
+            raise RuntimeError("prove_full_fs failed: " + err.value.decode())
+        proof = buf.raw[: ln.value]
+        import struct
+        return (proof, pt[:struct.unpack_from("<I", proof, 8)[0]].copy()) if return_point else proof
+
+    def fft_gkr_fs(self, lg, state):
+        """fft_gkr(lg) non-interactive on the session's GPU (vp_fft_gkr_fs, include/vpgpu.h): every challenge is drawn on the device from the Fiat-Shamir chain
+        that starts at the 32-byte `state`.  Returns (msgs, tape, state_out): the messages and the tape drawn as (n, 2) uint64 arrays, the closing state as
+        bytes.  The host re-derives the tape and the state from the messages and raises if the device's differ."""
+        import numpy as np
+        state, lg = bytes(state), int(lg)
+        if len(state) != 32 or not 1 <= lg <= 19:
+            raise ValueError("fft_gkr_fs: lg in 1..19 and a 32-byte state")
+        msgs = np.zeros((84 + 6 * lg * lg + 8 * lg, 2), np.uint64)
+        tape = np.zeros((2 * lg * lg + 9 * lg + 96, 2), np.uint64)
+        st_in, st_out = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_fft_gkr_fs(self.h, lg, ctypes.cast(st_in, ctypes.c_void_p), msgs.ctypes.data, msgs.shape[0], tape.ctypes.data,
+                                       ctypes.cast(st_out, ctypes.c_void_p), err, len(err))
+        if rc:
+            raise RuntimeError("fft_gkr_fs failed: " + err.value.decode())
+        return msgs, tape, st_out.raw
 
     def last_commit_fs_times(self):
         """(host seconds, device milliseconds) of the last commit_fs's commit phase alone"""

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "vp_field.h"
 #include "vp_kernels_round.h"
+#include "vp_kernels_pc.h"
 
 namespace vp {
 
@@ -199,6 +200,163 @@ __global__ void __launch_bounds__(VP_BLOCK) k_fg_ifft_multi(const FgIfftJob *__r
         jb.M[v] = f_mul(f_mul(f_sub(t1, t2), e), winv[k << dep]);
         jb.A[v] = f_mul(f_mul(f_add(t1, t2), e), *jb.vu);
         jb.M[u] = f_zero(); jb.A[u] = f_zero();
+    }
+}
+
+// ---- vp_fft_gkr_fs: the sumchecks with every challenge drawn on the device (the chain's text: host/vphost.h) -------------------------------------
+// A challenge depends on the polynomial before it, so the rounds cannot share a launch the way k_sumfold3b / k_seg share them: a round is one launch on
+// every workgroup (k_fg_fs_round: fold by the challenge in its tape slot, sum the round's (a, b, c) into per-workgroup partials) and a closing launch on one
+// workgroup (k_fg_fs_close: sum the partials, write the polynomial, absorb it, draw), until the tables fit LDS; from there one launch of one workgroup runs
+// every round that is left (k_fg_fs_tail).  The chain itself is one lane's work (fs_absorb_draw's form: a dependent Keccak-f per step).
+constexpr int fg_fs_log2_floor(size_t x) { return x <= 1 ? 0 : 1 + fg_fs_log2_floor(x >> 1); }
+constexpr int FG_FS_TABLES = 3;                                                   // V, M and (inverse-FFT layers) A
+constexpr size_t FG_FS_LDS = 160 * 1024;                                          // per workgroup on gfx950
+constexpr int FG_FS_TAIL_LOG = fg_fs_log2_floor((FG_FS_LDS - 1024) / (FG_FS_TABLES * sizeof(F)));      // 1 KB kept for the reduction scratch and the challenge
+#ifdef VP_FFT_GKR_FS_TAIL_LOG
+static_assert(FG_FS_TAIL_LOG == VP_FFT_GKR_FS_TAIL_LOG, "include/vpgpu.h: VP_FFT_GKR_FS_TAIL_LOG");
+#endif
+constexpr u32 FG_FS_TAIL_N = 1u << FG_FS_TAIL_LOG;
+constexpr int FG_FS_TAIL_PER = (int) (FG_FS_TAIL_N / 2 / VP_BLOCK) > 0 ? (int) (FG_FS_TAIL_N / 2 / VP_BLOCK) : 1;      // fold outputs per thread and table
+
+__device__ __noinline__ Dig fg_fs_step(u64 m0, u64 m1, u64 m2, u64 m3, Dig s) { return hhash64(m0, m1, m2, m3, s); }
+__device__ __forceinline__ Dig fg_fs_elem(const Dig &s, const F &x) { return fg_fs_step(x.re, x.im, 0, 0x4d, s); }                 // E(x)
+__device__ __forceinline__ Dig fg_fs_challenge(const Dig &s, u64 counter, F *out) {                                                // C(counter)
+    const Dig t = fg_fs_step(counter, 0, 0, 0x43, s);
+    *out = f_make(fs_limb(t.w[0]), fs_limb(t.w[1]));
+    return t;
+}
+// One lane: E(absorb[i]), i < n_absorb, then tape[slot] = C(slot) for first <= slot < first + count.
+__global__ void k_fg_fs_draw(Dig *state, const F *__restrict__ absorb, u32 n_absorb, F *__restrict__ tape, u32 first, u32 count) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Dig s = *state;
+    for (u32 i = 0; i < n_absorb; ++i) s = fg_fs_elem(s, absorb[i]);
+    for (u32 k = first; k < first + count; ++k) { F r; s = fg_fs_challenge(s, k, &r); tape[k] = r; }
+    *state = s;
+}
+// one pair of one round: (m0 + t dm)(v0 + t dv) + a0 + t da, summed into acc = (a, b, c) of a t^2 + b t + c
+template <bool HAS_A>
+__device__ __forceinline__ void fg_fs_pair(const F &v0, const F &v1, const F &m0, const F &m1, const F &a0, const F &a1, F (&acc)[3]) {
+    const F dv = f_sub(v1, v0), dm = f_sub(m1, m0);
+    acc[0] = f_add(acc[0], f_mul(dm, dv));
+    F b = f_dot2cc<VP_MADSHIFT != 0>(dm, v0, m0, dv), c = f_mul(m0, v0);
+    if (HAS_A) { b = f_add(b, f_sub(a1, a0)); c = f_add(c, a0); }
+    acc[1] = f_add(acc[1], b);
+    acc[2] = f_add(acc[2], c);
+}
+// A round above the tail.  fold = 0 (round 1): the tables are read as they are, n entries each.  fold = 1: entry i of the out tables is the pair (2 i, 2 i + 1) of
+// the in tables folded by *r (the challenge of the round before, in its tape slot), n entries come out.  Either way the n / 2 pairs of the n entries are summed:
+// part[3 b .. 3 b + 3) = workgroup b's share of (a, b, c).
+struct FgFsRound { const F *inV, *inM, *inA; F *outV, *outM, *outA; const F *r; F *part; u32 n; int fold; };
+template <bool HAS_A>
+__global__ void __launch_bounds__(VP_BLOCK) k_fg_fs_round(FgFsRound a) {
+    __shared__ F lds[12];
+    F acc[3] = {f_zero(), f_zero(), f_zero()};
+    const u32 pairs = a.n >> 1;
+    const F r = a.fold ? *a.r : f_zero();
+    for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += gridDim.x * blockDim.x) {
+        F v0, v1, m0, m1, a0 = f_zero(), a1 = f_zero();
+        if (a.fold) {
+            const size_t q = (size_t) 4 * i;
+            v0 = fold_entry(a.inV[q], a.inV[q + 1], r); v1 = fold_entry(a.inV[q + 2], a.inV[q + 3], r);
+            m0 = fold_entry(a.inM[q], a.inM[q + 1], r); m1 = fold_entry(a.inM[q + 2], a.inM[q + 3], r);
+            a.outV[2 * (size_t) i] = v0; a.outV[2 * (size_t) i + 1] = v1;
+            a.outM[2 * (size_t) i] = m0; a.outM[2 * (size_t) i + 1] = m1;
+            if (HAS_A) {
+                a0 = fold_entry(a.inA[q], a.inA[q + 1], r); a1 = fold_entry(a.inA[q + 2], a.inA[q + 3], r);
+                a.outA[2 * (size_t) i] = a0; a.outA[2 * (size_t) i + 1] = a1;
+            }
+        } else {
+            const size_t q = (size_t) 2 * i;
+            v0 = a.inV[q]; v1 = a.inV[q + 1]; m0 = a.inM[q]; m1 = a.inM[q + 1];
+            if (HAS_A) { a0 = a.inA[q]; a1 = a.inA[q + 1]; }
+        }
+        fg_fs_pair<HAS_A>(v0, v1, m0, m1, a0, a1, acc);
+    }
+    block_sum<3>(acc, lds);
+    if (threadIdx.x == 0) { a.part[3 * blockIdx.x] = acc[0]; a.part[3 * blockIdx.x + 1] = acc[1]; a.part[3 * blockIdx.x + 2] = acc[2]; }
+}
+// The round's closing step, one workgroup: the polynomial = the sum of the nb partials -> poly[0..3); E(a), E(b), E(c); tape[slot] = C(slot).
+__global__ void __launch_bounds__(VP_BLOCK) k_fg_fs_close(const F *__restrict__ part, u32 nb, F *__restrict__ poly, Dig *state, F *__restrict__ tape, u32 slot) {
+    __shared__ F lds[12];
+    F acc[3] = {f_zero(), f_zero(), f_zero()};
+    for (u32 b = threadIdx.x; b < nb; b += blockDim.x) { acc[0] = f_add(acc[0], part[3 * b]); acc[1] = f_add(acc[1], part[3 * b + 1]); acc[2] = f_add(acc[2], part[3 * b + 2]); }
+    block_sum<3>(acc, lds);
+    if (threadIdx.x == 0) {
+        Dig s = *state;
+        for (int t = 0; t < 3; ++t) { poly[t] = acc[t]; s = fg_fs_elem(s, acc[t]); }
+        F r; s = fg_fs_challenge(s, slot, &r);
+        tape[slot] = r;
+        *state = s;
+    }
+}
+// The tail of a sumcheck (or all of it), one workgroup, tables of n = 2^rounds <= 2^FG_FS_TAIL_LOG entries in LDS.  r_fold null: the tables are read as they are;
+// else entry i is the pair (2 i, 2 i + 1) of the in tables folded by *r_fold.  Per round k < rounds: (a, b, c) -> poly[3 k ..), E(a), E(b), E(c),
+// tape[slot0 + k] = C(slot0 + k), the workgroup folds by it.  Then v = V[0] -> poly[3 rounds], E(v), and tape[slot] = C(slot) for the n_extra slots from extra0
+// (the one-phase layers' r_v; alpha and beta behind a depth's second phase).
+// Launch contract: ONE workgroup of VP_BLOCK threads (block_sum and the in-place fold are written for it), n = 2^rounds <= 2^FG_FS_TAIL_LOG, dynamic LDS of
+// FG_FS_TABLES * sizeof(F) * n bytes; a launch outside it does nothing.
+static_assert(FG_FS_TAIL_PER * VP_BLOCK * 2 >= (int) FG_FS_TAIL_N, "k_fg_fs_tail: a thread folds FG_FS_TAIL_PER pairs per table");
+struct FgFsTail { const F *inV, *inM, *inA, *r_fold; F *poly; Dig *state; F *tape; u32 n, slot0, extra0, n_extra; int rounds; };
+template <bool HAS_A>
+__global__ void __launch_bounds__(VP_BLOCK) k_fg_fs_tail(FgFsTail a) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    __shared__ F lds[12];
+    __shared__ F s_r;
+    if (blockDim.x != VP_BLOCK || blockIdx.x != 0 || a.n > FG_FS_TAIL_N || a.n != (1u << a.rounds)) return;      // the launch contract above
+    F *V = reinterpret_cast<F *>(smem_raw), *M = V + a.n, *A = M + a.n;
+    const F rf = a.r_fold ? *a.r_fold : f_zero();
+    for (u32 i = threadIdx.x; i < a.n; i += blockDim.x) {
+        if (a.r_fold) {
+            V[i] = fold_entry(a.inV[2 * (size_t) i], a.inV[2 * (size_t) i + 1], rf);
+            M[i] = fold_entry(a.inM[2 * (size_t) i], a.inM[2 * (size_t) i + 1], rf);
+            if (HAS_A) A[i] = fold_entry(a.inA[2 * (size_t) i], a.inA[2 * (size_t) i + 1], rf);
+        } else {
+            V[i] = a.inV[i]; M[i] = a.inM[i];
+            if (HAS_A) A[i] = a.inA[i];
+        }
+    }
+    __syncthreads();
+    Dig s;
+    if (threadIdx.x == 0) s = *a.state;
+    u32 len = a.n;
+    for (int k = 0; k < a.rounds; ++k, len >>= 1) {
+        const u32 pairs = len >> 1;
+        F acc[3] = {f_zero(), f_zero(), f_zero()};
+        for (u32 i = threadIdx.x; i < pairs; i += blockDim.x)
+            fg_fs_pair<HAS_A>(V[2 * i], V[2 * i + 1], M[2 * i], M[2 * i + 1], HAS_A ? A[2 * i] : f_zero(), HAS_A ? A[2 * i + 1] : f_zero(), acc);
+        block_sum<3>(acc, lds);
+        if (threadIdx.x == 0) {
+            for (int t = 0; t < 3; ++t) { a.poly[3 * k + t] = acc[t]; s = fg_fs_elem(s, acc[t]); }
+            F r; s = fg_fs_challenge(s, a.slot0 + k, &r);
+            a.tape[a.slot0 + k] = r;
+            s_r = r;
+        }
+        __syncthreads();
+        const F r = s_r;
+        // in place: every thread reads its pairs, the workgroup meets, every thread writes
+        F o[FG_FS_TABLES][FG_FS_TAIL_PER];
+#pragma unroll
+        for (int j = 0; j < FG_FS_TAIL_PER; ++j) {
+            const u32 i = threadIdx.x + j * VP_BLOCK;
+            if (i < pairs) {
+                o[0][j] = fold_entry(V[2 * i], V[2 * i + 1], r); o[1][j] = fold_entry(M[2 * i], M[2 * i + 1], r);
+                if (HAS_A) o[2][j] = fold_entry(A[2 * i], A[2 * i + 1], r);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < FG_FS_TAIL_PER; ++j) {
+            const u32 i = threadIdx.x + j * VP_BLOCK;
+            if (i < pairs) { V[i] = o[0][j]; M[i] = o[1][j]; if (HAS_A) A[i] = o[2][j]; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const F v = V[0];
+        a.poly[3 * a.rounds] = v;
+        s = fg_fs_elem(s, v);
+        for (u32 q = a.extra0; q < a.extra0 + a.n_extra; ++q) { F r; s = fg_fs_challenge(s, q, &r); a.tape[q] = r; }
+        *a.state = s;
     }
 }
 

@@ -26,6 +26,7 @@ struct FgkState {
     int lg = 0;
     F *B = nullptr, *S = nullptr, *Pm = nullptr, *winv = nullptr, *sq = nullptr, *xsq = nullptr, *g = nullptr, *eu = nullptr, *hi = nullptr, *part = nullptr, *xt = nullptr;
     F *tape = nullptr, *msgs = nullptr;
+    Dig *fs_state = nullptr; F *fs_part = nullptr;      // vp_fft_gkr_fs: the chain's state (behind msgs and tape, one block), per-workgroup sums of a round
     Lane lane;
     std::vector<void *> allocs;
     // asynchronous form (vp_fft_gkr_begin / _end): a stream and an event pair of its own, host copies that outlive the call
@@ -68,12 +69,18 @@ int fgk_prepare(vp_ctx *ctx, int lg) {
     VPCHK(fgk_alloc(ctx, s, &s.B, (size_t) (lg + 1) * N)); VPCHK(fgk_alloc(ctx, s, &s.S, N)); VPCHK(fgk_alloc(ctx, s, &s.Pm, 64 * N));
     VPCHK(fgk_alloc(ctx, s, &s.winv, std::max<size_t>(1, N / 2))); VPCHK(fgk_alloc(ctx, s, &s.sq, 32)); VPCHK(fgk_alloc(ctx, s, &s.xsq, (size_t) 64 * lg)); VPCHK(fgk_alloc(ctx, s, &s.xt, ((size_t) 64 << std::min(lg, 9)) + ((size_t) 64 << (lg - std::min(lg, 9)))));
     VPCHK(fgk_alloc(ctx, s, &s.g, N)); VPCHK(fgk_alloc(ctx, s, &s.eu, N)); VPCHK(fgk_alloc(ctx, s, &s.hi, 64)); VPCHK(fgk_alloc(ctx, s, &s.part, (size_t) 64 * nblk(N)));
-    VPCHK(fgk_alloc(ctx, s, &s.tape, o.n)); VPCHK(fgk_alloc(ctx, s, &s.msgs, FgkOffsets::n_msgs(lg)));
+    // messages | tape | the chain's state in one block: vp_fft_gkr_fs returns all three in one copy
+    VPCHK(fgk_alloc(ctx, s, &s.msgs, FgkOffsets::n_msgs(lg) + o.n + 2));
+    s.tape = s.msgs + FgkOffsets::n_msgs(lg); s.fs_state = reinterpret_cast<Dig *>(s.tape + o.n);
+    VPCHK(fgk_alloc(ctx, s, &s.fs_part, (size_t) 3 * MAX_BLOCKS));
     HIPCHK(hipHostMalloc((void **) &s.h_tape, (o.n + 32) * sizeof(F), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **) &s.h_msgs, FgkOffsets::n_msgs(lg) * sizeof(F), hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void **) &s.h_msgs, (FgkOffsets::n_msgs(lg) + o.n + 2) * sizeof(F), hipHostMallocDefault));
     for (int b = 0; b < 2; ++b)
         for (int t = 0; t < 3; ++t) VPCHK(fgk_alloc(ctx, s, &s.lane.tab[b][t], t == 2 ? N : 64 * N));     // the add table exists only in the 2^lg-entry sumchecks
     VPCHK(fgk_alloc(ctx, s, &s.lane.part2, (size_t) 16 * MAX_BLOCKS * 3));
+    // vp_fft_gkr_fs: its tail kernel holds up to 96 KB of tables in dynamic LDS (once per set of buffers, off the per-call path)
+    HIPCHK(hipFuncSetAttribute((const void *) k_fg_fs_tail<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (FG_FS_TABLES * sizeof(F) * FG_FS_TAIL_N)));
+    HIPCHK(hipFuncSetAttribute((const void *) k_fg_fs_tail<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (FG_FS_TABLES * sizeof(F) * FG_FS_TAIL_N)));
     s.lane.stream = ctx->stream;
     s.lg = lg;
     return VP_OK;
@@ -173,6 +180,28 @@ int vp_fft_gkr_sizes(int lg, uint64_t *n_tape, uint64_t *n_msgs) {
     return VP_OK;
 }
 
+// the circuit (build_circuit, :22-101) from the r and x slots of s.tape, in stream order: every layer, the products, the 64 outputs -> s.msgs[0..64)
+static int fgk_circuit(vp_ctx *ctx, FgkState &s, int lg, hipStream_t st) {
+    const FgkOffsets o(lg);
+    const u32 N = 1u << lg;
+    {
+        F w = host_pow(host_root_of_unity(lg), (unsigned __int128) P61 * P61 - 2);                 // inv_rou (:36)
+        F *sq_host = s.h_tape + o.n;
+        for (int b = 0; b < 32; ++b) { sq_host[b] = w; w = f_mul(w, w); }
+        HIPCHK(hipMemcpyAsync(s.sq, sq_host, 32 * sizeof(F), hipMemcpyHostToDevice, st));
+    }
+    const F inv_n = host_inv_real((u64) N);
+    hipLaunchKernelGGL(k_fg_pows, dim3(nblk(std::max<u32>(1, N / 2))), dim3(VP_BLOCK), 0, st, (const F *) s.sq, std::max(0, lg - 1), std::max<u32>(1, N / 2), s.winv);
+    hipLaunchKernelGGL(k_fg_expand, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.r), lg, s.B);
+    for (int t = 1; t <= lg; ++t)
+        hipLaunchKernelGGL(k_fg_butterfly, dim3(nblk(N / 2)), dim3(VP_BLOCK), 0, st, (const F *) (s.B + (size_t) (t - 1) * N), s.B + (size_t) t * N,
+                           (const F *) s.winv, lg, lg - t, t == lg ? s.S : (F *) nullptr, inv_n);
+    hipLaunchKernelGGL(k_fg_xsq, dim3(1), dim3(64), 0, st, (const F *) (s.tape + o.x), lg, s.xsq);
+    hipLaunchKernelGGL(k_fg_xtab, dim3(nblk((64u << std::min(lg, 9)) + (64u << (lg - std::min(lg, 9))))), dim3(VP_BLOCK), 0, st, (const F *) s.xsq, lg, s.xt);
+    hipLaunchKernelGGL(k_fg_polyeval, dim3(nblk(N), 64), dim3(VP_BLOCK), 0, st, (const F *) s.S, (const F *) s.xt, lg, s.Pm, s.part);
+    hipLaunchKernelGGL(k_fg_rowsum, dim3(64), dim3(VP_BLOCK), 0, st, (const F *) s.part, nblk(N), s.msgs);
+    return VP_OK;
+}
 // everything of vp_fft_gkr up to (not including) the wait, on stream `st` (the context's own, or FgkState::own_stream for the asynchronous form)
 static int fgk_enqueue(vp_ctx *ctx, int lg, const vp_F *tape, uint64_t n_tape, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
     const FgkOffsets o(lg);
@@ -188,23 +217,7 @@ static int fgk_enqueue(vp_ctx *ctx, int lg, const vp_F *tape, uint64_t n_tape, h
     memcpy(s.h_tape, tape, n_tape * sizeof(F));                   // the caller's buffer may go away before the copy runs
     HIPCHK(hipMemcpyAsync(s.tape, s.h_tape, n_tape * sizeof(F), hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(e0, st));
-    // ---- the circuit (build_circuit, :22-101)
-    {
-        F w = host_pow(host_root_of_unity(lg), (unsigned __int128) P61 * P61 - 2);                 // inv_rou (:36)
-        F *sq_host = s.h_tape + n_tape;
-        for (int b = 0; b < 32; ++b) { sq_host[b] = w; w = f_mul(w, w); }
-        HIPCHK(hipMemcpyAsync(s.sq, sq_host, 32 * sizeof(F), hipMemcpyHostToDevice, st));
-    }
-    const F inv_n = host_inv_real((u64) N);
-    hipLaunchKernelGGL(k_fg_pows, dim3(nblk(std::max<u32>(1, N / 2))), dim3(VP_BLOCK), 0, st, (const F *) s.sq, std::max(0, lg - 1), std::max<u32>(1, N / 2), s.winv);
-    hipLaunchKernelGGL(k_fg_expand, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.r), lg, s.B);
-    for (int t = 1; t <= lg; ++t)
-        hipLaunchKernelGGL(k_fg_butterfly, dim3(nblk(N / 2)), dim3(VP_BLOCK), 0, st, (const F *) (s.B + (size_t) (t - 1) * N), s.B + (size_t) t * N,
-                           (const F *) s.winv, lg, lg - t, t == lg ? s.S : (F *) nullptr, inv_n);
-    hipLaunchKernelGGL(k_fg_xsq, dim3(1), dim3(64), 0, st, (const F *) (s.tape + o.x), lg, s.xsq);
-    hipLaunchKernelGGL(k_fg_xtab, dim3(nblk((64u << std::min(lg, 9)) + (64u << (lg - std::min(lg, 9))))), dim3(VP_BLOCK), 0, st, (const F *) s.xsq, lg, s.xt);
-    hipLaunchKernelGGL(k_fg_polyeval, dim3(nblk(N), 64), dim3(VP_BLOCK), 0, st, (const F *) s.S, (const F *) s.xt, lg, s.Pm, s.part);
-    hipLaunchKernelGGL(k_fg_rowsum, dim3(64), dim3(VP_BLOCK), 0, st, (const F *) s.part, nblk(N), s.msgs);
+    VPCHK(fgk_circuit(ctx, s, lg, st));
     u64 pos = 64;
     // ---- addition layer (:190-309): claim point r_0[0..6), alpha = 1, beta = 0
     hipLaunchKernelGGL(k_fg_gtab, dim3(1), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.r0), (const F *) nullptr, 6, (const F *) nullptr, (const F *) nullptr, s.hi);
@@ -340,6 +353,124 @@ int vp_fft_gkr_cancel(vp_ctx *ctx) {
     return VP_OK;
 }
 
+// ---- vp_fft_gkr_fs: every challenge drawn on the device (include/vpgpu.h; kernels: vp_kernels_fftgkr.h) ----------------------------------------------------
+// One sumcheck over 2^rounds entries: V of round 1 is V0 (read only: a circuit layer), M and A are s.lane.tab[0][1 / 2].  Challenge k goes to tape slot slot0 + k,
+// the messages to out[0 .. 3 rounds].  Above 2^FG_FS_TAIL_LOG entries a round is k_fg_fs_round + k_fg_fs_close, the folded tables alternating between the lane's
+// two table sets; the rest is one k_fg_fs_tail, which also absorbs v and draws the n_extra slots from extra0.
+static void fgk_fs_sumcheck(vp_ctx *ctx, FgkState &s, hipStream_t st, const F *V0, int rounds, bool has_a, u32 slot0, F *out, u32 extra0, u32 n_extra) {
+    const int above = std::max(0, rounds - FG_FS_TAIL_LOG);
+    const F *inV = V0, *inM = s.lane.tab[0][1], *inA = has_a ? s.lane.tab[0][2] : nullptr;
+    int cur = 0;
+    for (int k = 1; k <= above; ++k) {
+        FgFsRound a{};
+        a.n = 1u << (rounds - k + 1); a.fold = k > 1; a.part = s.fs_part;
+        a.inV = inV; a.inM = inM; a.inA = inA;
+        if (a.fold) {
+            const int nxt = cur ^ 1;
+            a.outV = s.lane.tab[nxt][0]; a.outM = s.lane.tab[nxt][1]; a.outA = has_a ? s.lane.tab[nxt][2] : nullptr;
+            a.r = s.tape + slot0 + (k - 2);
+            cur = nxt;
+        }
+        const u32 pairs = a.n >> 1, grid = grid_for(pairs);
+        const u64 tabs = has_a ? 3 : 2;
+        int sl = prof_begin(ctx, st, VP_K_ROUND, grid, 1, 16ull * tabs * ((a.fold ? 2ull * a.n : 0ull) + a.n), pairs, 1, (u32) k);
+        if (has_a) hipLaunchKernelGGL(k_fg_fs_round<true>, dim3(grid), dim3(VP_BLOCK), 0, st, a);
+        else hipLaunchKernelGGL(k_fg_fs_round<false>, dim3(grid), dim3(VP_BLOCK), 0, st, a);
+        prof_end(ctx, st, sl);
+        sl = prof_begin(ctx, st, VP_K_EMIT, 1, 1, 48ull * grid, 4, 1, (u32) k);
+        hipLaunchKernelGGL(k_fg_fs_close, dim3(1), dim3(VP_BLOCK), 0, st, (const F *) s.fs_part, grid, out + 3 * (k - 1), s.fs_state, s.tape, slot0 + (u32) (k - 1));
+        prof_end(ctx, st, sl);
+        ctx->st.launches += 2;
+        if (a.fold) { inV = a.outV; inM = a.outM; inA = a.outA; }
+    }
+    FgFsTail t{};
+    t.inV = inV; t.inM = inM; t.inA = inA; t.r_fold = above ? s.tape + slot0 + (above - 1) : nullptr;
+    t.rounds = rounds - above; t.n = 1u << t.rounds;
+    t.poly = out + 3 * above; t.state = s.fs_state; t.tape = s.tape; t.slot0 = slot0 + (u32) above; t.extra0 = extra0; t.n_extra = n_extra;
+    const u32 lds = (u32) (FG_FS_TABLES * sizeof(F)) * t.n;
+    const int sl = prof_begin(ctx, st, VP_K_SEG, 1, 1, 16ull * (has_a ? 3 : 2) * (above ? 2ull * t.n : t.n), 4ull * t.rounds + 1 + n_extra, (u32) t.rounds, (u32) above + 1);
+    if (has_a) hipLaunchKernelGGL(k_fg_fs_tail<true>, dim3(1), dim3(VP_BLOCK), lds, st, t);
+    else hipLaunchKernelGGL(k_fg_fs_tail<false>, dim3(1), dim3(VP_BLOCK), lds, st, t);
+    prof_end(ctx, st, sl);
+    ++ctx->st.launches;
+    ctx->st.rounds += rounds;
+}
+
+int vp_fft_gkr_fs(vp_ctx *ctx, int lg, const uint8_t state_in[32], vp_F *msgs, uint64_t capacity, uint64_t *n_written, vp_F *tape_out, uint8_t state_out[32]) {
+    if (!ctx) return VP_EINVAL;
+    VP_ENTER(ctx);
+    // every refusal before anything is allocated or queued
+    if (!state_in || !msgs || !tape_out || !state_out) { ctx->err = "vp_fft_gkr_fs: a null argument"; return VP_EINVAL; }
+    if (lg < 1 || lg > 19) { ctx->err = "vp_fft_gkr_fs: lg out of range (1..19)"; return VP_ELIMIT; }
+    const FgkOffsets o(lg);
+    const u64 n_out = FgkOffsets::n_msgs(lg);
+    if (capacity < n_out) { ctx->err = "vp_fft_gkr_fs: message buffer size (vp_fft_gkr_sizes)"; return VP_EINVAL; }
+    if (ctx->rec) { ctx->err = "vp_fft_gkr_fs: a launch plan is being recorded"; return VP_EINVAL; }
+    if (ctx->fgk && ctx->fgk->pending_lg) { ctx->err = "vp_fft_gkr_fs: an asynchronous run is pending (vp_fft_gkr_end / vp_fft_gkr_cancel)"; return VP_EINVAL; }
+    VPCHK(fgk_prepare(ctx, lg));
+    FgkState &s = *ctx->fgk;
+    const hipStream_t st = ctx->stream;
+    const u32 N = 1u << lg;
+    s.lane.stream = st;
+    ctx->st.launches = 0; ctx->st.rounds = 0;
+    if (ctx->profiling) ensure_event_pool(ctx);
+    ctx->ev_used = 0;
+    memcpy(s.h_tape, state_in, 32);                        // pinned; the caller's buffer may be pageable
+    HIPCHK(hipMemcpyAsync(s.fs_state, s.h_tape, 32, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ctx->ev0, st));
+    // ---- r and x, the circuit, the outputs, r_0 and r_1
+    int sl = prof_begin(ctx, st, VP_K_MERKLE, 1, 1, 16ull * (lg + 64), (u64) lg + 64);
+    hipLaunchKernelGGL(k_fg_fs_draw, dim3(1), dim3(64), 0, st, s.fs_state, (const F *) nullptr, 0u, s.tape, (u32) o.r, (u32) lg + 64u);
+    prof_end(ctx, st, sl);
+    VPCHK(fgk_circuit(ctx, s, lg, st));
+    sl = prof_begin(ctx, st, VP_K_MERKLE, 1, 1, 16ull * (64 + 2 * (lg + 10)), 64ull + 2 * (lg + 10));
+    hipLaunchKernelGGL(k_fg_fs_draw, dim3(1), dim3(64), 0, st, s.fs_state, (const F *) s.msgs, 64u, s.tape, (u32) o.r0, 2u * ((u32) lg + 10u));
+    prof_end(ctx, st, sl);
+    ctx->st.launches += 2;
+    u64 pos = 64;
+    // ---- addition layer: claim point r_0[0..6), alpha = 1, beta = 0; its r_v are drawn behind v_u
+    hipLaunchKernelGGL(k_fg_gtab, dim3(1), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.r0), (const F *) nullptr, 6, (const F *) nullptr, (const F *) nullptr, s.hi);
+    hipLaunchKernelGGL(k_fg_add_init, dim3(nblk((u64) 64 * N)), dim3(VP_BLOCK), 0, st, (const F *) s.hi, lg, s.lane.tab[0][1]);
+    fgk_fs_sumcheck(ctx, s, st, s.Pm, lg + 6, false, (u32) o.ru_a, s.msgs + pos, (u32) o.rv_a, (u32) lg + 6u);
+    pos += 3 * (lg + 6) + 1;
+    // ---- multiplication layer: claim point = the addition layer's r_u
+    hipLaunchKernelGGL(k_fg_gtab, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.ru_a), (const F *) nullptr, lg, (const F *) nullptr, (const F *) nullptr, s.g);
+    hipLaunchKernelGGL(k_fg_gtab, dim3(1), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.ru_a + lg), (const F *) nullptr, 6, (const F *) nullptr, (const F *) nullptr, s.hi);
+    hipLaunchKernelGGL(k_fg_mul_init, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, (const F *) s.g, (const F *) s.hi, (const F *) s.xt, lg, s.lane.tab[0][1]);
+    fgk_fs_sumcheck(ctx, s, st, s.S, lg, false, (u32) o.ru_m, s.msgs + pos, (u32) o.rv_m, (u32) lg);
+    pos += 3 * lg + 1;
+    // ---- inverse FFT, top layer first, depth by depth (the per-depth loop of fgk_enqueue: depth d's tables need the draws of depth d - 1)
+    for (int d = 0; d < lg; ++d) {
+        const F *r0 = s.tape + (d ? o.ru_d(d - 1) : o.ru_m), *r1 = s.tape + (d ? o.rv_d(d - 1) : o.rv_m);
+        const F *al = d ? s.tape + o.alpha_d(d - 1) : nullptr, *be = d ? s.tape + o.beta_d(d - 1) : nullptr;
+        const F *pre = s.B + (size_t) (lg - d - 1) * N;
+        hipLaunchKernelGGL(k_fg_gtab, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, r0, r1, lg, al, be, s.g);
+        hipLaunchKernelGGL(k_fg_ifft_p1, dim3(nblk(N / 2)), dim3(VP_BLOCK), 0, st, (const F *) s.g, pre, (const F *) s.winv, lg, d, s.lane.tab[0][1], s.lane.tab[0][2]);
+        fgk_fs_sumcheck(ctx, s, st, pre, lg, true, (u32) o.ru_d(d), s.msgs + pos, 0u, 0u);
+        const F *vu = s.msgs + pos + 3 * lg;
+        pos += 3 * lg + 1;
+        hipLaunchKernelGGL(k_fg_gtab, dim3(nblk(N)), dim3(VP_BLOCK), 0, st, (const F *) (s.tape + o.ru_d(d)), (const F *) nullptr, lg, (const F *) nullptr, (const F *) nullptr, s.eu);
+        hipLaunchKernelGGL(k_fg_ifft_p2, dim3(nblk(N / 2)), dim3(VP_BLOCK), 0, st, (const F *) s.g, (const F *) s.eu, vu, (const F *) s.winv, lg, d, s.lane.tab[0][1], s.lane.tab[0][2]);
+        fgk_fs_sumcheck(ctx, s, st, pre, lg, true, (u32) o.rv_d(d), s.msgs + pos, (u32) o.alpha_d(d), 2u);
+        pos += 3 * lg + 1;
+    }
+    if (pos != n_out) { (void) hipStreamSynchronize(st); ctx->err = "internal: fft_gkr message count"; return VP_EINVAL; }
+    HIPCHK(hipEventRecord(ctx->ev1, st));
+    // ---- messages | tape | state: one block, one copy
+    HIPCHK(hipMemcpyAsync(s.h_msgs, s.msgs, (n_out + o.n + 2) * sizeof(F), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    memcpy(msgs, s.h_msgs, n_out * sizeof(F));
+    memcpy(tape_out, s.h_msgs + n_out, o.n * sizeof(F));
+    memcpy(state_out, s.h_msgs + n_out + o.n, 32);
+    float ms = 0;
+    hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+    ctx->commit_ms = ms;
+    if (ctx->profiling) prof_collect(ctx);
+    if (n_written) *n_written = n_out;
+    return VP_OK;
+}
+
 }  // extern "C"
 
 // vp_warm (include/vpgpu.h): first-use set-up ahead of the first prover call.  VP_WARM_COMMITMENT: pc_warm (vpgpu_pc.inc).  VP_WARM_FFT_GKR: the buffers of
@@ -362,6 +493,7 @@ static void warm_kernel_functions() {
         (const void *) k_fg_rowsum, (const void *) k_fg_gtab, (const void *) k_fg_add_init, (const void *) k_fg_mul_init, (const void *) k_fg_gtab_multi, (const void *) k_fg_dot_multi,
         (const void *) k_fg_ifft_multi, (const void *) k_fg_ifft_p1, (const void *) k_fg_ifft_p2, (const void *) k_sumfold3b<true>, (const void *) k_sumfold3b<false>,
         (const void *) k_seg<true>, (const void *) k_seg<false>, (const void *) k_emit,
+        (const void *) k_fg_fs_draw, (const void *) k_fg_fs_round<true>, (const void *) k_fg_fs_round<false>, (const void *) k_fg_fs_close, (const void *) k_fg_fs_tail<true>, (const void *) k_fg_fs_tail<false>,
         // the batched proof and the interactive entry points
         (const void *) k_light_multi, (const void *) k_chunks_multi, (const void *) k_combine_multi, (const void *) k_dot_multi, (const void *) k_dotfin_multi,
         (const void *) k_sumfold3b_multi, (const void *) k_sumfold3b_gen_multi, (const void *) k_seg_multi, (const void *) k_emit_multi, (const void *) k_fixup,

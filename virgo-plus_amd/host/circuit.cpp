@@ -92,18 +92,20 @@ void layeredCircuit::structuralHash(u64 out[2]) const {
     out[0] = a; out[1] = b;
 }
 
-void layeredCircuit::statementDigest(u64 out[4]) const {
+void layeredCircuit::statementDigest(u64 out[4], bool with_inputs) const {
     // recomputed on every call (O(|C|), the order of the verifier's own work): `circuit` is a public member, a cached digest would keep
     // binding the Fiat-Shamir challenges to a statement that was edited after the first proof
     vph::sha3_256 h;
-    h.put64(0x76697267ull);                       // domain tag
+    h.put64(with_inputs ? 0x76697267ull : 0x76697268ull);      // domain tag; the second one: the statement without the input layer's values (the joined proof:
+                                                               // the input is the witness root_l commits to, only the layer's size and gate types are public)
     h.put64((u64) size);
     for (int i = 0; i < size; ++i) {
         const layer &L = circuit[i];
         h.put64(L.size); h.put64((u64) (i64) L.bitLength);
         for (u64 g = 0; g < L.size; ++g) {
             const gate &G = L.gates[g];
-            const u64 rec[7] = {(u64) (i64) G.ty | ((u64) (G.is_assert ? 1 : 0) << 32), (u64) (i64) G.l, G.u, G.v, G.lv, G.c.real, G.c.img};
+            u64 rec[7] = {(u64) (i64) G.ty | ((u64) (G.is_assert ? 1 : 0) << 32), (u64) (i64) G.l, G.u, G.v, G.lv, G.c.real, G.c.img};
+            if (!with_inputs && i == 0) rec[2] = rec[3] = rec[4] = rec[5] = rec[6] = 0;
             h.update(rec, sizeof rec);
         }
         h.put64((u64) (i64) L.maxDadBitLength); h.put64(L.maxDadSize);

@@ -61,7 +61,8 @@ public:
     // layer 0 — the input values): the statement digest the Fiat-Shamir mode binds its challenges to.  structuralHash is
     // only a loader-parity fingerprint (FNV + xor-multiply, invertible); this one is collision resistant.  Not cached (the gate
     // tables are public and may be edited between proofs).
-    void statementDigest(u64 out[4]) const;
+    // with_inputs = false: the same digest under another domain tag with every operand and constant of the input layer left out (verifier::proveFullFS)
+    void statementDigest(u64 out[4], bool with_inputs = true) const;
 };
 
 namespace vph {

@@ -1,5 +1,6 @@
 #include "prover.hpp"
 #include "pc_fs.hpp"
+#include "fft_gkr_fs.hpp"
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -605,6 +606,21 @@ std::vector<uint8_t> prover::commitFS(const std::vector<F> &point, int reps, con
     put(ans.data(), ans.size());
     return out;
 }
+void prover::friCommitFS(vph::fs_chain &ch, std::vector<uint8_t> &roots) {
+    if (shard_pc) throw std::runtime_error("friCommitFS: not built for a sharded commitment");
+    const int ln = C.circuit[0].bitLength - 6;
+    roots.assign(32 * (size_t) ln, 0);
+    std::vector<F> fr((size_t) ln);
+    uint8_t st_in[32], st_out[32];
+    memcpy(st_in, ch.s.w, 32);
+    check(vp_fri_commit_fs(ctx, st_in, roots.data(), mF(fr.data()), st_out), "vp_fri_commit_fs");
+    F r = pcFsFirstChallenge(ch);
+    for (int k = 0; k < ln; ++k) {
+        if (memcmp(&r, &fr[k], sizeof(F))) throw std::runtime_error("vp_fri_commit_fs: challenge " + std::to_string(k) + " is not the chain's");
+        pcFsLevel(ch, k, ln, &roots[32 * (size_t) k], &r);
+    }
+    if (memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_fri_commit_fs: the closing state is not the chain's");
+}
 prover::hhash_digest prover::friStep(const F &r) {
     hhash_digest d;
     if (shard_pc) {
@@ -757,6 +773,25 @@ std::vector<F> prover::fftGkrEnd(int lg) {
     return msgs;
 }
 void prover::fftGkrCancel() noexcept { (void) vp_fft_gkr_cancel(ctx); }
+std::vector<F> prover::fftGkrFS(int lg, uint8_t state[32], std::vector<F> &tape) {
+    uint64_t nt = 0, nm = 0;
+    check(vp_fft_gkr_sizes(lg, &nt, &nm), "vp_fft_gkr_sizes");
+    std::vector<F> msgs(nm);
+    tape.assign(nt, F_ZERO);
+    uint8_t st_out[32];
+    uint64_t written = 0;
+    check(vp_fft_gkr_fs(ctx, lg, state, mF(msgs.data()), nm, &written, mF(tape.data()), st_out), "vp_fft_gkr_fs");
+    if (written != nm) throw std::runtime_error("vp_fft_gkr_fs: message count");
+    vph::fs_chain ch;
+    memcpy(ch.s.w, state, 32);
+    std::vector<F> want(nt);
+    vph::fftGkrFsTape(lg, ch, msgs.data(), want.data());
+    for (uint64_t i = 0; i < nt; ++i)
+        if (memcmp(&want[i], &tape[i], sizeof(F))) throw std::runtime_error("vp_fft_gkr_fs: tape slot " + std::to_string(i) + " is not the chain's");
+    if (memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_fft_gkr_fs: the closing state is not the chain's");
+    memcpy(state, st_out, 32);
+    return msgs;
+}
 double prover::commitDeviceMs() { double ms = 0; check(vp_commit_stats(ctx, &ms), "vp_commit_stats"); return ms; }
 
 void prover::gkrSizes(u64 &n_tape, u64 &n_bytes) {

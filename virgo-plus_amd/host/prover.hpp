@@ -14,6 +14,7 @@
 #include "../../include/vpgpu.h"
 #include "circuit.hpp"
 #include "polynomial.hpp"
+#include "sha3.hpp"
 
 class timer {          // accumulate semantics of lib/virgo/src/timer.hpp:11-25
 public:
@@ -109,6 +110,9 @@ public:
     // challenge from the root it has just computed (checked here against the host's chain over the returned roots); false: the vp_fri_step loop with the chain on
     // the host, one wait per level — a second implementation with the same bytes.  Throws on a sharded commitment (not built).
     std::vector<uint8_t> commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_draws = true);
+    // vp_fri_commit_fs from the chain's state, the roots returned; the device's challenges and closing state are checked against the chain walked over those
+    // roots (steps 8 and 9 of the commitment's chain), which is left behind the last level.  After commit_public_eq.
+    void friCommitFS(vph::fs_chain &ch, std::vector<uint8_t> &roots);
     double fsPhaseSec() const { return fs_phase_sec; }      // host wall clock of the last commitFS's commit phase (step 5 alone)
     double fsPhaseDeviceMs() const { return fs_phase_ms; }  // its device time (the levels' sum in the vp_fri_step loop)
     hhash_digest friStep(const F &r);
@@ -129,6 +133,10 @@ public:
     void fftGkrBegin(int lg, const std::vector<F> &tape);
     std::vector<F> fftGkrEnd(int lg);
     void fftGkrCancel() noexcept;                   // drop a begun run (a pass that failed between begin and end)
+    // fft_gkr non-interactive (vp_fft_gkr_fs): the device draws the whole tape from the chain, starting at `state` (the chain's text: vphost.h); returns the
+    // messages, `tape` = the tape drawn, `state` = the closing state.  The tape and the state are re-derived here from the returned messages
+    // (fft_gkr_fs.hpp); throws if either differs from what the device returned.
+    std::vector<F> fftGkrFS(int lg, uint8_t state[32], std::vector<F> &tape);
     double commitDeviceMs();
 
     double proveTime() const { return prove_timer.elapse_sec(); }

@@ -1,5 +1,7 @@
 #include "verifier.hpp"
 #include "fft_gkr_verify.hpp"
+#include "fft_gkr_fs.hpp"
+#include "pc_fs.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -41,13 +43,13 @@ verifier::verifier(prover *pr, const layeredCircuit &cir) : p(pr), C(cir) {     
 // ---- Fiat-Shamir: state' = SHA3-256(block || state) over the same 64-byte block function as the commitment (sha3.hpp) ----
 // absorb a prover message:  block = {real, img, 0, 0x4d};  squeeze challenge number c:  block = {c, 0, 0, 0x43}, then the two
 // limbs are the first two digest words reduced to 61 bits (p itself maps to 0; the bias is 2^-61).
-void verifier::fsInit() {
+void verifier::fsInit(bool with_inputs) {
     fs_state = vph::fs_chain{};
     fs_ctr = 0;
     // statement: SHA3-256 over the serialised levelised circuit, subset tables and input values (layeredCircuit::statementDigest);
     // the non-cryptographic structuralHash is a test fingerprint only and is not used here
     u64 h[4];
-    C.statementDigest(h);
+    C.statementDigest(h, with_inputs);
     fs_state.step(h[0], h[1], h[2], h[3]);
     fs_state.step((uint64_t) C.size, 0, 0, 0x53);
 }
@@ -991,6 +993,154 @@ bool verifier::checkFull(const std::vector<uint8_t> &record) {
     } catch (const std::runtime_error &) { ok = false; }      // short record / non-canonical element
     rec = nullptr; input_check_by_commitment = false;
     return ok;
+}
+
+// ---- the joined non-interactive proof (chain and layout: vphost.h, "The joined proof") ------------------------------------------------------------------------
+constexpr uint32_t FULLFS_MAGIC = 0x46465056u, FULLFS_VERSION = 1;      // "VPFF", version 1
+// steps 1 and 2 of the chain: the statement without the input values, then the head
+void verifier::fullFsHead(int n, u64 reps, u64 ms, const std::vector<F> &pub_mask, const uint8_t root_l[32]) {
+    fsInit(false);
+    const u64 n_pub = ms == 1 ? 0 : pub_mask.size();
+    fs_state.param((u64) n, reps, ms, n_pub);
+    for (u64 i = 0; i < n_pub; ++i) fs_state.elem(pub_mask[i].real, pub_mask[i].img);
+    fs_state.digest(0, root_l);
+}
+std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask) {
+    if (!p) throw std::runtime_error("proveFullFS(): no prover attached");
+    if (p->world() > 1 || p->commitmentSharded()) throw std::runtime_error("proveFullFS: not built for a sharded session");
+    const int n = C.circuit[0].bitLength, ln = n - 6;
+    if (n < 7) throw std::runtime_error("proveFullFS: the commitment needs an input layer of at least 2^7 wires");
+    if (reps < 1 || reps > 4096) throw std::runtime_error("proveFullFS: 1 .. 4096 repetitions");
+    const prover::hhash_digest root_l = p->commit_private(pri_mask);
+    u64 ms = 1;
+    if (p->isMasked()) {
+        const u64 M = 1ull << (n - 1);
+        u64 gap = 1;
+        while (gap * 2 <= M / pri_mask.size()) gap *= 2;
+        ms = M / gap;
+    }
+    const std::vector<F> pm = ms > 1 ? pub_mask : std::vector<F>();
+    // ---- the GKR part: run() in FS mode, the claim left to the commitment
+    replay = false; fs = true; tape_.clear(); tr.clear();
+    fullFsHead(n, (u64) reps, ms, pm, root_l.b);
+    input_check_by_commitment = true;
+    bool ok = false;
+    try { ok = run(); } catch (...) { fs = false; input_check_by_commitment = false; throw; }
+    fs = false; input_check_by_commitment = false;
+    if (!ok) throw std::runtime_error("proveFullFS: the GKR part of the prover's own proof is rejected");
+    const std::vector<uint8_t> gkr = tr;
+    full_fs_point_.assign(r_liu.begin(), r_liu.begin() + n);
+    // ---- the commitment head
+    F input_0;
+    std::vector<F> all_sum;
+    const prover::hhash_digest root_h = p->commit_public_eq(full_fs_point_, pm, input_0, all_sum);
+    vph::fs_chain ch = fs_state;
+    ch.elem(input_0.real, input_0.img);
+    for (int i = 0; i < 65; ++i) ch.elem(all_sum[i].real, all_sum[i].img);
+    ch.digest(1, root_h.b);
+    // ---- fft_gkr, every challenge drawn on the device; fftGkrFS re-derives the tape and the state from the returned messages
+    uint8_t st[32];
+    memcpy(st, ch.s.w, 32);
+    std::vector<F> ftape;
+    const std::vector<F> fmsgs = p->fftGkrFS(ln, st, ftape);
+    memcpy(ch.s.w, st, 32);
+    // ---- the FRI commit phase from that state, checked against the host's chain over the returned roots
+    std::vector<uint8_t> roots;
+    p->friCommitFS(ch, roots);
+    const std::vector<F> fin = p->friFinal(), fm = p->friFinalMask();
+    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm);
+    const std::vector<uint8_t> ans = p->friQuery(lf);
+    std::vector<uint8_t> out;
+    auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); out.insert(out.end(), q, q + k); };
+    const uint32_t h32[4] = {FULLFS_MAGIC, FULLFS_VERSION, (uint32_t) n, (uint32_t) reps};
+    const uint64_t h64[2] = {ms, ms == 1 ? 0 : pm.size()};
+    put(h32, sizeof h32); put(h64, sizeof h64);
+    if (ms != 1) put(pm.data(), pm.size() * sizeof(F));
+    put(root_l.b, 32);
+    put(gkr.data(), gkr.size());
+    put(root_h.b, 32);
+    put(&input_0, sizeof(F));
+    put(all_sum.data(), 65 * sizeof(F));
+    put(fmsgs.data(), fmsgs.size() * sizeof(F));
+    put(roots.data(), roots.size());
+    put(fin.data(), fin.size() * sizeof(F));
+    put(fm.data(), fm.size() * sizeof(F));
+    put(ans.data(), ans.size());
+    return out;
+}
+int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev) {
+    auto bad = [&](const char *m) { why = m; return -1; };
+    full_fs_point_.clear();
+    if (!proof) return bad("no proof");
+    u64 at = 0;
+    auto have = [&](u64 k) { return k <= len - at; };            // (at <= len throughout)
+    if (!have(32)) return bad("proof shorter than its header");
+    uint32_t h32[4]; u64 h64[2];
+    memcpy(h32, proof, 16); memcpy(h64, proof + 16, 16); at = 32;
+    if (h32[0] != FULLFS_MAGIC) return bad("not a joined proof (magic)");
+    if (h32[1] != FULLFS_VERSION) return bad("a joined proof of another version");
+    const u64 n = h32[2], reps = h32[3], ms = h64[0], n_pub = h64[1];
+    if (n < 7 || n > 30 || (int) n != C.circuit[0].bitLength) return bad("n is not the bit length of the circuit's input layer (7 .. 30)");
+    if (reps < 1 || reps > 4096) return bad("1 .. 4096 repetitions");
+    if (ms != 1 && (ms < 8 || (ms & (ms - 1)) || ms > (1ull << 16) || ms > (1ull << (n - 2)))) return bad("ms is neither 1 nor a power of two in [8, min(2^16, 2^(n-2))]");
+    if (ms == 1 ? n_pub != 0 : n_pub > ms) return bad("public mask longer than ms (none with the zero mask)");
+    const u64 ln = n - 6;
+    bool canon = true;
+    auto elems = [&](std::vector<F> &v, u64 k) {
+        if (!have(16 * k)) return false;
+        v.resize(k);
+        for (u64 i = 0; i < k; ++i) {
+            unsigned long long w[2]; memcpy(w, proof + at, 16); at += 16;
+            if (w[0] >= F::mod || w[1] >= F::mod) canon = false;
+            v[i].real = w[0]; v[i].img = w[1];
+        }
+        return true;
+    };
+    auto bytes = [&](uint8_t *dst, u64 k) { if (!have(k)) return false; memcpy(dst, proof + at, k); at += k; return true; };
+    PcCommitment c;
+    c.n = (int) n; c.ms = ms;
+    if (!elems(c.pub_mask, n_pub) || !bytes(c.root_l, 32)) return bad("proof shorter than its sections");
+    if (!canon) return bad("non-canonical field element in the proof");
+    // ---- the GKR part: the replay of checkFS on the bytes behind root_l; it ends where run() stops reading
+    const std::vector<uint8_t> rest(proof + at, proof + len);
+    static const std::vector<F> no_tape;
+    replay = true; fs = true; rtape = &no_tape; rtr = &rest; tape_pos = 0; tr_pos = 0; tr.clear(); tape_.clear();
+    fullFsHead((int) n, reps, ms, c.pub_mask, c.root_l);
+    input_check_by_commitment = true;
+    bool ok = false, malformed = false;
+    try { ok = run(); } catch (const std::exception &e) { malformed = true; why = e.what(); }      // the proof ends inside the GKR part / a non-canonical element
+    fs = false; input_check_by_commitment = false;
+    if (malformed) return -1;
+    full_fs_point_.assign(r_liu.begin(), r_liu.begin() + n);      // as far as the replay got: a rejected GKR part leaves the coordinates it had derived
+    if (!ok) { why = "the GKR part is rejected (a sumcheck round, a layer's final value or a Liu sumcheck)"; return 1; }
+    at += tr_pos;
+    c.point = full_fs_point_;
+    // ---- the sections behind it
+    std::vector<F> input_0, fmsgs;
+    c.fri_roots.resize(32 * ln);
+    if (!bytes(c.root_h, 32) || !elems(input_0, 1) || !elems(c.all_sum, 65) || !elems(fmsgs, vph::FftGkrLayout((int) ln).n_msgs) || !bytes(c.fri_roots.data(), 32 * ln) ||
+        !elems(c.final_code, 2048) || !elems(c.final_mask, 32))
+        return bad("proof shorter than its sections");
+    if (!canon) return bad("non-canonical field element in the proof");
+    c.n_bytes = pcQueryAnswerBytes((int) n, reps);
+    if (len - at != c.n_bytes) return bad("the proof does not end where the answer ends");
+    c.answer = proof + at;
+    c.claim = input_0[0];
+    // ---- the chain behind the GKR part: the commitment head, fft_gkr's tape, the fold challenges, the positions
+    vph::fs_chain ch = fs_state;
+    ch.elem(c.claim.real, c.claim.img);
+    for (int i = 0; i < 65; ++i) ch.elem(c.all_sum[i].real, c.all_sum[i].img);
+    ch.digest(1, c.root_h);
+    std::vector<F> ftape(vph::FftGkrLayout((int) ln).n_tape);
+    vph::fftGkrFsTape((int) ln, ch, fmsgs.data(), ftape.data());
+    c.fr.resize(ln);
+    c.fr[0] = pcFsFirstChallenge(ch);
+    for (u64 k = 0; k < ln; ++k) { F next; if (pcFsLevel(ch, (int) k, (int) ln, &c.fri_roots[32 * k], &next)) c.fr[k + 1] = next; }
+    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask);
+    // ---- the checks: nothing of the joined proof's own beyond the hand-over of the claim
+    if (last_claim != c.claim) { why = "the GKR part's claim on the input layer is not input_0 (final input check)"; return 1; }
+    if (!vph::fft_gkr_check<F>((int) ln, ftape.data(), ftape.size(), fmsgs.data(), fmsgs.size(), F::getRootOfUnity((int) ln).inv())) { why = "fft_gkr is rejected"; return 1; }
+    return pcVerifyCommitment(c, why, dev);
 }
 
 // checkFull with the verifier's heavy loops on `device`, on a prover context made for the call (circuit uploaded and evaluated: vp_liu_gr builds its table on an

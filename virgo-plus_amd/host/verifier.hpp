@@ -76,6 +76,15 @@ public:
     //   checkFS()   needs no prover and no tape: re-derives every challenge from the proof and runs the same checks.
     bool proveFS();
     bool checkFS(const std::vector<uint8_t> &proof);
+    // The joined non-interactive proof of the whole protocol (chain and layout: vphost.h, "The joined proof"): commit_private, the GKR part exactly as run() in
+    // FS mode with the input check by commitment, commit_public_eq at the derived point, fft_gkr with its challenges drawn on the device (vp_fft_gkr_fs), the
+    // FRI commit phase from the state it leaves (vp_fri_commit_fs), the final codewords, the derived positions and their openings.  Throws on a sharded session,
+    // an input layer below 2^7 wires, or a prover whose own proof the checks reject.
+    std::vector<uint8_t> proveFullFS(int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {});
+    // A verifier that holds only the circuit: parses under checkFull's rules, replays run(), derives every challenge, calls fft_gkr_check and pcVerifyCommitment
+    // unchanged (dev: the commitment's heavy loops on a device context).  0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).
+    int checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr);
+    const std::vector<F> &fullFsPoint() const { return full_fs_point_; }      // the point the last proveFullFS / checkFullFS derived (checkFullFS: r_liu as far as the replay of the GKR part got)
     std::vector<F> drawTape();                                  // the verifier's draws, in its own order
     bool check(const std::vector<F> &tape, const std::vector<uint8_t> &transcript);   // replay
 
@@ -110,7 +119,9 @@ private:
     bool fs = false;                                   // challenges derived from the transcript
     vph::fs_chain fs_state{};
     uint64_t fs_ctr = 0;
-    void fsInit();
+    void fsInit(bool with_inputs = true);
+    void fullFsHead(int n, u64 reps, u64 ms, const std::vector<F> &pub_mask, const uint8_t root_l[32]);
+    std::vector<F> full_fs_point_;
     const std::vector<F> *rtape = nullptr;
     const std::vector<uint8_t> *rtr = nullptr;
     size_t tape_pos = 0, tr_pos = 0;

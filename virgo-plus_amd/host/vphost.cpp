@@ -8,6 +8,7 @@
 #include <string>
 
 #include "circuit.hpp"
+#include "fft_gkr_fs.hpp"
 #include "prover.hpp"
 #include "verifier.hpp"
 
@@ -616,6 +617,95 @@ int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r
         memcpy(r_pairs, c.fr.data(), c.fr.size() * sizeof(F));
         for (size_t q = 0; q < c.leaf0.size(); ++q) leaf0[q] = c.leaf0[q];
         return 0;
+    } catch (const std::exception &) { return -1; }
+}
+
+// ---- the joined non-interactive proof of the whole protocol (verifier::proveFullFS / checkFullFS) ----
+int vph_prove_full_fs(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                      uint64_t *len, uint64_t *point_pairs, char *err, int errlen) {
+    if (!s || !len || (n_mask && !mask_pairs) || (n_pub_mask && !pub_mask_pairs)) { set_err(err, errlen, "vph_prove_full_fs: a null argument"); return -1; }
+    try {
+        verifier v(s->p.get(), s->circ->c);
+        const std::vector<uint8_t> proof = v.proveFullFS(reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask));
+        *len = proof.size();
+        if (!out || cap < proof.size()) { set_err(err, errlen, "vph_prove_full_fs: output buffer too small (*len: the proof's size)"); return -1; }
+        memcpy(out, proof.data(), proof.size());
+        if (point_pairs) memcpy(point_pairs, v.fullFsPoint().data(), v.fullFsPoint().size() * sizeof(F));
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+int vph_verify_full_fs(vph_circuit *c, const uint8_t *proof, uint64_t len, int device, uint64_t *point_pairs, char *err, int errlen) {
+    if (!c) { set_err(err, errlen, "vph_verify_full_fs: no circuit"); return -1; }
+    vp_ctx *ctx = nullptr;
+    try {
+        if (device >= 0 && vp_create(device, &ctx) != VP_OK) { ctx = nullptr; throw std::runtime_error("vph_verify_full_fs: no context on the device"); }
+        verifier v(nullptr, c->c);
+        std::string why;
+        const int rc = v.checkFullFS(proof, len, why, ctx);
+        if (ctx) vp_destroy(ctx);
+        if (rc) set_err(err, errlen, why);
+        if (point_pairs && !v.fullFsPoint().empty()) memcpy(point_pairs, v.fullFsPoint().data(), v.fullFsPoint().size() * sizeof(F));
+        return rc;
+    } catch (const std::exception &e) {
+        if (ctx) vp_destroy(ctx);
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
+// fft_gkr's part of the chain, the derivation alone (fft_gkr_fs.hpp): the tape and the closing state of vp_fft_gkr_fs from its messages
+static bool fgk_pairs_ok(int lg, const uint64_t *pairs, uint64_t n, uint64_t want) {
+    if (lg < 1 || lg > 19 || !pairs || n != want) return false;
+    for (uint64_t i = 0; i < 2 * n; ++i) if (pairs[i] >= 2305843009213693951ull) return false;
+    return true;
+}
+int vph_fft_gkr_fs_tape(int lg, const uint8_t state_in[32], const uint64_t *msgs_pairs, uint64_t n_msgs, uint64_t *tape_pairs, uint8_t state_out[32]) {
+    if (lg < 1 || lg > 19) return -1;
+    const vph::FftGkrLayout L(lg);
+    if (!state_in || !tape_pairs || !state_out || !fgk_pairs_ok(lg, msgs_pairs, n_msgs, L.n_msgs)) return -1;
+    try {
+        std::vector<F> msgs(L.n_msgs), tape(L.n_tape);
+        memcpy(static_cast<void *>(msgs.data()), msgs_pairs, L.n_msgs * sizeof(F));
+        vph::fs_chain ch;
+        memcpy(ch.s.w, state_in, 32);
+        vph::fftGkrFsTape(lg, ch, msgs.data(), tape.data());
+        memcpy(tape_pairs, tape.data(), L.n_tape * sizeof(F));
+        memcpy(state_out, ch.s.w, 32);
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+int vph_fft_gkr_fs(vph_session *s, int lg, const uint8_t state_in[32], uint64_t *msgs_pairs, uint64_t cap_elems, uint64_t *tape_pairs, uint8_t state_out[32],
+                   char *err, int errlen) {
+    if (!s || !state_in || !msgs_pairs || !tape_pairs || !state_out) { set_err(err, errlen, "vph_fft_gkr_fs: a null argument"); return -1; }
+    if (lg < 1 || lg > 19) { set_err(err, errlen, "vph_fft_gkr_fs: lg out of range (1..19)"); return -1; }
+    const vph::FftGkrLayout L(lg);
+    if (cap_elems < L.n_msgs) { set_err(err, errlen, "vph_fft_gkr_fs: message buffer size"); return -1; }
+    try {
+        uint8_t st[32];
+        memcpy(st, state_in, 32);
+        std::vector<F> tape;
+        const std::vector<F> msgs = s->p->fftGkrFS(lg, st, tape);
+        memcpy(msgs_pairs, msgs.data(), msgs.size() * sizeof(F));
+        memcpy(tape_pairs, tape.data(), tape.size() * sizeof(F));
+        memcpy(state_out, st, 32);
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+int vph_fft_gkr_check(int lg, const uint64_t *tape_pairs, uint64_t n_tape, const uint64_t *msgs_pairs, uint64_t n_msgs) {
+    if (lg < 1 || lg > 19) return -1;
+    const vph::FftGkrLayout L(lg);
+    if (!fgk_pairs_ok(lg, tape_pairs, n_tape, L.n_tape) || !fgk_pairs_ok(lg, msgs_pairs, n_msgs, L.n_msgs)) return -1;
+    try {
+        std::vector<F> msgs(L.n_msgs), tape(L.n_tape);
+        memcpy(static_cast<void *>(msgs.data()), msgs_pairs, L.n_msgs * sizeof(F));
+        memcpy(static_cast<void *>(tape.data()), tape_pairs, L.n_tape * sizeof(F));
+        return vph::fft_gkr_check<F>(lg, tape.data(), tape.size(), msgs.data(), msgs.size(), F::getRootOfUnity(lg).inv()) ? 0 : 1;
     } catch (const std::exception &) { return -1; }
 }
 

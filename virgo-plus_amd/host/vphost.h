@@ -225,6 +225,53 @@ int vph_commit_fs(vph_session *, const uint64_t *point_pairs, int n_point, int r
 void vph_last_commit_fs_times(vph_session *, double out[2]);
 int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen);
 int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r_pairs /* n - 6 */, uint64_t *leaf0 /* reps */);
+/* The transcript chain: fft_gkr.  vp_fft_gkr_fs (include/vpgpu.h) continues a chain of the steps above from a 32-byte state and draws fft_gkr's whole tape from it
+ * on the device.  A slot's counter is its index in the tape layout (r[lg] | x[64] | r_0[lg+10] | r_1[lg+10] | addition layer r_u[lg+6], r_v[lg+6] | multiplication
+ * layer r_u[lg], r_v[lg] | per depth r_u[lg], r_v[lg], alpha, beta); messages are in vp_fft_gkr's layout.  The order:
+ *      1. r[i] = C(slot), i < lg; x[i] = C(slot), i < 64
+ *      2. E(O[i]), i < 64; every slot of r_0, then of r_1 = C(slot)
+ *      3. addition layer: per round k < lg + 6: E(a), E(b), E(c), r_u[k] = C(slot); E(v_u); r_v[k] = C(slot), k < lg + 6 (they multiply beta = 0 and are
+ *         don't-cares of the prover; fft_gkr_check reads them, so they are drawn)
+ *      4. multiplication layer: the same with lg rounds
+ *      5. per inverse-FFT depth d < lg: phase 1 per round E(a), E(b), E(c), r_u[k] = C(slot); E(v_u); phase 2 per round E(a), E(b), E(c), r_v[k] = C(slot);
+ *         E(v_v); alpha = C(slot), beta = C(slot)
+ * A draw never precedes the polynomial it challenges.  fft_gkr is self-contained in the reference: its inputs are draws, and it binds nothing of a commitment —
+ * what ties it to one is only the chain state it starts from.
+ * vph_fft_gkr_fs_tape: the derivation alone, on the host — the tape (n_tape pairs) and the closing state from state_in and the messages; 0, or -1 (lg outside
+ * 1..19, a null pointer, n_msgs not vp_fft_gkr_sizes', a non-canonical limb).  vph_fft_gkr_check: fft_gkr_check (fft_gkr_verify.hpp) on a tape and messages by
+ * value: 0 accepted, 1 rejected, -1 malformed by the same rules.  vph_fft_gkr_check and vph_fft_gkr_fs are test and diagnostic entry points: the joined proof
+ * calls fft_gkr_check and prover::fftGkrFS itself.                                                                                          */
+int vph_fft_gkr_fs_tape(int lg, const uint8_t state_in[32], const uint64_t *msgs_pairs, uint64_t n_msgs, uint64_t *tape_pairs, uint8_t state_out[32]);
+int vph_fft_gkr_check(int lg, const uint64_t *tape_pairs, uint64_t n_tape, const uint64_t *msgs_pairs, uint64_t n_msgs);
+/* vp_fft_gkr_fs on the session's context (prover::fftGkrFS): messages (cap_elems >= n_msgs), the tape drawn and the closing state; the host re-derives the tape and
+ * the state from the returned messages and fails if the device's differ.  0 = done, -1 = a bad argument, -2 = refused or failed (err).                      */
+int vph_fft_gkr_fs(vph_session *, int lg, const uint8_t state_in[32], uint64_t *msgs_pairs, uint64_t cap_elems, uint64_t *tape_pairs, uint8_t state_out[32],
+                   char *err, int errlen);
+/* ---- The joined proof: one block of bytes for the whole protocol, checked by a verifier that holds only the circuit ----------------------------------------------
+ * No tape, no session, no input values.  The chain is the one above, in this order:
+ *      1. the statement: the four words of layeredCircuit::statementDigest(with_inputs = false) — the digest of vph_prove_fs under another domain tag with the input
+ *         layer's values left out (here the input is the witness that root_l commits to) — as one step, then {size, 0, 0, 0x53}
+ *      2. the head: P(n, reps, ms, n_pub); E(pub_mask[i]), i < n_pub (n_pub = 0 when ms = 1); D(0, root_l) — before any GKR draw
+ *      3. the GKR part: exactly vph_prove_fs's schedule with the input check left to the commitment — every prover element E, every challenge C(counter) with the
+ *         counter running from 0; it ends with the point r_liu (the first n coordinates) and the claim on the input layer
+ *      4. the commitment head at that point: E(input_0), E(all_sum[i]), i < 65, D(1, root_h)
+ *      5. fft_gkr at lg = n - 6 from that state ("The transcript chain: fft_gkr" below)
+ *      6. the FRI commit phase from the state fft_gkr leaves, as steps 8 and 9 of the commitment proof: r_0 = C(0); per level D(2 + k, root_k), r_(k+1) = C(k + 1)
+ *      7. E over the final codeword (2048), E over the final mask codeword (32), Q(q), q < reps
+ * Proof bytes: header u32 magic 0x46465056 ("VPFF") | u32 version = 1 | u32 n | u32 reps | u64 ms | u64 n_pub; then the public mask (16 n_pub) | root_l (32) | the GKR
+ * bytes (vph_prove_fs's proof for this chain) | root_h (32) | input_0 (16) | all_sum (65 x 16) | the fft_gkr messages | the FRI roots (32 (n - 6)) | the final codeword |
+ * the final mask | the answer in vp_fri_query's layout.  The point is not in the proof: it is derived.
+ * vph_verify_full_fs parses under vph_verify_full_record's rules (bounds on every read, canonical limbs, the proof ends where the answer ends; n must be the circuit's
+ * input bit length; ms and n_pub by vph_verify_commitment's rules), replays the GKR part, compares its claim with input_0, derives fft_gkr's tape and calls
+ * fft_gkr_check unchanged, fills the commitment by value and calls vph_verify_commitment's checks unchanged (device >= 0: their heavy loops on that GPU): no algebra of
+ * its own.  0 accepted, 1 rejected (err: the failed check), -1 malformed (err), -2 no device.  point_pairs (may be null): the n derived coordinates, written unless
+ * the proof is malformed (a rejected GKR part: as far as its replay got).  vph_prove_full_fs: verifier::proveFullFS on the session (masks as vph_commit_fs); 0 done, -1 a bad argument or cap too small (*len: the
+ * size), -2 refused or failed (a sharded session, a mask outside the limits, ...).  Limits: unsharded sessions; masks: ONE rule in two places, as for
+ * vph_verify_commitment_fs — the parser takes every ms a prover can commit (1, or a power of two in [8, min(2^16, 2^(n-2))]: anything else is malformed), and the
+ * commitment's checks then reject ms > 2^(n-6) as the reference's verifier does ("Fri msk rs code check fail"), so an accepted masked proof has n >= 9.       */
+int vph_prove_full_fs(vph_session *, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                      uint64_t *len, uint64_t *point_pairs /* n, or null */, char *err, int errlen);
+int vph_verify_full_fs(vph_circuit *, const uint8_t *proof, uint64_t len, int device, uint64_t *point_pairs /* n, or null */, char *err, int errlen);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
