@@ -441,6 +441,26 @@ int vp_fft_gkr_cancel(vp_ctx *);
 #define VP_FFT_GKR_FS_TAIL_LOG 11
 int vp_fft_gkr_fs(vp_ctx *, int lg, const uint8_t state_in[32], vp_F *msgs, uint64_t capacity, uint64_t *n_written,
                   vp_F *tape_out /* vp_fft_gkr_sizes' n_tape */, uint8_t state_out[32]);
+/* The GKR part NON-INTERACTIVE: Vres and every sumcheck of vp_prove_gkr, but the tape is not an argument — the device draws every challenge from the Fiat-Shamir
+ * chain that starts at state_in (steps E and C of host/vphost.h, "The transcript chain"; the counter of C runs from 0 over the draws of the call) and returns the
+ * tape it drew.  The schedule is vph_prove_fs's (host/vphost.h, "The GKR part on the device"):
+ *     r_liu[j] = C, j < bl(output layer); E(Vres); per layer from the top: assert_random = C; phase 1 per round E(a), E(b), E(c), r_u[j] = C; E(claim_u);
+ *     phase 2 (if the layer has one) per round E(a), E(b), E(c), r_v[j] = C; E(claim), `layer` of them; every entry of sig = C; the Liu sumcheck per round
+ *     E(a), E(b), E(c), r_liu[j] = C; E(vr).
+ * tape_out (vp_gkr_sizes' n_tape elements) holds the draws in the slots where vp_prove_gkr reads them, zero where the schedule draws nothing; transcript is
+ * vp_prove_gkr's layout, so vp_prove_gkr on tape_out returns the same bytes.  *n_draws: the number of challenges drawn; state_out: the chain behind E(vr).
+ * A challenge follows the polynomial it answers, so a round is a launch: the per-round kernels of vp_round with one more step on their closing lane, which
+ * absorbs the polynomial and draws the challenge the next round folds by (in the multi-workgroup form: lane 0 of the workgroup that arrives last); one
+ * single-lane launch between the sumchecks absorbs the claims and draws assert_random / sig.  The chain's state and counter stay in device memory; nothing
+ * waits on the host between the first draw and the one pinned block that returns transcript, tape, count and state.
+ * Refused with VP_EINVAL before anything is queued: a context not evaluated, a null argument (n_written may be null), capacity below vp_gkr_sizes' bytes, a
+ * chain-sharded (vp_set_shard), index-split (vp_set_shard_split) or round-sharded (vp_set_round_shard) context, a recording plan.  A deferred context is flushed
+ * first.  A sumcheck left open on the interactive entry points is abandoned, as by vp_vres.
+ * vp_get_stats after the call: rounds = the sumcheck rounds, launches = every launch of the call, gkr_ms = its device time.  Launch table (vp_set_profiling(1)), no
+ * kernel ids of its own: a round of more pairs than one workgroup takes (k_round_main_fs; VP_ROUND_FUSED_MAX) is a VP_K_ROUND row (workgroups, rounds = 1,
+ * first_round = the round, work = pairs), a single-lane launch a VP_K_MERKLE row with work = chain steps, as the draws of vp_fft_gkr_fs.                      */
+int vp_prove_gkr_fs(vp_ctx *, const uint8_t state_in[32], uint8_t *transcript, uint64_t capacity, uint64_t *n_written,
+                    vp_F *tape_out /* vp_gkr_sizes' n_tape */, uint64_t *n_draws, uint8_t state_out[32]);
 /* ---- the mask slice with CONTENT (round 6) ------------------------------------------------------------------------------------------------
  * lib/virgo's commit_private_array / commit_public_array take a mask vector that fills the 65th slice (lib/virgo/src/poly_commit.h:42,55-86,138-161,187-247).
  * The reference's own prover and verifier only ever pass one zero (src/prover.cpp:526, src/verifier.cpp:375-377): vp_commit_private / vp_commit_public.  These

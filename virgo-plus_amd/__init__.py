@@ -26,12 +26,12 @@ LIB_GPU_TESTDRV = os.path.join(ROOT, "tools", "_build", "testdrv", "libvpgpu.so"
 LIB_HOST = os.path.join(HOST, "libvphost.so")
 CLI = os.path.join(HOST, "virgo_plus_run")
 
-GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vpgpu_pc.inc", "vpgpu_pc_shard.inc", "vpgpu_pcverify.inc", "vp_kernels_pcverify.h", "vpgpu_fftgkr.inc", "vpgpu_upload.inc", "vp_kernels_fftgkr.h", "vp_kernels.h", "vp_kernels_round.h", "vp_kernels_persist.h", "vp_kernels_batch.h",
+GPU_SRC = [os.path.join(CSRC, f) for f in ("vpgpu.hip", "vpgpu_batched.inc", "vpgpu_pc.inc", "vpgpu_pc_shard.inc", "vpgpu_pcverify.inc", "vp_kernels_pcverify.h", "vpgpu_fftgkr.inc", "vpgpu_gkrfs.inc", "vpgpu_upload.inc", "vp_kernels_fftgkr.h", "vp_kernels_gkrfs.h", "vp_kernels.h", "vp_kernels_round.h", "vp_kernels_persist.h", "vp_kernels_batch.h",
                                               "vp_kernels_plan.h", "vp_kernels_pc.h", "vp_kernels_ntt8.h", "vp_kernels_ntt_long.h", "vp_keccak_asm.h", "vp_check.h", "vp_field.h", "vp_fri_layout.h", "vp_pc_live.h", "vp_pc_corners.h")] + [
     os.path.join(ROOT, "include", "vpgpu.h")]
 HOST_SRC = [os.path.join(HOST, f) for f in ("circuit.cpp", "prover.cpp", "verifier.cpp", "vphost.cpp")]
 HOST_HDR = [os.path.join(HOST, f) for f in ("circuit.hpp", "prover.hpp", "verifier.hpp", "vphost.h", "field.hpp",
-                                              "polynomial.hpp", "sha3.hpp", "pc_fs.hpp", "fft_gkr_fs.hpp", "fft_gkr_verify.hpp")]
+                                              "polynomial.hpp", "sha3.hpp", "pc_fs.hpp", "fft_gkr_fs.hpp", "gkr_fs.hpp", "fft_gkr_verify.hpp")]
 
 
 def _stale(target, sources):
@@ -262,6 +262,11 @@ def lib_host():
         L.vph_commitment_fs_challenges.argtypes = [vp, u64, vp, vp]
         L.vph_prove_full_fs.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_verify_full_fs.argtypes = [vp, vp, u64, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
+        L.vph_prove_full_fs_ex.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_prove_fs_ex.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(VphResult), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_gkr_sizes.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.vph_gkr_fs_tape.argtypes = [vp, vp, vp, u64, vp, ctypes.POINTER(u64), vp]
+        L.vph_prove_gkr_fs.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64), vp, ctypes.POINTER(u64), vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_fft_gkr_fs_tape.argtypes = [ctypes.c_int, vp, vp, u64, vp, vp]
         L.vph_fft_gkr_check.argtypes = [ctypes.c_int, vp, u64, vp, u64]
         L.vph_fft_gkr_fs.argtypes = [vp, ctypes.c_int, vp, vp, u64, vp, vp, ctypes.c_char_p, ctypes.c_int]
@@ -834,6 +839,32 @@ class Circuit:
             raise ValueError("fft_gkr_check: malformed tape or messages")
         return rc == 0
 
+    def gkr_sizes(self):
+        """(tape elements, transcript bytes) of the circuit's GKR part (vph_gkr_sizes): the sizes of vp_prove_gkr and vp_prove_gkr_fs.  No GPU."""
+        nt, nb = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if lib_host().vph_gkr_sizes(self.h, ctypes.byref(nt), ctypes.byref(nb)):
+            raise ValueError("gkr_sizes: a circuit of at least two layers")
+        return int(nt.value), int(nb.value)
+
+    def gkr_fs_tape(self, transcript, state):
+        """The GKR part of the Fiat-Shamir chain, the derivation alone (vph_gkr_fs_tape; the schedule: host/vphost.h, "The GKR part on the device"): from the
+        32-byte chain state and a GKR transcript in vp_prove_gkr's layout, the tape Session.prove_gkr_fs draws as an (n_tape, 2) uint64 array (slots the
+        schedule never draws zero), the number of draws and the closing state.  A walk over the bytes: nothing is verified.  No GPU.  Raises ValueError on a
+        state that is not 32 bytes, a transcript of another length than the circuit's, or a non-canonical limb."""
+        import numpy as np
+        state, transcript = bytes(state), bytes(transcript)
+        nt, nb = self.gkr_sizes()
+        if len(state) != 32 or len(transcript) != nb:
+            raise ValueError("gkr_fs_tape: a 32-byte state and a transcript of %d bytes" % nb)
+        tape = np.zeros((nt, 2), np.uint64)
+        st_in, st_out = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32)
+        buf = ctypes.create_string_buffer(transcript, max(len(transcript), 1))
+        nd = ctypes.c_uint64(0)
+        if lib_host().vph_gkr_fs_tape(self.h, ctypes.cast(st_in, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p), len(transcript), tape.ctypes.data, ctypes.byref(nd),
+                                      ctypes.cast(st_out, ctypes.c_void_p)):
+            raise ValueError("gkr_fs_tape: malformed transcript")
+        return tape, int(nd.value), st_out.raw
+
     def verify_fs(self, proof):
         """Verify a Fiat-Shamir proof (Session.prove_fs) on the host: no GPU, no tape."""
         buf = ctypes.create_string_buffer(bytes(proof), len(proof))
@@ -1029,10 +1060,36 @@ class Session:
         res["init_sec"], res["round_sec"], res["finalize_sec"] = b[0], b[1], b[2]
         return tr, res, rc == 0
 
-    def prove_fs(self):
-        """Non-interactive GKR proof (Fiat-Shamir over SHA3-256): returns (proof bytes, stats, accepted by the built-in verifier)."""
+    def prove_fs(self, device_draws=False):
+        """Non-interactive GKR proof (Fiat-Shamir over SHA3-256): returns (proof bytes, stats, accepted by the built-in verifier).
+        device_draws: the prover alone in one device pass (vph_prove_fs_ex with VPH_FS_DEVICE_GKR, vp_prove_gkr_fs) — every challenge drawn on the device, the
+        same bytes; nothing is verified and the third value is None: Circuit.verify_fs is the check.  Not on a sharded session."""
+        if device_draws:
+            tr, res, _ = self._call(lambda h, buf, cap, n, r, err, errlen: lib_host().vph_prove_fs_ex(h, buf, cap, n, r, 2, err, errlen))
+            return tr, res, None
         tr, res, rc = self._call(lib_host().vph_prove_fs)
         return tr, res, rc == 0
+
+    def prove_gkr_fs(self, state):
+        """The GKR part non-interactive on the session's GPU (vp_prove_gkr_fs, include/vpgpu.h): every challenge is drawn on the device from the Fiat-Shamir
+        chain that starts at the 32-byte `state`.  Returns (transcript bytes, tape, n_draws, state_out): the transcript in prove_gkr's layout, the draws in
+        prove_gkr's tape slots as an (n_tape, 2) uint64 array, their number, the closing state as bytes.  The host re-derives tape, count and state from the
+        transcript (Circuit.gkr_fs_tape's walk) and raises if the device's differ.  Not on a sharded session."""
+        import numpy as np
+        state = bytes(state)
+        if len(state) != 32:
+            raise ValueError("prove_gkr_fs: a 32-byte state")
+        nt, nb = self.circuit.gkr_sizes()
+        tape = np.zeros((nt, 2), np.uint64)
+        buf = ctypes.create_string_buffer(max(nb, 1))
+        st_in, st_out = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32)
+        n, nd = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        err = ctypes.create_string_buffer(512)
+        rc = lib_host().vph_prove_gkr_fs(self.h, ctypes.cast(st_in, ctypes.c_void_p), ctypes.cast(buf, ctypes.c_void_p), nb, ctypes.byref(n), tape.ctypes.data, ctypes.byref(nd),
+                                         ctypes.cast(st_out, ctypes.c_void_p), err, len(err))
+        if rc:
+            raise RuntimeError("prove_gkr_fs failed: " + err.value.decode())
+        return buf.raw[: n.value], tape, int(nd.value), st_out.raw
 
     def draw_tape(self):
         lib_host().vph_draw_tape(self.h)
@@ -1244,11 +1301,12 @@ class Session:
             raise RuntimeError("commit_fs failed: " + err.value.decode())
         return buf.raw[: ln.value]
 
-    def prove_full_fs(self, reps=33, mask=None, pub_mask=None, return_point=False):
+    def prove_full_fs(self, reps=33, mask=None, pub_mask=None, return_point=False, device_gkr=False):
         """The joined non-interactive proof of the whole protocol on the session's circuit and input (vph_prove_full_fs, host/vphost.h): commit_private(mask), the GKR
         part as prove_fs with the input check left to the commitment, commit_public_eq at the derived point, fft_gkr with its challenges drawn on the device, the
         FRI commit phase, final codewords, derived positions and their openings, on one Fiat-Shamir chain — one block of bytes for Circuit.verify_full_fs.
-        Not on a sharded session."""
+        device_gkr: the GKR part in one device pass with its challenges drawn on the device (vp_prove_gkr_fs) instead of the verifier-driven loop: the same
+        bytes; the prover's own GKR proof is then not verified on the way.  Not on a sharded session."""
         import numpy as np
         arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 2)
         m, pm = arr(mask), arr(pub_mask)
@@ -1260,8 +1318,8 @@ class Session:
         cap = 1 << 22
         for _ in range(2):                                     # a proof larger than the first buffer: the call reports its size and is made again
             buf = ctypes.create_string_buffer(cap)
-            rc = lib_host().vph_prove_full_fs(self.h, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), pt.ctypes.data,
-                                              err, len(err))
+            rc = lib_host().vph_prove_full_fs_ex(self.h, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), pt.ctypes.data,
+                                                 2 if device_gkr else 0, err, len(err))
             if rc != -1 or ln.value <= cap:
                 break
             cap = ln.value

@@ -11,7 +11,8 @@
 // assembled from pairs (T_k[2p], T_k[2p+1]).  Same field values, half the bytes.
 //
 // Files: vp_kernels_round.h (reductions, eq tables, evaluation, per-round kernels)  vp_kernels_batch.h (batched init +
-// fold kernels)  vp_kernels_plan.h (segment / closing kernels, batched launches)  vp_kernels_pc.h (polynomial commitment)  vp_kernels_fftgkr.h (circuit and tables of fft_gkr).
+// fold kernels)  vp_kernels_plan.h (segment / closing kernels, batched launches)  vp_kernels_pc.h (polynomial commitment)  vp_kernels_fftgkr.h (circuit and tables of fft_gkr)
+// vp_kernels_gkrfs.h (the per-round kernels with the Fiat-Shamir chain step on their closing lane).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vp_field.h"
@@ -23,3 +24,4 @@
 #include "vp_kernels_pc.h"
 #include "vp_kernels_pcverify.h"
 #include "vp_kernels_fftgkr.h"
+#include "vp_kernels_gkrfs.h"

@@ -598,7 +598,32 @@ int wait_ticket(vp_ctx *ctx) {
     }
 }
 
-int do_round(vp_ctx *ctx, const F *rp, const F &rv, F *poly_dev, F *poly_host) {
+// The launches of a round of vp_prove_gkr_fs (do_round has laid out `a`): the FS siblings of the three round kernels.  Every k_round_main_fs launch is a
+// VP_K_ROUND row of a profiled call, whatever its size.
+int do_round_fs(vp_ctx *ctx, const RoundArgs &a, u32 pairs, u64 bytes, F *poly_dev, GkrFs *fs, F *fs_slot) {
+    SumcheckState &s = ctx->sc;
+    const int k = s.round + 1;
+    if (pairs <= (u32) ctx->opt.round_fused_max) {
+        hipLaunchKernelGGL(k_round_fused_fs, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, a, ctx->add_term(), ctx->scalarV(), poly_dev, fs, fs_slot);
+    } else {                             // the same three cases as do_round
+        const RoundOut ro{ctx->add_term(), ctx->scalarV(), poly_dev, nullptr, nullptr, 0};
+        if (pairs) {
+            const u32 grid = grid_for(pairs);
+            const int sl = prof_begin(ctx, ctx->stream, VP_K_ROUND, grid, 1, bytes, pairs, 1, (u32) k);
+            hipLaunchKernelGGL(k_round_main_fs, dim3(grid), dim3(VP_BLOCK), 0, ctx->stream, a, ctx->partials, ctx->round_arrivals, ro, fs, fs_slot);
+            prof_end(ctx, ctx->stream, sl);
+        } else {
+            hipLaunchKernelGGL(k_round_final_fs, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, a, ro, fs, fs_slot);
+        }
+    }
+    count_launch(ctx);
+    s.round = k;
+    ++ctx->st.rounds;
+    return VP_OK;
+}
+
+// fs / fs_slot (vp_prove_gkr_fs): the closing lane also absorbs the polynomial into the chain at fs and draws the next challenge into *fs_slot
+int do_round(vp_ctx *ctx, const F *rp, const F &rv, F *poly_dev, F *poly_host, GkrFs *fs = nullptr, F *fs_slot = nullptr) {
     SumcheckState &s = ctx->sc;
     const int k = s.round + 1;
     RoundArgs a{};
@@ -630,6 +655,7 @@ int do_round(vp_ctx *ctx, const F *rp, const F &rv, F *poly_dev, F *poly_host) {
     }
     a.total_pairs = pairs;
     const u32 fused_max = (u32) ctx->opt.round_fused_max;
+    if (fs) return do_round_fs(ctx, a, pairs, bytes, poly_dev, fs, fs_slot);
     if (pairs <= fused_max) {            // one workgroup: fold + sums + closing in a single launch
         hipLaunchKernelGGL(k_round_fused, dim3(1), dim3(VP_BLOCK), 0, ctx->stream, a, ctx->add_term(), ctx->scalarV(), poly_dev, poly_host,
                            (poly_host && ctx->poll) ? ctx->h_seq : nullptr, ++ctx->seq);
@@ -1332,7 +1358,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     if (up_dbg) fprintf(stderr, "  shared %.3f", up_since());
     compute_layout(ctx);
     VPCHK(dalloc(ctx, &ctx->d_tape, (size_t) ctx->n_tape));
-    VPCHK(dalloc(ctx, &ctx->d_tr, (size_t) ctx->n_tr + 3 + VP_MAX_TAB));
+    VPCHK(dalloc(ctx, &ctx->d_tr, (size_t) ctx->n_tr + 3 + VP_MAX_TAB + sizeof(GkrFs) / sizeof(F)));      // ... | scratch of the interactive rounds | the chain of vp_prove_gkr_fs
     HIPCHK(hipMemset(ctx->d_tape, 0, ctx->n_tape * sizeof(F)));
     // ---- Liu jobs (src/prover.cpp:396,402-414): eq tables over r_u and every later layer's r_v ----
     for (int i = 1; i < n_layers; ++i) {
@@ -2195,3 +2221,4 @@ int vp_test_beta(vp_ctx *ctx, const vp_F *r, int n, const vp_F *init, vp_F *out)
 #include "vpgpu_pc_shard.inc"
 #include "vpgpu_pcverify.inc"
 #include "vpgpu_fftgkr.inc"
+#include "vpgpu_gkrfs.inc"

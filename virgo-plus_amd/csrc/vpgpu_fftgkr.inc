@@ -499,6 +499,8 @@ static void warm_kernel_functions() {
         (const void *) k_sumfold3b_multi, (const void *) k_sumfold3b_gen_multi, (const void *) k_seg_multi, (const void *) k_emit_multi, (const void *) k_fixup,
         (const void *) k_beta_half_direct, (const void *) k_beta_half_multi, (const void *) k_vres, (const void *) k_vres2, (const void *) k_tape_in, (const void *) k_ship, (const void *) k_ticket,
         (const void *) k_round_main<0>, (const void *) k_round_main<1>, (const void *) k_round_fused, (const void *) k_round_final, (const void *) k_finalize, (const void *) k_phase,
+        // vp_prove_gkr_fs
+        (const void *) k_gkr_fs_span, (const void *) k_round_main_fs, (const void *) k_round_fused_fs, (const void *) k_round_final_fs, (const void *) k_gkr_fs_ship,
     };
     for (const void *f : fns) { hipFuncAttributes a; (void) hipFuncGetAttributes(&a, f); }
     (void) hipGetLastError();

@@ -1,6 +1,7 @@
 #include "prover.hpp"
 #include "pc_fs.hpp"
 #include "fft_gkr_fs.hpp"
+#include "gkr_fs.hpp"
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -791,6 +792,34 @@ std::vector<F> prover::fftGkrFS(int lg, uint8_t state[32], std::vector<F> &tape)
     if (memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_fft_gkr_fs: the closing state is not the chain's");
     memcpy(state, st_out, 32);
     return msgs;
+}
+std::vector<uint8_t> prover::proveGkrFS(uint8_t state[32], std::vector<F> &tape, u64 &n_draws) {
+    if (world() > 1) throw std::runtime_error("proveGkrFS: not built for a sharded session");
+    const vph::GkrLayout L(C);
+    u64 nt = 0, nb = 0;
+    gkrSizes(nt, nb);
+    if (nt != L.n_tape || nb != L.n_tr * sizeof(F)) throw std::runtime_error("proveGkrFS: the device's tape / transcript sizes are not the circuit's");
+    std::vector<uint8_t> tr(nb);
+    tape.assign(nt, F_ZERO);
+    uint8_t st_out[32];
+    uint64_t written = 0, draws = 0;
+    prove_timer.start();
+    const int rc = vp_prove_gkr_fs(ctx, state, tr.data(), nb, &written, mF(tape.data()), &draws, st_out);
+    prove_timer.stop();
+    check(rc, "vp_prove_gkr_fs");
+    if (written != nb) throw std::runtime_error("vp_prove_gkr_fs: transcript size");
+    std::vector<F> elems(L.n_tr), want(nt);
+    memcpy(static_cast<void *>(elems.data()), tr.data(), nb);
+    vph::fs_chain ch;
+    memcpy(ch.s.w, state, 32);
+    const u64 want_draws = vph::gkrFsTape(C, L, ch, elems.data(), want.data());
+    for (u64 i = 0; i < nt; ++i)
+        if (memcmp(&want[i], &tape[i], sizeof(F))) throw std::runtime_error("vp_prove_gkr_fs: tape slot " + std::to_string(i) + " is not the chain's");
+    if (draws != want_draws) throw std::runtime_error("vp_prove_gkr_fs: the number of draws is not the schedule's");
+    if (memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_prove_gkr_fs: the closing state is not the chain's");
+    memcpy(state, st_out, 32);
+    n_draws = draws;
+    return tr;
 }
 double prover::commitDeviceMs() { double ms = 0; check(vp_commit_stats(ctx, &ms), "vp_commit_stats"); return ms; }
 

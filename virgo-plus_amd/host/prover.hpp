@@ -137,6 +137,11 @@ public:
     // messages, `tape` = the tape drawn, `state` = the closing state.  The tape and the state are re-derived here from the returned messages
     // (fft_gkr_fs.hpp); throws if either differs from what the device returned.
     std::vector<F> fftGkrFS(int lg, uint8_t state[32], std::vector<F> &tape);
+    // The GKR part non-interactive (vp_prove_gkr_fs): Vres and every sumcheck with the device drawing each challenge from the chain that starts at `state`
+    // (the schedule: vphost.h, "The GKR part on the device").  Returns the transcript (vp_prove_gkr's layout), `tape` = the draws in vp_prove_gkr's slots,
+    // `state` = the closing state, and the number of draws.  Tape, count and state are re-derived here from the returned transcript (gkr_fs.hpp: a walk over
+    // the bytes, no verifier sums); throws if any differs from what the device returned.  Throws on a sharded prover (not built).
+    std::vector<uint8_t> proveGkrFS(uint8_t state[32], std::vector<F> &tape, u64 &n_draws);
     double commitDeviceMs();
 
     double proveTime() const { return prove_timer.elapse_sec(); }

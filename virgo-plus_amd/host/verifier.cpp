@@ -1,6 +1,7 @@
 #include "verifier.hpp"
 #include "fft_gkr_verify.hpp"
 #include "fft_gkr_fs.hpp"
+#include "gkr_fs.hpp"
 #include "pc_fs.hpp"
 
 #include <algorithm>
@@ -120,6 +121,18 @@ bool verifier::proveFS() {
     const bool ok = run();
     fs = false;
     return ok;
+}
+u64 verifier::proveFSDevice() {
+    if (!p) throw std::runtime_error("proveFSDevice(): no prover attached");
+    replay = false; fs = false; tape_.clear(); tr.clear();
+    fsInit();
+    uint8_t st[32];
+    memcpy(st, fs_state.s.w, 32);
+    u64 draws = 0;
+    tr = p->proveGkrFS(st, tape_, draws);
+    memcpy(fs_state.s.w, st, 32);
+    fs_ctr = draws;
+    return draws;
 }
 bool verifier::checkFS(const std::vector<uint8_t> &proof) {
     static const std::vector<F> no_tape;
@@ -1005,7 +1018,7 @@ void verifier::fullFsHead(int n, u64 reps, u64 ms, const std::vector<F> &pub_mas
     for (u64 i = 0; i < n_pub; ++i) fs_state.elem(pub_mask[i].real, pub_mask[i].img);
     fs_state.digest(0, root_l);
 }
-std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask) {
+std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_gkr) {
     if (!p) throw std::runtime_error("proveFullFS(): no prover attached");
     if (p->world() > 1 || p->commitmentSharded()) throw std::runtime_error("proveFullFS: not built for a sharded session");
     const int n = C.circuit[0].bitLength, ln = n - 6;
@@ -1021,13 +1034,28 @@ std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_m
     }
     const std::vector<F> pm = ms > 1 ? pub_mask : std::vector<F>();
     // ---- the GKR part: run() in FS mode, the claim left to the commitment
-    replay = false; fs = true; tape_.clear(); tr.clear();
+    replay = false; fs = !device_gkr; tape_.clear(); tr.clear();
     fullFsHead(n, (u64) reps, ms, pm, root_l.b);
+    if (device_gkr) {
+        // the prover alone: every challenge drawn on the device; the point is r_liu of layer 1 in its tape slots, the claim the transcript's last element
+        uint8_t st[32];
+        memcpy(st, fs_state.s.w, 32);
+        u64 draws = 0;
+        tr = p->proveGkrFS(st, tape_, draws);
+        memcpy(fs_state.s.w, st, 32);
+        fs_ctr = draws;
+        const vph::GkrLayout L(C);
+        for (int j = 0; j < n; ++j) r_liu[j] = tape_[L.rl[1] + j];
+        unsigned long long w[2];
+        memcpy(w, tr.data() + tr.size() - 16, 16);
+        last_claim.real = w[0]; last_claim.img = w[1];
+    } else {
     input_check_by_commitment = true;
     bool ok = false;
     try { ok = run(); } catch (...) { fs = false; input_check_by_commitment = false; throw; }
     fs = false; input_check_by_commitment = false;
     if (!ok) throw std::runtime_error("proveFullFS: the GKR part of the prover's own proof is rejected");
+    }
     const std::vector<uint8_t> gkr = tr;
     full_fs_point_.assign(r_liu.begin(), r_liu.begin() + n);
     // ---- the commitment head

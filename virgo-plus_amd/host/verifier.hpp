@@ -75,12 +75,18 @@ public:
     //   proveFS()   runs the prover (interactive entry points, one vp_round per derived challenge); transcript() is the proof;
     //   checkFS()   needs no prover and no tape: re-derives every challenge from the proof and runs the same checks.
     bool proveFS();
+    // The same proof with the prover alone (vph_prove_fs_ex, VPH_FS_DEVICE_GKR): prover::proveGkrFS from the state behind fsInit() — the device draws every
+    // challenge, one pass, no host round trip per challenge and no verifier sums.  transcript() is the proof, the same bytes as proveFS(); tape() holds the
+    // draws in vp_prove_gkr's slots (not in draw order).  Nothing is verified here: checkFS is the check.  Returns the number of draws.
+    u64 proveFSDevice();
     bool checkFS(const std::vector<uint8_t> &proof);
     // The joined non-interactive proof of the whole protocol (chain and layout: vphost.h, "The joined proof"): commit_private, the GKR part exactly as run() in
     // FS mode with the input check by commitment, commit_public_eq at the derived point, fft_gkr with its challenges drawn on the device (vp_fft_gkr_fs), the
     // FRI commit phase from the state it leaves (vp_fri_commit_fs), the final codewords, the derived positions and their openings.  Throws on a sharded session,
     // an input layer below 2^7 wires, or a prover whose own proof the checks reject.
-    std::vector<uint8_t> proveFullFS(int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {});
+    // device_gkr: the GKR part is prover::proveGkrFS from the head's state instead of run() (the point from the tape's r_liu slots of layer 1, the claim from the
+    // transcript's last element); the same bytes, and the prover's own GKR proof is not verified here.
+    std::vector<uint8_t> proveFullFS(int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_gkr = false);
     // A verifier that holds only the circuit: parses under checkFull's rules, replays run(), derives every challenge, calls fft_gkr_check and pcVerifyCommitment
     // unchanged (dev: the commitment's heavy loops on a device context).  0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).
     int checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr);

@@ -19,8 +19,8 @@
 #include "verifier.hpp"
 
 int main(int argc, char **argv) {
-    if (argc < 2) { fprintf(stderr, "usage: %s <file.pws> [--blocks B] [--batched | --fs] [--device D] [--dump out.bin]\n", argv[0]); return 2; }
-    int blocks = 1, device = 0; bool batched = false, fsmode = false; const char *dump = nullptr, *record = nullptr, *check_record = nullptr;
+    if (argc < 2) { fprintf(stderr, "usage: %s <file.pws> [--blocks B] [--batched | --fs | --fs-device] [--device D] [--dump out.bin]\n", argv[0]); return 2; }
+    int blocks = 1, device = 0; bool batched = false, fsmode = false, fs_device = false; const char *dump = nullptr, *record = nullptr, *check_record = nullptr;
     bool device_verifier = false;
     int first = 2;
     if (!strcmp(argv[1], "--check-record")) {
@@ -33,6 +33,7 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
         else if (a == "--batched") batched = true;
         else if (a == "--fs") fsmode = true;
+        else if (a == "--fs-device") fsmode = fs_device = true;      // the same proof with every challenge drawn on the device (verifier::proveFSDevice)
         else if (a == "--device-verifier" && check_record) device_verifier = true;
         else if (a == "--seed" && i + 1 < argc) srandom((unsigned) atol(argv[++i]));      // witness draw (default: glibc's initial state, as the reference)
         else if (a == "--dump" && i + 1 < argc) dump = argv[++i];
@@ -70,7 +71,7 @@ int main(int argc, char **argv) {
         double vt = 0, pc_pt = -1;
         if (fsmode) {
             verifier v(&p, c);
-            ok = v.proveFS();
+            ok = fs_device ? (v.proveFSDevice(), true) : v.proveFS();
             tr = v.transcript();
             verifier w(nullptr, c);                  // a verifier that has only the proof
             ok = ok && w.checkFS(tr);

@@ -9,6 +9,7 @@
 
 #include "circuit.hpp"
 #include "fft_gkr_fs.hpp"
+#include "gkr_fs.hpp"
 #include "prover.hpp"
 #include "verifier.hpp"
 
@@ -181,6 +182,27 @@ int vph_prove_interactive(vph_session *s, uint8_t *transcript, uint64_t capacity
 }
 
 int vph_prove_fs(vph_session *s, uint8_t *proof, uint64_t capacity, uint64_t *n_written, vph_result *res, char *err, int errlen) {
+    return vph_prove_fs_ex(s, proof, capacity, n_written, res, 0, err, errlen);
+}
+int vph_prove_fs_ex(vph_session *s, uint8_t *proof, uint64_t capacity, uint64_t *n_written, vph_result *res, int flags, char *err, int errlen) {
+    if (flags & VPH_FS_DEVICE_GKR) {       // the prover alone: one device pass, nothing verified (vph_verify_fs is the check)
+        if (!s || !proof) { set_err(err, errlen, "vph_prove_fs_ex: a null argument"); return -1; }
+        try {
+            verifier v(s->p.get(), s->circ->c);
+            const double t0 = s->p->proveTime();
+            v.proveFSDevice();
+            const auto &tr = v.transcript();
+            if (tr.size() > capacity) { set_err(err, errlen, "proof buffer too small"); return -1; }
+            memcpy(proof, tr.data(), tr.size());
+            if (n_written) *n_written = tr.size();
+            fill(res, *s->p, s->p->proveTime() - t0, 0, false);
+            if (res) res->proof_kb = (double) tr.size() / 1024.0;
+            return 0;
+        } catch (const std::exception &e) {
+            set_err(err, errlen, e.what());
+            return -2;
+        }
+    }
     try {
         verifier v(s->p.get(), s->circ->c);
         const double t0 = s->p->proveTime();
@@ -623,10 +645,14 @@ int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r
 // ---- the joined non-interactive proof of the whole protocol (verifier::proveFullFS / checkFullFS) ----
 int vph_prove_full_fs(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
                       uint64_t *len, uint64_t *point_pairs, char *err, int errlen) {
+    return vph_prove_full_fs_ex(s, reps, mask_pairs, n_mask, pub_mask_pairs, n_pub_mask, out, cap, len, point_pairs, 0, err, errlen);
+}
+int vph_prove_full_fs_ex(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                         uint64_t *len, uint64_t *point_pairs, int flags, char *err, int errlen) {
     if (!s || !len || (n_mask && !mask_pairs) || (n_pub_mask && !pub_mask_pairs)) { set_err(err, errlen, "vph_prove_full_fs: a null argument"); return -1; }
     try {
         verifier v(s->p.get(), s->circ->c);
-        const std::vector<uint8_t> proof = v.proveFullFS(reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask));
+        const std::vector<uint8_t> proof = v.proveFullFS(reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask), (flags & VPH_FS_DEVICE_GKR) != 0);
         *len = proof.size();
         if (!out || cap < proof.size()) { set_err(err, errlen, "vph_prove_full_fs: output buffer too small (*len: the proof's size)"); return -1; }
         memcpy(out, proof.data(), proof.size());
@@ -651,6 +677,53 @@ int vph_verify_full_fs(vph_circuit *c, const uint8_t *proof, uint64_t len, int d
         return rc;
     } catch (const std::exception &e) {
         if (ctx) vp_destroy(ctx);
+        set_err(err, errlen, e.what());
+        return -2;
+    }
+}
+
+// ---- the GKR part of the chain (vphost.h, "The GKR part on the device"): sizes, the derivation alone (gkr_fs.hpp), the device call ----
+int vph_gkr_sizes(const vph_circuit *c, uint64_t *n_tape, uint64_t *n_transcript_bytes) {
+    if (!c || c->c.size < 2) return -1;
+    const vph::GkrLayout L(c->c);
+    if (n_tape) *n_tape = L.n_tape;
+    if (n_transcript_bytes) *n_transcript_bytes = L.n_tr * sizeof(F);
+    return 0;
+}
+int vph_gkr_fs_tape(const vph_circuit *c, const uint8_t state_in[32], const uint8_t *transcript, uint64_t n, uint64_t *tape_pairs, uint64_t *n_draws, uint8_t state_out[32]) {
+    if (!c || c->c.size < 2 || !state_in || !transcript || !tape_pairs || !n_draws || !state_out) return -1;
+    try {
+        const vph::GkrLayout L(c->c);
+        if (n != L.n_tr * sizeof(F)) return -1;                    // truncated or over-long
+        std::vector<F> tr(L.n_tr), tape(L.n_tape);
+        memcpy(static_cast<void *>(tr.data()), transcript, n);
+        for (const F &x : tr) if (x.real >= F::mod || x.img >= F::mod) return -1;
+        vph::fs_chain ch;
+        memcpy(ch.s.w, state_in, 32);
+        *n_draws = vph::gkrFsTape(c->c, L, ch, tr.data(), tape.data());
+        if (L.n_tape) memcpy(tape_pairs, tape.data(), L.n_tape * sizeof(F));
+        memcpy(state_out, ch.s.w, 32);
+        return 0;
+    } catch (const std::exception &) { return -1; }
+}
+int vph_prove_gkr_fs(vph_session *s, const uint8_t state_in[32], uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint64_t *tape_pairs, uint64_t *n_draws,
+                     uint8_t state_out[32], char *err, int errlen) {
+    if (!s || !state_in || !transcript || !tape_pairs || !n_draws || !state_out) { set_err(err, errlen, "vph_prove_gkr_fs: a null argument"); return -1; }
+    try {
+        const vph::GkrLayout L(s->circ->c);
+        if (capacity < L.n_tr * sizeof(F)) { set_err(err, errlen, "vph_prove_gkr_fs: transcript buffer size (vph_gkr_sizes)"); return -1; }
+        uint8_t st[32];
+        memcpy(st, state_in, 32);
+        std::vector<F> tape;
+        u64 draws = 0;
+        const std::vector<uint8_t> tr = s->p->proveGkrFS(st, tape, draws);
+        memcpy(transcript, tr.data(), tr.size());
+        if (n_written) *n_written = tr.size();
+        if (!tape.empty()) memcpy(tape_pairs, tape.data(), tape.size() * sizeof(F));
+        *n_draws = draws;
+        memcpy(state_out, st, 32);
+        return 0;
+    } catch (const std::exception &e) {
         set_err(err, errlen, e.what());
         return -2;
     }

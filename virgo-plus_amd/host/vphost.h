@@ -247,6 +247,38 @@ int vph_fft_gkr_check(int lg, const uint64_t *tape_pairs, uint64_t n_tape, const
  * the state from the returned messages and fails if the device's differ.  0 = done, -1 = a bad argument, -2 = refused or failed (err).                      */
 int vph_fft_gkr_fs(vph_session *, int lg, const uint8_t state_in[32], uint64_t *msgs_pairs, uint64_t cap_elems, uint64_t *tape_pairs, uint8_t state_out[32],
                    char *err, int errlen);
+/* The GKR part on the device (the transcript chain, continued).  vp_prove_gkr_fs (include/vpgpu.h) continues a chain of the steps above from a 32-byte state and draws every
+ * challenge of the GKR part on the device.  The schedule is vph_prove_fs's (verifier::run() in Fiat-Shamir mode), unchanged; the counter of C runs from 0 over the
+ * draws in the order below, whatever the slot a draw lands in:
+ *      1. r_liu[j] = C, j < the output layer's bit length
+ *      2. E(Vres)
+ *      3. per layer i from the top:
+ *           assert_random = C
+ *           phase 1: per round j < bitLength(i - 1): E(a), E(b), E(c), r_u[j] = C; then E(claim_u)
+ *           phase 2, if maxDadBitLength(i) != -1: per round j < maxDadBitLength(i): E(a), E(b), E(c), r_v[i][j] = C; then E of each of the i claims
+ *           sig[j] = C for all `size` entries
+ *           the Liu sumcheck: per round j < bitLength(i - 1): E(a), E(b), E(c), r_liu[j] = C; then E(vr)
+ * A draw never precedes the polynomial it challenges.  The draws are returned where vp_prove_gkr reads them (its tape layout: r_0 | per layer r_u[max_bl],
+ * assert_random, r_v, sig[size], r_liu[max_bl]); a slot the schedule never draws — the coordinates of r_u / r_liu beyond a layer's bit length — is zero.  The
+ * transcript is vp_prove_gkr's, hence vph_prove_fs's proof bytes; vp_prove_gkr on the returned tape returns it again.
+ * vph_gkr_sizes: the circuit's tape length (elements) and transcript size (bytes), no GPU.  vph_gkr_fs_tape: the derivation alone, by value, on the host — a walk
+ * over the transcript's bytes (no sumcheck is checked): the tape, the number of draws and the closing state from state_in and the n transcript bytes; 0, or -1 (a
+ * null pointer, n not the circuit's transcript size, a non-canonical limb).  vph_prove_gkr_fs: vp_prove_gkr_fs on the session's context (prover::proveGkrFS): the
+ * host re-derives tape, count and state from the returned transcript with that walk and fails if the device's differ.  0 = done, -1 = a bad argument (err),
+ * -2 = refused or failed (err: a sharded session, ...).
+ * vph_prove_fs_ex / vph_prove_full_fs_ex: vph_prove_fs / vph_prove_full_fs with flags.  0 is that call exactly.  VPH_FS_DEVICE_GKR: the GKR part is
+ * prover::proveGkrFS — the prover without the verifier in its loop: no host round trip per challenge, none of the verifier's O(|C|) sums — and the same bytes.
+ * With the flag nothing is verified: vph_prove_fs_ex returns 0 = done (res->verified = 0, res->gkr_device_ms = the call's device time), and vph_verify_fs /
+ * vph_verify_full_fs are the check.  In vph_prove_full_fs_ex the point is read from the tape's r_liu slots of layer 1 and the claim is the transcript's last
+ * element.                                                                                                                                                       */
+enum { VPH_FS_DEVICE_GKR = 2 };
+int vph_gkr_sizes(const vph_circuit *, uint64_t *n_tape, uint64_t *n_transcript_bytes);
+int vph_gkr_fs_tape(const vph_circuit *, const uint8_t state_in[32], const uint8_t *transcript, uint64_t n, uint64_t *tape_pairs, uint64_t *n_draws, uint8_t state_out[32]);
+int vph_prove_gkr_fs(vph_session *, const uint8_t state_in[32], uint8_t *transcript, uint64_t capacity, uint64_t *n_written, uint64_t *tape_pairs, uint64_t *n_draws,
+                     uint8_t state_out[32], char *err, int errlen);
+int vph_prove_fs_ex(vph_session *, uint8_t *proof, uint64_t capacity, uint64_t *n_written, vph_result *res, int flags, char *err, int errlen);
+int vph_prove_full_fs_ex(vph_session *, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                         uint64_t *len, uint64_t *point_pairs /* n, or null */, int flags, char *err, int errlen);
 /* ---- The joined proof: one block of bytes for the whole protocol, checked by a verifier that holds only the circuit ----------------------------------------------
  * No tape, no session, no input values.  The chain is the one above, in this order:
  *      1. the statement: the four words of layeredCircuit::statementDigest(with_inputs = false) — the digest of vph_prove_fs under another domain tag with the input
