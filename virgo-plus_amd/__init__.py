@@ -299,6 +299,7 @@ def lib_host():
         L.vph_commit_private.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_double), ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_fs.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(VphResult), ctypes.c_char_p, ctypes.c_int]
         L.vph_verify_fs.argtypes = [vp, vp, u64]
+        L.vph_last_gkr_failure.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
         L.vph_commit_device_ms.restype = ctypes.c_double
         L.vph_commit_device_ms.argtypes = [vp]
         L.vph_set_shard.argtypes = [vp, ctypes.c_int, ctypes.c_int]
@@ -309,6 +310,17 @@ def lib_host():
         L.vph_transcript_bytes.argtypes = [vp]
         _host = L
     return _host
+
+
+GKR_CHECKS = (None, "phase1", "phase2", "semi_final", "liu", "liu_semi_final", "input")
+
+
+def last_gkr_failure():
+    """The first failed check of this thread's last GKR replay (vph_last_gkr_failure, host/vphost.h): None, or (kind, layer, round) with kind one of GKR_CHECKS and
+    round -1 for a closing check.  Set by Circuit.verify_transcript(_tape), verify_fs, verify_full_record, verify_full_fs and Session.check."""
+    layer, rnd = ctypes.c_int(0), ctypes.c_int(-1)
+    kind = lib_host().vph_last_gkr_failure(ctypes.byref(layer), ctypes.byref(rnd))
+    return (GKR_CHECKS[kind], layer.value, rnd.value) if kind else None
 
 
 def sum_transcripts(parts):

@@ -23,6 +23,16 @@ void initBetaTable(std::vector<F> &beta, int n, const std::vector<F>::const_iter
     }
 }
 
+namespace {
+thread_local GkrFailure gkr_failure;
+bool gkrFails(int kind, int layer, int round) { gkr_failure.kind = kind; gkr_failure.layer = layer; gkr_failure.round = round; return false; }
+}  // namespace
+GkrFailure lastGkrFailure() { return gkr_failure; }
+const char *gkrCheckName(int kind) {
+    static const char *const names[] = {"none", "phase1", "phase2", "semi_final", "liu", "liu_semi_final", "input"};
+    return kind >= 0 && kind <= GKR_INPUT ? names[kind] : "?";
+}
+
 verifier::verifier(prover *pr, const layeredCircuit &cir) : p(pr), C(cir) {       // verifier.cpp:12-48
     final_claims_v.resize(C.size);
     for (int i = 1; i < C.size; ++i) final_claims_v[i].assign(i, F_ZERO);
@@ -152,6 +162,7 @@ bool verifier::check(const std::vector<F> &tape, const std::vector<uint8_t> &tra
 
 bool verifier::run() {                          // verifier.cpp:134-169 (GKR part)
     // a verification starts here: the launch log of the device its loops run on (prover::verifierLaunches) starts with it
+    gkr_failure = GkrFailure{};
     if (pred_dev) pred_dev->clearLaunchLog();
     if (poly_dev && poly_dev != pred_dev) poly_dev->clearLaunchLog();
     for (int i = 0; i < C.circuit[C.size - 1].bitLength; ++i) r_liu[i] = draw();
@@ -172,7 +183,7 @@ bool verifier::run() {                          // verifier.cpp:134-169 (GKR par
             verify_timer.stop();
             if (previousSum != test_value) {
                 fprintf(stderr, "Verification fail, semi final, circuit level %d\n", i);
-                return false;
+                return gkrFails(GKR_SEMI_FINAL, i, -1);
             }
         }
         if (!verifyLiu(i, previousSum)) return false;
@@ -192,7 +203,7 @@ bool verifier::verifyPhase1(int layer_id, F &previousSum) {      // verifier.cpp
         const quadratic_poly poly = nextPoly(1, previousRandom);
         if (poly.eval(F_ZERO) + poly.eval(F_ONE) != previousSum) {
             fprintf(stderr, "Verification fail, phase1, circuit %d, current bit %d\n", layer_id, j);
-            return false;
+            return gkrFails(GKR_PHASE1, layer_id, j);
         }
         if (fs) r_u[j] = draw();                    // Fiat-Shamir: the challenge of round j follows its polynomial
         previousRandom = r_u[j];
@@ -212,7 +223,7 @@ bool verifier::verifyPhase2(int layer_id, F &previousSum) {      // verifier.cpp
         const quadratic_poly poly = nextPoly(2, previousRandom);
         if (poly.eval(F_ZERO) + poly.eval(F_ONE) != previousSum) {
             fprintf(stderr, "Verification fail, phase2, circuit level %d, current bit %d\n", layer_id, j);
-            return false;
+            return gkrFails(GKR_PHASE2, layer_id, j);
         }
         if (fs) r_v[layer_id][j] = draw();
         previousRandom = r_v[layer_id][j];
@@ -240,7 +251,7 @@ bool verifier::verifyLiu(int layer_id, F &previousSum) {         // verifier.cpp
         const quadratic_poly poly = nextPoly(3, previousRandom);
         if (poly.eval(F_ZERO) + poly.eval(F_ONE) != previousSum) {
             fprintf(stderr, "Liu fail, circuit %d, current bit %d\n", layer_id, j);
-            return false;
+            return gkrFails(GKR_LIU, layer_id, j);
         }
         if (fs) r_liu[j] = draw();
         previousRandom = r_liu[j];
@@ -266,7 +277,7 @@ bool verifier::verifyLiu(int layer_id, F &previousSum) {         // verifier.cpp
     }
     const bool ok = (vr * gr == previousSum);
     verify_timer.stop();
-    if (!ok) { fprintf(stderr, "Liu fail, semi final, circuit %d\n", layer_id); return false; }
+    if (!ok) { fprintf(stderr, "Liu fail, semi final, circuit %d\n", layer_id); return gkrFails(GKR_LIU_SEMI_FINAL, layer_id, -1); }
     previousSum = vr;
     return true;
 }
@@ -343,14 +354,14 @@ F verifier::getFinalValue(int layer_id, const F &cu, const std::vector<F> &cv) {
 bool verifier::checkInput(const F &claim) {
     const layer &L0 = C.circuit[0];
     if (pred_dev) {                                       // the input layer's MLE at r_liu on the device (vp_layer_mle)
-        if (pred_dev->layerMle(0, r_liu, L0.bitLength) != claim) { fprintf(stderr, "Verification fail, final input check fail.\n"); return false; }
+        if (pred_dev->layerMle(0, r_liu, L0.bitLength) != claim) { fprintf(stderr, "Verification fail, final input check fail.\n"); return gkrFails(GKR_INPUT, 0, -1); }
         return true;
     }
     std::vector<F> beta;
     initBetaTable(beta, L0.bitLength, r_liu.begin(), F_ONE);
     F acc = F_ZERO;
     for (u64 g = 0; g < L0.size; ++g) acc = acc + beta[g] * F((long long) L0.gates[g].u);
-    if (acc != claim) { fprintf(stderr, "Verification fail, final input check fail.\n"); return false; }
+    if (acc != claim) { fprintf(stderr, "Verification fail, final input check fail.\n"); return gkrFails(GKR_INPUT, 0, -1); }
     return true;
 }
 
@@ -647,7 +658,7 @@ bool verifier::verifyPoly(const prover::hhash_digest &root_l_raw, const F &claim
     { const uint8_t *b = reinterpret_cast<const uint8_t *>(all_sum.data()); full_tr.insert(full_tr.end(), b, b + 65 * 16); }
     const vph::hhash_digest root_h = dig(root_h_raw);
     poly_timer.start();
-    if (claim != input_0) { fprintf(stderr, "Verification fail, final input check fail.\n"); return false; }   // verifier.cpp:383
+    if (claim != input_0) { fprintf(stderr, "Verification fail, final input check fail.\n"); return gkrFails(GKR_INPUT, 0, -1); }   // verifier.cpp:383
     std::vector<F> fr(ln);
     PcSliceCheck chk(n, mask_ms, all_sum, fr);
     auto failed = [&](const std::string &why) { if (why.empty()) return false; fprintf(stderr, "%s\n", why.c_str()); return true; };
@@ -1140,7 +1151,12 @@ int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ct
     fs = false; input_check_by_commitment = false;
     if (malformed) return -1;
     full_fs_point_.assign(r_liu.begin(), r_liu.begin() + n);      // as far as the replay got: a rejected GKR part leaves the coordinates it had derived
-    if (!ok) { why = "the GKR part is rejected (a sumcheck round, a layer's final value or a Liu sumcheck)"; return 1; }
+    if (!ok) {
+        const GkrFailure f = lastGkrFailure();
+        why = "the GKR part is rejected (a sumcheck round, a layer's final value or a Liu sumcheck): " + std::string(gkrCheckName(f.kind)) + ", layer " + std::to_string(f.layer) +
+              ", round " + std::to_string(f.round);
+        return 1;
+    }
     at += tr_pos;
     c.point = full_fs_point_;
     // ---- the sections behind it
@@ -1166,7 +1182,7 @@ int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ct
     for (u64 k = 0; k < ln; ++k) { F next; if (pcFsLevel(ch, (int) k, (int) ln, &c.fri_roots[32 * k], &next)) c.fr[k + 1] = next; }
     c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask);
     // ---- the checks: nothing of the joined proof's own beyond the hand-over of the claim
-    if (last_claim != c.claim) { why = "the GKR part's claim on the input layer is not input_0 (final input check)"; return 1; }
+    if (last_claim != c.claim) { gkrFails(GKR_INPUT, 0, -1); why = "the GKR part's claim on the input layer is not input_0 (final input check)"; return 1; }
     if (!vph::fft_gkr_check<F>((int) ln, ftape.data(), ftape.size(), fmsgs.data(), fmsgs.size(), F::getRootOfUnity((int) ln).inv())) { why = "fft_gkr is rejected"; return 1; }
     return pcVerifyCommitment(c, why, dev);
 }

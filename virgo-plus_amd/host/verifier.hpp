@@ -17,6 +17,13 @@
 #include "sha3.hpp"
 #include "pc_fs.hpp"
 
+// The first failed check of the GKR part (run, verifyPhase1, verifyPhase2, verifyLiu, checkInput and the hand-over of the claim to the commitment) in the calling
+// thread's last run or replay: kind GKR_NONE when every check held (a malformed transcript is rejected without one).  round: -1 for a closing check.
+enum GkrCheck { GKR_NONE = 0, GKR_PHASE1 = 1, GKR_PHASE2 = 2, GKR_SEMI_FINAL = 3, GKR_LIU = 4, GKR_LIU_SEMI_FINAL = 5, GKR_INPUT = 6 };
+struct GkrFailure { int kind = GKR_NONE, layer = 0, round = -1; };
+GkrFailure lastGkrFailure();
+const char *gkrCheckName(int kind);
+
 class verifier {
 public:
     verifier(prover *pr, const layeredCircuit &cir);

@@ -1096,6 +1096,13 @@ int vph_verify_transcript_tape(vph_circuit *c, const uint64_t *tape_pairs, uint6
     } catch (const std::exception &) { return 1; }
 }
 
+int vph_last_gkr_failure(int *layer, int *round) {
+    const GkrFailure f = lastGkrFailure();
+    if (layer) *layer = f.layer;
+    if (round) *round = f.round;
+    return f.kind;
+}
+
 uint64_t vph_transcript_bytes(vph_session *s) {
     u64 a = 0, b = 0;
     s->p->gkrSizes(a, b);

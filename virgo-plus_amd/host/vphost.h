@@ -389,6 +389,14 @@ int vph_verify_transcript_tape(vph_circuit *, const uint64_t *tape_pairs, uint64
 int vph_prove_fs(vph_session *, uint8_t *proof, uint64_t capacity, uint64_t *n_written, vph_result *res, char *err, int errlen);
 /* No GPU, no tape: re-derive the challenges from `proof` and run the verifier's checks.  0 = accepted, 1 = rejected.   */
 int vph_verify_fs(vph_circuit *, const uint8_t *proof, uint64_t n);
+/* Which check of the GKR part rejected: the first failed check of the calling thread's last GKR replay, through vph_verify_transcript(_tape), vph_verify_fs,
+ * vph_check, vph_verify_full_record(_dev) and vph_verify_full_fs.  Returns the kind: 0 none (accepted, or rejected without a failed check: a transcript of the
+ * wrong length or with a non-canonical element), 1 phase1 / 2 phase2 / 4 liu (a sumcheck round: p(0) + p(1) against the running claim), 3 semi_final (a layer's
+ * closing value from the wiring predicates), 5 liu_semi_final (vr * gr against the Liu sumcheck's last value), 6 input (the last claim against the input layer, or
+ * against the commitment's input_0 where the commitment takes the claim over: then the replay's other checks all held).  *layer: the layer the check belongs to
+ * (0 for input); *round: the round, -1 for a closing check.  Either pointer may be null.  A call that never reaches the replay (a tape that does not fit, a
+ * malformed header) leaves the previous answer.                                                                                                                  */
+int vph_last_gkr_failure(int *layer, int *round);
 /* vp_commit_stats: device milliseconds of the last commit_private / commit_public / FRI call on this session. */
 double vph_commit_device_ms(vph_session *);
 /* One proof over `world` GPUs (vp_set_shard): vph_prove_gkr on this session then proves only the sumchecks dealt to `rank`
