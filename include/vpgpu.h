@@ -681,6 +681,22 @@ int vp_test_fft(vp_ctx *, const vp_F *coefs, int coef_len, int order, int invers
  * (low 61 bits, p -> 0) -> state_out, the first two also -> r_out; state, label and counter are not read.                                             */
 int vp_test_fs_draw(vp_ctx *, int op, const uint8_t state[32], const uint8_t root[32], uint64_t label, uint64_t counter, uint8_t state_out[32], vp_F *r_out);
 
+/* ---- the proof of work of the non-interactive proofs (grinding; the step's text: host/vphost.h, "The proof of work") ----------------------------------------
+ * W(bits, nonce) is the chain step state = SHA3-256({nonce, bits, 0, 0x57} || state), words little-endian u64; the work is met when the low `bits` bits of the
+ * new state's first word are zero.  vp_fs_grind returns the SMALLEST nonce in [first, first + max_tries) that meets it, and the state behind W — the same on
+ * every run.  It needs no circuit: any context will do.
+ * VP_ELIMIT: the range holds no such nonce (nonce and state_out untouched).  VP_EINVAL, before anything is queued: a null pointer, bits outside 1 .. 48,
+ * max_tries = 0, a range that would pass 2^64 (first + max_tries > 2^64).
+ * The search (k_fs_grind) runs as ascending, disjoint windows queued in stream order: window w holds 2^min(16 + 2 w, 24) nonces, the last one cut at max_tries;
+ * eight windows are queued per host wait.  24 and eight are the defaults of the internal tuning grind_window_log / grind_batch (VP_GRIND_WINDOW_LOG 16 .. 28,
+ * VP_GRIND_BATCH 1 .. 64 at vp_create: tests / A-B only, profiles/fs_grind.md); they move the windows and the launch table, never the answer.  A window first reads the hit slot and leaves at once if an earlier window has a hit, so the result is the minimum
+ * of the first window with a hit.  Every launch does a bounded amount of work; no kernel waits on a flag or on the host.
+ * Launch table (vp_set_profiling(1)): one row per window launched, kind VP_K_FS_GRIND (vp_kernel_name: "k_fs_grind"), first_round = w, rounds = nonces per
+ * lane, jobs = the workgroups that searched, work = the Keccak-f they evaluated (their nonces; 0 for a window queued behind a hit); the closing one-lane
+ * launch that computes state_out has no row.  VP_K_FS_GRIND stands outside the enum above, whose last entry other code relies on.                       */
+enum { VP_K_FS_GRIND = VP_K_COUNT };
+int vp_fs_grind(vp_ctx *, const uint8_t state_in[32], int bits, uint64_t first, uint64_t max_tries, uint64_t *nonce, uint8_t state_out[32]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,7 @@ def lib_gpu():
         L.vp_fri_commit.argtypes = [vp, vp, ctypes.c_int, vp]
         L.vp_fri_commit_fs.argtypes = [vp, vp, vp, vp, vp]
         L.vp_test_fs_draw.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp]
+        L.vp_fs_grind.argtypes = [vp, vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), vp]
         L.vp_fri_step.argtypes = [vp, vp, vp]
         L.vp_commit_private_masked.argtypes = [vp, vp, ctypes.c_uint64, vp]
         L.vp_shard_pending.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
@@ -263,6 +264,12 @@ def lib_host():
         L.vph_prove_full_fs.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_verify_full_fs.argtypes = [vp, vp, u64, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_full_fs_ex.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_fs_grind_host.argtypes = [vp, ctypes.c_int, u64, u64, ctypes.POINTER(u64), vp]
+        L.vph_commit_fs_pow.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, u64, vp, u64, ctypes.c_int, ctypes.c_int, vp, u64, ctypes.POINTER(u64), ctypes.c_char_p, ctypes.c_int]
+        L.vph_verify_commitment_fs_min.argtypes = [vp, u64, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_fs_pow.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.vph_prove_full_fs_pow.argtypes = [vp, ctypes.c_int, vp, u64, vp, u64, vp, u64, ctypes.POINTER(u64), vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.vph_verify_full_fs_min.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, vp, ctypes.c_char_p, ctypes.c_int]
         L.vph_prove_fs_ex.argtypes = [vp, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(VphResult), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.vph_gkr_sizes.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.vph_gkr_fs_tape.argtypes = [vp, vp, vp, u64, vp, ctypes.POINTER(u64), vp]
@@ -313,6 +320,32 @@ def lib_host():
 
 
 GKR_CHECKS = (None, "phase1", "phase2", "semi_final", "liu", "liu_semi_final", "input")
+
+
+def _fs_grind_args(state, bits, first, max_tries):
+    state, bits, first = bytes(state), int(bits), int(first)
+    if len(state) != 32:
+        raise ValueError("fs_grind: a 32-byte state")
+    if max_tries is None:                                      # 64 x 2^bits tries, as the provers search, cut at 2^64
+        max_tries = min(64 << max(bits, 0), (1 << 64) - first) if 0 <= first < 1 << 64 else 0
+    max_tries = int(max_tries)
+    if not (1 <= bits <= 48 and 0 <= first < 1 << 64 and 1 <= max_tries and first + max_tries <= 1 << 64):
+        raise ValueError("fs_grind: bits in 1..48 and a non-empty range [first, first + max_tries) within 2^64")
+    return state, bits, first, max_tries
+
+
+def fs_grind_host(state, bits, first=0, max_tries=None):
+    """The proof-of-work search on the CPU (vph_fs_grind_host, host/vphost.h): the smallest nonce in [first, first + max_tries) whose chain step
+    W(bits, nonce) on the 32-byte `state` leaves the low `bits` bits of the new state's first word zero.  Returns (nonce, state_out); raises ValueError on
+    arguments outside the limits and RuntimeError when the range holds no such nonce.  max_tries None: 64 x 2^bits."""
+    state, bits, first, max_tries = _fs_grind_args(state, bits, first, max_tries)
+    st_in, st_out, nonce = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+    rc = lib_host().vph_fs_grind_host(ctypes.cast(st_in, ctypes.c_void_p), bits, first, max_tries, ctypes.byref(nonce), ctypes.cast(st_out, ctypes.c_void_p))
+    if rc == -5:
+        raise RuntimeError("fs_grind_host: no nonce in the range meets the work")
+    if rc:
+        raise ValueError("fs_grind_host: refused")
+    return int(nonce.value), st_out.raw
 
 
 def last_gkr_failure():
@@ -772,14 +805,15 @@ class Circuit:
         return rc == 0, err.value.decode() if rc else ""
 
     @staticmethod
-    def verify_commitment_fs(proof, device=None):
+    def verify_commitment_fs(proof, device=None, min_pow_bits=0):
         """Verify a non-interactive commitment proof (Session.commit_fs; layout and chain: host/vphost.h): no tape, no session, no circuit.  The fold challenges
         and query positions are derived from the proof itself, then verify_commitment's checks run unchanged.  device=k: the heavy loops on GPU k.  Returns
-        (accepted, reason); raises ValueError on a malformed proof and RuntimeError when the device could not run the loops."""
+        (accepted, reason); raises ValueError on a malformed proof and RuntimeError when the device could not run the loops.  min_pow_bits: the proof of work
+        the verifier demands (commit_fs(pow_bits=)); a proof that carries less, or whose work is not met, is rejected."""
         proof = bytes(proof)
         buf = ctypes.create_string_buffer(proof, max(len(proof), 1))
         err = ctypes.create_string_buffer(512)
-        rc = lib_host().vph_verify_commitment_fs(ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), err, len(err))
+        rc = lib_host().vph_verify_commitment_fs_min(ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), int(min_pow_bits), err, len(err))
         if rc == -1:
             raise ValueError("verify_commitment_fs: " + err.value.decode())
         if rc < 0:
@@ -804,17 +838,30 @@ class Circuit:
             raise ValueError("commitment_fs_challenges: malformed proof")
         return r, [int(x) for x in lf]
 
-    def verify_full_fs(self, proof, device=None, return_point=False):
+    @staticmethod
+    def fs_pow(proof):
+        """(pow_bits, nonce) of a commitment proof or a joined proof, read from its header (vph_fs_pow): (0, 0) for a version-1 proof.  Raises ValueError on a
+        malformed header."""
+        proof = bytes(proof)
+        buf = ctypes.create_string_buffer(proof, max(len(proof), 1))
+        bits, nonce = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        if lib_host().vph_fs_pow(ctypes.cast(buf, ctypes.c_void_p), len(proof), ctypes.byref(bits), ctypes.byref(nonce)):
+            raise ValueError("fs_pow: malformed proof")
+        return int(bits.value), int(nonce.value)
+
+    def verify_full_fs(self, proof, device=None, return_point=False, min_pow_bits=0):
         """Verify a joined non-interactive proof of the whole protocol (Session.prove_full_fs; chain and layout: host/vphost.h, "The joined proof") holding only this
         circuit: no tape, no session, no input values.  device=k: the commitment's heavy loops on GPU k.  Returns (accepted, reason) — with return_point also the
-        derived point as an (n, 2) uint64 array (a rejected GKR part: as far as its replay got); raises ValueError on a malformed proof and RuntimeError without the device."""
+        derived point as an (n, 2) uint64 array (a rejected GKR part: as far as its replay got); raises ValueError on a malformed proof and RuntimeError without the device.
+        min_pow_bits: the proof of work the verifier demands (prove_full_fs(pow_bits=)); a proof that carries less, or whose work is not met, is rejected."""
         import numpy as np
         proof = bytes(proof)
         buf = ctypes.create_string_buffer(proof, max(len(proof), 1))
         err = ctypes.create_string_buffer(512)
         n = self.layer_bitlen(0)
         pt = np.full((max(n, 1), 2), (1 << 64) - 1, np.uint64)
-        rc = lib_host().vph_verify_full_fs(self.h, ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), pt.ctypes.data, err, len(err))
+        rc = lib_host().vph_verify_full_fs_min(self.h, ctypes.cast(buf, ctypes.c_void_p), len(proof), -1 if device is None else int(device), int(min_pow_bits), pt.ctypes.data,
+                                               err, len(err))
         if rc == -1:
             raise ValueError("verify_full_fs: " + err.value.decode())
         if rc < 0:
@@ -896,7 +943,8 @@ _TUNING_ENV = {"gkr_path": "VP_GKR_PATH", "serial": "VP_GKR_SERIAL", "fuse_init"
                "dot_blocks": "VP_DOT_BLOCKS", "plan_align": "VP_PLAN_ALIGN", "round_fused_max": "VP_ROUND_FUSED_MAX",
                "kernel_copies": "VP_KERNEL_COPIES", "fold_branches": "VP_FOLD_BRANCHES", "fuse_combine": "VP_FUSE_COMBINE",
                "graph_explicit": "VP_GRAPH_EXPLICIT", "ntt_r8": "VP_NTT_R8", "fuse_p2": "VP_FUSE_P2", "leaf_asm": "VP_LEAF_ASM",
-               "fft_gkr_batched": "VP_FFT_GKR_BATCHED", "split_vu": "VP_SPLIT_VU", "pc_live": "VP_PC_LIVE"}
+               "fft_gkr_batched": "VP_FFT_GKR_BATCHED", "split_vu": "VP_SPLIT_VU", "pc_live": "VP_PC_LIVE",
+               "grind_window_log": "VP_GRIND_WINDOW_LOG", "grind_batch": "VP_GRIND_BATCH"}
 VP_OPTIONS_ABI = 0x76700005
 
 
@@ -1292,12 +1340,27 @@ class Session:
             raise RuntimeError("vp_commit_public_eq failed: %d %s" % (rc, (lib_gpu().vp_last_error(ctx) or b"").decode()))
         return out.raw[:32], out.raw[32:48], out.raw[48:], self.commit_device_ms()
 
-    def commit_fs(self, point, reps=33, mask=None, pub_mask=None, device_draws=True):
+    def fs_grind(self, state, bits, first=0, max_tries=None):
+        """The proof-of-work search on the session's GPU (vp_fs_grind, include/vpgpu.h): the smallest nonce in [first, first + max_tries) whose chain step
+        W(bits, nonce) on the 32-byte `state` leaves the low `bits` bits of the new state's first word zero.  Returns (nonce, state_out); raises ValueError on
+        arguments outside the limits and RuntimeError when the range holds no such nonce (VP_ELIMIT).  max_tries None: 64 x 2^bits."""
+        state, bits, first, max_tries = _fs_grind_args(state, bits, first, max_tries)
+        ctx = lib_host().vph_session_ctx(self.h)
+        st_in, st_out, nonce = ctypes.create_string_buffer(state, 32), ctypes.create_string_buffer(32), ctypes.c_uint64(0)
+        rc = lib_gpu().vp_fs_grind(ctx, ctypes.cast(st_in, ctypes.c_void_p), bits, first, max_tries, ctypes.byref(nonce), ctypes.cast(st_out, ctypes.c_void_p))
+        if rc:
+            raise RuntimeError("fs_grind failed: %d %s" % (rc, (lib_gpu().vp_last_error(ctx) or b"").decode()))
+        return int(nonce.value), st_out.raw
+
+    def commit_fs(self, point, reps=33, mask=None, pub_mask=None, device_draws=True, pow_bits=0):
         """The non-interactive commitment proof of the session's input layer at `point` (vph_commit_fs, host/vphost.h): one block of bytes for
         Circuit.verify_commitment_fs.  mask / pub_mask: the vectors of a hiding commitment, as for commit_private(mask) and commit_public_eq(pub_mask=).
         device_draws: the commit phase draws every fold challenge on the device (vp_fri_commit_fs); False: the vp_fri_step loop with the chain on the host —
-        the same bytes.  Not on a session with a sharded commitment."""
+        the same bytes.  pow_bits (0 .. 32): grind that many bits of proof of work in front of the query positions (a version-2 proof; the search is
+        fs_grind, with device_draws=False the host's); 0: the version-1 proof.  Not on a session with a sharded commitment."""
         import numpy as np
+        if not 0 <= int(pow_bits) <= 32:
+            raise ValueError("commit_fs: pow_bits in 0..32")
         arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 2)
         pt, m, pm = arr(point), arr(mask), arr(pub_mask)
         ptr = lambda a: a.ctypes.data if a is not None and a.shape[0] else None
@@ -1307,19 +1370,22 @@ class Session:
         buf = ctypes.create_string_buffer(cap)
         ln = ctypes.c_uint64(0)
         err = ctypes.create_string_buffer(512)
-        rc = lib_host().vph_commit_fs(self.h, pt.ctypes.data, n, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), 0 if device_draws else 1, ctypes.cast(buf, ctypes.c_void_p), cap,
-                                      ctypes.byref(ln), err, len(err))
+        rc = lib_host().vph_commit_fs_pow(self.h, pt.ctypes.data, n, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), 0 if device_draws else 1, int(pow_bits),
+                                          ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), err, len(err))
         if rc:
             raise RuntimeError("commit_fs failed: " + err.value.decode())
         return buf.raw[: ln.value]
 
-    def prove_full_fs(self, reps=33, mask=None, pub_mask=None, return_point=False, device_gkr=False):
+    def prove_full_fs(self, reps=33, mask=None, pub_mask=None, return_point=False, device_gkr=False, pow_bits=0):
         """The joined non-interactive proof of the whole protocol on the session's circuit and input (vph_prove_full_fs, host/vphost.h): commit_private(mask), the GKR
         part as prove_fs with the input check left to the commitment, commit_public_eq at the derived point, fft_gkr with its challenges drawn on the device, the
         FRI commit phase, final codewords, derived positions and their openings, on one Fiat-Shamir chain — one block of bytes for Circuit.verify_full_fs.
         device_gkr: the GKR part in one device pass with its challenges drawn on the device (vp_prove_gkr_fs) instead of the verifier-driven loop: the same
-        bytes; the prover's own GKR proof is then not verified on the way.  Not on a sharded session."""
+        bytes; the prover's own GKR proof is then not verified on the way.  pow_bits (0 .. 32): grind that many bits of proof of work in front of the query
+        positions (a version-2 proof, the search on the device); 0: the version-1 proof.  Not on a sharded session."""
         import numpy as np
+        if not 0 <= int(pow_bits) <= 32:
+            raise ValueError("prove_full_fs: pow_bits in 0..32")
         arr = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 2)
         m, pm = arr(mask), arr(pub_mask)
         ptr = lambda a: a.ctypes.data if a is not None and a.shape[0] else None
@@ -1330,8 +1396,8 @@ class Session:
         cap = 1 << 22
         for _ in range(2):                                     # a proof larger than the first buffer: the call reports its size and is made again
             buf = ctypes.create_string_buffer(cap)
-            rc = lib_host().vph_prove_full_fs_ex(self.h, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), pt.ctypes.data,
-                                                 2 if device_gkr else 0, err, len(err))
+            rc = lib_host().vph_prove_full_fs_pow(self.h, int(reps), ptr(m), cnt(m), ptr(pm), cnt(pm), ctypes.cast(buf, ctypes.c_void_p), cap, ctypes.byref(ln), pt.ctypes.data,
+                                                  2 if device_gkr else 0, int(pow_bits), err, len(err))
             if rc != -1 or ln.value <= cap:
                 break
             cap = ln.value

@@ -177,8 +177,18 @@ __device__ __constant__ const u64 KECCAK_RC[24] = {
     0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
     0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
     0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
-// four rounds on the 2 x 25 halves, rnd0 .. rnd0 + 3
-__device__ __forceinline__ void keccak_rounds4(u32 (&al)[25], u32 (&ah)[25], int rnd0) {
+// four rounds on the 2 x 25 halves, rnd0 .. rnd0 + 3.  PHASED (k_fs_grind alone; every other caller is the plain form, unchanged): logic (v_bitop3_b32, full
+// rate) and rotations (v_alignbit_b32, half rate) are kept apart in the instruction stream, and a workgroup barrier stands at the END of each of the two rotation
+// phases of a round, so that the waves of a SIMD start a logic phase together — the round structure of the generated leaf chains (tools/gen_keccak_asm.py, where
+// barriers at both ends of the rotation phases measured 6 % slower and a barrier in front of them alone worse than none; profiles/r04_micro_phase_separation_keccak.txt:
+// 2.9 against 4.0 cycles per wave-instruction at four waves per SIMD).  Every lane of the workgroup must then run every round: no lane leaves a loop around it early.
+template <bool PHASED> __device__ __forceinline__ void keccak_rot_begin() {
+    if constexpr (PHASED) __builtin_amdgcn_sched_barrier(0);
+}
+template <bool PHASED> __device__ __forceinline__ void keccak_rot_end() {
+    if constexpr (PHASED) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
+}
+template <bool PHASED = false> __device__ __forceinline__ void keccak_rounds4(u32 (&al)[25], u32 (&ah)[25], int rnd0) {
     const u64 *RC = KECCAK_RC;
 #pragma unroll
     for (int rnd = rnd0; rnd < rnd0 + 4; ++rnd) {
@@ -189,14 +199,17 @@ __device__ __forceinline__ void keccak_rounds4(u32 (&al)[25], u32 (&ah)[25], int
             cl[x] = xor3(xor3(al[x], al[x + 5], al[x + 10]), al[x + 15], al[x + 20]);
             ch[x] = xor3(xor3(ah[x], ah[x + 5], ah[x + 10]), ah[x + 15], ah[x + 20]);
         }
+        keccak_rot_begin<PHASED>();
 #pragma unroll
         for (int x = 0; x < 5; ++x) rot<1>(cl[x], ch[x], rl[x], rh[x]);
+        keccak_rot_end<PHASED>();
 #pragma unroll
         for (int i = 0; i < 25; ++i) {                       // A ^= D, D[x] = C[x-1] ^ rotl(C[x+1], 1), without materialising D
             al[i] = xor3(al[i], cl[(i + 4) % 5], rl[(i + 1) % 5]);
             ah[i] = xor3(ah[i], ch[(i + 4) % 5], rh[(i + 1) % 5]);
         }
         // rho + pi
+        keccak_rot_begin<PHASED>();
         u32 bl[25], bh[25];
         rot<0>(al[0], ah[0], bl[0], bh[0]);
         rot<1>(al[1], ah[1], bl[10], bh[10]);
@@ -223,6 +236,7 @@ __device__ __forceinline__ void keccak_rounds4(u32 (&al)[25], u32 (&ah)[25], int
         rot<61>(al[22], ah[22], bl[9], bh[9]);
         rot<56>(al[23], ah[23], bl[19], bh[19]);
         rot<14>(al[24], ah[24], bl[4], bh[4]);
+        keccak_rot_end<PHASED>();
         // chi + iota
 #pragma unroll
         for (int y = 0; y < 25; y += 5) {
@@ -367,6 +381,67 @@ __global__ void __launch_bounds__(VP_BLOCK) k_merkle_top_fs(MerkleArgs a, Dig *r
 // the chain's steps alone: the first challenge C(0) of vp_fri_commit_fs (root null) and the test hook (vp_test_fs_draw)
 __global__ void k_fs_draw(Dig *state, const Dig *root, u64 label, u64 counter, F *r_out) {
     if (blockIdx.x == 0 && threadIdx.x == 0) fs_absorb_draw(state, root, label, counter, r_out);
+}
+// ---- the proof of work of the non-interactive proofs (vp_fs_grind; the step's text: host/vphost.h, "The proof of work") ---------------------------------------
+// W(bits, nonce) is the chain step state = SHA3-256({nonce, bits, 0, 0x57} || state); the work is met when the low `bits` bits of the new state's first word
+// are zero.  One window of the search: `count` nonces from first + base, one nonce per lane per iteration, a workgroup — 1024 lanes, a whole CU at four waves
+// per SIMD, the rounds in phase (keccak_rounds4<true>) — taking iters x 1024 consecutive ones.
+// The state, bits and the mask are kernel arguments — scalar registers: of the block's 25 lanes only lane 0 differs between the lanes of a wave, so what the
+// first round does to the other 24 is scalar work — and nothing is loaded.  The last group of four rounds is peeled as in keccak_f1600 and only w0 is read
+// from it (HI = false: only its low half, bits <= 32), so the compiler keeps of round 24 only what reaches that word.
+// Windows are queued in ascending order on one stream: a window first reads the slot and leaves at once if an EARLIER window has a hit (slot < base: a hit of
+// this window is >= base and must not stop a workgroup that may hold a smaller one).  A hit is an atomicMin of its offset from `first` on the slot (empty: all
+// ones, which no offset reaches: offsets are below max_tries <= 2^64 - 1).  A workgroup that searches counts itself in *worked.  The work of a launch is
+// bounded by count; nothing waits on a flag or on the host.
+struct FsGrindArgs {
+    u64 s[4];                                          // the state W absorbs
+    u64 bits, mask;                                    // mask = 2^bits - 1
+    u64 first, base, count;                            // this window: nonces first + base + [0, count)
+    u32 iters;                                         // nonces per lane
+    unsigned long long *slot;                          // the smallest offset from `first` that met the work so far
+    u32 *worked;                                       // workgroups of this window that searched
+};
+#define VP_FS_GRIND_BLOCK 1024
+template <bool HI> __global__ void __launch_bounds__(VP_FS_GRIND_BLOCK) k_fs_grind(FsGrindArgs a) {
+    __shared__ u32 leave;
+    if (threadIdx.x == 0) {
+        leave = __hip_atomic_load(a.slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < a.base ? 1u : 0u;
+        if (!leave) atomicAdd(a.worked, 1u);
+    }
+    __syncthreads();
+    if (leave) return;                                 // (the whole workgroup: the rounds below hold barriers)
+    const u64 off0 = (u64) blockIdx.x * ((u64) VP_FS_GRIND_BLOCK * a.iters) + threadIdx.x;
+    const u32 mlo = (u32) a.mask, mhi = (u32) (a.mask >> 32);
+    u64 best = ~0ull;
+    for (u32 it = 0; it < a.iters; ++it) {
+        const u64 off = off0 + (u64) it * VP_FS_GRIND_BLOCK;
+        const bool inside = off < a.count;             // a lane past the window's end keeps step with its workgroup and reports nothing
+        const u64 nonce = a.first + a.base + (inside ? off : 0);
+        u32 al[25], ah[25];
+#pragma unroll
+        for (int i = 0; i < 25; ++i) al[i] = ah[i] = 0;
+        al[0] = (u32) nonce; ah[0] = (u32) (nonce >> 32);
+        al[1] = (u32) a.bits;
+        al[3] = 0x57;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { al[4 + i] = (u32) a.s[i]; ah[4 + i] = (u32) (a.s[i] >> 32); }
+        al[8] = 0x06;                                  // domain bits + first pad bit (byte 64)
+        ah[16] = 0x80000000u;                          // last pad bit (byte 135, rate 136)
+        keccak_rounds4<true>(al, ah, 0);
+#pragma unroll 1
+        for (int rnd0 = 4; rnd0 < 20; rnd0 += 4) keccak_rounds4<true>(al, ah, rnd0);
+        keccak_rounds4<true>(al, ah, 20);
+        const bool hit = HI ? ((al[0] & mlo) | (ah[0] & mhi)) == 0 : (al[0] & mlo) == 0;
+        if (hit && inside && best == ~0ull) best = a.base + off;      // a lane's nonces ascend: its first hit is its smallest
+    }
+    if (best != ~0ull) atomicMin(a.slot, (unsigned long long) best);
+}
+// the state behind W(bits, nonce), one lane: what vp_fs_grind returns beside the nonce
+__global__ void k_fs_work_state(const u64 *__restrict__ state, u64 bits, u64 nonce, u64 *__restrict__ out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    Dig s; s.w[0] = state[0]; s.w[1] = state[1]; s.w[2] = state[2]; s.w[3] = state[3];
+    s = hhash64(nonce, bits, 0, 0x57, s);
+    out[0] = s.w[0]; out[1] = s.w[1]; out[2] = s.w[2]; out[3] = s.w[3];
 }
 __global__ void k_test_fs_limbs(const u64 *__restrict__ in, u64 *__restrict__ out, u32 n) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;

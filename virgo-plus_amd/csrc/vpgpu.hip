@@ -172,6 +172,8 @@ struct VpOpt {
     int32_t fft_gkr_batched;        // VP_FFT_GKR_BATCHED: the 2 lg inverse-FFT sumchecks of vp_fft_gkr as one batch                                      [1]
     int32_t split_vu;               // VP_SPLIT_VU: index-split proof: V_u of a split phase 2 from per-rank partial inner products ahead of the graph      [1]
     int32_t pc_live;                // VP_PC_LIVE: the unsharded, unmasked commitment transforms and folds only the slices the input layer fills (0: all 64)  [1]
+    int32_t grind_window_log;       // VP_GRIND_WINDOW_LOG: vp_fs_grind's windows grow from 2^16 nonces by a factor of four up to 2^this (16 .. 28; profiles/fs_grind.md)  [24]
+    int32_t grind_batch;            // VP_GRIND_BATCH: windows vp_fs_grind queues before the host waits and reads the hit slot (1 .. 64)  [8]
 };
 
 struct vp_ctx {
@@ -237,6 +239,7 @@ struct vp_ctx {
     // vp_fri_open_many / vp_fri_query: records on the device, descriptor table + request list on the device, pinned staging of both directions
     PcOpenRec *pc_many_buf = nullptr; unsigned char *pc_many_in = nullptr; u32 pc_many_cap = 0; unsigned char *h_many = nullptr; size_t h_many_cap = 0;
     Dig *pc_fri_roots = nullptr;
+    u64 *fs_grind_buf = nullptr;                          // vp_fs_grind: the hit slot | the state behind W (4 words) | one counter of working blocks per queued window
     Dig *pc_fs = nullptr;                                 // vp_fri_commit_fs: roots[VP_FRI_MAX] | challenges (VP_FRI_MAX elements of F) | the chain's state, one block for one copy
     Dig *pc_fri_tree = nullptr; int fri_step = -1; bool pc_public_done = false;       // fri_step: FRI levels committed (openable); -1: no FRI phase begun
     // the mask slice with content (vp_commit_private_masked / vp_commit_public_masked; 0 = the protocol's zero mask, nothing below is touched): padded mask length,
@@ -392,7 +395,7 @@ void pc_forget(vp_ctx *ctx) {
     ctx->pc_pub = ctx->pc_qcw = ctx->pc_hcw = ctx->pc_tmp = ctx->pc_small = nullptr; ctx->pc_tree_h = nullptr; ctx->pc_private_done = false;
     ctx->pc_q0 = nullptr; ctx->pc_eq = nullptr; ctx->pc_cbuf = nullptr; ctx->pc_cbuf_lm = -1; ctx->pc_flag = nullptr; ctx->pc_q_tensor = false;
     ctx->pc_scr = nullptr; ctx->pc_scr_cap = 0; ctx->pc_fri_all = nullptr; ctx->pc_open_buf = nullptr; ctx->pc_many_buf = nullptr; ctx->pc_many_in = nullptr; ctx->pc_many_cap = 0;
-    ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->pc_fs = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
+    ctx->pc_fri_tree = nullptr; ctx->pc_fri_roots = nullptr; ctx->pc_fs = nullptr; ctx->fs_grind_buf = nullptr; ctx->fri_step = -1; ctx->pc_public_done = false;
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
     ctx->pc_lv = PcLive(); ctx->pc_zf_cw = ctx->pc_zf_hcw = ctx->pc_zf_fri = 64;
 }
@@ -1072,6 +1075,7 @@ static void opt_defaults(VpOpt *o) {
     o->fft_gkr_batched = 1;
     o->split_vu = 1;
     o->pc_live = 1;
+    o->grind_window_log = 24; o->grind_batch = 8;
 }
 static void opt_to_public(const VpOpt &o, vp_options *p) {
     memset(p, 0, sizeof *p);
@@ -1103,7 +1107,8 @@ static const OptName g_opt_names[] = {
     {"fold_branches", &VpOpt::fold_branches}, {"fuse_combine", &VpOpt::fuse_combine}, {"plan_autotune", &VpOpt::plan_autotune},
     {"pc_tensor_pub", &VpOpt::pc_tensor_pub}, {"persistent_timeout_ms", &VpOpt::persistent_timeout_ms}, {"graph_explicit", &VpOpt::graph_explicit}, {"ntt_r8", &VpOpt::ntt_r8},
     {"interactive_fast_init", &VpOpt::interactive_fast_init}, {"fuse_p2", &VpOpt::fuse_p2}, {"leaf_asm", &VpOpt::leaf_asm},
-    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}, {"pc_live", &VpOpt::pc_live}};
+    {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}, {"pc_live", &VpOpt::pc_live},
+    {"grind_window_log", &VpOpt::grind_window_log}, {"grind_batch", &VpOpt::grind_batch}};
 int vp_tuning_get(const vp_ctx *ctx, const char *name, int32_t *value) {
     if (!ctx || !name || !value) return VP_EINVAL;
     for (const OptName &n : g_opt_names) if (!strcmp(n.name, name)) { *value = ctx->opt.*(n.field); return VP_OK; }
@@ -1146,6 +1151,8 @@ static int resolve_options(VpOpt *o, const vp_options *user, uint32_t *pinned) {
     flag("VP_FFT_GKR_BATCHED", o->fft_gkr_batched);
     flag("VP_SPLIT_VU", o->split_vu);
     flag("VP_PC_LIVE", o->pc_live);
+    num("VP_GRIND_WINDOW_LOG", o->grind_window_log); num("VP_GRIND_BATCH", o->grind_batch);
+    o->grind_window_log = std::min(28, std::max(16, o->grind_window_log)); o->grind_batch = std::min(64, std::max(1, o->grind_batch));
     flag("VP_PC_TENSOR", o->pc_tensor_pub);
     num("VP_PERSIST_TIMEOUT_MS", o->persistent_timeout_ms);
     num("VP_GRAPH_EXPLICIT", o->graph_explicit);
@@ -2168,6 +2175,7 @@ const char *vp_kernel_name(int kind) {
         "k_sumfold3b_gen_multi", "k_sumfold3b_multi", "k_seg_multi", "k_emit_multi", "k_fixup", "k_ntt_split", "k_ntt_lds", "k_ntt_unsplit",
         "k_leaf_hash", "k_merkle", "k_pc_pointwise", "k_fri_fold", "k_round", "k_ntt8_cols", "k_ntt8_rows",
         "k_ntt_long_split", "k_ntt_long_merge", "k_pc_poly_eval", "k_pc_poly_eval_fin", "k_pc_opening_digests", "k_pc_open_many"};
+    if (kind == VP_K_FS_GRIND) return "k_fs_grind";
     return (kind >= 0 && kind < VP_K_COUNT) ? names[kind] : "?";
 }
 

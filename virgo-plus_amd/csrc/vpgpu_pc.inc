@@ -1398,6 +1398,80 @@ int vp_test_fs_draw(vp_ctx *ctx, int op, const uint8_t state[32], const uint8_t 
     return VP_OK;
 }
 
+// The proof-of-work search (include/vpgpu.h).  Windows ascend and are disjoint: window w holds 2^min(16 + 2 w, 24) nonces (cut at max_tries), so a few bits of
+// work cost one short launch and many bits run in launches of 2^24; eight windows are queued behind each other before the host waits and reads the slot (a
+// window behind a hit leaves on its first instruction).  The schedule is a function of max_tries alone, so the result is the same on every run — and of the
+// internal tuning grind_window_log / grind_batch (24 / 8: profiles/fs_grind.md), which moves the windows and not the answer.
+constexpr int FS_GRIND_BATCH_MAX = 64;
+int vp_fs_grind(vp_ctx *ctx, const uint8_t state_in[32], int bits, uint64_t first, uint64_t max_tries, uint64_t *nonce, uint8_t state_out[32]) {
+    if (!ctx) return VP_EINVAL;
+    // every refusal before anything is queued
+    if (!state_in || !nonce || !state_out) { ctx->err = "vp_fs_grind: a null argument"; return VP_EINVAL; }
+    if (bits < 1 || bits > 48) { ctx->err = "vp_fs_grind: bits outside 1 .. 48"; return VP_EINVAL; }
+    if (max_tries == 0 || first + (max_tries - 1) < first) { ctx->err = "vp_fs_grind: an empty range, or one that passes 2^64"; return VP_EINVAL; }
+    VP_ENTER(ctx);
+    constexpr size_t WORDS = 1 + 4 + 4 + FS_GRIND_BATCH_MAX / 2;  // slot | state out | state in | one 32-bit counter per window of a batch
+    const u64 window_log = (u64) ctx->opt.grind_window_log;
+    const int batch = ctx->opt.grind_batch;
+    if (!ctx->fs_grind_buf) VPCHK(dalloc(ctx, &ctx->fs_grind_buf, WORDS));
+    u64 *d = ctx->fs_grind_buf;
+    u32 *d_worked = reinterpret_cast<u32 *>(d + 9);
+    u64 h[WORDS];
+    FsGrindArgs a{};
+    memcpy(a.s, state_in, 32);
+    a.bits = (u64) bits; a.mask = (1ull << bits) - 1; a.first = first;
+    a.slot = reinterpret_cast<unsigned long long *>(d);
+    if (ctx->profiling) ensure_event_pool(ctx);
+    ctx->ev_used = 0;
+    std::vector<std::pair<size_t, u32>> rows;             // per launch: its row of the table (or none) and the workgroups that searched
+    std::vector<int> slots;
+    u64 base = 0, found = ~0ull;
+    for (u64 w = 0; base < max_tries && found == ~0ull;) {
+        memset(h, 0, sizeof h);
+        h[0] = ~0ull;
+        memcpy(h + 5, state_in, 32);
+        HIPCHK(hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, ctx->stream));      // (pageable: the copy is staged before the call returns)
+        slots.clear();
+        for (int q = 0; q < batch && base < max_tries; ++q, ++w) {
+            a.base = base; a.count = std::min<u64>(1ull << std::min<u64>(16 + 2 * w, window_log), max_tries - base);
+            a.iters = (u32) std::max<u64>(1, a.count / ((u64) VP_FS_GRIND_BLOCK * 4096));
+            a.worked = d_worked + q;
+            const u64 per = (u64) VP_FS_GRIND_BLOCK * a.iters;
+            const u32 grid = (u32) ((a.count + per - 1) / per);
+            const int sl = prof_begin(ctx, ctx->stream, VP_K_FS_GRIND, grid, 1, 0, a.count, (u32) a.iters, (u32) w);
+            if (bits > 32) hipLaunchKernelGGL(k_fs_grind<true>, dim3(grid), dim3(VP_FS_GRIND_BLOCK), 0, ctx->stream, a);
+            else hipLaunchKernelGGL(k_fs_grind<false>, dim3(grid), dim3(VP_FS_GRIND_BLOCK), 0, ctx->stream, a);
+            prof_end(ctx, ctx->stream, sl);
+            count_launch(ctx);
+            slots.push_back(sl);
+            base += a.count;
+        }
+        HIPCHK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        VPCHK(check_stream(ctx));
+        found = h[0];
+        const u32 *hw = reinterpret_cast<const u32 *>(h + 9);
+        for (size_t q = 0; q < slots.size(); ++q) if (slots[q] >= 0) rows.emplace_back((size_t) slots[q], hw[q]);
+    }
+    if (ctx->profiling) {
+        // a row's work: the nonces of the workgroups that searched (the last one may be cut at the window's end) — zero for a window behind a hit
+        prof_collect(ctx);
+        for (const auto &r : rows) {
+            vp_launch_stat &st = ctx->lstats[r.first];
+            st.work = std::min<u64>(st.work, (u64) r.second * VP_FS_GRIND_BLOCK * st.rounds);
+            st.jobs = r.second;
+        }
+    }
+    if (found == ~0ull) { ctx->err = "vp_fs_grind: no nonce in the range meets the work"; return VP_ELIMIT; }
+    hipLaunchKernelGGL(k_fs_work_state, dim3(1), dim3(64), 0, ctx->stream, (const u64 *) (d + 5), (u64) bits, (u64) (first + found), d + 1);
+    count_launch(ctx);
+    HIPCHK(hipMemcpyAsync(h, d, 5 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    VPCHK(check_stream(ctx));
+    if (h[1] & a.mask) { ctx->err = "vp_fs_grind: internal: the nonce found does not meet the work"; return VP_EHIP; }
+    *nonce = first + found;
+    memcpy(state_out, h + 1, 32);
+    return VP_OK;
+}
+
 int vp_fri_final(vp_ctx *ctx, vp_F *final_code) {
     if (!ctx || !final_code) return VP_EINVAL;
     VP_ENTER_Q(ctx);

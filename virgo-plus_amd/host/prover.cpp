@@ -541,8 +541,28 @@ std::vector<F> prover::pcMaskEvals(int n, const std::vector<F> &pub_mask, u64 ms
     logLaunches();
     return out;
 }
-std::vector<uint8_t> prover::commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_draws) {
+u64 prover::fsGrind(const vph::hhash_digest &state, int bits, bool on_device) {
+    if (bits < 1 || bits > PCFS_POW_PROVER_BITS) throw std::invalid_argument("fsGrind: 1 .. 32 bits");
+    const uint64_t tries = 64ull << bits;
+    uint64_t nonce = 0;
+    if (!on_device) {
+        if (!vph::fs_grind(state, bits, 0, tries, &nonce)) throw std::runtime_error("proof of work: no nonce below 64 x 2^" + std::to_string(bits) + " meets " + std::to_string(bits) + " bits");
+        return nonce;
+    }
+    uint8_t st_in[32], st_out[32];
+    memcpy(st_in, state.w, 32);
+    const int rc = vp_fs_grind(ctx, st_in, bits, 0, tries, &nonce, st_out);
+    if (rc == VP_ELIMIT) throw std::runtime_error("proof of work: no nonce below 64 x 2^" + std::to_string(bits) + " meets " + std::to_string(bits) + " bits");
+    check(rc, "vp_fs_grind");
+    // the host's step on the device's nonce: the work is met and the state is the chain's
+    vph::fs_chain ch;
+    ch.s = state;
+    if (!ch.work((u64) bits, nonce) || memcmp(ch.s.w, st_out, 32)) throw std::runtime_error("vp_fs_grind: the nonce or the state behind it is not the chain's");
+    return nonce;
+}
+std::vector<uint8_t> prover::commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_draws, int pow_bits) {
     if (shard_pc) throw std::runtime_error("commitFS: not built for a sharded commitment");
+    if (pow_bits < 0 || pow_bits > PCFS_POW_PROVER_BITS) throw std::invalid_argument("commitFS: pow_bits outside 0 .. 32");
     const int n = C.circuit[0].bitLength, ln = n - 6;
     if (n < 7 || (int) point.size() != n) throw std::runtime_error("commitFS: a point of n >= 7 coordinates, n the input layer's bit length");
     if (reps < 1 || reps > 4096) throw std::runtime_error("commitFS: 1 .. 4096 repetitions");
@@ -589,13 +609,17 @@ std::vector<uint8_t> prover::commitFS(const std::vector<F> &point, int reps, con
         fs_phase_sec = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
     }
     const std::vector<F> fin = friFinal(), fm = friFinalMask();
-    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm);
+    PcFsWork work;
+    work.bits = (u64) pow_bits;
+    work.find = [&](const vph::hhash_digest &st) { return fsGrind(st, pow_bits, device_draws); };
+    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm, &work);
     const std::vector<uint8_t> ans = friQuery(lf);
     std::vector<uint8_t> out;
     auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); out.insert(out.end(), q, q + k); };
-    const uint32_t h32[4] = {PCFS_MAGIC, PCFS_VERSION, (uint32_t) n, (uint32_t) reps};
+    const uint32_t h32[4] = {PCFS_MAGIC, pow_bits ? PCFS_VERSION_POW : PCFS_VERSION, (uint32_t) n, (uint32_t) reps};
     const uint64_t h64[2] = {ms, ms == 1 ? 0 : pm.size()};
     put(h32, sizeof h32); put(h64, sizeof h64);
+    if (pow_bits) { const uint64_t hw[2] = {work.bits, work.nonce}; put(hw, sizeof hw); }
     put(point.data(), point.size() * sizeof(F));
     if (ms != 1) put(pm.data(), pm.size() * sizeof(F));
     put(&claim, sizeof(F));

@@ -109,7 +109,13 @@ public:
     // of bytes that pcVerifyCommitmentFS checks with no tape and no session.  device_draws: the commit phase is vp_fri_commit_fs, the device drawing each
     // challenge from the root it has just computed (checked here against the host's chain over the returned roots); false: the vp_fri_step loop with the chain on
     // the host, one wait per level — a second implementation with the same bytes.  Throws on a sharded commitment (not built).
-    std::vector<uint8_t> commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_draws = true);
+    // pow_bits (0 .. 32): the proof of work in front of the positions and a version-2 proof; 0 is the version-1 proof, byte for byte.  The nonce is fsGrind's,
+    // on the device with device_draws and on the host without.
+    std::vector<uint8_t> commitFS(const std::vector<F> &point, int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_draws = true,
+                                  int pow_bits = 0);
+    // The smallest nonce whose W(bits, nonce) on `state` meets the work, searched from 0 through 64 x 2^bits tries: vp_fs_grind on the context (on_device) or
+    // the host's search.  Throws std::invalid_argument for bits outside 1 .. 32 and std::runtime_error when the range holds no such nonce.
+    u64 fsGrind(const vph::hhash_digest &state, int bits, bool on_device);
     // vp_fri_commit_fs from the chain's state, the roots returned; the device's challenges and closing state are checked against the chain walked over those
     // roots (steps 8 and 9 of the commitment's chain), which is left behind the last level.  After commit_public_eq.
     void friCommitFS(vph::fs_chain &ch, std::vector<uint8_t> &roots);

@@ -68,7 +68,19 @@ struct fs_chain {
     void challenge(uint64_t c, uint64_t &re, uint64_t &im) { step(c, 0, 0, 0x43); re = limb(s.w[0]); im = limb(s.w[1]); }   // C(c)
     // Q(q): a leaf in [2^(n-7), 2^(n-2)), the range pcVerifyCommitment accepts
     uint64_t position(uint64_t q, int n) { step(q, 0, 0, 0x51); const uint64_t lo = 1ull << (n - 7); return lo + s.w[0] % ((1ull << (n - 2)) - lo); }
+    // W(b, nonce): the proof-of-work step; the work is met when the low b bits of the new state's first word are zero (b in 1 .. 48)
+    bool work(uint64_t bits, uint64_t nonce) { step(nonce, bits, 0, 0x57); return (s.w[0] & ((1ull << bits) - 1)) == 0; }
 };
+// The smallest nonce in [first, first + max_tries) whose W(bits, nonce) on `from` meets the work: true and *nonce, or false (nothing is written).  The caller
+// has checked bits in 1 .. 48, max_tries >= 1 and first + max_tries <= 2^64.
+inline bool fs_grind(const hhash_digest &from, int bits, uint64_t first, uint64_t max_tries, uint64_t *nonce) {
+    const uint64_t mask = (1ull << bits) - 1, m3 = 0x57;
+    for (uint64_t i = 0; i < max_tries; ++i) {
+        const uint64_t m[4] = {first + i, (uint64_t) bits, 0, m3};
+        if ((hhash(m, from).w[0] & mask) == 0) { *nonce = first + i; return true; }
+    }
+    return false;
+}
 
 // Streaming SHA3-256 (FIPS 202 sponge, rate 136 bytes): the statement digest of the Fiat-Shamir mode absorbs the whole
 // serialised circuit and its input values through it (verifier::fsInit).

@@ -878,7 +878,13 @@ int pcParseCommitmentFS(const uint8_t *proof, u64 len, PcCommitment &c, std::str
     uint32_t h32[4]; u64 h64[2];
     memcpy(h32, proof, 16); memcpy(h64, proof + 16, 16); at = 32;
     if (h32[0] != PCFS_MAGIC) return bad("not a commitment proof (magic)");
-    if (h32[1] != PCFS_VERSION) return bad("a commitment proof of another version");
+    if (h32[1] != PCFS_VERSION && h32[1] != PCFS_VERSION_POW) return bad("a commitment proof of another version");
+    PcFsWork work;
+    if (h32[1] == PCFS_VERSION_POW) {
+        if (!have(16)) return bad("proof shorter than its header");
+        if (!pcFsWorkHeader(proof + at, work)) return bad("pow_bits outside 1 .. 48 (no work is version 1)");
+        at += 16;
+    }
     const u64 n = h32[2], reps = h32[3], ms = h64[0], n_pub = h64[1];
     if (n < 7 || n > 30) return bad("n outside 7 .. 30");
     if (reps < 1 || reps > 4096) return bad("1 .. 4096 repetitions");
@@ -915,12 +921,22 @@ int pcParseCommitmentFS(const uint8_t *proof, u64 len, PcCommitment &c, std::str
     c.fr.resize(ln);
     c.fr[0] = pcFsFirstChallenge(ch);
     for (u64 k = 0; k < ln; ++k) { F next; if (pcFsLevel(ch, (int) k, (int) ln, &c.fri_roots[32 * k], &next)) c.fr[k + 1] = next; }
-    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask);
+    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask, &work);
+    c.pow_bits = work.bits; c.pow_nonce = work.nonce; c.pow_met = work.met;
     return 0;
 }
-int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev) {
+int pcCheckWork(u64 pow_bits, u64 pow_nonce, bool met, int min_pow_bits, std::string &why) {
+    if (!met) { why = "proof of work not met: W(" + std::to_string(pow_bits) + ", " + std::to_string(pow_nonce) + ") leaves a non-zero bit among the low " + std::to_string(pow_bits); return 1; }
+    if (min_pow_bits > 0 && pow_bits < (u64) min_pow_bits) {
+        why = "proof of work of " + std::to_string(pow_bits) + " bits, the verifier demands " + std::to_string(min_pow_bits);
+        return 1;
+    }
+    return 0;
+}
+int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev, int min_pow_bits) {
     PcCommitment c;
     if (pcParseCommitmentFS(proof, len, c, why) != 0) return -1;
+    if (pcCheckWork(c.pow_bits, c.pow_nonce, c.pow_met, min_pow_bits, why)) return 1;
     return pcVerifyCommitment(c, why, dev);
 }
 
@@ -1029,9 +1045,10 @@ void verifier::fullFsHead(int n, u64 reps, u64 ms, const std::vector<F> &pub_mas
     for (u64 i = 0; i < n_pub; ++i) fs_state.elem(pub_mask[i].real, pub_mask[i].img);
     fs_state.digest(0, root_l);
 }
-std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_gkr) {
+std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_mask, const std::vector<F> &pub_mask, bool device_gkr, int pow_bits) {
     if (!p) throw std::runtime_error("proveFullFS(): no prover attached");
     if (p->world() > 1 || p->commitmentSharded()) throw std::runtime_error("proveFullFS: not built for a sharded session");
+    if (pow_bits < 0 || pow_bits > PCFS_POW_PROVER_BITS) throw std::invalid_argument("proveFullFS: pow_bits outside 0 .. 32");
     const int n = C.circuit[0].bitLength, ln = n - 6;
     if (n < 7) throw std::runtime_error("proveFullFS: the commitment needs an input layer of at least 2^7 wires");
     if (reps < 1 || reps > 4096) throw std::runtime_error("proveFullFS: 1 .. 4096 repetitions");
@@ -1087,13 +1104,18 @@ std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_m
     std::vector<uint8_t> roots;
     p->friCommitFS(ch, roots);
     const std::vector<F> fin = p->friFinal(), fm = p->friFinalMask();
-    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm);
+    PcFsWork work;
+    work.bits = (u64) pow_bits;
+    work.find = [&](const vph::hhash_digest &st) { return p->fsGrind(st, pow_bits, true); };
+    const std::vector<u64> lf = pcFsPositions(ch, n, (u64) reps, fin, fm, &work);
+    if (!work.met) throw std::runtime_error("proveFullFS: the device's nonce does not meet the work");
     const std::vector<uint8_t> ans = p->friQuery(lf);
     std::vector<uint8_t> out;
     auto put = [&](const void *b, size_t k) { const uint8_t *q = static_cast<const uint8_t *>(b); out.insert(out.end(), q, q + k); };
-    const uint32_t h32[4] = {FULLFS_MAGIC, FULLFS_VERSION, (uint32_t) n, (uint32_t) reps};
+    const uint32_t h32[4] = {FULLFS_MAGIC, pow_bits ? PCFS_VERSION_POW : FULLFS_VERSION, (uint32_t) n, (uint32_t) reps};
     const uint64_t h64[2] = {ms, ms == 1 ? 0 : pm.size()};
     put(h32, sizeof h32); put(h64, sizeof h64);
+    if (pow_bits) { const uint64_t hw[2] = {work.bits, work.nonce}; put(hw, sizeof hw); }
     if (ms != 1) put(pm.data(), pm.size() * sizeof(F));
     put(root_l.b, 32);
     put(gkr.data(), gkr.size());
@@ -1107,9 +1129,10 @@ std::vector<uint8_t> verifier::proveFullFS(int reps, const std::vector<F> &pri_m
     put(ans.data(), ans.size());
     return out;
 }
-int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev) {
+int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev, int min_pow_bits) {
     auto bad = [&](const char *m) { why = m; return -1; };
     full_fs_point_.clear();
+    full_fs_pow_[0] = full_fs_pow_[1] = 0;
     if (!proof) return bad("no proof");
     u64 at = 0;
     auto have = [&](u64 k) { return k <= len - at; };            // (at <= len throughout)
@@ -1117,12 +1140,21 @@ int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ct
     uint32_t h32[4]; u64 h64[2];
     memcpy(h32, proof, 16); memcpy(h64, proof + 16, 16); at = 32;
     if (h32[0] != FULLFS_MAGIC) return bad("not a joined proof (magic)");
-    if (h32[1] != FULLFS_VERSION) return bad("a joined proof of another version");
+    if (h32[1] != FULLFS_VERSION && h32[1] != PCFS_VERSION_POW) return bad("a joined proof of another version");
+    PcFsWork work;
+    if (h32[1] == PCFS_VERSION_POW) {
+        if (!have(16)) return bad("proof shorter than its header");
+        if (!pcFsWorkHeader(proof + at, work)) return bad("pow_bits outside 1 .. 48 (no work is version 1)");
+        at += 16;
+    }
     const u64 n = h32[2], reps = h32[3], ms = h64[0], n_pub = h64[1];
     if (n < 7 || n > 30 || (int) n != C.circuit[0].bitLength) return bad("n is not the bit length of the circuit's input layer (7 .. 30)");
     if (reps < 1 || reps > 4096) return bad("1 .. 4096 repetitions");
     if (ms != 1 && (ms < 8 || (ms & (ms - 1)) || ms > (1ull << 16) || ms > (1ull << (n - 2)))) return bad("ms is neither 1 nor a power of two in [8, min(2^16, 2^(n-2))]");
     if (ms == 1 ? n_pub != 0 : n_pub > ms) return bad("public mask longer than ms (none with the zero mask)");
+    // the verifier's demand is decided by the header: no replay of the GKR part for a proof that carries too little work (the work itself: where the chain reaches it)
+    full_fs_pow_[0] = work.bits; full_fs_pow_[1] = work.nonce;
+    if (pcCheckWork(work.bits, work.nonce, true, min_pow_bits, why)) return 1;
     const u64 ln = n - 6;
     bool canon = true;
     auto elems = [&](std::vector<F> &v, u64 k) {
@@ -1180,8 +1212,9 @@ int verifier::checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ct
     c.fr.resize(ln);
     c.fr[0] = pcFsFirstChallenge(ch);
     for (u64 k = 0; k < ln; ++k) { F next; if (pcFsLevel(ch, (int) k, (int) ln, &c.fri_roots[32 * k], &next)) c.fr[k + 1] = next; }
-    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask);
-    // ---- the checks: nothing of the joined proof's own beyond the hand-over of the claim
+    c.leaf0 = pcFsPositions(ch, (int) n, reps, c.final_code, c.final_mask, &work);
+    // ---- the checks: the work, then nothing of the joined proof's own beyond the hand-over of the claim
+    if (pcCheckWork(work.bits, work.nonce, work.met, min_pow_bits, why)) return 1;
     if (last_claim != c.claim) { gkrFails(GKR_INPUT, 0, -1); why = "the GKR part's claim on the input layer is not input_0 (final input check)"; return 1; }
     if (!vph::fft_gkr_check<F>((int) ln, ftape.data(), ftape.size(), fmsgs.data(), fmsgs.size(), F::getRootOfUnity((int) ln).inv())) { why = "fft_gkr is rejected"; return 1; }
     return pcVerifyCommitment(c, why, dev);

@@ -93,10 +93,15 @@ public:
     // an input layer below 2^7 wires, or a prover whose own proof the checks reject.
     // device_gkr: the GKR part is prover::proveGkrFS from the head's state instead of run() (the point from the tape's r_liu slots of layer 1, the claim from the
     // transcript's last element); the same bytes, and the prover's own GKR proof is not verified here.
-    std::vector<uint8_t> proveFullFS(int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_gkr = false);
+    // pow_bits (0 .. 32): the proof of work in front of the positions (prover::fsGrind on the device) and a version-2 proof; 0 is the version-1 proof, byte for byte.
+    std::vector<uint8_t> proveFullFS(int reps, const std::vector<F> &pri_mask = {}, const std::vector<F> &pub_mask = {}, bool device_gkr = false, int pow_bits = 0);
     // A verifier that holds only the circuit: parses under checkFull's rules, replays run(), derives every challenge, calls fft_gkr_check and pcVerifyCommitment
     // unchanged (dev: the commitment's heavy loops on a device context).  0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).
-    int checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr);
+    // min_pow_bits: the work the verifier demands; a proof that carries less (a version-1 proof carries none) is rejected from its header, before the replay;
+    // one whose work is not met, once the chain has reached W.
+    int checkFullFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr, int min_pow_bits = 0);
+    u64 fullFsPowBits() const { return full_fs_pow_[0]; }       // the two fields of the last checkFullFS's header (0, 0: version 1, or malformed before them)
+    u64 fullFsPowNonce() const { return full_fs_pow_[1]; }
     const std::vector<F> &fullFsPoint() const { return full_fs_point_; }      // the point the last proveFullFS / checkFullFS derived (checkFullFS: r_liu as far as the replay of the GKR part got)
     std::vector<F> drawTape();                                  // the verifier's draws, in its own order
     bool check(const std::vector<F> &tape, const std::vector<uint8_t> &transcript);   // replay
@@ -135,6 +140,7 @@ private:
     void fsInit(bool with_inputs = true);
     void fullFsHead(int n, u64 reps, u64 ms, const std::vector<F> &pub_mask, const uint8_t root_l[32]);
     std::vector<F> full_fs_point_;
+    u64 full_fs_pow_[2] = {0, 0};
     const std::vector<F> *rtape = nullptr;
     const std::vector<uint8_t> *rtr = nullptr;
     size_t tape_pos = 0, tr_pos = 0;
@@ -203,7 +209,11 @@ struct PcCommitment {
     std::vector<F> final_code, final_mask;       // 2048, 32
     std::vector<u64> leaf0;                      // one per repetition, in [2^(n-7), 2^(n-2))
     const uint8_t *answer = nullptr; u64 n_bytes = 0;      // vp_fri_query's layout for (n, leaf0.size())
+    u64 pow_bits = 0, pow_nonce = 0;             // a non-interactive proof's work (0: none, version 1) and whether W(pow_bits, pow_nonce) met it; pcVerifyCommitment
+    bool pow_met = true;                         // does not read them: pcCheckWork decides
 };
+// The proof of work of a parsed non-interactive proof against the verifier's demand: 0, or 1 with the reason (the work is not met; fewer bits than demanded).
+int pcCheckWork(u64 pow_bits, u64 pow_nonce, bool met, int min_pow_bits, std::string &why);
 // 0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).  dev: a device context for the heavy loops (vp_pc_public_evals, vp_pc_mask_evals,
 // vp_fri_query_digests), or null for the host's; a device call that fails throws std::runtime_error.
 int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev = nullptr);
@@ -213,7 +223,7 @@ int pcVerifyCommitment(const PcCommitment &c, std::string &why, vp_ctx *dev = nu
 // rules) and derives fr and leaf0 from the chain: c is ready for pcVerifyCommitment, its answer pointing into `proof`.  0, or -1 with the reason.
 int pcParseCommitmentFS(const uint8_t *proof, u64 len, PcCommitment &c, std::string &why);
 // Parse, derive, pcVerifyCommitment unchanged: no algebra of its own.  0 = accepted, 1 = rejected (why: the failed check), -1 = malformed (why).
-int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr);
+int pcVerifyCommitmentFS(const uint8_t *proof, u64 len, std::string &why, vp_ctx *dev = nullptr, int min_pow_bits = 0);
 
 // verifier::checkFull (after F::init()) with pred_dev and poly_dev on a context made for the call on `device`; throws std::runtime_error without a usable device
 bool checkFullOnDevice(const layeredCircuit &c, int device, const std::vector<uint8_t> &record);

@@ -10,6 +10,7 @@
 #include "circuit.hpp"
 #include "fft_gkr_fs.hpp"
 #include "gkr_fs.hpp"
+#include "pc_fs.hpp"
 #include "prover.hpp"
 #include "verifier.hpp"
 
@@ -599,11 +600,16 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
 // ---- the non-interactive commitment proof (vphost.h: "The transcript chain", "Proof bytes") ----------------------------------------------------------------
 int vph_commit_fs(vph_session *s, const uint64_t *point_pairs, int n_point, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs,
                   uint64_t n_pub_mask, int flags, uint8_t *out, uint64_t cap, uint64_t *len, char *err, int errlen) {
+    return vph_commit_fs_pow(s, point_pairs, n_point, reps, mask_pairs, n_mask, pub_mask_pairs, n_pub_mask, flags, 0, out, cap, len, err, errlen);
+}
+int vph_commit_fs_pow(vph_session *s, const uint64_t *point_pairs, int n_point, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs,
+                      uint64_t n_pub_mask, int flags, int pow_bits, uint8_t *out, uint64_t cap, uint64_t *len, char *err, int errlen) {
     if (!s || !point_pairs || n_point < 1 || !len || (n_mask && !mask_pairs) || (n_pub_mask && !pub_mask_pairs)) { set_err(err, errlen, "vph_commit_fs: a null argument"); return -1; }
+    if (pow_bits < 0 || pow_bits > PCFS_POW_PROVER_BITS) { set_err(err, errlen, "vph_commit_fs_pow: pow_bits outside 0 .. 32"); return -1; }
     for (uint64_t i = 0; i < 2 * (uint64_t) n_point; ++i) if (point_pairs[i] >= F::mod) { set_err(err, errlen, "vph_commit_fs: non-canonical coordinate"); return -1; }
     try {
         const std::vector<uint8_t> proof = s->p->commitFS(pc_elems(point_pairs, (uint64_t) n_point), reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask),
-                                                          !(flags & VPH_FS_HOST_DRAWS));
+                                                          !(flags & VPH_FS_HOST_DRAWS), pow_bits);
         *len = proof.size();
         if (!out || cap < proof.size()) { set_err(err, errlen, "vph_commit_fs: output buffer too small (*len: the proof's size)"); return -1; }
         memcpy(out, proof.data(), proof.size());
@@ -614,12 +620,14 @@ int vph_commit_fs(vph_session *s, const uint64_t *point_pairs, int n_point, int 
     }
 }
 void vph_last_commit_fs_times(vph_session *s, double out[2]) { out[0] = s ? s->p->fsPhaseSec() : 0; out[1] = s ? s->p->fsPhaseDeviceMs() : 0; }
-int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen) {
+int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen) { return vph_verify_commitment_fs_min(proof, len, device, 0, err, errlen); }
+int vph_verify_commitment_fs_min(const uint8_t *proof, uint64_t len, int device, int min_pow_bits, char *err, int errlen) {
     vp_ctx *ctx = nullptr;
     try {
         PcCommitment c;
         std::string why;
         if (pcParseCommitmentFS(proof, len, c, why) != 0) { set_err(err, errlen, why); return -1; }      // malformed: before a context is made
+        if (pcCheckWork(c.pow_bits, c.pow_nonce, c.pow_met, min_pow_bits, why)) { set_err(err, errlen, why); return 1; }      // one hash: before a context is made, too
         if (device >= 0 && vp_create(device, &ctx) != VP_OK) { ctx = nullptr; throw std::runtime_error("vph_verify_commitment_fs: no context on the device"); }
         const int rc = pcVerifyCommitment(c, why, ctx);
         if (ctx) vp_destroy(ctx);
@@ -645,14 +653,19 @@ int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r
 // ---- the joined non-interactive proof of the whole protocol (verifier::proveFullFS / checkFullFS) ----
 int vph_prove_full_fs(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
                       uint64_t *len, uint64_t *point_pairs, char *err, int errlen) {
-    return vph_prove_full_fs_ex(s, reps, mask_pairs, n_mask, pub_mask_pairs, n_pub_mask, out, cap, len, point_pairs, 0, err, errlen);
+    return vph_prove_full_fs_pow(s, reps, mask_pairs, n_mask, pub_mask_pairs, n_pub_mask, out, cap, len, point_pairs, 0, 0, err, errlen);
 }
 int vph_prove_full_fs_ex(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
                          uint64_t *len, uint64_t *point_pairs, int flags, char *err, int errlen) {
+    return vph_prove_full_fs_pow(s, reps, mask_pairs, n_mask, pub_mask_pairs, n_pub_mask, out, cap, len, point_pairs, flags, 0, err, errlen);
+}
+int vph_prove_full_fs_pow(vph_session *s, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                          uint64_t *len, uint64_t *point_pairs, int flags, int pow_bits, char *err, int errlen) {
     if (!s || !len || (n_mask && !mask_pairs) || (n_pub_mask && !pub_mask_pairs)) { set_err(err, errlen, "vph_prove_full_fs: a null argument"); return -1; }
+    if (pow_bits < 0 || pow_bits > PCFS_POW_PROVER_BITS) { set_err(err, errlen, "vph_prove_full_fs_pow: pow_bits outside 0 .. 32"); return -1; }
     try {
         verifier v(s->p.get(), s->circ->c);
-        const std::vector<uint8_t> proof = v.proveFullFS(reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask), (flags & VPH_FS_DEVICE_GKR) != 0);
+        const std::vector<uint8_t> proof = v.proveFullFS(reps, pc_elems(mask_pairs, n_mask), pc_elems(pub_mask_pairs, n_pub_mask), (flags & VPH_FS_DEVICE_GKR) != 0, pow_bits);
         *len = proof.size();
         if (!out || cap < proof.size()) { set_err(err, errlen, "vph_prove_full_fs: output buffer too small (*len: the proof's size)"); return -1; }
         memcpy(out, proof.data(), proof.size());
@@ -664,13 +677,16 @@ int vph_prove_full_fs_ex(vph_session *s, int reps, const uint64_t *mask_pairs, u
     }
 }
 int vph_verify_full_fs(vph_circuit *c, const uint8_t *proof, uint64_t len, int device, uint64_t *point_pairs, char *err, int errlen) {
+    return vph_verify_full_fs_min(c, proof, len, device, 0, point_pairs, err, errlen);
+}
+int vph_verify_full_fs_min(vph_circuit *c, const uint8_t *proof, uint64_t len, int device, int min_pow_bits, uint64_t *point_pairs, char *err, int errlen) {
     if (!c) { set_err(err, errlen, "vph_verify_full_fs: no circuit"); return -1; }
     vp_ctx *ctx = nullptr;
     try {
         if (device >= 0 && vp_create(device, &ctx) != VP_OK) { ctx = nullptr; throw std::runtime_error("vph_verify_full_fs: no context on the device"); }
         verifier v(nullptr, c->c);
         std::string why;
-        const int rc = v.checkFullFS(proof, len, why, ctx);
+        const int rc = v.checkFullFS(proof, len, why, ctx, min_pow_bits);
         if (ctx) vp_destroy(ctx);
         if (rc) set_err(err, errlen, why);
         if (point_pairs && !v.fullFsPoint().empty()) memcpy(point_pairs, v.fullFsPoint().data(), v.fullFsPoint().size() * sizeof(F));
@@ -680,6 +696,29 @@ int vph_verify_full_fs(vph_circuit *c, const uint8_t *proof, uint64_t len, int d
         set_err(err, errlen, e.what());
         return -2;
     }
+}
+
+// ---- the proof of work (vphost.h, "The proof of work"): the host's search, and the two fields of either kind of proof ----
+int vph_fs_grind_host(const uint8_t state_in[32], int bits, uint64_t first, uint64_t max_tries, uint64_t *nonce, uint8_t state_out[32]) {
+    if (!state_in || !nonce || !state_out || bits < 1 || bits > PCFS_POW_MAX_BITS || max_tries == 0 || first + (max_tries - 1) < first) return -1;
+    vph::fs_chain ch;
+    memcpy(ch.s.w, state_in, 32);
+    uint64_t found = 0;
+    if (!vph::fs_grind(ch.s, bits, first, max_tries, &found)) return -5;
+    ch.work((uint64_t) bits, found);
+    *nonce = found;
+    memcpy(state_out, ch.s.w, 32);
+    return 0;
+}
+int vph_fs_pow(const uint8_t *proof, uint64_t len, uint64_t *bits, uint64_t *nonce) {
+    if (!proof || !bits || !nonce || len < 32) return -1;
+    uint32_t h32[2];
+    memcpy(h32, proof, 8);
+    if ((h32[0] != PCFS_MAGIC && h32[0] != 0x46465056u) || (h32[1] != PCFS_VERSION && h32[1] != PCFS_VERSION_POW)) return -1;
+    PcFsWork w;
+    if (h32[1] == PCFS_VERSION_POW && (len < 48 || !pcFsWorkHeader(proof + 32, w))) return -1;
+    *bits = w.bits; *nonce = w.nonce;
+    return 0;
 }
 
 // ---- the GKR part of the chain (vphost.h, "The GKR part on the device"): sizes, the derivation alone (gkr_fs.hpp), the device call ----

@@ -180,7 +180,7 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
 /* ---- The non-interactive commitment proof: Fiat-Shamir over the commitment by value ---------------------------------------------------------------------------
  * One block of bytes that anyone checks with no tape and no session: the level of vph_verify_commitment, with the fold challenges and the query positions
  * derived from the prover's own messages instead of handed over.  What it proves: that the committed vector's inner product with eq(point, .) is the claim, with
- * the reference's soundness per repetition (no proof of work on top); the multiple-of-32 corner of h is what it is for vph_verify_commitment.  Limits: unsharded
+ * the reference's soundness per repetition (a proof of work on top is the prover's choice: "The proof of work" below); the multiple-of-32 corner of h is what it is for vph_verify_commitment.  Limits: unsharded
  * sessions, the point form of the public vector, masks within vp_commit_private_masked's limits (the verifier accepts ms <= 2^(n-6)).  Joining it to vph_prove_fs
  * and fft_gkr into one proof of the whole protocol is the next step and not part of this.
  *
@@ -191,6 +191,7 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
  *     D(t, d)        a digest under label t: two steps, {t, 0, 0, 0x44}, then the digest's four words
  *     C(c)           challenge number c: {c, 0, 0, 0x43}; the element is (s.w0 & P, s.w1 & P), P = 2^61 - 1, with a limb equal to P mapped to 0
  *     Q(q)           position number q: {q, 0, 0, 0x51}; leaf0 = 2^(n-7) + (s.w0 mod (2^(n-2) - 2^(n-7))), the range vph_verify_commitment accepts
+ *     W(b, nonce)    proof of work: {nonce, b, 0, 0x57}; met when the low b bits of s.w0 are zero ("The proof of work" below)
  * With ln = n - 6 the order is:
  *      1. P(n, reps, ms, n_pub)
  *      2. D(0, root_l)
@@ -203,12 +204,14 @@ int vph_verify_commitment(int n, const uint64_t *point_pairs, const uint64_t *pu
  *      9. for k = 0 .. ln - 1: fold by r_k, which gives root_k; D(2 + k, root_k); for k + 1 < ln also r_(k+1) = C(k + 1)
  *     10. E over the 2048 elements of vp_fri_final
  *     11. E over the 32 elements of vp_fri_final_mask (zeros for the zero mask)
- *     12. Q(q), q < reps
+ *    11w. in a version-2 proof only: W(pow_bits, nonce) ("The proof of work" below); a version-1 proof has no such step
+ *     12. Q(q), q < reps, from the state step 11 (version 1) or W (version 2) leaves
  * Positions may repeat.  The point comes after root_l, so the committer cannot choose the witness after seeing it.
  *
  * Proof bytes, little-endian.  Header, 32 bytes: u32 magic 0x46435056 ("VPCF") | u32 version = 1 | u32 n | u32 reps | u64 ms | u64 n_pub.  Then, in this order:
  * the point (16 n bytes) | the public mask (16 n_pub) | the claim (16) | root_l (32) | root_h (32) | all_sum (65 x 16) | the FRI roots (32 ln) | the final codeword
  * (2048 x 16) | the final mask (32 x 16) | the answer in vp_fri_query's layout for (n, reps).
+ * Version 2 (a proof with work): the same with version = 2 and 16 bytes behind the header, u64 pow_bits | u64 nonce; everything else keeps its place.
  *
  * vph_commit_fs: prover::commitFS on the session — commit_private(mask; null or all zero: the zero mask), commit_public_eq(point[, pub_mask]), the commit phase,
  * the final codewords, the positions, vp_fri_query.  flags 0: the commit phase is vp_fri_commit_fs (the device draws every challenge from the root it has just
@@ -225,6 +228,33 @@ int vph_commit_fs(vph_session *, const uint64_t *point_pairs, int n_point, int r
 void vph_last_commit_fs_times(vph_session *, double out[2]);
 int vph_verify_commitment_fs(const uint8_t *proof, uint64_t len, int device, char *err, int errlen);
 int vph_commitment_fs_challenges(const uint8_t *proof, uint64_t len, uint64_t *r_pairs /* n - 6 */, uint64_t *leaf0 /* reps */);
+/* The proof of work (grinding) of the commitment proof and of the joined proof.  W(b, nonce) is the chain step state = H({nonce, b, 0, 0x57}, state); the work is
+ * met when the low b bits of the new state's first word (little-endian u64, as everywhere in the chain) are zero.  It stands behind the two final codewords and in
+ * front of the positions, which are drawn from the state it leaves: the nonce moves every position, so a prover cannot grind after seeing them, and each bit
+ * doubles the work of a prover who re-draws the positions of a commitment that would not pass — it buys soundness against the query phase alone, nothing
+ * for the GKR and fft_gkr parts.  A proof with work is version 2 of its kind ("VPCF" or "VPFF"): the 32-byte header is followed by u64 pow_bits | u64 nonce.
+ * Parser: pow_bits in 1 .. 48, anything else is malformed — a version-2 proof with pow_bits = 0 too: version 1 is the only encoding of "no work"; a version-1
+ * body under a version-2 header is 16 bytes short of its answer and malformed by that rule.  Verdicts: work not met is REJECTED (1; err names the proof of
+ * work), not malformed; pow_bits below the verifier's demand min_pow_bits is rejected (err names both numbers), and so is a version-1 proof under
+ * min_pow_bits >= 1.  In the commitment proof both are decided after the parse and before any other check.  In the joined proof the demand is decided by the
+ * header, before the GKR part is replayed (a proof with too little work under a well-formed header is rejected whatever lies behind it), and the work where the
+ * chain reaches it: after the replay and the parse of the remaining sections, before fft_gkr's and the commitment's checks.
+ * vph_fs_grind_host: the smallest nonce in [first, first + max_tries) that meets `bits` bits of work on state_in, and the state behind W; sha3.hpp on one
+ * thread — the second implementation of vp_fs_grind (include/vpgpu.h) and the search of VPH_FS_HOST_DRAWS.  0; -5 (vp_fs_grind's VP_ELIMIT) when the range
+ * holds none, outputs untouched; -1 for a null pointer, bits outside 1 .. 48, max_tries = 0, a range that would pass 2^64.
+ * vph_commit_fs_pow / vph_prove_full_fs_pow: vph_commit_fs / vph_prove_full_fs_ex with pow_bits.  0 is that call exactly and its version-1 bytes; 1 .. 32 grinds
+ * from nonce 0 through 64 x 2^pow_bits tries (failing all of them has probability e^-64) and returns -2 with a reason when none meets the work; anything else is
+ * a bad argument (-1).  The nonce is vp_fs_grind's on the session's context, checked against the host's step; under VPH_FS_HOST_DRAWS (commitment proof) it is
+ * vph_fs_grind_host's — the same bytes.  Sharded sessions are refused as before.
+ * vph_verify_commitment_fs_min / vph_verify_full_fs_min: the verifiers with the demand; vph_verify_commitment_fs / vph_verify_full_fs are these with
+ * min_pow_bits = 0 and so accept a well-formed version-2 proof whose work is met.  vph_commitment_fs_challenges reads both versions.
+ * vph_fs_pow: the two fields of either kind of proof, from the header alone (the body is not parsed): version 1 gives 0, 0; -1 for a null pointer, fewer bytes
+ * than the header, another magic or version, pow_bits outside 1 .. 48.                                                                                      */
+int vph_fs_grind_host(const uint8_t state_in[32], int bits, uint64_t first, uint64_t max_tries, uint64_t *nonce, uint8_t state_out[32]);
+int vph_commit_fs_pow(vph_session *, const uint64_t *point_pairs, int n_point, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs,
+                      uint64_t n_pub_mask, int flags, int pow_bits, uint8_t *out, uint64_t cap, uint64_t *len, char *err, int errlen);
+int vph_verify_commitment_fs_min(const uint8_t *proof, uint64_t len, int device, int min_pow_bits, char *err, int errlen);
+int vph_fs_pow(const uint8_t *proof, uint64_t len, uint64_t *bits, uint64_t *nonce);
 /* The transcript chain: fft_gkr.  vp_fft_gkr_fs (include/vpgpu.h) continues a chain of the steps above from a 32-byte state and draws fft_gkr's whole tape from it
  * on the device.  A slot's counter is its index in the tape layout (r[lg] | x[64] | r_0[lg+10] | r_1[lg+10] | addition layer r_u[lg+6], r_v[lg+6] | multiplication
  * layer r_u[lg], r_v[lg] | per depth r_u[lg], r_v[lg], alpha, beta); messages are in vp_fft_gkr's layout.  The order:
@@ -289,10 +319,11 @@ int vph_prove_full_fs_ex(vph_session *, int reps, const uint64_t *mask_pairs, ui
  *      4. the commitment head at that point: E(input_0), E(all_sum[i]), i < 65, D(1, root_h)
  *      5. fft_gkr at lg = n - 6 from that state ("The transcript chain: fft_gkr" below)
  *      6. the FRI commit phase from the state fft_gkr leaves, as steps 8 and 9 of the commitment proof: r_0 = C(0); per level D(2 + k, root_k), r_(k+1) = C(k + 1)
- *      7. E over the final codeword (2048), E over the final mask codeword (32), Q(q), q < reps
+ *      7. E over the final codeword (2048), E over the final mask codeword (32), in a version-2 proof W(pow_bits, nonce), then Q(q), q < reps
  * Proof bytes: header u32 magic 0x46465056 ("VPFF") | u32 version = 1 | u32 n | u32 reps | u64 ms | u64 n_pub; then the public mask (16 n_pub) | root_l (32) | the GKR
  * bytes (vph_prove_fs's proof for this chain) | root_h (32) | input_0 (16) | all_sum (65 x 16) | the fft_gkr messages | the FRI roots (32 (n - 6)) | the final codeword |
- * the final mask | the answer in vp_fri_query's layout.  The point is not in the proof: it is derived.
+ * the final mask | the answer in vp_fri_query's layout.  The point is not in the proof: it is derived.  Version 2: version = 2 and u64 pow_bits | u64 nonce behind
+ * the header ("The proof of work" above), everything else in its place.
  * vph_verify_full_fs parses under vph_verify_full_record's rules (bounds on every read, canonical limbs, the proof ends where the answer ends; n must be the circuit's
  * input bit length; ms and n_pub by vph_verify_commitment's rules), replays the GKR part, compares its claim with input_0, derives fft_gkr's tape and calls
  * fft_gkr_check unchanged, fills the commitment by value and calls vph_verify_commitment's checks unchanged (device >= 0: their heavy loops on that GPU): no algebra of
@@ -304,6 +335,9 @@ int vph_prove_full_fs_ex(vph_session *, int reps, const uint64_t *mask_pairs, ui
 int vph_prove_full_fs(vph_session *, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
                       uint64_t *len, uint64_t *point_pairs /* n, or null */, char *err, int errlen);
 int vph_verify_full_fs(vph_circuit *, const uint8_t *proof, uint64_t len, int device, uint64_t *point_pairs /* n, or null */, char *err, int errlen);
+int vph_prove_full_fs_pow(vph_session *, int reps, const uint64_t *mask_pairs, uint64_t n_mask, const uint64_t *pub_mask_pairs, uint64_t n_pub_mask, uint8_t *out, uint64_t cap,
+                          uint64_t *len, uint64_t *point_pairs /* n, or null */, int flags, int pow_bits, char *err, int errlen);
+int vph_verify_full_fs_min(vph_circuit *, const uint8_t *proof, uint64_t len, int device, int min_pow_bits, uint64_t *point_pairs /* n, or null */, char *err, int errlen);
 /* FRI commit phase of the last vph_prove_and_verify_full: Merkle root per fold step (32 bytes each), final codeword (2048
  * elements), fold challenges (one element per step); any pointer may be NULL.  Returns the number of steps or -1. */
 int vph_last_fri(vph_session *, uint8_t *roots, uint64_t roots_cap, uint64_t *final_pairs, uint64_t *r_pairs);
