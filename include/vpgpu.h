@@ -142,7 +142,36 @@ int vp_checked_build(void);
 
 /* prover::prover(const layeredCircuit&) (src/prover.cpp:14) — the circuit is copied to HBM together
  * with the per-layer target-sorted gate indices the init kernels use.  May be called again to replace
- * the circuit.                                                                                         */
+ * the circuit.
+ *
+ * The upload is the library's trust boundary: it validates the whole description, and no kernel of the product build checks an index of it
+ * again (a -DVP_CHECKED build keeps such checks).  What is refused, in this order, with the vp_last_error text in quotes:
+ *   1. before the context is touched — the previous circuit, its witness and everything else stay as they were:
+ *        VP_EINVAL  ctx or layers NULL, n_layers < 2 (no text);          VP_ELIMIT  n_layers > 64 "too many layers";
+ *   2. every layer's size, in layer order:
+ *        VP_ELIMIT  size == 0 or size > 2^30 "bad layer size";           VP_EINVAL  bit_length != ceil(log2(size)) "bad layer size"
+ *        (the reference always stores that value, and the padded length of every table follows from it);
+ *   3. then layer by layer, i = 1 .. n_layers - 1, all VP_EINVAL:
+ *        one of ty, l, u, v, lv, dad_size, dad_bitlen, dad_id NULL, or dad_id[j] NULL for a non-empty subset      "layer arrays missing";
+ *        by j < i:  dad_size[j] > size of layer j                                                                  "dadSize too large";
+ *                   dad_size[j] != 0 and dad_bitlen[j] != ceil(log2(dad_size[j]))                                  "dadBitLength mismatch";
+ *        an entry dad_id[j][k] >= size of layer j                                                                   "dadId out of range";
+ *        the LOWEST gate g that fails, and within it the first of:
+ *                   ty > VP_COPY or ty == VP_INPUT                                                                  "bad gate type";
+ *                   u >= size of layer i - 1                                                                        "gate.u out of range";
+ *                   Addc / Mulc / Not / Copy with l != -1                                                           "unary gate with l != -1";
+ *                   a binary gate with l < 0, l >= i or v >= size of layer l                                        "gate.v out of range";
+ *                   lv >= dad_size[l] or dad_id[l][lv] != v                                                          "gate.lv inconsistent with dadId";
+ *        c == NULL in a layer with an Addc or Mulc gate                                                             "Addc/Mulc gates without constants".
+ *      A HIP error at any point is VP_EHIP.
+ * A refusal of kind 2 or 3 (and a VP_EHIP) leaves an EMPTY context: the previous circuit is gone, whatever had been built of the new one is freed,
+ * vp_last_error keeps the reason, and every entry point that needs a circuit or a witness answers VP_EINVAL until an upload succeeds.
+ * A successful upload discards everything that belonged to the previous circuit: its witness (vp_evaluate again), an interactive sumcheck in
+ * progress (vp_round / vp_finalize answer VP_EINVAL until the next init call; vp_get_round_stats is empty), the launch plan with its captured
+ * graph and tuning, and the commitment with its FRI levels.  The caller's settings stay: options, vp_set_shard / vp_set_shard_split,
+ * vp_set_round_shard, vp_set_deferred, vp_pc_hash_late, vp_set_profiling, an attached communicator.  vp_pc_load_input replaces the circuit the
+ * same way, by a lone input layer: the commitment entry points work on it, the GKR ones answer VP_EINVAL.
+ * Not checked: a wire listed twice in one dad_id[j] (in range; the reference's subsetInit never produces it) — the result is unspecified.      */
 int vp_circuit_upload(vp_ctx *, int n_layers, const vp_layer_desc *layers);
 
 /* prover::evaluate() (src/prover.cpp:27-91).  `inputs` are the layer-0 values (size of layer 0).

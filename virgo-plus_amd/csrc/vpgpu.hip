@@ -399,6 +399,37 @@ void pc_forget(vp_ctx *ctx) {
     ctx->pc_mask_ms = 0; ctx->pc_lm_cw = ctx->pc_qm_cw = ctx->pc_hm_cw = ctx->pc_fm = ctx->pc_mtmp = nullptr; ctx->pc_mtmp_cap = 0; ctx->pc_mB = 0;
     ctx->pc_lv = PcLive(); ctx->pc_zf_cw = ctx->pc_zf_hcw = ctx->pc_zf_fri = 64;
 }
+// The circuit went with free_all (vp_circuit_upload, vp_pc_load_input): the context holds NO circuit until the caller's rebuild has finished.  Every member
+// that points into `allocs` or is sized by the circuit is reset here (the list with the members that survive, and why: DESIGN.md, "What a circuit upload
+// resets"), so that nothing of the replaced circuit — a table, a layout, an open sumcheck, a commitment — can be reached through the new one.
+void circuit_forget(vp_ctx *ctx) {
+    ctx->L.clear(); ctx->n_layers = 0; ctx->max_bl = 0; ctx->evaluated = false;
+    ctx->d_vals = nullptr; ctx->d_valsr = nullptr; ctx->vreal = 0; ctx->plan_vreal = 0;
+    ctx->beta_g = ctx->beta_u = ctx->bf = ctx->bs = ctx->liu_half = nullptr; ctx->half_cap = 0;
+    for (int b = 0; b < 2; ++b) for (int t = 0; t < 3; ++t) ctx->tab[b][t] = nullptr;
+    ctx->cap = 0; ctx->partials = nullptr; ctx->round_arrivals = nullptr; ctx->small = nullptr; ctx->chunk_part = nullptr; ctx->chunk_cap = 0;
+    ctx->d_tape = nullptr; ctx->n_tape = 0; ctx->d_tr = nullptr; ctx->n_tr = 0; ctx->d_trs = nullptr; ctx->n_exp = 0;
+    ctx->d_flag = nullptr; ctx->d_vcplx = nullptr;
+    ctx->ru_off.clear(); ctx->as_off.clear(); ctx->rv_off.clear(); ctx->sig_off.clear(); ctx->rliu_off.clear();
+    // an interactive sumcheck of the replaced circuit is over (VP_ENTER has told a resident round kernel to leave): vp_round / vp_finalize refuse until the next init
+    ctx->sc = SumcheckState(); ctx->sc_open = false; ctx->r1_pending = 0; ctx->rlog.clear(); ctx->rlog_round = 0;
+    ctx->tail_args = PTailArgs{}; ctx->tail_save = nullptr;
+    if (ctx->rsh) { ctx->rsh->live = false; ctx->rsh->packed = false; ctx->rsh->nx = 0; ctx->rsh->split = 0; }
+    ctx->all_jobs = nullptr; ctx->n_all_jobs = 0; ctx->beta_bpj = 1; ctx->half_pool = nullptr; ctx->part2 = nullptr;
+    ctx->lane0 = Lane(); ctx->ln = nullptr; ctx->lanes.clear();
+    ctx->pred_r = ctx->pred_pool = ctx->pred_part = ctx->pred_out = nullptr; ctx->pred_jobs = nullptr; ctx->pred_bpj = 1; ctx->pred_dot = nullptr; ctx->pred_map = nullptr;
+    ctx->chain_owner.clear(); ctx->chain_cost.clear(); ctx->split.clear(); ctx->vu_supplied = false; ctx->vu_tape_tag = 0;
+    ctx->rec_fix.clear(); ctx->graph_failed = false; ctx->plan_tuned = false; ctx->plan_tune_cached = false;
+    pc_forget(ctx);
+    // What survives, and why.  Owned outside `allocs` and not sized by the circuit: stream, lane_streams / lane_events / ev_fork (reused, grown on demand), ev0 / ev1,
+    // ev_pool, the pinned buffers (h_pin, h_seq, h_req, h_rep, h_aux, h_stage, h_io, h_ring, h_pub, h_many: each grown on demand behind its own capacity), fgk (its
+    // own arrays, sized by vp_fft_gkr's lg), cm, rsh's send / recv (own hipMalloc behind rsh->cap), pending (flushed by VP_ENTER before the circuit is replaced).
+    // The caller's settings: opt, poll, tail_enabled, deferred, hash_late, profiling, shard_rank / shard_world, split_lw / split_min_log, rsh's rank / world / min_log,
+    // plan_cache_path, opt_pinned.  Counters and reports of past calls: st, lstats, phase_ms, commit_ms, tail_resumes, tail_seq, seq, graph_launches, private_epoch.
+    // plan, gkr_graph and pcs have destructors of their own (free_plan, hipGraphExecDestroy, vp_free_shard_state): the callers run them before free_all.
+}
+// n_layers >= 2 <=> a circuit is uploaded (0: none, or the last upload was refused; 1: the lone input layer of vp_pc_load_input)
+inline bool has_circuit(const vp_ctx *ctx) { return ctx->n_layers >= 2; }
 
 inline u32 nblk(u64 n) { return (u32) ((n + VP_BLOCK - 1) / VP_BLOCK); }
 inline u32 grid_for(u64 n) { return std::max<u32>(1, std::min<u32>(nblk(n), MAX_BLOCKS)); }
@@ -1297,21 +1328,23 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     VPCHK(pc_hash_outstanding(ctx, 3u));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (ctx->gkr_graph) { (void) hipGraphExecDestroy(ctx->gkr_graph); ctx->gkr_graph = nullptr; }
-    ctx->graph_failed = false; ctx->plan_tuned = false; ctx->plan_tune_cached = false;
     free_plan(ctx);
     vp_free_shard_state(ctx);
     free_all(ctx);
+    circuit_forget(ctx);
+    // from here on the previous circuit is gone.  A refusal below (a malformed description, a limit, a HIP error) must not leave a half-built one that the
+    // other entry points take for uploaded: whatever the partial build allocated is freed and the context is left without a circuit; vp_last_error stays.
+    struct Refused {
+        vp_ctx *c; bool armed = true;
+        ~Refused() { if (armed) { (void) hipStreamSynchronize(c->stream); free_all(c); circuit_forget(c); } }
+    } refused{ctx};
     ctx->L.assign(n_layers, LayerDev());
     ctx->n_layers = n_layers;
-    ctx->evaluated = false;
-    ctx->chain_owner.clear(); ctx->chain_cost.clear();
-    ctx->chunk_cap = 0;
-    ctx->pred_r = ctx->pred_pool = ctx->pred_part = ctx->pred_out = nullptr; ctx->pred_jobs = nullptr; ctx->pred_dot = nullptr; ctx->pred_map = nullptr;
-    pc_forget(ctx);
     int max_bl = 0;
     for (int i = 0; i < n_layers; ++i) {
-        if (ld[i].size == 0 || ld[i].size > (1ull << 30) || ld[i].bit_length < 0 || ld[i].bit_length > 30 ||
-            (1ull << ld[i].bit_length) < ld[i].size) { ctx->err = "bad layer size"; return VP_ELIMIT; }
+        if (ld[i].size == 0 || ld[i].size > (1ull << 30)) { ctx->err = "bad layer size"; return VP_ELIMIT; }
+        // the reference stores ceil(log2(size)) (src/circuit.cpp) and nothing here has ever proved at another value: the padded length of every table follows from it
+        if (ld[i].bit_length != ceil_log2(ld[i].size)) { ctx->err = "bad layer size"; return VP_EINVAL; }
         max_bl = std::max(max_bl, (int) ld[i].bit_length);
     }
     ctx->max_bl = max_bl;
@@ -1500,6 +1533,7 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
     }
 #endif
     ensure_event_pool(ctx);
+    refused.armed = false;
     return VP_OK;
 }
 
@@ -1695,7 +1729,7 @@ static int pred_inner_product(vp_ctx *ctx, const vp_F *r, int n, const F *table,
 }
 
 int vp_layer_mle(vp_ctx *ctx, int layer, const vp_F *r, int n, vp_F *out) {
-    if (!ctx || !ctx->evaluated || layer < 0 || layer >= ctx->n_layers || !out || n != ctx->L[layer].bl || (n && !r)) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !ctx->evaluated || layer < 0 || layer >= ctx->n_layers || !out || n != ctx->L[layer].bl || (n && !r)) return VP_EINVAL;
     if (!pred_canonical(r, n)) { ctx->err = "vp_layer_mle: r is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     return pred_inner_product(ctx, r, n, ctx->L[layer].val, (u32) ctx->L[layer].size, out);
@@ -1731,7 +1765,7 @@ int vp_liu_gr(vp_ctx *ctx, int layer, const vp_F *r_u, const vp_F *const *r_v, c
 }
 
 int vp_vres(vp_ctx *ctx, const vp_F *r_0, int r_0_size, vp_F *out) {
-    if (!ctx || !ctx->evaluated || !out || r_0_size != ctx->L[ctx->n_layers - 1].bl || (r_0_size && !r_0)) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !ctx->evaluated || !out || r_0_size != ctx->L[ctx->n_layers - 1].bl || (r_0_size && !r_0)) return VP_EINVAL;
     if (!pred_canonical(r_0, r_0_size)) { ctx->err = "vp_vres: r_0 is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     ctx->rlog.clear();
@@ -2033,7 +2067,7 @@ int vp_shard_chains(vp_ctx *ctx, int32_t *owner, double *cost, int capacity, int
 
 int vp_prove_gkr(vp_ctx *ctx, const vp_F *tape, uint64_t n_tape, uint8_t *transcript, uint64_t capacity,
                  uint64_t *n_written) {
-    if (!ctx || !ctx->evaluated || !tape || !transcript || n_tape != ctx->n_tape) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !ctx->evaluated || !tape || !transcript || n_tape != ctx->n_tape) return VP_EINVAL;
     if (!pred_canonical(tape, n_tape)) { ctx->err = "vp_prove_gkr: a tape element is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     { uint64_t need = 0; (void) vp_gkr_sizes(ctx, nullptr, &need); if (ctx->opt.debug & 1) fprintf(stderr, "[vp] vp_prove_gkr: capacity %llu need %llu\n", (unsigned long long) capacity, (unsigned long long) need); if (capacity < need) return VP_EINVAL; }
     if (!ctx->simple_path) return prove_gkr_fused(ctx, tape, n_tape, transcript, n_written);

@@ -1566,7 +1566,7 @@ static int prove_gkr_fused(vp_ctx *ctx, const vp_F *tape, uint64_t n_tape, uint8
 
 // Index-split proof, caller-side exchange of the split phase-2 chains' V_u (include/vpgpu.h): this rank's partial inner products ...
 int vp_shard_vu_partials(vp_ctx *ctx, const vp_F *tape_, uint64_t n_tape, vp_F *partials, uint64_t capacity, uint64_t *n_out) {
-    if (!ctx || !ctx->evaluated || !n_out || (n_tape && !tape_) || n_tape != ctx->n_tape) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !ctx->evaluated || !n_out || (n_tape && !tape_) || n_tape != ctx->n_tape) return VP_EINVAL;
     if (!pred_canonical(tape_, n_tape)) { ctx->err = "vp_shard_vu_partials: a tape element is not canonical (limb >= 2^61 - 1)"; return VP_EINVAL; }
     VP_ENTER(ctx);
     *n_out = 0;
@@ -1592,7 +1592,7 @@ int vp_shard_vu_partials(vp_ctx *ctx, const vp_F *tape_, uint64_t n_tape, vp_F *
 }
 // ... and their u64 sum over the ranks, for the next vp_prove_gkr of this context (same tape)
 int vp_shard_vu_set(vp_ctx *ctx, const vp_F *sums, uint64_t n) {
-    if (!ctx || !ctx->evaluated || (n && !sums)) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !ctx->evaluated || (n && !sums)) return VP_EINVAL;
     VP_ENTER(ctx);
     if (!(ctx->split_lw > 0 && ctx->shard_world > 1 && ctx->plan_path != 0 && ctx->opt.split_vu)) return n ? VP_EINVAL : VP_OK;
     if (ctx->plan && ctx->plan_vreal != ctx->vreal) free_plan(ctx);
@@ -1609,7 +1609,7 @@ int vp_shard_vu_set(vp_ctx *ctx, const vp_F *sums, uint64_t n) {
 // of the ranks' vp_prove_gkr outputs (transcript + export area, vp_gkr_sizes bytes); reduces them mod p and finishes the split tables' last
 // rounds with the tape of this context's last proof.  The first n_tr * 16 bytes of `buf` are then the transcript.
 int vp_shard_finish(vp_ctx *ctx, uint8_t *buf, uint64_t n_bytes, uint64_t *n_transcript_bytes) {
-    if (!ctx || !buf || !ctx->h_io) return VP_EINVAL;
+    if (!ctx || !has_circuit(ctx) || !buf || !ctx->h_io) return VP_EINVAL;
     split_layout(ctx);
     const u64 n = ctx->n_tr + 3 * ctx->n_exp;
     if (n_bytes < n * sizeof(F)) return VP_EINVAL;

@@ -7,7 +7,7 @@ extern "C" {
 int vp_prove_gkr_fs(vp_ctx *ctx, const uint8_t state_in[32], uint8_t *transcript, uint64_t capacity, uint64_t *n_written, vp_F *tape_out, uint64_t *n_draws,
                     uint8_t state_out[32]) {
     if (!ctx) return VP_EINVAL;
-    if (!ctx->evaluated) { ctx->err = "vp_prove_gkr_fs: vp_evaluate has not run"; return VP_EINVAL; }
+    if (!has_circuit(ctx) || !ctx->evaluated) { ctx->err = "vp_prove_gkr_fs: vp_evaluate has not run"; return VP_EINVAL; }
     if (!state_in || !transcript || !tape_out || !n_draws || !state_out) { ctx->err = "vp_prove_gkr_fs: a null argument"; return VP_EINVAL; }
     if (ctx->shard_world > 1 || ctx->split_lw > 0 || ctx->rsh) { ctx->err = "vp_prove_gkr_fs: not on a chain-sharded, round-sharded or index-split context"; return VP_EINVAL; }
     if (ctx->rec) { ctx->err = "vp_prove_gkr_fs: a launch plan is being recorded"; return VP_EINVAL; }

@@ -588,15 +588,17 @@ int vp_pc_load_input(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs, int bit
     free_plan(ctx);
     free_all(ctx);
     vp_free_shard_state(ctx);
+    // the circuit this layer replaces is gone with everything that belonged to it (tables, layouts, an open sumcheck, a commitment): vp_round / vp_finalize and the
+    // GKR entry points refuse until a circuit is uploaded again.  vreal = 0: caller data, possibly complex — vp_evaluate's finding about an earlier witness does not
+    // hold for it (the paired transforms of vp_commit_private read .re only)
+    circuit_forget(ctx);
     ctx->L.assign(1, LayerDev());
     ctx->n_layers = 1;
     ctx->L[0].size = n_inputs; ctx->L[0].bl = bit_length;
-    ctx->vreal = 0; ctx->plan_vreal = 0;          // caller data, possibly complex: vp_evaluate's finding about an earlier witness does not hold for it (the paired transforms of vp_commit_private read .re only)
     VPCHK(dalloc(ctx, &ctx->L[0].val, (size_t) 1 << bit_length));
     HIPCHK(hipMemsetAsync(ctx->L[0].val, 0, sizeof(F) << bit_length, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->L[0].val, inputs, n_inputs * sizeof(F), hipMemcpyHostToDevice, ctx->stream));
     VPCHK(check_stream(ctx));
-    pc_forget(ctx);
     ctx->evaluated = true;
     ensure_event_pool(ctx);
     return VP_OK;

@@ -254,6 +254,7 @@ int upload_layer_dev(vp_ctx *ctx, UpScratch &S, int i, const vp_layer_desc *ld, 
         if (L.dad_size[j] > ld[j].size) { ctx->err = "dadSize too large"; return VP_EINVAL; }
         D.dad_bl[j] = L.dad_size[j] ? ceil_log2(L.dad_size[j]) : 0;
         if (L.dad_size[j]) {
+            if (!L.dad_id[j]) { ctx->err = "layer arrays missing"; return VP_EINVAL; }
             if (L.dad_bitlen[j] != D.dad_bl[j]) { ctx->err = "dadBitLength mismatch"; return VP_EINVAL; }
             D.max_dad_bl = std::max(D.max_dad_bl, D.dad_bl[j]);
         }
@@ -263,8 +264,8 @@ int upload_layer_dev(vp_ctx *ctx, UpScratch &S, int i, const vp_layer_desc *ld, 
     }
     D.p2_total = off; D.n_gather = n_gather;
     unsigned long long *d_err = nullptr; u32 *d_needc = nullptr;
-    VPCHK(up_tmp(ctx, S, &d_err, 1)); VPCHK(up_tmp(ctx, S, &d_needc, 1));
-    HIPCHK(hipMemsetAsync(d_err, 0xff, sizeof(unsigned long long), ctx->stream));
+    VPCHK(up_tmp(ctx, S, &d_err, 2)); VPCHK(up_tmp(ctx, S, &d_needc, 1));      // [0]: the gates' error word, [1]: the subsets' (reported first: the gate check reads dadId)
+    HIPCHK(hipMemsetAsync(d_err, 0xff, 2 * sizeof(unsigned long long), ctx->stream));
     HIPCHK(hipMemsetAsync(d_needc, 0, sizeof(u32), ctx->stream));
     VPCHK(dalloc(ctx, &D.g_slot, (size_t) n_gather)); VPCHK(dalloc(ctx, &D.g_layer, (size_t) n_gather)); VPCHK(dalloc(ctx, &D.g_idx, (size_t) n_gather));
     VPCHK(dalloc(ctx, &D.s_layer, (size_t) D.p2_total)); VPCHK(dalloc(ctx, &D.s_idx, (size_t) D.p2_total));
@@ -277,7 +278,7 @@ int upload_layer_dev(vp_ctx *ctx, UpScratch &S, int i, const vp_layer_desc *ld, 
             const u32 m = (u32) L.dad_size[j];
             VPCHK(dalloc(ctx, &D.dad_id[j], (size_t) m));
             HIPCHK(hipMemcpyAsync(D.dad_id[j], L.dad_id[j], (size_t) m * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_up_check_range, dim3(nblk(m)), dim3(VP_BLOCK), 0, ctx->stream, D.dad_id[j], m, ld[j].size, d_err);
+            hipLaunchKernelGGL(k_up_check_range, dim3(nblk(m)), dim3(VP_BLOCK), 0, ctx->stream, D.dad_id[j], m, ld[j].size, d_err + 1);
             hipLaunchKernelGGL(k_up_subset, dim3(nblk(m)), dim3(VP_BLOCK), 0, ctx->stream, D.dad_id[j], m, D.t_off[j], gat, (uint8_t) j,
                                D.g_slot, D.g_layer, D.g_idx, D.s_layer, D.s_idx);
             gat += m;
@@ -315,10 +316,13 @@ int upload_layer_dev(vp_ctx *ctx, UpScratch &S, int i, const vp_layer_desc *ld, 
     a.key1 = key1; a.key2 = key2; a.bkey = bkey; a.asf = asf; a.err = d_err; a.need_c = d_needc;
     hipLaunchKernelGGL(k_up_prepare, dim3(nblk(n)), dim3(VP_BLOCK), 0, ctx->stream, a);
     hipLaunchKernelGGL(k_up_iota, dim3(nblk((u64) 2 * n)), dim3(VP_BLOCK), 0, ctx->stream, iota2, 2 * n, n);       // g, then g again for the Addc bias entries
-    unsigned long long err = 0; u32 need_c = 0;
-    HIPCHK(hipMemcpyAsync(&err, d_err, sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long err2[2] = {0, 0}; u32 need_c = 0;
+    HIPCHK(hipMemcpyAsync(err2, d_err, sizeof err2, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(&need_c, d_needc, sizeof need_c, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    // a subset entry out of range goes first, then the lowest failing gate: a bad dadId entry also fails the lv check of the gate that points at it, and which of
+    // the two one shared word reported depended on whether the entry's position or the gate's index was the smaller
+    const unsigned long long err = err2[1] != ~0ull ? err2[1] : err2[0];
     if (err != ~0ull) { ctx->err = up_error_text((int) (err & 0xff)); return VP_EINVAL; }
     if (need_c && !L.c) { ctx->err = "Addc/Mulc gates without constants"; return VP_EINVAL; }
     if (need_c) {
