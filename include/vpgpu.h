@@ -679,6 +679,9 @@ typedef struct {
 /* Copies up to `capacity` entries; *n receives the number available.                                                */
 int vp_get_launch_stats(vp_ctx *, vp_launch_stat *out, int capacity, int *n);
 const char *vp_kernel_name(int kind);
+/* The fused-init jobs of the launch plan the last vp_prove_gkr ran (k_sumfold3b_gen_multi), by what they generate: out[1] phase-1 inits, out[2] Liu
+ * gathers, out[3] phase-2 inits in the row-pointer form; out[5], out[6], out[7] the same in the row-record form (VP_GEN_REC).  Zeros without a plan. */
+int vp_get_gen_jobs(vp_ctx *, uint32_t out[8]);
 
 /* ---- primitives exported for parity tests (thin wrappers over the device functions) -------------- */
 /* out[i] = a[i] op b[i], op: 0 add, 1 sub, 2 mul (device arithmetic of fieldElement.cpp:34-104); op 3: out[i] = a[i] b[i] + a[i+1] b[i+1] (cyclic) through the

@@ -184,6 +184,7 @@ def lib_gpu():
         L.vp_set_profiling.argtypes = [vp, ctypes.c_int]
         L.vp_get_launch_stats.argtypes = [vp, ctypes.POINTER(LaunchStat), ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
         L.vp_kernel_name.argtypes = [ctypes.c_int]
+        L.vp_get_gen_jobs.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
         L.vp_kernel_name.restype = ctypes.c_char_p
         _gpu = L
     return _gpu
@@ -944,7 +945,7 @@ _TUNING_ENV = {"gkr_path": "VP_GKR_PATH", "serial": "VP_GKR_SERIAL", "fuse_init"
                "kernel_copies": "VP_KERNEL_COPIES", "fold_branches": "VP_FOLD_BRANCHES", "fuse_combine": "VP_FUSE_COMBINE",
                "graph_explicit": "VP_GRAPH_EXPLICIT", "ntt_r8": "VP_NTT_R8", "fuse_p2": "VP_FUSE_P2", "leaf_asm": "VP_LEAF_ASM",
                "fft_gkr_batched": "VP_FFT_GKR_BATCHED", "split_vu": "VP_SPLIT_VU", "pc_live": "VP_PC_LIVE",
-               "grind_window_log": "VP_GRIND_WINDOW_LOG", "grind_batch": "VP_GRIND_BATCH"}
+               "grind_window_log": "VP_GRIND_WINDOW_LOG", "grind_batch": "VP_GRIND_BATCH", "gen_rec": "VP_GEN_REC"}
 VP_OPTIONS_ABI = 0x76700005
 
 
@@ -1042,6 +1043,15 @@ class Session:
             out.append({"kernel": lib_gpu().vp_kernel_name(e.kind).decode(), "step": e.step, "workgroups": e.workgroups, "jobs": e.jobs,
                         "rounds": e.rounds, "first_round": e.first_round, "bytes": e.bytes, "work": e.work, "us": e.us})
         return out
+
+    def gen_jobs(self):
+        """Fused-init jobs of the launch plan the last prove_gkr ran, by what they generate: {mode: (row-pointer form, row-record form)} for mode
+        1 (phase-1 init), 2 (Liu gather), 3 (phase-2 init); vp_get_gen_jobs."""
+        out = (ctypes.c_uint32 * 8)()
+        err = lib_gpu().vp_get_gen_jobs(lib_host().vph_session_ctx(self.h), out)
+        if err:
+            raise RuntimeError("vp_get_gen_jobs failed: %d" % err)
+        return {m: (int(out[m]), int(out[4 + m])) for m in (1, 2, 3)}
 
     def world(self):
         """Ranks of a round-sharded session (1 otherwise)."""

@@ -7,6 +7,8 @@
 //           4 Liu gather list (row pointers, half-table selector)        5 store of a folded table entry beyond the buffers' capacity
 //           6 LDS slot of a transform tile                               7 codeword position of a leaf
 //           8 table entry of a round-sharded gather (pack / unpack)               9 request of an opening (oracle, leaf, bound)
+//          10 index of a row record into the arena of circuit values or the pool of half tables (which: 1 phase-1 operand, 2 Liu factor, 3 phase-2 V entry;
+//             index; bound)                                                      11 a row record's count against the row pointers (row, count, rows' length)
 #pragma once
 
 namespace vp {

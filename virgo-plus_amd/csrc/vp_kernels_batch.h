@@ -46,6 +46,28 @@ __device__ __forceinline__ F val_at(const InitArgs2 &a, int l, u32 x) {         
     return (a.vreal && a.valsr) ? f_make(a.valsr[l][x], 0) : a.vals[l][x];
 }
 
+// The phase-2 contribution of gate g once its two eq values are there (== the arithmetic of contrib2<2>, for a caller that has issued the loads of
+// several rows first: GenP2R): t = eq(r_liu, g) (assert gates: already scaled), eu = eq(r_u, u).
+__device__ __forceinline__ void p2_apply(const InitArgs2 &a, u32 g, u32 tl, F t, const F &eu, F &m, F &ad, const F &vu) {
+    const int ty = (tl >> 8) & 0x7f;
+    t = f_mul(t, eu);
+    const F tv = f_mul(t, vu);                         // t * V_u
+    switch (ty) {                                      // SURVEY.md Appendix A, phase-2 column
+        case T_ADD: m = f_add(m, t); ad = f_add(ad, tv); break;
+        case T_SUB: m = f_sub(m, t); ad = f_add(ad, tv); break;
+        case T_ANTISUB: m = f_add(m, t); ad = f_sub(ad, tv); break;
+        case T_MUL: m = f_add(m, tv); break;
+        case T_NAAB: m = f_add(m, f_sub(t, tv)); break;
+        case T_ANTINAAB: m = f_sub(m, tv); ad = f_add(ad, tv); break;
+        case T_XOR: ad = f_add(ad, tv); m = f_add(m, f_sub(t, f_dbl(tv))); break;
+        case T_COPY: ad = f_add(ad, tv); break;
+        case T_NOT: ad = f_add(ad, f_sub(t, tv)); break;
+        case T_ADDC: ad = f_add(ad, f_mul(t, f_add(a.gc[g], vu))); break;
+        case T_MULC: ad = f_add(ad, f_mul(tv, a.gc[g])); break;
+        default: break;
+    }
+}
+
 template <int PHASE>
 __device__ __forceinline__ void contrib2(const InitArgs2 &a, u32 e, F &m, F &ad, const F &vu) {       // vu = V_u (phase 2), loaded once per row
     const u32 g = a.e_g[e], x = a.e_x[e], tl = a.e_tl[e];
@@ -306,7 +328,7 @@ struct Sf3bLds { F s1[3][256]; F s2[3][128]; F red[4][9]; Lz acc2[3][128]; Lz ac
 // the inner product V_u = sum eq(r_u,u) V[u] of its layer (it has V[u] in registers anyway).
 struct GenLoad { static constexpr int MODE = 0; };
 struct GenP1 {
-    static constexpr int MODE = 1;
+    static constexpr int MODE = 1; static constexpr bool REC = false;
     const InitArgs2 *a; Half dot_h; F *dot_part;
     __device__ __forceinline__ void row(u32 row, u32 valid, F &m, F &ad) const {
         m = f_zero(); ad = f_zero();
@@ -347,7 +369,7 @@ struct GenP1 {
     }
 };
 struct GenLiu {
-    static constexpr int MODE = 2;
+    static constexpr int MODE = 2; static constexpr bool REC = false;
     const u32 *rowptr; const uint8_t *e_q; const u32 *e_g; const Half *H;
     __device__ __forceinline__ void row(u32 u, u32 valid, F &m, F &ad) const {
         ad = f_zero(); m = f_zero();
@@ -393,7 +415,7 @@ struct GenLiu {
 // written nor read back (x1024: 48 B written + 48 B read per slot).  The tables of a phase 2 lie side by side in one slot space (t_off), so a
 // row index is the global slot; the short subsets (< one chunk) keep their light-row init (they are folded by k_seg / k_emit from memory).
 struct GenP2 {
-    static constexpr int MODE = 3;
+    static constexpr int MODE = 3; static constexpr bool REC = false;
     const InitArgs2 *a;
     __device__ __forceinline__ F vrow(u32 row, u32 vend) const {
         if (row >= vend || row >= a->n_rows) return f_zero();
@@ -420,6 +442,127 @@ struct GenP2 {
         const F vu = *a->Vu;
         // the two rows' lists side by side: two dependent chains (record -> half-table entries -> products) in flight per lane
         u32 k0 = heavy0 ? e0 : b0, k1 = heavy1 ? e1 : e0;
+        while (k0 < e0 && k1 < e1) { contrib2<2>(*a, k0++, m0, a0, vu); contrib2<2>(*a, k1++, m1, a1, vu); }
+        for (; k0 < e0; ++k0) contrib2<2>(*a, k0, m0, a0, vu);
+        for (; k1 < e1; ++k1) contrib2<2>(*a, k1, m1, a1, vu);
+    }
+};
+
+// Row records (VP_GEN_REC, built at upload by k_up_rowrec / k_up_liu_rec).  The generators above reach a row's first operand through four
+// dependent loads: row pointers -> entry arrays (three of them) -> half-table entries and the layer's value pointer -> the value.  Which entry a
+// row starts with and where its operand lies are fixed by the circuit, so the upload writes them side by side: one 16-byte record per row,
+//   phase 1   { g, xg, tl | count << 16, next }     xg: index of the operand in the arena of real circuit values (~0: unary gate, no operand)
+//   phase 2   { g, u,  tl | count << 16, next }
+//   Liu       { bf, bs, count, next }               bf, bs: indices of the first list term's two factors in the proof's pool of half tables
+// count: contributions of the row (0xffff in phases 1 / 2: a heavy row, summed ahead into M / A), next: position of the row's second contribution in
+// the entry arrays (e_g / e_xg / e_tl, e_g / e_x / e_tl, l_bf / l_bs).  A lane loads the records of its two rows, then every operand of both rows,
+// then multiplies: two dependent loads.  Same field operations on the same operands as GenP1 / GenLiu / GenP2.  The phase-1 / phase-2 forms read
+// circuit values from the arena of real parts, so they serve all-real witnesses only (a complex witness keeps the generators above).
+struct GenRecArgs {
+    const uint4 *rec; const u32 *e_xg; const unsigned long long *arena; const u32 *s_gidx;     // s_gidx: phase 2, slot -> arena index of its V entry (~0: zero / padding slot)
+    const u32 *l_bf; const u32 *l_bs; const F *pool;
+    u32 arena_n, pool_n;      // checked build: ends of the arena and of the pool
+    int on, pad;
+};
+__device__ __forceinline__ u32 rec_count(const uint4 &q) { return q.z >> 16; }
+// checked build: the record's count against the row pointers it was built from (site 11)
+__device__ __forceinline__ bool rec_chk(const u32 *rowptr, u32 row, const uint4 &q, u32 count) {
+#ifdef VP_CHECKED
+    const u32 n = rowptr[row + 1] - rowptr[row];
+    return VP_CHK(count == n && (n == 0 || q.w == rowptr[row] + 1), 11, row, count, n);
+#else
+    return true;
+#endif
+}
+struct GenP1R {
+    static constexpr int MODE = 1; static constexpr bool REC = true;
+    const InitArgs2 *a; const GenRecArgs *r; Half dot_h; F *dot_part;
+    __device__ __forceinline__ P1Vals gather(const P1Entry &c) const {
+        P1Vals v;
+        v.bf = a->hg.bf[c.g & ((1u << a->hg.h1) - 1)]; v.bs = a->hg.bs[c.g >> a->hg.h1];
+        v.y = (c.x != ~0u && VP_CHK(c.x < r->arena_n, 10, 1, c.x, r->arena_n)) ? f_make(r->arena[c.x], 0) : f_zero();
+        return v;
+    }
+    __device__ __forceinline__ void row2(u32 r0, u32 valid, F &m0, F &a0, F &m1, F &a1) const {
+        m0 = f_zero(); a0 = f_zero(); m1 = f_zero(); a1 = f_zero();
+        const u32 lim = min(valid, a->n_rows);
+        uint4 q0 = make_uint4(0, 0, 0, 0), q1 = make_uint4(0, 0, 0, 0);
+        if (r0 < lim) q0 = r->rec[r0];
+        if (r0 + 1 < lim) q1 = r->rec[r0 + 1];
+        const u32 n0 = rec_count(q0), n1 = rec_count(q1);
+        const bool heavy0 = n0 == 0xffffu, heavy1 = n1 == 0xffffu;
+        const bool f0 = !heavy0 && n0 && rec_chk(a->rowptr, r0, q0, n0), f1 = !heavy1 && n1 && rec_chk(a->rowptr, r0 + 1, q1, n1);
+        const P1Entry c0{q0.x, q0.y, q0.z & 0xffffu}, c1{q1.x, q1.y, q1.z & 0xffffu};
+        P1Vals v0{}, v1{};
+        if (f0) v0 = gather(c0);
+        if (f1) v1 = gather(c1);
+        if (heavy0) { m0 = a->M[r0]; a0 = a->A[r0]; }
+        if (heavy1) { m1 = a->M[r0 + 1]; a1 = a->A[r0 + 1]; }
+        if (f0) p1_apply(*a, c0, v0, m0, a0);
+        if (f1) p1_apply(*a, c1, v1, m1, a1);
+        if (f0) for (u32 k = q0.w, ke = q0.w + n0 - 1; k < ke; ++k) { const P1Entry c{a->e_g[k], r->e_xg[k], a->e_tl[k]}; p1_apply(*a, c, gather(c), m0, a0); }
+        if (f1) for (u32 k = q1.w, ke = q1.w + n1 - 1; k < ke; ++k) { const P1Entry c{a->e_g[k], r->e_xg[k], a->e_tl[k]}; p1_apply(*a, c, gather(c), m1, a1); }
+    }
+};
+struct GenLiuR {
+    static constexpr int MODE = 2; static constexpr bool REC = true;
+    const u32 *rowptr; const Half *H; const GenRecArgs *r;
+    __device__ __forceinline__ F at(u32 i) const { return VP_CHK(i < r->pool_n, 10, 2, i, r->pool_n) ? r->pool[i] : f_zero(); }
+    __device__ __forceinline__ void row2(u32 u0, u32 valid, F &m0, F &a0, F &m1, F &a1) const {
+        m0 = f_zero(); a0 = f_zero(); m1 = f_zero(); a1 = f_zero();
+        if (u0 >= valid) return;
+        const bool ok1 = u0 + 1 < valid;
+        const Half h0 = H[0];
+        const uint4 *lrec = r->rec;
+        uint4 q0 = lrec[u0], q1 = make_uint4(0, 0, 0, 0);
+        if (ok1) q1 = lrec[u0 + 1];
+        // base terms eq(r_u, u): address arithmetic on the thread's own rows
+        const F bf0 = h0.bf[u0 & ((1u << h0.h1) - 1)], bs0 = h0.bs[u0 >> h0.h1];
+        F bf1 = f_zero(), bs1 = f_zero();
+        if (ok1) { bf1 = h0.bf[(u0 + 1) & ((1u << h0.h1) - 1)]; bs1 = h0.bs[(u0 + 1) >> h0.h1]; }
+#ifdef VP_CHECKED
+        if (!VP_CHK(q0.z == rowptr[u0 + 1] - rowptr[u0], 11, u0, q0.z, rowptr[u0 + 1] - rowptr[u0])) q0.z = 0;
+        if (ok1 && !VP_CHK(q1.z == rowptr[u0 + 2] - rowptr[u0 + 1], 11, u0 + 1, q1.z, rowptr[u0 + 2] - rowptr[u0 + 1])) q1.z = 0;
+#endif
+        F xf0 = f_zero(), xs0 = f_zero(), xf1 = f_zero(), xs1 = f_zero();
+        if (q0.z) { xf0 = at(q0.x); xs0 = at(q0.y); }
+        if (q1.z) { xf1 = at(q1.x); xs1 = at(q1.y); }
+        m0 = f_dot2cc<VP_MADSHIFT != 0>(bf0, bs0, xf0, xs0);
+        if (ok1) m1 = f_dot2cc<VP_MADSHIFT != 0>(bf1, bs1, xf1, xs1);
+        if (q0.z) for (u32 k = q0.w, ke = q0.w + q0.z - 1; k < ke; ++k) m0 = f_mad31c<false, VP_MADSHIFT != 0>(at(r->l_bf[k]), at(r->l_bs[k]), m0);
+        if (q1.z) for (u32 k = q1.w, ke = q1.w + q1.z - 1; k < ke; ++k) m1 = f_mad31c<false, VP_MADSHIFT != 0>(at(r->l_bf[k]), at(r->l_bs[k]), m1);
+    }
+};
+struct GenP2R {
+    static constexpr int MODE = 3; static constexpr bool REC = true;
+    const InitArgs2 *a; const GenRecArgs *r;
+    __device__ __forceinline__ F vrow(u32 row, u32 vend) const {
+        if (row >= vend || row >= a->n_rows) return f_zero();
+        const u32 gi = r->s_gidx[row];
+        if (gi == ~0u || !VP_CHK(gi < r->arena_n, 10, 3, gi, r->arena_n)) return f_zero();
+        return f_make(r->arena[gi], 0);
+    }
+    __device__ __forceinline__ void row2(u32 r0, u32 valid, F &m0, F &a0, F &m1, F &a1) const {
+        m0 = f_zero(); a0 = f_zero(); m1 = f_zero(); a1 = f_zero();
+        const u32 lim = min(valid, a->n_rows);
+        uint4 q0 = make_uint4(0, 0, 0, 0), q1 = make_uint4(0, 0, 0, 0);
+        if (r0 < lim) q0 = r->rec[r0];
+        if (r0 + 1 < lim) q1 = r->rec[r0 + 1];
+        const u32 n0 = rec_count(q0), n1 = rec_count(q1);
+        const bool heavy0 = n0 == 0xffffu, heavy1 = n1 == 0xffffu;
+        const bool f0 = !heavy0 && n0 && rec_chk(a->rowptr, r0, q0, n0), f1 = !heavy1 && n1 && rec_chk(a->rowptr, r0 + 1, q1, n1);
+        const Half &hg = a->hg, &hu = a->hu;
+        F g0f = f_zero(), g0s = f_zero(), u0f = f_zero(), u0s = f_zero(), g1f = f_zero(), g1s = f_zero(), u1f = f_zero(), u1s = f_zero();
+        if (f0) { g0f = hg.bf[q0.x & ((1u << hg.h1) - 1)]; g0s = hg.bs[q0.x >> hg.h1]; u0f = hu.bf[q0.y & ((1u << hu.h1) - 1)]; u0s = hu.bs[q0.y >> hu.h1]; }
+        if (f1) { g1f = hg.bf[q1.x & ((1u << hg.h1) - 1)]; g1s = hg.bs[q1.x >> hg.h1]; u1f = hu.bf[q1.y & ((1u << hu.h1) - 1)]; u1s = hu.bs[q1.y >> hu.h1]; }
+        if (heavy0) { m0 = a->M[r0]; a0 = a->A[r0]; }
+        if (heavy1) { m1 = a->M[r0 + 1]; a1 = a->A[r0 + 1]; }
+        const F vu = *a->Vu;
+        if (f0) { F t = f_mul(g0f, g0s); if (q0.z & 0x8000) t = f_mul(t, *a->assert_r); p2_apply(*a, q0.x, q0.z, t, f_mul(u0f, u0s), m0, a0, vu); }
+        if (f1) { F t = f_mul(g1f, g1s); if (q1.z & 0x8000) t = f_mul(t, *a->assert_r); p2_apply(*a, q1.x, q1.z, t, f_mul(u1f, u1s), m1, a1, vu); }
+        // the further contributions of the two rows side by side, from the entry arrays
+        u32 k0 = q0.w, k1 = q1.w;
+        const u32 e0 = f0 ? q0.w + n0 - 1 : k0, e1 = f1 ? q1.w + n1 - 1 : k1;
         while (k0 < e0 && k1 < e1) { contrib2<2>(*a, k0++, m0, a0, vu); contrib2<2>(*a, k1++, m1, a1, vu); }
         for (; k0 < e0; ++k0) contrib2<2>(*a, k0, m0, a0, vu);
         for (; k1 < e1; ++k1) contrib2<2>(*a, k1, m1, a1, vu);
@@ -476,9 +619,12 @@ __device__ __forceinline__ void sumfold3b_body(const SfArgs &a, u32 bid, u32 nb,
                     if (HAS_A) { a0 = ld_or_zero(a.inA, i0, vend); a1 = ld_or_zero(a.inA, i0 + 1, vend); }
                 }
             } else {                      // generated tables (GenP1 / GenLiu: one table per job, offset 0; GenP2: rows = global slots)
-                u32 cb0, ce0, ce1;                       // (requesting them one chunk ahead was measured: no gain)
-                gen.ptrs(i0, vend, cb0, ce0, ce1);
-                gen.row2(i0, vend, cb0, ce0, ce1, m0, a0, m1, a1);
+                if constexpr (Gen::REC) gen.row2(i0, vend, m0, a0, m1, a1);
+                else {
+                    u32 cb0, ce0, ce1;                   // (requesting them one chunk ahead was measured: no gain)
+                    gen.ptrs(i0, vend, cb0, ce0, ce1);
+                    gen.row2(i0, vend, cb0, ce0, ce1, m0, a0, m1, a1);
+                }
                 if constexpr (Gen::MODE == 1) {
                     if (gen.dot_part) {
                         if (vreal) {

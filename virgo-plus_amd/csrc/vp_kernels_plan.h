@@ -613,12 +613,23 @@ __global__ void __launch_bounds__(VP_BLOCK, VP_SF_MINB) k_sumfold3b_multi(const 
     if (a.has_a) sumfold3b_body<true>(a, m.bid, a.nblk, sm, GenLoad()); else sumfold3b_body<false>(a, m.bid, a.nblk, sm, GenLoad());
 }
 // First fold launch of a phase-1 / Liu / phase-2 sumcheck with its init fused in (see GenP1 / GenLiu / GenP2).
-struct SfGenJob { SfArgs sf; InitArgs2 a; GatherJob g; Half dot_h; F *dot_part; int mode; int pad; };   // mode 1: phase-1 init (GenP1), 2: Liu gather (GenLiu), 3: phase-2 init (GenP2)
+struct SfGenJob { SfArgs sf; InitArgs2 a; GatherJob g; Half dot_h; F *dot_part; int mode; int pad; GenRecArgs r; };   // mode 1: phase-1 init (GenP1), 2: Liu gather (GenLiu), 3: phase-2 init (GenP2); r.on: their row-record forms
 __global__ void __launch_bounds__(VP_BLOCK, VP_SF_MINB) k_sumfold3b_gen_multi(const SfGenJob *__restrict__ jobs, const BlkMap *__restrict__ map) {
     __shared__ Sf3bLds sm;
     const BlkMap m = map[blockIdx.x];
     const SfGenJob &j = jobs[m.job];
-    if (j.mode == 1) {
+    if (j.r.on) {
+        if (j.mode == 1) {
+            GenP1R g; g.a = &j.a; g.r = &j.r; g.dot_h = j.dot_h; g.dot_part = j.dot_part;
+            sumfold3b_body<true>(j.sf, m.bid, j.sf.nblk, sm, g);
+        } else if (j.mode == 3) {
+            GenP2R g; g.a = &j.a; g.r = &j.r;
+            sumfold3b_body<true>(j.sf, m.bid, j.sf.nblk, sm, g);
+        } else {
+            GenLiuR g; g.rowptr = j.g.rowptr; g.H = j.g.H; g.r = &j.r;
+            sumfold3b_body<false>(j.sf, m.bid, j.sf.nblk, sm, g);
+        }
+    } else if (j.mode == 1) {
         GenP1 g; g.a = &j.a; g.dot_h = j.dot_h; g.dot_part = j.dot_part;
         sumfold3b_body<true>(j.sf, m.bid, j.sf.nblk, sm, g);
     } else if (j.mode == 3) {

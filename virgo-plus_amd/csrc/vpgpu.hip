@@ -33,6 +33,7 @@ struct Csr {                 // contributions of one layer sorted by target row 
     u32 n_rows = 0, n_entries = 0, n_heavy = 0, n_chunks = 0, n_heavy_entries = 0;
     u32 *rowptr = nullptr, *e_g = nullptr, *e_x = nullptr;
     uint16_t *e_tl = nullptr;
+    uint4 *rec = nullptr; u32 *e_xg = nullptr;       // row records of the fused inits and the entries' arena indices (phase 1); vp_kernels_batch.h, GenRecArgs
     u32 *heavy_row = nullptr, *heavy_cptr = nullptr, *chunk_beg = nullptr, *chunk_end = nullptr;
     u32 *chunk_h = nullptr, *heavy_cnt = nullptr;      // heavy-row index of every chunk; arrival counters of the rows cut into several chunks (zero between proofs)
     std::vector<u32> h_heavy_row, h_heavy_cptr;      // host copies (a handful of rows): row-range init jobs of the index-split proof
@@ -56,6 +57,8 @@ struct LayerDev {
     u32 n_jobs = 0; BetaJob *jobs = nullptr; std::vector<int> job_k, job_h1;
     // batched path: per-slot V gather map, Liu gather lists, half tables of this layer's sumchecks
     uint8_t *s_layer = nullptr; u32 *s_idx = nullptr;
+    u32 *s_gidx = nullptr;                                       // slot -> arena index of its V entry (GenP2R)
+    uint4 *l_rec = nullptr; u32 *l_bf = nullptr, *l_bs = nullptr;  // Liu row records and the entries' pre-resolved half-table indices (GenLiuR)
     u32 *lrow = nullptr, *l_g = nullptr; uint8_t *l_q = nullptr; u32 l_n = 0;      // l_n: entries of the Liu gather lists
     Half hg{}, hu{};
     Half *liu_H = nullptr;
@@ -129,6 +132,7 @@ struct Plan {
     hipStream_t streams[4] = {nullptr, nullptr, nullptr, nullptr};   // [0] = ctx->stream; [1..3] owned: fold (low priority), seg, emit (high)
     hipEvent_t ev_root = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     u64 rounds = 0; int n_steps = 0;
+    u32 gen_jobs[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // fused-init jobs by mode ([1..3]: GenP1 / GenLiu / GenP2, [5..7]: their row-record forms); vp_get_gen_jobs
     FixJob *d_fix = nullptr; u32 n_fix = 0;          // k_fixup jobs (when round 1 of the sumchecks leaves its b to the fix-up pass)
     std::vector<void *> allocs;                      // device arrays owned by the plan (freed with it)
     // index-split proof: V_u of the split phase-2 chains ahead of the graph (vu_pre_*): per chain one inner-product job over this rank's share of
@@ -174,6 +178,7 @@ struct VpOpt {
     int32_t pc_live;                // VP_PC_LIVE: the unsharded, unmasked commitment transforms and folds only the slices the input layer fills (0: all 64)  [1]
     int32_t grind_window_log;       // VP_GRIND_WINDOW_LOG: vp_fs_grind's windows grow from 2^16 nonces by a factor of four up to 2^this (16 .. 28; profiles/fs_grind.md)  [24]
     int32_t grind_batch;            // VP_GRIND_BATCH: windows vp_fs_grind queues before the host waits and reads the hit slot (1 .. 64)  [8]
+    int32_t gen_rec;                // VP_GEN_REC: the fused inits read one 16-byte record per row and gather through arena / pool indices; bit 0: phase-1 and phase-2 inits, bit 1: Liu gathers (0: row pointers, entry arrays, layer pointers)  [3]
 };
 
 struct vp_ctx {
@@ -184,6 +189,9 @@ struct vp_ctx {
     std::vector<LayerDev> L;
     F **d_vals = nullptr;
     unsigned long long **d_valsr = nullptr;      // per layer: the real parts of its values as a dense array (all-real circuits, vp_evaluate), else nullptr
+    // One arena behind every LayerDev::valr (layer l at element val_off[l], a multiple of 16): the fused inits' row records address a circuit value by one
+    // 32-bit index.  gen_rec_ok: the records exist (VP_GEN_REC, and the arena and the pool of half tables are shorter than 2^32 elements).
+    unsigned long long *valr_arena = nullptr; std::vector<u32> val_off; u32 *d_val_off = nullptr; u64 arena_n = 0, pool_n = 0; bool gen_rec_ok = false;
     F *beta_g = nullptr, *beta_u = nullptr, *bf = nullptr, *bs = nullptr, *liu_half = nullptr;
     u32 half_cap = 0;
     F *tab[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
@@ -405,6 +413,7 @@ void pc_forget(vp_ctx *ctx) {
 void circuit_forget(vp_ctx *ctx) {
     ctx->L.clear(); ctx->n_layers = 0; ctx->max_bl = 0; ctx->evaluated = false;
     ctx->d_vals = nullptr; ctx->d_valsr = nullptr; ctx->vreal = 0; ctx->plan_vreal = 0;
+    ctx->valr_arena = nullptr; ctx->val_off.clear(); ctx->d_val_off = nullptr; ctx->arena_n = 0; ctx->pool_n = 0; ctx->gen_rec_ok = false;
     ctx->beta_g = ctx->beta_u = ctx->bf = ctx->bs = ctx->liu_half = nullptr; ctx->half_cap = 0;
     for (int b = 0; b < 2; ++b) for (int t = 0; t < 3; ++t) ctx->tab[b][t] = nullptr;
     ctx->cap = 0; ctx->partials = nullptr; ctx->round_arrivals = nullptr; ctx->small = nullptr; ctx->chunk_part = nullptr; ctx->chunk_cap = 0;
@@ -1087,6 +1096,12 @@ int vp_checked_build(void) {
 #endif
 }
 const char *vp_version(void) { return "vpgpu 0.1 (gfx950)"; }
+int vp_get_gen_jobs(vp_ctx *ctx, uint32_t out[8]) {
+    if (!ctx || !out) return VP_EINVAL;
+    VP_LOCK(ctx);
+    for (int q = 0; q < 8; ++q) out[q] = ctx->plan ? ctx->plan->gen_jobs[q] : 0u;
+    return VP_OK;
+}
 const char *vp_last_error(const vp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 static void opt_defaults(VpOpt *o) {
@@ -1107,6 +1122,7 @@ static void opt_defaults(VpOpt *o) {
     o->split_vu = 1;
     o->pc_live = 1;
     o->grind_window_log = 24; o->grind_batch = 8;
+    o->gen_rec = 3;
 }
 static void opt_to_public(const VpOpt &o, vp_options *p) {
     memset(p, 0, sizeof *p);
@@ -1139,7 +1155,7 @@ static const OptName g_opt_names[] = {
     {"pc_tensor_pub", &VpOpt::pc_tensor_pub}, {"persistent_timeout_ms", &VpOpt::persistent_timeout_ms}, {"graph_explicit", &VpOpt::graph_explicit}, {"ntt_r8", &VpOpt::ntt_r8},
     {"interactive_fast_init", &VpOpt::interactive_fast_init}, {"fuse_p2", &VpOpt::fuse_p2}, {"leaf_asm", &VpOpt::leaf_asm},
     {"real_pairs", &VpOpt::real_pairs}, {"fft_gkr_batched", &VpOpt::fft_gkr_batched}, {"split_vu", &VpOpt::split_vu}, {"pc_live", &VpOpt::pc_live},
-    {"grind_window_log", &VpOpt::grind_window_log}, {"grind_batch", &VpOpt::grind_batch}};
+    {"grind_window_log", &VpOpt::grind_window_log}, {"grind_batch", &VpOpt::grind_batch}, {"gen_rec", &VpOpt::gen_rec}};
 int vp_tuning_get(const vp_ctx *ctx, const char *name, int32_t *value) {
     if (!ctx || !name || !value) return VP_EINVAL;
     for (const OptName &n : g_opt_names) if (!strcmp(n.name, name)) { *value = ctx->opt.*(n.field); return VP_OK; }
@@ -1182,6 +1198,7 @@ static int resolve_options(VpOpt *o, const vp_options *user, uint32_t *pinned) {
     flag("VP_FFT_GKR_BATCHED", o->fft_gkr_batched);
     flag("VP_SPLIT_VU", o->split_vu);
     flag("VP_PC_LIVE", o->pc_live);
+    num("VP_GEN_REC", o->gen_rec); o->gen_rec &= 3;
     num("VP_GRIND_WINDOW_LOG", o->grind_window_log); num("VP_GRIND_BATCH", o->grind_batch);
     o->grind_window_log = std::min(28, std::max(16, o->grind_window_log)); o->grind_batch = std::min(64, std::max(1, o->grind_batch));
     flag("VP_PC_TENSOR", o->pc_tensor_pub);
@@ -1359,6 +1376,14 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
         for (int i = 0; i < n_layers; ++i) sizes[i] = ld[i].size;
         VPCHK(dupload(ctx, &d_sizes, sizes));
     }
+    {   // the arena of real circuit values: layer offsets (the arena itself is allocated by the first vp_evaluate that finds an all-real witness)
+        std::vector<u32> off(n_layers, 0);
+        u64 at = 0;
+        for (int i = 0; i < n_layers; ++i) { off[i] = (u32) at; at += (ld[i].size + 15) & ~15ull; }
+        ctx->arena_n = at;
+        ctx->gen_rec_ok = ctx->opt.gen_rec != 0 && at < (1ull << 32);
+        if (ctx->gen_rec_ok) { ctx->val_off = off; VPCHK(dupload(ctx, &ctx->d_val_off, off)); }
+    }
     for (int i = 0; i < n_layers; ++i) {
         LayerDev &D = ctx->L[i];
         const vp_layer_desc &L = ld[i];
@@ -1443,6 +1468,8 @@ int vp_circuit_upload(vp_ctx *ctx, int n_layers, const vp_layer_desc *ld) {
         size_t total = 0;
         for (size_t q = 0; q < jobs.size(); ++q) total += need[q];
         VPCHK(dalloc(ctx, &ctx->half_pool, total));
+        ctx->pool_n = total;
+        if (total >= (1ull << 32)) ctx->gen_rec_ok = false;         // (the lists built so far keep their records; no job will point at them)
         size_t at = 0;
         for (size_t q = 0; q < jobs.size(); ++q) {
             jobs[q].bf = ctx->half_pool + at;
@@ -1567,6 +1594,10 @@ int vp_evaluate(vp_ctx *ctx, const vp_F *inputs, uint64_t n_inputs) {
         std::vector<unsigned long long *> vr(ctx->n_layers);
         for (int i = 0; i < ctx->n_layers; ++i) {
             LayerDev &D = ctx->L[i];
+            if (!D.valr && ctx->gen_rec_ok) {
+                if (!ctx->valr_arena) VPCHK(dalloc(ctx, &ctx->valr_arena, (size_t) ctx->arena_n));
+                D.valr = ctx->valr_arena + ctx->val_off[i];
+            }
             if (!D.valr) VPCHK(dalloc(ctx, &D.valr, (size_t) D.size));
             hipLaunchKernelGGL(k_real_parts, dim3(nblk(D.size)), dim3(VP_BLOCK), 0, ctx->stream, D.val, (u32) D.size, D.valr);
             vr[i] = D.valr;

@@ -541,6 +541,10 @@ static int submit_gkr(vp_ctx *ctx, bool serial) {
             if (fuse_big) {
                 ctx->rec->cur = 2 * (i - 1) + 1;
                 ctx->rec_gen.mode = 2;
+                if (ctx->gen_rec_ok && (ctx->opt.gen_rec & 2) && cur.l_rec) {      // row records: the first list term's half-table entries by pool index, no descriptor load
+                    GenRecArgs &gr = ctx->rec_gen.r;
+                    gr.rec = cur.l_rec; gr.l_bf = cur.l_bf; gr.l_bs = cur.l_bs; gr.pool = ctx->half_pool; gr.pool_n = (u32) ctx->pool_n; gr.on = 1;
+                }
                 ctx->rec_gen.g.rowptr = cur.lrow; ctx->rec_gen.g.e_q = cur.l_q; ctx->rec_gen.g.e_g = cur.l_g; ctx->rec_gen.g.H = cur.liu_H;
                 ctx->rec_gen.g.M = nullptr; ctx->rec_gen.g.size = (u32) pre.size;
                 ctx->rec_gen_bytes = 5 * (u64) cur.l_n + 4 * (u64) pre.size; ctx->rec_gen_work = cur.l_n;      // 5-byte (subset, position) record per entry; the eq values come from L2-resident half tables
@@ -599,6 +603,10 @@ static int submit_gkr(vp_ctx *ctx, bool serial) {
             ctx->rec_gen = SfGenJob{};
             const bool fuse_p1 = ctx->rec && ctx->fuse_init && pbl >= std::max(plan_sf_big_log(), plan_fuse_min_log());
             if (fuse_p1) ctx->rec_gen.mode = 1;
+            if (fuse_p1 && ctx->gen_rec_ok && (ctx->opt.gen_rec & 1) && ctx->vreal && ctx->valr_arena && cur.c1.rec) {      // row records: operands by arena index (the arena holds real parts: all-real witnesses only)
+                GenRecArgs &gr = ctx->rec_gen.r;
+                gr.rec = cur.c1.rec; gr.e_xg = cur.c1.e_xg; gr.arena = ctx->valr_arena; gr.arena_n = (u32) ctx->arena_n; gr.on = 1;
+            }
             // with the init fused into the first fold launch, V_u riding on it would hold phase 2 back until that launch ends:
             // phase 2 then takes V_u from the separate inner-product pass and starts at step 0 (VP_FUSE_DOT=1: ride anyway)
             const bool fuse_dot = ctx->opt.fuse_dot != 0;
@@ -671,6 +679,10 @@ static int submit_gkr(vp_ctx *ctx, bool serial) {
                 const bool fuse_p2 = ctx->rec && ctx->fuse_init && ctx->opt.fuse_p2 && mdb >= std::max(plan_sf_big_log(), plan_fuse_min_log());
                 if (fuse_p2) {
                     ctx->rec_gen.mode = 3;
+                    if (ctx->gen_rec_ok && (ctx->opt.gen_rec & 1) && ctx->vreal && ctx->valr_arena && cur.c2.rec && cur.s_gidx) {
+                        GenRecArgs &gr = ctx->rec_gen.r;
+                        gr.rec = cur.c2.rec; gr.s_gidx = cur.s_gidx; gr.arena = ctx->valr_arena; gr.arena_n = (u32) ctx->arena_n; gr.on = 1;
+                    }
                     u64 rows_big = 0;
                     for (int j = 0; j < i; ++j) if (cur.t_len[j] >= SFC0) rows_big += cur.dad_size[j];
                     const Csr &c = cur.c2;
@@ -1058,6 +1070,7 @@ static int build_plan(vp_ctx *ctx) {
     VPCHK(dupload(ctx, &P->d_light, light)); VPCHK(dupload(ctx, &P->d_chunks, chunks));
     VPCHK(dupload(ctx, &P->d_combine, combine)); VPCHK(dupload(ctx, &P->d_sf, sf)); VPCHK(dupload(ctx, &P->d_sfgen, sfgen)); VPCHK(dupload(ctx, &P->d_seg, seg));
     VPCHK(dupload(ctx, &P->d_emit, emit)); VPCHK(dupload(ctx, &P->d_map, map));
+    for (const SfGenJob &gj : sfgen) ++P->gen_jobs[(gj.mode & 3) + (gj.r.on ? 4 : 0)];
     if (ctx->drop_round1) { VPCHK(dupload(ctx, &P->d_fix, ctx->rec_fix)); P->n_fix = (u32) ctx->rec_fix.size(); }
     if (ctx->split_lw > 0 && ctx->shard_world > 1 && ctx->opt.split_vu) {
         // V_u of the index-split phase-2 chains (same list on every rank: split_layout depends on the circuit and the world size only)

@@ -135,6 +135,51 @@ __global__ void __launch_bounds__(VP_BLOCK) k_up_liu_gather(const u32 *__restric
     const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p < n) { const u32 s = sidx[p]; eg[p] = gcat[s]; eq[p] = qcat[s]; }
 }
+// Row records of a target-sorted list (GenP1R / GenP2R, vp_kernels_batch.h): { g, x, tl | count << 16, position of the second entry } of the row's first
+// entry; count 0xffff marks a heavy row.  val_off (phase 1 only): x becomes the operand's index in the arena of circuit values, ~0 for a unary entry, and
+// every entry's index goes to e_xg.
+__global__ void __launch_bounds__(VP_BLOCK) k_up_rowrec(const u32 *__restrict__ rowptr, const u32 *__restrict__ e_g, const u32 *__restrict__ e_x, const uint16_t *__restrict__ e_tl,
+                                                        const u32 *__restrict__ val_off, u32 n_rows, u32 n, uint4 *__restrict__ rec, u32 *__restrict__ e_xg) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (val_off && i < n) { const u32 l = e_tl[i] & 0xffu; e_xg[i] = l == 0xffu ? ~0u : val_off[l] + e_x[i]; }
+    if (i >= n_rows) return;
+    const u32 b = rowptr[i], cnt = rowptr[i + 1] - b;
+    uint4 q = make_uint4(0, 0, 0, 0);
+    if (cnt > VP_LIGHT_MAX) q.z = 0xffffu << 16;
+    else if (cnt) {
+        const u32 tl = e_tl[b], l = tl & 0xffu;
+        q.x = e_g[b]; q.y = !val_off ? e_x[b] : l == 0xffu ? ~0u : val_off[l] + e_x[b];
+        q.z = tl | (cnt << 16); q.w = b + 1;
+    }
+    rec[i] = q;
+}
+// phase-2 slot -> arena index of its V entry (~0: an empty subset's slot or a padding slot, both read as zero)
+__global__ void __launch_bounds__(VP_BLOCK) k_up_sgidx(const uint8_t *__restrict__ s_layer, const u32 *__restrict__ s_idx, const u32 *__restrict__ val_off, u32 n, u32 *__restrict__ s_gidx) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 l = s_layer[i];
+    s_gidx[i] = l >= 0xfeu ? ~0u : val_off[l] + s_idx[i];
+}
+// Liu row records (GenLiuR): { bf, bs, count, position of the second entry }, bf / bs = where the two factors of eq_q(g) lie in the pool of half
+// tables (H[q].h1 depends on bit lengths only); l_bf / l_bs: the same pair for every entry
+__global__ void __launch_bounds__(VP_BLOCK) k_up_liu_rec(const u32 *__restrict__ rowptr, const uint8_t *__restrict__ l_q, const u32 *__restrict__ l_g, const Half *__restrict__ H,
+                                                         const F *pool, u32 rows, u32 n, uint4 *__restrict__ rec, u32 *__restrict__ l_bf, u32 *__restrict__ l_bs) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const Half h = H[l_q[i]];
+        const u32 g = l_g[i];
+        l_bf[i] = (u32) (h.bf - pool) + (g & ((1u << h.h1) - 1)); l_bs[i] = (u32) (h.bs - pool) + (g >> h.h1);
+    }
+    if (i >= rows) return;
+    const u32 b = rowptr[i], cnt = rowptr[i + 1] - b;
+    uint4 q = make_uint4(0, 0, cnt, b + 1);
+    if (cnt) {
+        const Half h = H[l_q[b]];
+        const u32 g = l_g[b];
+        q.x = (u32) (h.bf - pool) + (g & ((1u << h.h1) - 1)); q.y = (u32) (h.bs - pool) + (g >> h.h1);
+    }
+    rec[i] = q;
+}
 
 }  // namespace vp
 
@@ -179,7 +224,8 @@ inline int bits_for(u64 n_values) { int b = 1; while ((1ull << b) < n_values) ++
 
 // Target-sorted contribution list of one layer and one phase, built on the device (the counting sort of round 1, see the file header).
 // key / ex / etl: per gate, in gate order.
-int build_csr_dev(vp_ctx *ctx, UpScratch &S, Csr &c, u32 n_rows, u32 n, const u32 *d_key, const u32 *d_iota, const u32 *d_ex, const uint16_t *d_etl) {
+// d_val_off: phase 1, the layers' offsets in the arena of circuit values (row records with pre-added operand indices); nullptr: phase 2.
+int build_csr_dev(vp_ctx *ctx, UpScratch &S, Csr &c, u32 n_rows, u32 n, const u32 *d_key, const u32 *d_iota, const u32 *d_ex, const uint16_t *d_etl, const u32 *d_val_off) {
     c.n_rows = n_rows; c.n_entries = n;
     VPCHK(dalloc(ctx, &c.rowptr, (size_t) n_rows + 1));
     VPCHK(dalloc(ctx, &c.e_g, (size_t) n)); VPCHK(dalloc(ctx, &c.e_x, (size_t) n)); VPCHK(dalloc(ctx, &c.e_tl, (size_t) n));
@@ -188,6 +234,12 @@ int build_csr_dev(vp_ctx *ctx, UpScratch &S, Csr &c, u32 n_rows, u32 n, const u3
     VPCHK(up_sort_pairs(ctx, S, d_key, ks, d_iota, c.e_g, n, bits_for(std::max<u64>(2, n_rows))));
     hipLaunchKernelGGL(k_up_rowptr, dim3(nblk((u64) n_rows + 1)), dim3(VP_BLOCK), 0, ctx->stream, ks, n, c.rowptr, n_rows);
     if (n) hipLaunchKernelGGL(k_up_gather_entries, dim3(nblk(n)), dim3(VP_BLOCK), 0, ctx->stream, c.e_g, n, d_ex, d_etl, c.e_x, c.e_tl);
+    if (ctx->gen_rec_ok && (ctx->opt.gen_rec & 1)) {
+        VPCHK(dalloc(ctx, &c.rec, (size_t) n_rows));
+        if (d_val_off) VPCHK(dalloc(ctx, &c.e_xg, (size_t) n));
+        const u64 span = std::max<u64>(n_rows, d_val_off ? n : 0);
+        if (span) hipLaunchKernelGGL(k_up_rowrec, dim3(nblk(span)), dim3(VP_BLOCK), 0, ctx->stream, c.rowptr, c.e_g, c.e_x, c.e_tl, d_val_off, n_rows, n, c.rec, c.e_xg);
+    }
     // heavy rows: count, then fetch (row, begin, end)
     u32 *d_cnt = nullptr, *d_hv = nullptr;
     VPCHK(up_tmp(ctx, S, &d_cnt, 1));
@@ -373,8 +425,12 @@ int upload_layer_dev(vp_ctx *ctx, UpScratch &S, int i, const vp_layer_desc *ld, 
         VPCHK(dupload(ctx, &D.p_cbeg, cbeg)); VPCHK(dupload(ctx, &D.p_cend, cend)); VPCHK(dupload(ctx, &D.p_bptr, bptr));
     }
     // ---- contribution lists ----
-    VPCHK(build_csr_dev(ctx, S, D.c1, (u32) ld[i - 1].size, n, key1, iota2, D.gv, d_etl));
-    VPCHK(build_csr_dev(ctx, S, D.c2, D.p2_total, n, key2, iota2, D.gu, d_etl));
+    VPCHK(build_csr_dev(ctx, S, D.c1, (u32) ld[i - 1].size, n, key1, iota2, D.gv, d_etl, ctx->d_val_off));
+    VPCHK(build_csr_dev(ctx, S, D.c2, D.p2_total, n, key2, iota2, D.gu, d_etl, nullptr));
+    if (ctx->gen_rec_ok && (ctx->opt.gen_rec & 1)) {
+        VPCHK(dalloc(ctx, &D.s_gidx, (size_t) D.p2_total));
+        if (D.p2_total) hipLaunchKernelGGL(k_up_sgidx, dim3(nblk(D.p2_total)), dim3(VP_BLOCK), 0, ctx->stream, D.s_layer, D.s_idx, ctx->d_val_off, D.p2_total, D.s_gidx);
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     up_release(S);
     return VP_OK;
@@ -405,6 +461,11 @@ int upload_liu_dev(vp_ctx *ctx, UpScratch &S, int i) {
     hipLaunchKernelGGL(k_up_rowptr, dim3(nblk((u64) rows + 1)), dim3(VP_BLOCK), 0, ctx->stream, ks, tn, D.lrow, rows);
     if (tn) hipLaunchKernelGGL(k_up_liu_gather, dim3(nblk(tn)), dim3(VP_BLOCK), 0, ctx->stream, sidx, tn, gcat, qcat, D.l_g, D.l_q);
     D.l_n = tn;
+    if (ctx->gen_rec_ok && (ctx->opt.gen_rec & 2)) {
+        VPCHK(dalloc(ctx, &D.l_rec, (size_t) rows)); VPCHK(dalloc(ctx, &D.l_bf, (size_t) tn)); VPCHK(dalloc(ctx, &D.l_bs, (size_t) tn));
+        hipLaunchKernelGGL(k_up_liu_rec, dim3(nblk(std::max<u64>(rows, tn))), dim3(VP_BLOCK), 0, ctx->stream, D.lrow, D.l_q, D.l_g, D.liu_H, ctx->half_pool, rows, tn,
+                           D.l_rec, D.l_bf, D.l_bs);
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     up_release(S);
     return VP_OK;
